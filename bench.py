@@ -7,7 +7,15 @@ BASELINE.json's metric is quoted on (configs[1]).  Inputs (resized u8 frame, tok
 HBM before the timed region.  Weights are seeded random bf16 at the exact 7B shapes (no checkpoint exists
 offline), so timing is valid and the generated text is noise.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line: the headline (``metric``, ``value``,
+``unit``, ``ms_per_step`` = milliseconds of one timed step), ``config`` and the ``prefill_mfma`` / ``decode`` split of
+the timed steps' own HIP events (``prefill_mfma``: prefill FLOPs / prefill time against the dense bf16 MFMA peak,
+BASELINE.md section 3).  ``--dump-outputs DIR`` writes what the last timed step computed (tokens.npy: the
+generated token ids a caller receives; logits.npy: the f32 logits of the final decode step) as float arrays; the
+inputs are seeded, so two builds compare output for output.  Everything that takes runs of its own is measured only
+with ``--full``.
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (``python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N``: RANK / WORLD_SIZE are then in the environment) or - when
@@ -18,10 +26,9 @@ one RCCL all_gather of the per-image result records, and the reported time is th
 ``--backend gloo --dry-device cpu`` runs the same launcher / rendezvous / gather / max-over-ranks plumbing
 with NO model (records only) - the CPU rehearsal of the N > 1 path used by tests/test_bench_launcher.py.
 
-The single JSON line also carries
+With --full the JSON line also carries (--no-extras / --no-blocks / --no-cpu-baseline leave parts out)
   roofline     - the dominant kernel (decode weight-streaming GEMV, HBM-bound): algorithmic bytes per
                  launch / average launch duration, measured live with HIP events;
-  prefill_mfma - prefill FLOPs / prefill time against the dense bf16 MFMA peak (BASELINE.md section 3);
   cpu_baseline - the oracle (CPU port of the same arithmetic) timed on this host's cores on a bounded
                  sample of the same workload;
   microbench   - measured peak-GEMM and stream-copy figures of THIS box with the
@@ -467,6 +474,23 @@ def plumbing_baseline(n_images: int = 24, size: int = 448):
             "what": "configs[0]: run_multi_image_inspection, canned-response client, no model, no GPU (host logic only)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # the engine's 64 sequences' f32 logits at 152064 entries are 39 MB
+
+
+def dump_outputs(path: str, tokens, logits=None) -> None:
+    """--dump-outputs: what the last timed step computed, as ``<path>/<name>.npy`` - tokens.npy [sequences, new tokens]
+    (float64 token ids) and, when given, logits.npy [sequences, vocab] (float32).  64 MB at most in all."""
+    arrays = {"tokens": np.asarray(tokens, dtype=np.float64)}
+    if logits is not None:
+        arrays["logits"] = np.asarray(logits, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def free_port() -> int:
     import socket
     s = socket.socket()
@@ -510,12 +534,14 @@ def run_dry(args, rank: int, world: int) -> None:
     if world > 1:
         dist.init_process_group(args.backend)
     rng = np.random.default_rng(rank)
+    last = []
 
     def one_step():
         toks = rng.integers(0, 1000, args.new_tokens).tolist()
         rec = gather_records([{"image": f"synthetic_{rank}_{b}", "tokens": toks} for b in range(args.batch)], world)
         if len(rec) != world * args.batch:
             raise RuntimeError(f"rank {rank}: gathered {len(rec)} records, expected {world * args.batch}")
+        last[:] = [r["tokens"] for r in rec]
     for _ in range(args.warmup):
         one_step()
     if world > 1:
@@ -530,6 +556,8 @@ def run_dry(args, rank: int, world: int) -> None:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     if rank == 0:
         print(json.dumps({"metric": "DRY RUN (no model): record exchange only", "value": world * args.steps * args.batch / elapsed,
                           "unit": "records/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -707,10 +735,15 @@ def main():
     ap.add_argument("--image-size", type=int, default=1024)
     ap.add_argument("--prompt-tokens", type=int, default=1024)
     ap.add_argument("--new-tokens", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the microbench / e2e / plumbing blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: roofline (GEMV-only graph replay), microbench, e2e, "
+                         "plumbing, the batch64 / seam64 / dual / fp8_batch4 blocks and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the microbench / e2e / plumbing blocks")
     ap.add_argument("--no-blocks", action="store_true",
-                    help="skip the batch64 / seam64 / dual / fp8_batch4 blocks (configs[2]/[3]/[4] per-GPU slices, ~2 min)")
+                    help="--full: skip the batch64 / seam64 / dual / fp8_batch4 blocks (configs[2]/[3]/[4] per-GPU slices, ~2 min)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, the product path) or gloo (CPU rehearsal, with --dry-device cpu)")
@@ -746,6 +779,10 @@ def main():
                     help="images per step per GPU; > 1 uses the batched decode path (BASELINE configs[3]/[4] style "
                          "batch inspection) - NOT the headline single-image configuration")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "step":
+        ap.error("--dump-outputs applies to the step workload")
 
     if args.dry_device == "cpu":
         # a dry run must not open the GPU at all (torch.cuda.is_available() would, in every rank): hide it before any
@@ -801,7 +838,7 @@ def main():
     new = args.new_tokens
     B = args.batch
 
-    pre_ev, step_records = [], []
+    pre_ev, step_records, last_tokens = [], [], []
 
     def one_step_batched(timed: bool):
         s = torch.cuda.Event(enable_timing=True)
@@ -822,6 +859,7 @@ def main():
         if timed:
             pre_ev.append((s, m, e))
             step_records.append(len(rec))
+            last_tokens[:] = [r["tokens"] for r in rec]
 
     def one_step(timed: bool):
         if B > 1:
@@ -844,6 +882,7 @@ def main():
         if timed:
             pre_ev.append((s, m, e))
             step_records.append(len(rec))
+            last_tokens[:] = [r["tokens"] for r in rec]
 
     for _ in range(args.warmup):
         one_step(False)
@@ -861,6 +900,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.share_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:    # before --full's replays, which write the logits buffers again
+        dump_outputs(args.dump_outputs, last_tokens, engine.logits_b[:B].cpu().numpy())
 
     if rank == 0:
         if any(n != world * B for n in step_records):
@@ -869,27 +910,9 @@ def main():
         t_dec = sum(m.elapsed_time(e) for s, m, e in pre_ev) / len(pre_ev) * 1e-3
         fp8 = args.decode_weights == "fp8"
         p8 = args.prefill_dtype == "fp8"
-        if B > 1:
-            k_avg, k_launches = measure_decode_gemm(engine, B)
-            kernel = ("decode_proj_kernel" if engine.fused_proj else "gemm_decode_stream_kernel") + \
-                ("<fp8>" if fp8 and engine.fp8_batched else "") + \
-                f" (batched decode projection, weights streamed once for {B} sequences" + \
-                (", split-K reduction and epilogue in the same launch)" if engine.fused_proj else ")")
-        else:
-            k_avg, k_launches = measure_gemv(engine)
-            kernel = ("gemv_fp8w_kernel" if fp8 else "gemv_bf16_kernel") + " (decode weight streaming)"
         step_bytes = gemv_bytes_per_step(cfg) / (2 if fp8 else 1)
         if B > 1 and fp8 and engine.fp8_batched:      # the o projection stays bf16 in the batched fp8 step
             step_bytes += cfg.layers * cfg.heads * cfg.head_dim * cfg.hidden
-        kernel_bytes = step_bytes
-        if B == 1 and engine.chain_sync is not None:  # qkv / o weights stream inside the chained layer-head launch
-            D_ = cfg.head_dim
-            kernel_bytes -= 2.0 * cfg.layers * (cfg.hidden * (cfg.heads + 2 * cfg.kv_heads) * D_ + cfg.heads * D_ * cfg.hidden)
-            kernel_bytes -= 2.0 * cfg.hidden * cfg.vocab
-            kernel = "gemv_bf16_kernel<1, false> (decode weight streaming: the gate/up and down projections, 81 % of a token's " \
-                     "weight bytes; qkv / o run inside decode_chain_kernel, the lm_head as gemv_bf16_kernel<1, true>)"
-        bytes_per_launch = kernel_bytes / k_launches
-        achieved = bytes_per_launch / k_avg / 1e9
         flops = prefill_flops(cfg, n_patches, S) * B          # B full prompt passes' worth of arithmetic per step
         out = {
             "metric": {"7b": "inspected images/sec (1024x1024, Qwen2-VL-7B)",
@@ -916,16 +939,6 @@ def main():
                        "weights": "seeded random bf16 at exact 7B shapes",
                        "parallelism": f"dp{world} (whole images)" if not args.share_gpu else
                        f"REHEARSAL: {world} ranks sharing ONE GPU, records over gloo - not a scaling measurement"},
-            "roofline": {"bound": "hbm", "kernel": kernel,
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": None if (fp8 or B > 1) else measured_traffic("gemv", True)[0],
-                         # not measured in this run: read from the tracked rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
-                         "traffic_source": None if (fp8 or B > 1) else measured_traffic("gemv", True)[1],
-                         "bytes_per_launch": bytes_per_launch,
-                         "avg_launch_us": k_avg * 1e6, "launches_per_token": k_launches,
-                         # the same bound over the WHOLE decode token (every weight byte of a step / the step's time): the
-                         # figure that stays comparable when the set of kernels behind `kernel` changes between rounds
-                         "whole_token_frac": step_bytes * (new - 1) / t_dec / 1e9 / HBM_PEAK_GBS},
             "prefill_mfma": {"flops": flops, "ms": t_pre * 1e3, "images": B, "achieved": flops / t_pre / 1e12,
                              "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s", "frac": flops / t_pre / 1e12 / MFMA_BF16_PEAK_TF,
                              "note": ("FLOPs of B full prompt passes / time of the B prompt passes of a step; with a "
@@ -936,7 +949,36 @@ def main():
                        "weight_GBps": step_bytes * (new - 1) / t_dec / 1e9,
                        "sequences_per_step": B},
         }
-        extras = not args.no_extras and args.model == "7b" and world == 1
+        if args.full:     # per-kernel figure from replays of its own
+            if B > 1:
+                k_avg, k_launches = measure_decode_gemm(engine, B)
+                kernel = ("decode_proj_kernel" if engine.fused_proj else "gemm_decode_stream_kernel") + \
+                    ("<fp8>" if fp8 and engine.fp8_batched else "") + \
+                    f" (batched decode projection, weights streamed once for {B} sequences" + \
+                    (", split-K reduction and epilogue in the same launch)" if engine.fused_proj else ")")
+            else:
+                k_avg, k_launches = measure_gemv(engine)
+                kernel = ("gemv_fp8w_kernel" if fp8 else "gemv_bf16_kernel") + " (decode weight streaming)"
+            kernel_bytes = step_bytes
+            if B == 1 and engine.chain_sync is not None:  # qkv / o weights stream inside the chained layer-head launch
+                D_ = cfg.head_dim
+                kernel_bytes -= 2.0 * cfg.layers * (cfg.hidden * (cfg.heads + 2 * cfg.kv_heads) * D_ + cfg.heads * D_ * cfg.hidden)
+                kernel_bytes -= 2.0 * cfg.hidden * cfg.vocab
+                kernel = "gemv_bf16_kernel<1, false> (decode weight streaming: the gate/up and down projections, 81 % of a token's " \
+                         "weight bytes; qkv / o run inside decode_chain_kernel, the lm_head as gemv_bf16_kernel<1, true>)"
+            bytes_per_launch = kernel_bytes / k_launches
+            achieved = bytes_per_launch / k_avg / 1e9
+            out["roofline"] = {"bound": "hbm", "kernel": kernel,
+                               "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": None if (fp8 or B > 1) else measured_traffic("gemv", True)[0],
+                               # not measured in this run: read from the tracked rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
+                               "traffic_source": None if (fp8 or B > 1) else measured_traffic("gemv", True)[1],
+                               "bytes_per_launch": bytes_per_launch,
+                               "avg_launch_us": k_avg * 1e6, "launches_per_token": k_launches,
+                               # the same bound over the WHOLE decode token (every weight byte of a step / the step's time): the
+                               # figure that stays comparable when the set of kernels behind `kernel` changes between rounds
+                               "whole_token_frac": step_bytes * (new - 1) / t_dec / 1e9 / HBM_PEAK_GBS}
+        extras = args.full and not args.no_extras and args.model == "7b" and world == 1
         if extras:
             mb = microbench(dev)
             best = max(v for k, v in mb.items() if k.startswith("gemm_") and v)
@@ -956,7 +998,7 @@ def main():
                 import bench_blocks
                 out.update(bench_blocks.run_all(cfg, weights, dev, frame, n_patches, n_img_tok, new, args.prompt_tokens,
                                                 log=lambda m: print(f"[bench] {m}", file=sys.stderr, flush=True)))
-        if not args.no_cpu_baseline and args.model == "7b" and world == 1:     # rank 0 at N = 1 only (the other ranks would idle)
+        if args.full and not args.no_cpu_baseline and args.model == "7b" and world == 1:     # rank 0 at N = 1 only (the other ranks would idle)
             out["cpu_baseline"] = cpu_baseline(cfg, n_patches, S, new)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -74,3 +74,18 @@ def test_batch256_host_only_ingest_two_ranks_on_cpu():
     assert "host-only stand-in" in out["config"]["workload"]
     assert [p["images"] for p in out["per_rank"]] == [5, 5]
     assert all(p["engine_device_s"] == 0.0 for p in out["per_rank"])
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the records every rank receives in the last timed step, as float64 DIR/tokens.npy; the inputs are
+    seeded, so a second run writes the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        r = _run(["--gpus", "2", "--batch", "2", "--new-tokens", "16", "--dump-outputs", str(tmp_path / run)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert _json_line(r.stdout)["steps"] == 3
+        toks = np.load(tmp_path / run / "tokens.npy")
+        assert toks.dtype == np.float64 and toks.shape == (4, 16)
+        dumps.append(toks)
+    assert np.array_equal(dumps[0], dumps[1])

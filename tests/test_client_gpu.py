@@ -222,6 +222,33 @@ def test_bench_two_ranks_sharing_the_gpu_rehearsal():
     assert "REHEARSAL" in out["config"]["parallelism"]
 
 
+def test_bench_plain_run_dumps_its_outputs_and_full_adds_the_roofline(device, tmp_path):
+    """A plain `bench.py --gpus 1` prints the headline of its timed steps and nothing that needs runs of its own;
+    --dump-outputs writes the last timed step's token ids and final-step logits as float arrays (the last token is the
+    logits' argmax); --full adds the roofline and leaves what the timed path computes unchanged."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--model", "tiny", "--image-size", "112",
+            "--prompt-tokens", "64", "--new-tokens", "8", "--steps", "2", "--warmup", "1"]
+    outs, dumps = [], []
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1]))
+        toks, logits = np.load(tmp_path / name / "tokens.npy"), np.load(tmp_path / name / "logits.npy")
+        assert toks.dtype == np.float64 and toks.shape == (1, 8)
+        assert logits.dtype == np.float32 and logits.ndim == 2 and logits.shape[0] == 1 and np.isfinite(logits).all()
+        assert int(np.argmax(logits[0])) == int(toks[0, -1])
+        dumps.append((toks, logits))
+    plain, full = outs
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert "roofline" not in plain and "prefill_mfma" in plain and "decode" in plain
+    assert full["roofline"]["achieved"] > 0
+    assert np.array_equal(dumps[0][0], dumps[1][0])
+    np.testing.assert_allclose(dumps[0][1], dumps[1][1], rtol=1e-3, atol=1e-3)
+
+
 def test_bench_batch256_workload_two_ranks_sharing_the_gpu():
     """`bench.py --gpus 2 --share-gpu --workload batch256` (BASELINE configs[3] as a workload) on tiny weights: rank 0 writes
     the PNG files, both ranks run the whole seam (a3 encode, data-URI decode, engine, parse, consensus, gates) on

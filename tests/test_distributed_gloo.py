@@ -90,9 +90,10 @@ def _worker_failure(rank, world, port, paths, outdir, mode):
     with open(os.path.join(outdir, f"rank{rank}.json"), "w") as f:
         json.dump(out, f, default=str)
     # no barrier / destroy: the default group is unusable once a rank is gone, which is the point of the test
-    if mode == "late" and rank == 0:     # rank 0 hosts the rendezvous store: stay until the late rank has read it
+    if rank == 0:     # rank 0 hosts the rendezvous store: stay until every other reporting rank has read it
+        others = range(1, world if mode == "late" else world - 1)
         for _ in range(200):
-            if os.path.exists(os.path.join(outdir, f"rank{world - 1}.json")):
+            if all(os.path.exists(os.path.join(outdir, f"rank{r}.json")) for r in others):
                 break
             time.sleep(0.1)
     os._exit(0)

@@ -2,7 +2,7 @@
 ran VLMInspectorAgent._encode_image_optimized, vlm_inspector.py:46-88, VLMAuditorAgent._encode_image_optimized,
 vlm_auditor.py:85-108, and INSPECTOR_PROMPT / AUDITOR_PROMPT .format, utils/prompts.py:18-174, in the dev container):
 the product's request-side encode must produce the byte-identical data URI (SHA-256 + length) or the same exception
-type, and - when the host application's utils.prompts is importable - the identical formatted prompt."""
+type; and with a host application's utils.prompts importable (a stand-in module here) its prompt text is used verbatim."""
 import base64
 import hashlib
 import importlib
@@ -71,38 +71,45 @@ def test_auditor_keeps_the_reference_quirks(agents, tmp_path):
     assert la["auditor_default"] == {"error": "OSError"} and "sha256" in la["inspector_default"]
 
 
-HOST = "/root/reference"
+# A stand-in for the host application's utils/prompts.py: templates with the same str.format fields as the real ones and
+# JSON braces escaped as there, so that the product's use of a host module is tested without the host application.
+HOST_PROMPTS_PY = '''INSPECTOR_PROMPT = """Host inspector. Criticality: {criticality}. Domain: {domain}. Notes: {user_notes}.
+Answer as {{"defects": []}}."""
+AUDITOR_PROMPT = """Host auditor. Criticality: {criticality}. Domain: {domain}.
+Answer as {{"defects": []}}."""
+'''
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(HOST, "utils", "prompts.py")),
-                    reason="the host application (reference checkout) is not present on this machine")
-def test_host_prompts_are_used_verbatim_and_format_identically(monkeypatch):
+def test_host_prompts_are_used_verbatim_and_format_identically(monkeypatch, tmp_path):
     """Drop-in deployment: with the host application's utils.prompts importable the product sends ITS prompt text
-    (a4); the formatted prompts for three contexts hash to what the reference's own call produced."""
+    (a4) verbatim, and formats it for the recorded contexts with the reference's defaults."""
     import types
+    host = tmp_path / "host_app" / "utils"
+    host.mkdir(parents=True)
+    (host / "prompts.py").write_text(HOST_PROMPTS_PY)
     pkg = types.ModuleType("utils")
-    pkg.__path__ = [os.path.join(HOST, "utils")]          # namespace package: utils/__init__.py needs dotenv
+    pkg.__path__ = [str(host)]          # namespace package, as a host utils/__init__.py may need third-party modules
     monkeypatch.setitem(sys.modules, "utils", pkg)
     monkeypatch.delitem(sys.modules, "utils.prompts", raising=False)
     import vision_inspection_system_amd.prompts as P
     P = importlib.reload(P)
     try:
+        hp = sys.modules["utils.prompts"]
         assert P.HOST_PROMPTS is True
-        for name, text in (("inspector", P.INSPECTOR_PROMPT), ("auditor", P.AUDITOR_PROMPT)):
-            b = text.encode("utf-8")
-            assert {"sha256": hashlib.sha256(b).hexdigest(), "length": len(b)} == VEC["prompt_templates"][name]
+        assert P.INSPECTOR_PROMPT == hp.INSPECTOR_PROMPT and P.AUDITOR_PROMPT == hp.AUDITOR_PROMPT
         for rec in VEC["prompts"]:
             ctx = rec["context"]
-            ins = P.INSPECTOR_PROMPT.format(criticality=ctx["criticality"], domain=ctx["domain"] or "general",
-                                            user_notes=ctx["user_notes"] or "None provided")
-            au = P.AUDITOR_PROMPT.format(criticality=ctx["criticality"], domain=ctx["domain"] or "general")
-            for text, want in ((ins, rec["inspector"]), (au, rec["auditor"])):
-                b = text.encode("utf-8")
-                assert {"sha256": hashlib.sha256(b).hexdigest(), "length": len(b)} == want
+            domain, notes = ctx["domain"] or "general", ctx["user_notes"] or "None provided"
+            ins = P.INSPECTOR_PROMPT.format(criticality=ctx["criticality"], domain=domain, user_notes=notes)
+            au = P.AUDITOR_PROMPT.format(criticality=ctx["criticality"], domain=domain)
+            assert ins == (f"Host inspector. Criticality: {ctx['criticality']}. Domain: {domain}. Notes: {notes}.\n"
+                           'Answer as {"defects": []}.')
+            assert au == f"Host auditor. Criticality: {ctx['criticality']}. Domain: {domain}.\n" + 'Answer as {"defects": []}.'
     finally:
         monkeypatch.undo()
         sys.modules.pop("utils.prompts", None)
         importlib.reload(P)
+    assert P.HOST_PROMPTS is False
 
 
 def test_agent_messages_use_the_same_format_call(agents, tmp_path):
