@@ -220,6 +220,18 @@ int vis_argmax_f32(const void* logits, int V, void* ws_val, void* ws_idx, void* 
 /* batch > 1: sequence b reads logits + b*ld_logits, writes tokens[b*max_tokens + step[b]], cur_token[b],
  * step_ptr[b]; ws_val / ws_idx need 256 entries per sequence. */
 
+/* Token log-probabilities of the pick vis_argmax_f32 / vis_gemv_bf16_argmax just made (csrc/logprobs.hip).  For sequence
+ * b < batch (logits + b * ld_logits, V f32 entries) at pos = step_ptr[b] - 1, if 0 <= pos < max_tokens:
+ *   lp[b][pos][0] = logits[tokens[b][pos]] - lse, lse = log(sum exp(logits)) (raw logits: temperature 1, no noise);
+ *   lp[b][pos][1 + i] = logits[id_i] - lse and top_ids[b][pos][i] = id_i for i < top_k, descending, ties to the lower index.
+ * lp is f32 [batch][max_tokens][21], top_ids int32 [batch][max_tokens][20]; entries past top_k are not written.  A row's results
+ * depend on its logits only (the reduction layout is fixed by V).  Own workspace of vis_logprobs_ws_bytes(V, batch) bytes;
+ * one launch at a time per workspace.  VIS_ERR_ARG: null pointer, V outside 1..262144, ld_logits < V, batch outside 1..64,
+ * top_k outside 0..min(20, V), max_tokens <= 0, ws_bytes too small. */
+long long vis_logprobs_ws_bytes(int V, int batch);
+int vis_logprobs_f32(const void* logits, int V, int ld_logits, const void* tokens, int max_tokens, const void* step_ptr,
+                     int top_k, void* lp, void* top_ids, void* ws, long long ws_bytes, int batch, vis_stream_t stream);
+
 /* K10 (batched decode), first half.  For up to 64 in-flight sequences the weight matrix is streamed from HBM
  * ONCE per step by <= 256 persistent workgroups (one per CU, 7-stage LDS-DMA ring, stream-K cut of the
  * (128-column tile, K-step) sequence).  part[slot][R][N] (f32), R = 16 / 32 / 64 for B <= 16 / 32 / 64 (one, two or four

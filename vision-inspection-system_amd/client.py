@@ -31,10 +31,32 @@ class _Message:
 
 
 @dataclass
+class TopLogprob:
+    token: str
+    bytes: List[int]
+    logprob: float
+
+
+@dataclass
+class TokenLogprob:
+    """One completion token of ``choice.logprobs.content`` (OpenAI's ChatCompletionTokenLogprob)."""
+    token: str
+    bytes: List[int]
+    logprob: float
+    top_logprobs: List[TopLogprob] = field(default_factory=list)
+
+
+@dataclass
+class ChoiceLogprobs:
+    content: List[TokenLogprob]
+
+
+@dataclass
 class _Choice:
     message: _Message
     index: int = 0
     finish_reason: str = "stop"
+    logprobs: Optional[ChoiceLogprobs] = None      # set only when the request asked for logprobs=True
 
 
 @dataclass
@@ -52,8 +74,10 @@ class _Completions:
         self._owner = owner
 
     def create(self, model: Optional[str] = None, messages: Optional[list] = None,
-               temperature: Optional[float] = None, max_tokens: Optional[int] = None, **kwargs) -> ChatCompletion:
-        return self._owner._complete(model, messages or [], temperature, max_tokens, **kwargs)
+               temperature: Optional[float] = None, max_tokens: Optional[int] = None, logprobs: bool = False,
+               top_logprobs: Optional[int] = None, **kwargs) -> ChatCompletion:
+        return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
+                                     top_logprobs=top_logprobs, **kwargs)
 
 
 class _Chat:
@@ -203,6 +227,30 @@ def _reply_text(model_id: str, decoded: str) -> str:
     return decoded
 
 
+def logprobs_k(logprobs, top_logprobs) -> Optional[int]:
+    """OpenAI's (logprobs, top_logprobs) -> None (off) or the number of alternatives per token.  Checked before any model
+    is loaded; the messages avoid the substrings the reference's retry logic keys on."""
+    from .logprobs import MAX_TOP_LOGPROBS
+    if top_logprobs is not None:
+        if not logprobs:
+            raise ValueError("top_logprobs needs logprobs=True")
+        if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, int) or not 0 <= top_logprobs <= MAX_TOP_LOGPROBS:
+            raise ValueError(f"top_logprobs must be an integer in 0..{MAX_TOP_LOGPROBS}")
+    if not logprobs:
+        return None
+    return int(top_logprobs or 0)
+
+
+def _choice_logprobs(tok, toks: List[int], rec) -> ChoiceLogprobs:
+    """An engine's TokenLogprobs record of one request -> choice.logprobs (one entry per completion token)."""
+    def entry(cls, t, lp, **kw):
+        b = tok.token_bytes(int(t))
+        return cls(tok.token_text(int(t)), list(b), float(lp), **kw)
+    return ChoiceLogprobs([entry(TokenLogprob, t, rec.token_logprobs[i],
+                                 top_logprobs=[entry(TopLogprob, a, la) for a, la in zip(rec.top_ids[i], rec.top_logprobs[i])])
+                           for i, t in enumerate(toks)])
+
+
 def drop_models() -> None:
     with _ENGINES_LOCK:
         _ENGINES.clear()
@@ -298,15 +346,22 @@ class LocalVLMClient:
         counts = [(th // cfg.patch) * (tw // cfg.patch) // cfg.merge ** 2 for _, (th, tw) in frames]
         return build_chat_ids(lm.tokenizer, messages, counts), frames
 
-    def _complete(self, model, messages, temperature, max_tokens, **kwargs) -> ChatCompletion:
-        return self.complete_many(model, [messages], temperature, max_tokens)[0]
+    def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None,
+                  **kwargs) -> ChatCompletion:
+        return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs)[0]
 
-    def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None) -> List[ChatCompletion]:
+    def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
+                      top_logprobs: Optional[int] = None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
-        the batch path; ``chat.completions.create`` is the single-request form of it."""
+        the batch path; ``chat.completions.create`` is the single-request form of it.
+        ``logprobs`` / ``top_logprobs`` (OpenAI's): every choice gets ``logprobs.content``, one entry per completion token -
+        the log-softmax of the model's raw logits (independent of temperature and seed) and the ``top_logprobs`` most
+        likely alternatives.  With VIS_SYNTHETIC_REPLY (synthetic models) they describe the generated tokens, not the
+        substituted text."""
         import torch
+        k = logprobs_k(logprobs, top_logprobs)
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
@@ -316,7 +371,7 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         out: List[ChatCompletion] = []
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -351,20 +406,23 @@ class LocalVLMClient:
             for i in range(0, len(futs), eng.max_batch):
                 idx = range(i, min(len(futs), i + eng.max_batch))
                 toks = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp, seed=self.seed,
-                                          ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1")
+                                          ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1",
+                                          **({"logprobs": k} if k is not None else {}))
+                recs = eng.last_logprobs if k is not None else [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", {}))
                 if timing:
                     TIMING_LOG.append({"model": model_id, **timing})
                     del TIMING_LOG[:-4096]
                     logger.debug("%s: %d request(s): prompt pass %.1f ms, %d decode steps in %.1f ms (device time)", model_id,
                                  len(idx), timing["prefill_ms"], timing["decode_steps"], timing["decode_ms"])
-                for j, t in zip(idx, toks):
+                for j, t, rec in zip(idx, toks, recs):
                     if isinstance(t, Exception):
                         if not lazy:
                             raise t
                         out.append(t)
                         continue
-                    out.append(ChatCompletion([_Choice(_Message(_reply_text(model_id, tok.decode(t))))], model=model_id,
+                    lp = _choice_logprobs(tok, t, rec) if rec is not None else None
+                    out.append(ChatCompletion([_Choice(_Message(_reply_text(model_id, tok.decode(t))), logprobs=lp)], model=model_id,
                                               usage={"prompt_tokens": n_ids[j], "completion_tokens": len(t),
                                                      "total_tokens": n_ids[j] + len(t)}, timings=timing))
         return out
@@ -390,7 +448,8 @@ class LocalVLMClient:
             raise ValueError("the mllama backend takes one image per request (what the reference sends)")
         return build_llama_chat_ids(lm.tokenizer, messages, len(frames)), (frames[0] if frames else None)
 
-    def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int) -> List[ChatCompletion]:
+    def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
+                              k: Optional[int] = None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -399,9 +458,11 @@ class LocalVLMClient:
         eng, tok = lm.engine, lm.tokenizer
         from . import ingest
         ignore_eos = os.environ.get("VIS_IGNORE_EOS") == "1"
+        lpk = {"logprobs": k} if k is not None else {}
 
-        def completion(n_ids, t):
-            return ChatCompletion([_Choice(_Message(_reply_text(lm.model_id, tok.decode(t))))], model=lm.model_id,
+        def completion(n_ids, t, rec=None):
+            lp = _choice_logprobs(tok, t, rec) if rec is not None else None
+            return ChatCompletion([_Choice(_Message(_reply_text(lm.model_id, tok.decode(t))), logprobs=lp)], model=lm.model_id,
                                   usage={"prompt_tokens": n_ids, "completion_tokens": len(t), "total_tokens": n_ids + len(t)},
                                   timings=dict(getattr(eng, "last_timing", {})))
 
@@ -423,28 +484,32 @@ class LocalVLMClient:
                 for g0 in range(0, len(futs), eng.max_batch):
                     idx = range(g0, min(len(futs), g0 + eng.max_batch))
                     outs = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp,
-                                              seed=self.seed, stop_on_eos=not ignore_eos)
+                                              seed=self.seed, stop_on_eos=not ignore_eos, **lpk)
+                    recs = eng.last_logprobs if k is not None else [None] * len(idx)
                     if getattr(eng, "last_timing", None):
                         TIMING_LOG.append({"model": lm.model_id, **eng.last_timing})
                         del TIMING_LOG[:-4096]
-                    out.extend(t if isinstance(t, Exception) else completion(n_ids[j], t) for j, t in zip(idx, outs))
+                    out.extend(t if isinstance(t, Exception) else completion(n_ids[j], t, r) for j, t, r in zip(idx, outs, recs))
             return out
         prepared = [f.result() for f in futs]
         toks_out: List[Optional[List[int]]] = [None] * len(prepared)
+        recs: list = [None] * len(prepared)
         with eng.lock:
             with_img = [i for i, (_, f) in enumerate(prepared) if f is not None]
             for g0 in range(0, len(with_img), eng.max_batch):
                 grp = with_img[g0:g0 + eng.max_batch]
                 reqs = [(prepared[i][0], _frame_to_device(prepared[i][1], eng.device)) for i in grp]
                 outs = eng.generate_batch(reqs, max_new_tokens=max_new, temperature=temp, seed=self.seed,
-                                          stop_on_eos=not ignore_eos)
-                for i, t in zip(grp, outs):
+                                          stop_on_eos=not ignore_eos, **lpk)
+                for n, (i, t) in enumerate(zip(grp, outs)):
                     toks_out[i] = t
+                    recs[i] = eng.last_logprobs[n] if k is not None else None
             for i, (ids, f) in enumerate(prepared):
                 if f is None:
                     toks_out[i] = eng.generate(ids, None, max_new_tokens=max_new, temperature=temp, seed=self.seed,
-                                               stop_on_eos=not ignore_eos)
-        return [completion(len(ids), t) for (ids, _), t in zip(prepared, toks_out)]
+                                               stop_on_eos=not ignore_eos, **lpk)
+                    recs[i] = eng.last_logprobs[0] if k is not None else None
+        return [completion(len(ids), t, r) for (ids, _), t, r in zip(prepared, toks_out, recs)]
 
 
 _MOCK_REPLY: List[Optional[Any]] = [None]

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .logprobs import LogprobsBuffers, check_k
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
 
@@ -319,6 +320,10 @@ class Qwen2VLEngine:
         self._decoded = 0
         self.decode_limit = 0
         self.last_first_logits: Optional[torch.Tensor] = None
+        # token log-probabilities (generate(..., logprobs=k)): k while a request asks for them, else None; buffers on first use
+        self.lp_k: Optional[int] = None
+        self._lp: Optional[LogprobsBuffers] = None
+        self.last_logprobs: Optional[list] = None
 
     # ------------------------------------------------------------------ vision tower
     def vision_forward(self, frames: Sequence[torch.Tensor], split_rows: bool = True) -> torch.Tensor:
@@ -655,6 +660,7 @@ class Qwen2VLEngine:
         hip.argmax(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
                    cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot)   # per-slot workspace: prefills
         # of different slots may run concurrently on different streams
+        self._logprobs_after_pick(1, slot)
         self.slot_prompt_len[slot] = S
         if slot == 0:
             self.prompt_len = S
@@ -832,6 +838,7 @@ class Qwen2VLEngine:
             hip.argmax(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
                        self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
                        self.seed + 0x9E3779B9 * slot)
+            self._logprobs_after_pick(1, slot)
             self.slot_prompt_len[slot] = S
             if slot == 0:
                 self.prompt_len = S
@@ -1051,6 +1058,19 @@ class Qwen2VLEngine:
         P = (P // 64) * 64
         return P if P >= self.min_shared_prefix else 0
 
+    # ------------------------------------------------------------------ token log-probabilities
+    def _begin_logprobs(self, logprobs: Optional[int]) -> None:
+        """Switch the per-pick logprobs launch on (k alternatives) or off (None) for the request about to run."""
+        self.lp_k = check_k(logprobs)
+        self.last_logprobs = None
+        if self.lp_k is not None and self._lp is None:
+            self._lp = LogprobsBuffers(self.max_batch, self.tokens_b.shape[1], self.cfg.vocab, self.device)
+
+    def _logprobs_after_pick(self, B: int, slot: int = 0) -> None:
+        """vis_logprobs_f32 on the logits of slots slot .. slot + B - 1, right after their pick (nothing when off)."""
+        if self.lp_k is not None:
+            self._lp.launch(self.logits_b[slot:slot + B], self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], self.lp_k, slot)
+
     # ------------------------------------------------------------------ decode
     def _decode_step(self, chained: Optional[bool] = None) -> None:
         cfg, w = self.cfg, self.w
@@ -1074,6 +1094,7 @@ class Qwen2VLEngine:
             hip.gemv_fp8(x[0], *self.q8_lm_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
             hip.argmax(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                        self.temperature, self.seed)
+            self._logprobs_after_pick(1)
             return
         for li, lw in enumerate(w.llm):
             if chained:
@@ -1100,10 +1121,12 @@ class Qwen2VLEngine:
         if chained:     # the pick's first stage rides in the lm_head epilogue
             hip.gemv_argmax(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                             norm_w=w.final_norm_w, eps=cfg.rms_eps, temperature=self.temperature, seed=self.seed)
+            self._logprobs_after_pick(1)
             return
         hip.gemv(x[0], w.lm_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
         hip.argmax(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                    self.temperature, self.seed)
+        self._logprobs_after_pick(1)
 
     # ---- batched decode: B in-flight sequences (slots 0..B-1) share every weight read of a step
     def _decode_step_batched(self, B: int) -> None:
@@ -1153,6 +1176,7 @@ class Qwen2VLEngine:
         hip.decode_gemm(xn, w.lm_head, out=self.logits_b[:B])
         hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
+        self._logprobs_after_pick(B)
 
     def _decode_step_fused(self, B: int, projections_only: bool = False) -> int:
         """One decode step for B in-flight sequences, every projection ONE launch (r05, csrc/decode_stream.hip): the stream-K
@@ -1222,6 +1246,7 @@ class Qwen2VLEngine:
         if not projections_only:
             hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                        self.temperature, self.seed)
+            self._logprobs_after_pick(B)
         return 4 * n_layers + 1
 
     def _decode_step_rows(self, B: int) -> None:
@@ -1255,6 +1280,7 @@ class Qwen2VLEngine:
         proj(x, self.q8_lm_head if fp8 else w.lm_head, self.logits_b[:B], norm_w=w.final_norm_w, eps=eps)
         hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
+        self._logprobs_after_pick(B)
 
     def _decode_step_batched_fp8(self, B: int) -> None:
         """Batched decode on e4m3 weights AND activations (BASELINE configs[4]): qkv, gate/up, down and the lm_head run
@@ -1298,10 +1324,11 @@ class Qwen2VLEngine:
         hip.decode_gemm_fp8(xq, sxq, *self.q8_lm_head, out=self.logits_b[:B])
         hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
+        self._logprobs_after_pick(B)
 
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
-        # sampling parameters (and the batch size) are kernel arguments baked into the graph
-        key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch)
+        # sampling parameters, the batch size and the logprobs k are kernel arguments baked into the graph
+        key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch, self.lp_k)
         if key in self._graphs:
             return self._graphs[key]
         step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
@@ -1417,10 +1444,13 @@ class Qwen2VLEngine:
 
     def generate(self, input_ids: Sequence[int], frames: Sequence[torch.Tensor] = (), max_new_tokens: int = 128,
                  ignore_eos: bool = False, use_graph: bool = True, check_every: int = 16,
-                 temperature: float = 0.0, seed: int = 0) -> List[int]:
+                 temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
-        first EOS (exclusive)."""
+        first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
+        (log-softmax of the raw logits - independent of temperature and seed - for every returned token, plus its k most
+        likely alternatives); None = off, no extra launch."""
+        self._begin_logprobs(logprobs)
         room = self.max_ctx - len(input_ids) - 1
         if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
             self._warned_clamp = True          # said once per engine: the reply may end before the model is done
@@ -1441,6 +1471,8 @@ class Qwen2VLEngine:
             _LOG.warning("%s - continuing on the unchained decode step", e)
             self.disable_chain()
             return self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
+        finally:
+            self.lp_k = None
 
     def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time (tracing)
@@ -1464,30 +1496,42 @@ class Qwen2VLEngine:
         self.last_timing = {"prompt_tokens": len(input_ids), "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": 1}
         if not ignore_eos:
-            for i, t in enumerate(toks):
-                if t in eos:
-                    return toks[:i]
+            toks = toks[:next((i for i, t in enumerate(toks) if t in eos), len(toks))]
+        if self.lp_k is not None:
+            self.last_logprobs = [self._lp.record(0, self.prompt_len - 1, len(toks), self.lp_k)]
         return toks
 
     # ------------------------------------------------------------------ batched generation
     def generate_batch(self, requests: Sequence,
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
-                       check_every: int = 16, temperature: float = 0.0, seed: int = 0) -> list:
+                       check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
-        Returns one token list per request; for a lazy request whose callable raised, the exception object instead."""
+        Returns one token list per request; for a lazy request whose callable raised, the exception object instead.
+        ``logprobs``: as in generate; ``last_logprobs`` then holds one record per request (None for a failed one)."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
+        check_k(logprobs)
         if n_req == 1:
             r = requests[0]
             if callable(r):
                 try:
                     r = r()
                 except Exception as e:      # noqa: BLE001
+                    self.last_logprobs = [None] if logprobs is not None else None
                     return [e]
-            return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)]
+            return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
+                                  logprobs=logprobs)]
+        self._begin_logprobs(logprobs)
+        try:
+            return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
+        finally:
+            self.lp_k = None
+
+    def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> list:
+        n_req = len(requests)
         # every prompt's own limit (prompt + new tokens <= context) is applied by its prefill; the shared loop below
         # runs to the limit of the longest one
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -1497,6 +1541,8 @@ class Qwen2VLEngine:
         live = [b for b in range(n_req) if slots[b] is not None]
         B = len(live)
         if B == 0:
+            if self.lp_k is not None:
+                self.last_logprobs = [None] * n_req
             return list(errors)
         longest = max(self.slot_prompt_len[slots[b]] for b in live)
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
@@ -1526,4 +1572,7 @@ class Qwen2VLEngine:
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
         if not ignore_eos:
             outs = [seq[:next((i for i, t in enumerate(seq) if t in eos), len(seq))] for seq in outs]
+        if self.lp_k is not None:
+            self.last_logprobs = [self._lp.record(slots[b], starts[slots[b]], len(outs[slots[b]]), self.lp_k)
+                                  if slots[b] is not None else None for b in range(n_req)]
         return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]

@@ -53,6 +53,8 @@ _SIGS = {
     "vis_decode_chain": "ppi" + "p" * 12 + "i" * 9 + "ff" + "p",
     "vis_gemv_bf16_argmax": "pppp" + "iii" + "f" + "ppp" + "i" + "pp" + "fu" + "p",
     "vis_argmax_f32": "p" + "i" + "ppp" + "i" + "pp" + "fu" + "ii" + "p",
+    "vis_logprobs_ws_bytes": "ii",
+    "vis_logprobs_f32": "p" + "ii" + "p" + "i" + "p" + "i" + "ppp" + "l" + "i" + "p",
     "vis_gemm_decode_ksplit": "ii",
     "vis_gemm_decode_bf16": "pppp" + "iiiiiiii" + "p",
     "vis_gemm_decode_fp8_ksplit": "ii",
@@ -195,6 +197,7 @@ def load() -> ctypes.CDLL:
         fn.argtypes = [_CT[c] for c in sig]
     lib.vis_decode_chain_ws_bytes.restype = ctypes.c_longlong
     lib.vis_decode_proj_ws_bytes.restype = ctypes.c_longlong
+    lib.vis_logprobs_ws_bytes.restype = ctypes.c_longlong
     _lib = _Lib(lib)
     return _lib
 
@@ -1026,6 +1029,41 @@ def argmax(logits: torch.Tensor, ws_val: torch.Tensor, ws_idx: torch.Tensor, tok
                                _ptr(cur_token), _ptr(step), (1.0 / temperature) if temperature > 0 else 0.0,
                                seed & 0xFFFFFFFF, B, logits.stride(0) if logits.dim() == 2 else V, _stream())
     _check(rc, "vis_argmax_f32")
+
+
+LOGPROBS_MAX_K = 20     # top_ids / lp row widths of vis_logprobs_f32 (OpenAI's top_logprobs limit)
+
+
+def logprobs_ws(V: int, batch: int, device) -> torch.Tensor:
+    """Workspace of vis_logprobs_f32 for up to ``batch`` rows of V logits, [batch, n] f32 (row b's slice serves one row)."""
+    n = int(load().vis_logprobs_ws_bytes(V, batch))
+    if n <= 0:
+        raise HipLibraryError(f"logprobs_ws: unsupported V={V} batch={batch}")
+    return torch.empty((batch, n // 4 // batch), dtype=torch.float32, device=device)
+
+
+def logprobs(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, top_k: int, lp: torch.Tensor,
+             top_ids: torch.Tensor, ws: torch.Tensor) -> None:
+    """Log-probabilities of the token the pick just stored at tokens[b][step[b] - 1] and of the top_k largest logits.
+    logits [V] (tokens [T], step [1], lp [T, 21], top_ids [T, 20]) or [B, V] (tokens [B, T], step [B], lp [B, T, 21],
+    top_ids [B, T, 20]); ws from logprobs_ws (rows >= B).  Raw logits: the values do not depend on the temperature."""
+    if logits.dtype != torch.float32 or tokens.dtype != torch.int32 or step.dtype != torch.int32:
+        raise HipLibraryError("logprobs: f32 logits / int32 tokens and step required")
+    if lp.dtype != torch.float32 or top_ids.dtype != torch.int32 or ws.dtype != torch.float32:
+        raise HipLibraryError("logprobs: f32 lp / ws and int32 top_ids required")
+    B = logits.shape[0] if logits.dim() == 2 else 1
+    V = logits.shape[-1]
+    if step.numel() != B or tokens.numel() % B or not 0 <= top_k <= LOGPROBS_MAX_K:
+        raise HipLibraryError("logprobs: bad state shapes / top_k")
+    T = tokens.numel() // B
+    if lp.numel() != B * T * (LOGPROBS_MAX_K + 1) or top_ids.numel() != B * T * LOGPROBS_MAX_K:
+        raise HipLibraryError("logprobs: lp / top_ids must be [B, T, 21] / [B, T, 20]")
+    if logits.stride(-1) != 1 or not (tokens.is_contiguous() and step.is_contiguous() and lp.is_contiguous()
+                                      and top_ids.is_contiguous() and ws.is_contiguous()):
+        raise HipLibraryError("logprobs: bad strides")
+    rc = load().vis_logprobs_f32(_ptr(logits), V, logits.stride(0) if logits.dim() == 2 else V, _ptr(tokens), T, _ptr(step),
+                                 top_k, _ptr(lp), _ptr(top_ids), _ptr(ws), ws.numel() * 4, B, _stream())
+    _check(rc, "vis_logprobs_f32")
 
 
 DP_PLAIN, DP_SWIGLU, DP_RESID_NORMW = 0, 1, 2

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .logprobs import LogprobsBuffers, check_k
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
 
 
@@ -193,6 +194,10 @@ class MllamaEngine:
         self._decoded = 0
         self.has_image = False
         self.decode_limit = 0
+        # token log-probabilities (generate(..., logprobs=k)), as in Qwen2VLEngine: k while a request asks for them, else None
+        self.lp_k: Optional[int] = None
+        self._lp: Optional[LogprobsBuffers] = None
+        self.last_logprobs: Optional[list] = None
 
     # ------------------------------------------------------------------ preprocessing (geometry on host, pixels on GPU)
     def prepare_image(self, frame: torch.Tensor):
@@ -470,6 +475,7 @@ class MllamaEngine:
         step.fill_(S - 1)
         hip.argmax(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
                    cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot)
+        self._logprobs_after_pick(1, slot)
         self.slot_prompt_len[slot] = S
         if slot == 0:
             self.prompt_len, self._decoded = S, 0
@@ -603,6 +609,7 @@ class MllamaEngine:
             hip.argmax(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
                        self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
                        self.seed + 0x9E3779B9 * slot)
+            self._logprobs_after_pick(1, slot)
             self.slot_prompt_len[slot] = S
             if slot == 0:
                 self.has_image = True
@@ -649,14 +656,28 @@ class MllamaEngine:
         if chained:     # the pick's first stage rides in the lm_head epilogue
             hip.gemv_argmax(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                             norm_w=w.norm_w, eps=cfg.rms_eps, temperature=self.temperature, seed=self.seed)
+            self._logprobs_after_pick(1)
             return
         hip.gemv(x[0], w.lm_head, self.logits, norm_w=w.norm_w, eps=cfg.rms_eps)
         hip.argmax(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step, self.temperature,
                    self.seed)
+        self._logprobs_after_pick(1)
+
+    def _begin_logprobs(self, logprobs: Optional[int]) -> None:
+        """Switch the per-pick logprobs launch on (k alternatives) or off (None) for the request about to run."""
+        self.lp_k = check_k(logprobs)
+        self.last_logprobs = None
+        if self.lp_k is not None and self._lp is None:
+            self._lp = LogprobsBuffers(self.max_batch, self.tokens_b.shape[1], self.cfg.vocab, self.device)
+
+    def _logprobs_after_pick(self, B: int, slot: int = 0) -> None:
+        """vis_logprobs_f32 on the logits of slots slot .. slot + B - 1, right after their pick (nothing when off)."""
+        if self.lp_k is not None:
+            self._lp.launch(self.logits_b[slot:slot + B], self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], self.lp_k, slot)
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained)
+        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k)
         if key in self._graphs:
             return self._graphs[key]
         snap = (self.step.clone(), self.cur_token.clone())
@@ -768,6 +789,7 @@ class MllamaEngine:
         hip.decode_gemm(xn, w.lm_head, out=self.logits_b[:B])
         hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
+        self._logprobs_after_pick(B)
 
     def _decode_step_fused(self, B: int) -> None:
         """The batched step with every projection as ONE launch (r05, csrc/decode_stream.hip; see Qwen2VLEngine._decode_step_fused):
@@ -817,9 +839,10 @@ class MllamaEngine:
         hip.decode_proj(xw, w.lm_head, ws, hip.DP_PLAIN, out=self.logits_b[:B], ssq_in=s1_in, norm_dim=H, eps=eps)
         hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
+        self._logprobs_after_pick(B)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B)
+        key = (self.temperature, self.seed, B, self.lp_k)
         if key in self._graphs_b:
             return self._graphs_b[key]
         snap = (self.step_b.clone(), self.cur_b.clone())
@@ -840,29 +863,41 @@ class MllamaEngine:
 
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                       chunk: int = 16) -> list:
+                       chunk: int = 16, logprobs: Optional[int] = None) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
         decode, so the prompt pass of image 0 runs while images 1.. are still being decoded); one that raises gets no
-        slot and its exception takes its place in the returned list."""
+        slot and its exception takes its place in the returned list.  ``logprobs``: as in generate; ``last_logprobs`` then
+        holds one record per request (None for a failed one)."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
+        check_k(logprobs)
         lazy = any(callable(r) for r in requests)
         if lazy and n_req == 1:
             # one lazy request (always the case with max_batch == 1, where the batched buffers do not even exist): the
             # single-sequence path; its failure stays its own, as in the batched form
             try:
                 ids, fr = requests[0]() if callable(requests[0]) else requests[0]
-                return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph)]
+                return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph, logprobs=logprobs)]
             except Exception as e:      # noqa: BLE001
+                self.last_logprobs = [None] if logprobs is not None else None
                 return [e]
         if not lazy and (n_req == 1 or any(fr is None for _, fr in requests)):
             if n_req > 1:
                 raise ValueError("generate_batch needs an image in every request (text-only prompts go through generate)")
             ids, fr = requests[0]
-            return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph)]
+            return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph, logprobs=logprobs)]
+        self._begin_logprobs(logprobs)
+        try:
+            return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
+        finally:
+            self.lp_k = None
+
+    def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> list:
+        n_req = len(requests)
+        lazy = any(callable(r) for r in requests)
         slots: List[Optional[int]] = [None] * n_req
         errors: List[Optional[Exception]] = [None] * n_req
         B = 0
@@ -948,6 +983,8 @@ class MllamaEngine:
                 cur.wait_stream(st)
         ev[1].record()
         if B == 0:
+            if self.lp_k is not None:
+                self.last_logprobs = [None] * n_req
             return list(errors)
         longest = max(self.slot_prompt_len[s] for s in range(B))
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
@@ -976,6 +1013,9 @@ class MllamaEngine:
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
         if stop_on_eos:
             outs = [seq[:next((i + 1 for i, t in enumerate(seq) if t in eos), len(seq))] for seq in outs]
+        if self.lp_k is not None:
+            self.last_logprobs = [self._lp.record(slots[b], starts[slots[b]], len(outs[slots[b]]), self.lp_k)
+                                  if slots[b] is not None else None for b in range(n_req)]
         return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]
 
     def generated(self, n: int) -> List[int]:
@@ -986,7 +1026,11 @@ class MllamaEngine:
 
     def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                 chunk: int = 32) -> List[int]:
+                 chunk: int = 32, logprobs: Optional[int] = None) -> List[int]:
+        """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
+        logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
+        None = off, no extra launch."""
+        self._begin_logprobs(logprobs)
         try:
             return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
         except hip.ChainStalled as e:
@@ -997,6 +1041,8 @@ class MllamaEngine:
             self.chain_sync = None
             self._graphs.clear()
             return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
+        finally:
+            self.lp_k = None
 
     def _generate(self, input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time, as in Qwen2VLEngine
@@ -1018,7 +1064,7 @@ class MllamaEngine:
         self.last_timing = {"prompt_tokens": len(input_ids), "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": 1}
         if stop_on_eos:
-            for i, t in enumerate(toks):
-                if t in eos:
-                    return toks[:i + 1]
+            toks = toks[:next((i + 1 for i, t in enumerate(toks) if t in eos), len(toks))]
+        if self.lp_k is not None:
+            self.last_logprobs = [self._lp.record(0, self.prompt_len - 1, len(toks), self.lp_k)]
         return toks

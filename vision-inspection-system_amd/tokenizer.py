@@ -6,6 +6,10 @@ Two tokenizers behind one interface:
   * ``ByteTokenizer`` is a self-contained byte-level vocabulary (256 bytes + specials) for the tiny
     synthetic model and the benchmark, where no vocabulary file exists offline.
 
+Every tokenizer also gives ``token_bytes(id)``, the exact UTF-8 bytes that one token adds to the decoded text (empty for
+special tokens, which decoding skips), and ``token_text(id)``, those bytes as text (``errors="replace"``; a special token
+gives its literal) - the per-token fields of an OpenAI ``logprobs`` reply.
+
 ``build_chat_ids`` lays a ``messages`` list out the way the Qwen2-VL chat template does
 (``<|im_start|>role\\n ... <|im_end|>\\n``, images as ``<|vision_start|><|image_pad|>*n<|vision_end|>`` in content
 order, default system prompt when the conversation has none, generation prompt ``<|im_start|>assistant\\n``).
@@ -16,6 +20,46 @@ import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 DEFAULT_SYSTEM = "You are a helpful assistant."
+
+
+def _gpt2_byte_decoder() -> Dict[str, int]:
+    """Inverse of GPT-2's bytes_to_unicode: byte-level BPE vocabularies spell byte b as a printable character."""
+    bs = list(range(ord("!"), ord("~") + 1)) + list(range(ord("\xa1"), ord("\xac") + 1)) + list(range(ord("\xae"), ord("\xff") + 1))
+    cs = bs[:]
+    n = 0
+    for b in range(256):
+        if b not in bs:
+            bs.append(b)
+            cs.append(256 + n)
+            n += 1
+    return {chr(c): b for b, c in zip(bs, cs)}
+
+
+_BYTE_DECODER = _gpt2_byte_decoder()
+
+
+class _ByteLevelTokenBytes:
+    """token_bytes / token_text of a byte-level BPE ``tokenizers.Tokenizer`` (self._tok)."""
+
+    def _token_tables(self):
+        if getattr(self, "_added", None) is None:
+            self._added = {i: (t.content, bool(t.special)) for i, t in self._tok.get_added_tokens_decoder().items()}
+        return self._added
+
+    def token_bytes(self, token_id: int) -> bytes:
+        added = self._token_tables().get(int(token_id))
+        if added is not None:                       # special: skipped by decode; other added tokens decode verbatim
+            return b"" if added[1] else added[0].encode("utf-8")
+        s = self._tok.id_to_token(int(token_id))
+        if s is None:
+            return b""
+        return bytes(_BYTE_DECODER[c] for c in s if c in _BYTE_DECODER)
+
+    def token_text(self, token_id: int) -> str:
+        added = self._token_tables().get(int(token_id))
+        if added is not None and added[1]:
+            return added[0]
+        return self.token_bytes(token_id).decode("utf-8", errors="replace")
 
 
 class ByteTokenizer:
@@ -40,8 +84,18 @@ class ByteTokenizer:
     def decode(self, ids: Sequence[int]) -> str:
         return bytes(i for i in ids if 0 <= i < 256).decode("utf-8", errors="replace")
 
+    def token_bytes(self, token_id: int) -> bytes:
+        return bytes([token_id]) if 0 <= token_id < 256 else b""
 
-class HFTokenizer:
+    def token_text(self, token_id: int) -> str:
+        names = {self.im_start_id: "<|im_start|>", self.image_token_id: "<|image_pad|>",
+                 self.vision_start_id: "<|vision_start|>", self.vision_end_id: "<|vision_end|>", self.im_end_id: "<|im_end|>"}
+        if token_id in names:
+            return names[token_id]
+        return self.token_bytes(token_id).decode("utf-8", errors="replace")
+
+
+class HFTokenizer(_ByteLevelTokenBytes):
     def __init__(self, model_dir: str, image_token_id: int, vision_start_id: int, vision_end_id: int,
                  eos_ids: Sequence[int]):
         from tokenizers import Tokenizer
@@ -130,8 +184,18 @@ class LlamaByteTokenizer:
     def decode(self, ids: Sequence[int]) -> str:
         return bytes(i for i in ids if 0 <= i < 256).decode("utf-8", errors="replace")
 
+    def token_bytes(self, token_id: int) -> bytes:
+        return bytes([token_id]) if 0 <= token_id < 256 else b""
 
-class LlamaHFTokenizer:
+    def token_text(self, token_id: int) -> str:
+        names = {self.bos_id: "<|begin_of_text|>", self.start_header_id: "<|start_header_id|>",
+                 self.end_header_id: "<|end_header_id|>", self.eot_id: "<|eot_id|>", self.image_token_id: "<|image|>"}
+        if token_id in names:
+            return names[token_id]
+        return self.token_bytes(token_id).decode("utf-8", errors="replace")
+
+
+class LlamaHFTokenizer(_ByteLevelTokenBytes):
     def __init__(self, model_dir: str, image_token_id: int, eos_ids: Sequence[int]):
         from tokenizers import Tokenizer
         path = os.path.join(model_dir, "tokenizer.json")
