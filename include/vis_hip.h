@@ -232,6 +232,33 @@ long long vis_logprobs_ws_bytes(int V, int batch);
 int vis_logprobs_f32(const void* logits, int V, int ld_logits, const void* tokens, int max_tokens, const void* step_ptr,
                      int top_k, void* lp, void* top_ids, void* ws, long long ws_bytes, int batch, vis_stream_t stream);
 
+/* JSON mode (csrc/json_mask.hip; the grammar is json_grammar.py's, byte for byte): RFC 8259 text whose top-level value is
+ * an object, strictly valid UTF-8, at most 32 open containers and 16 consecutive whitespace bytes.  Run before every pick of
+ * a JSON-mode sequence.  For sequence b < batch: state + b * 32 int32 (two slots of 12 words, chosen by the parity of
+ * step_ptr[b], and two counters; all zero = a fresh sequence), tokens + b * max_tokens.  The launch folds the tokens
+ * picked since the state was last advanced (positions pos .. step_ptr[b] - 1 below max_tokens; none on the first launch
+ * after a reset) into the state, then writes allow[b * ld_allow + w] (u64, bit i = token 64 w + i allowed; bits >= V clear).
+ * A token is allowed when the grammar accepts all of its bytes (tok_bytes[tok_off[t] .. tok_off[t + 1]), int32 tok_off
+ * [V + 1], tok_bytes 4-byte aligned with 4 bytes of padding); tokens without bytes never are; tokens whose tok_flags bit 0
+ * is set (EOS) only after the top-level '}'.  Flag bit 1 marks printable ASCII tokens without '"' and '\' (accepted whole
+ * inside a string).  A row with no allowed token gets its EOS ids (eos_ids[n_eos]) and the error bit of its state.
+ * VIS_ERR_ARG: null pointer, V outside 1..262144, max_tokens <= 0, n_eos outside 1..64, batch outside 1..64,
+ * ld_allow < ceil(V / 64), misaligned allow / tok_bytes / state. */
+int vis_json_mask(void* state, const void* tokens, int max_tokens, const void* step_ptr, const void* tok_off,
+                  const void* tok_bytes, const void* tok_flags, const void* eos_ids, int n_eos, int V, void* allow,
+                  int ld_allow, int batch, vis_stream_t stream);
+/* vis_argmax_f32 over the allowed ids only: sequence b skips id i unless bit i of allow + b * ld_allow is set.  The
+ * comparison (ties to the lower index) and the Gumbel noise are vis_argmax_f32's, so with every bit set the pick is the
+ * same bit for bit, and at temperature > 0 it samples the renormalised distribution over the allowed ids.  A row with no
+ * allowed id picks id 0.  VIS_ERR_ARG additionally: null allow, ld_allow < ceil(V / 64), allow not 8-byte aligned. */
+int vis_argmax_masked_f32(const void* logits, int V, void* ws_val, void* ws_idx, void* tokens, int max_tokens,
+                          void* cur_token, void* step_ptr, float inv_temp, unsigned seed, int batch, int ld_logits,
+                          const void* allow, int ld_allow, vis_stream_t stream);
+/* vis_gemv_bf16_argmax with the pick restricted to the ids allowed by allow[ceil(N / 64)] (every logit is still written). */
+int vis_gemv_bf16_argmax_masked(const void* x, const void* W, const void* norm_w, void* logits, int N, int K, int ldw,
+                                float eps, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
+                                void* step_ptr, float inv_temp, unsigned seed, const void* allow, vis_stream_t stream);
+
 /* K10 (batched decode), first half.  For up to 64 in-flight sequences the weight matrix is streamed from HBM
  * ONCE per step by <= 256 persistent workgroups (one per CU, 7-stage LDS-DMA ring, stream-K cut of the
  * (128-column tile, K-step) sequence).  part[slot][R][N] (f32), R = 16 / 32 / 64 for B <= 16 / 32 / 64 (one, two or four

@@ -11,6 +11,7 @@ reference's own remote client, so the same agent code serves both backends.
 from __future__ import annotations
 
 import logging
+import os
 import time
 from pathlib import Path
 from typing import Any, Dict, Optional
@@ -21,6 +22,12 @@ from .image_processing import direct_frames_enabled, encode_image_optimized, fra
 from .prompts import AUDITOR_PROMPT, INSPECTOR_PROMPT
 from .response_parsing import parse_json_robust, validate_and_fix_result
 from .schemas import InspectionContext, VLMAnalysisResult
+
+
+def json_mode_kwargs() -> dict:
+    """VIS_JSON_MODE=1 (default 0): the analysis requests ask for response_format={"type": "json_object"} - the engine then
+    only generates JSON objects (json_grammar).  The health check's one-word ping never does.  Off: the calls are as before."""
+    return {"response_format": {"type": "json_object"}} if os.environ.get("VIS_JSON_MODE", "0") == "1" else {}
 
 
 def _logger(name: str) -> logging.Logger:
@@ -48,7 +55,8 @@ class _BaseAgent:
         for attempt in range(max_retries):
             try:
                 completion = self.client.chat.completions.create(
-                    model=self.model_id, messages=messages, temperature=self.temperature, max_tokens=self.max_tokens)
+                    model=self.model_id, messages=messages, temperature=self.temperature, max_tokens=self.max_tokens,
+                    **json_mode_kwargs())
                 return completion.choices[0].message.content
             except Exception as e:
                 text = str(e)
@@ -286,12 +294,14 @@ def _many(agent, image_paths, contexts, prepared=None) -> list:
     if todo:
         try:
             if hasattr(agent.client, "complete_many"):
-                replies = agent.client.complete_many(agent.model_id, msgs, agent.temperature, agent.max_tokens)
+                replies = agent.client.complete_many(agent.model_id, msgs, agent.temperature, agent.max_tokens,
+                                                     **json_mode_kwargs())
                 texts = [r if isinstance(r, Exception) else r.choices[0].message.content for r in replies]
             else:
                 texts = [agent.client.chat.completions.create(model=agent.model_id, messages=m,
                                                               temperature=agent.temperature,
-                                                              max_tokens=agent.max_tokens).choices[0].message.content
+                                                              max_tokens=agent.max_tokens,
+                                                              **json_mode_kwargs()).choices[0].message.content
                          for m in msgs]
         except Exception as e:
             agent.logger.error(f"{agent.nickname}: batched call failed: {e}", exc_info=True)

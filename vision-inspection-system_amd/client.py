@@ -75,9 +75,9 @@ class _Completions:
 
     def create(self, model: Optional[str] = None, messages: Optional[list] = None,
                temperature: Optional[float] = None, max_tokens: Optional[int] = None, logprobs: bool = False,
-               top_logprobs: Optional[int] = None, **kwargs) -> ChatCompletion:
+               top_logprobs: Optional[int] = None, response_format: Optional[dict] = None, **kwargs) -> ChatCompletion:
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
-                                     top_logprobs=top_logprobs, **kwargs)
+                                     top_logprobs=top_logprobs, response_format=response_format, **kwargs)
 
 
 class _Chat:
@@ -101,6 +101,10 @@ class LoadedModel:
     cfg: Any
     model_id: str
     family: str = "qwen2_vl"      # or "mllama" (row f2: the Auditor's Llama-3.2-11B-Vision fallback)
+
+    def __post_init__(self):
+        if hasattr(self.engine, "tokenizer") and self.engine.tokenizer is None:
+            self.engine.tokenizer = self.tokenizer      # JSON mode builds its token table from the vocabulary's bytes
 
 
 def resolve_model_dir(model_id: str) -> Optional[str]:
@@ -241,6 +245,21 @@ def logprobs_k(logprobs, top_logprobs) -> Optional[int]:
     return int(top_logprobs or 0)
 
 
+def json_mode_of(response_format) -> bool:
+    """OpenAI's response_format -> JSON mode on / off: None or {"type": "text"} = off, {"type": "json_object"} = on
+    (json_grammar: the reply is a JSON object).  Anything else raises ValueError; checked before any model is loaded, and
+    the message avoids the substrings the reference's retry logic keys on."""
+    if response_format is None:
+        return False
+    kind = response_format.get("type") if isinstance(response_format, dict) else None
+    if kind == "text":
+        return False
+    if kind == "json_object":
+        return True
+    raise ValueError("response_format: only {'type': 'text'} and {'type': 'json_object'} are supported "
+                     "(json_schema and other grammars are not)")
+
+
 def _choice_logprobs(tok, toks: List[int], rec) -> ChoiceLogprobs:
     """An engine's TokenLogprobs record of one request -> choice.logprobs (one entry per completion token)."""
     def entry(cls, t, lp, **kw):
@@ -346,12 +365,13 @@ class LocalVLMClient:
         counts = [(th // cfg.patch) * (tw // cfg.patch) // cfg.merge ** 2 for _, (th, tw) in frames]
         return build_chat_ids(lm.tokenizer, messages, counts), frames
 
-    def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None,
+    def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
                   **kwargs) -> ChatCompletion:
-        return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs)[0]
+        return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
+                                  response_format=response_format)[0]
 
     def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
-                      top_logprobs: Optional[int] = None) -> List[ChatCompletion]:
+                      top_logprobs: Optional[int] = None, response_format: Optional[dict] = None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -359,9 +379,14 @@ class LocalVLMClient:
         ``logprobs`` / ``top_logprobs`` (OpenAI's): every choice gets ``logprobs.content``, one entry per completion token -
         the log-softmax of the model's raw logits (independent of temperature and seed) and the ``top_logprobs`` most
         likely alternatives.  With VIS_SYNTHETIC_REPLY (synthetic models) they describe the generated tokens, not the
-        substituted text."""
+        substituted text.
+        ``response_format`` (OpenAI's): {"type": "json_object"} restricts every generated token to the ones that continue a
+        JSON object (RFC 8259, strict UTF-8; the engines' json_mode): a reply that ended on EOS parses with json.loads, one cut
+        by max_tokens is a prefix of a JSON object; a request the vocabulary could not continue fails with JsonModeError.
+        None or {"type": "text"}: unchanged.  Logprobs keep their meaning: top_logprobs may list tokens the mask forbade."""
         import torch
         k = logprobs_k(logprobs, top_logprobs)
+        jm = json_mode_of(response_format)
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
@@ -371,7 +396,7 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         out: List[ChatCompletion] = []
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -407,7 +432,7 @@ class LocalVLMClient:
                 idx = range(i, min(len(futs), i + eng.max_batch))
                 toks = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp, seed=self.seed,
                                           ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1",
-                                          **({"logprobs": k} if k is not None else {}))
+                                          **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}))
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", {}))
                 if timing:
@@ -449,7 +474,7 @@ class LocalVLMClient:
         return build_llama_chat_ids(lm.tokenizer, messages, len(frames)), (frames[0] if frames else None)
 
     def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
-                              k: Optional[int] = None) -> List[ChatCompletion]:
+                              k: Optional[int] = None, jm: bool = False) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -459,6 +484,8 @@ class LocalVLMClient:
         from . import ingest
         ignore_eos = os.environ.get("VIS_IGNORE_EOS") == "1"
         lpk = {"logprobs": k} if k is not None else {}
+        if jm:
+            lpk["json_mode"] = True
 
         def completion(n_ids, t, rec=None):
             lp = _choice_logprobs(tok, t, rec) if rec is not None else None
@@ -531,8 +558,9 @@ class CannedResponseClient:
         self.calls: List[dict] = []
         self.chat = _Chat(self)
 
-    def _complete(self, model, messages, temperature, max_tokens, **kwargs) -> ChatCompletion:
-        self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens})
+    def _complete(self, model, messages, temperature, max_tokens, response_format=None, **kwargs) -> ChatCompletion:
+        self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
+                           "response_format": response_format})
         reply = self.reply(messages) if callable(self.reply) else self.reply
         return ChatCompletion([_Choice(_Message(reply))], model=model or "")
 

@@ -21,8 +21,10 @@
 // AMAX (lm_head of the single-sequence step): the greedy / Gumbel-max pick's first stage rides in the epilogue - every
 // workgroup leaves the (value, first index) maximum of ITS rows in amax_val / amax_idx[blockIdx.x] (argmax_stage1_kernel's
 // comparison, so the pick is the one the two-stage form makes), saving a launch per token.
-template <int NB, bool AMAX = false>
-__global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) {
+// MASK (vis_gemv_bf16_argmax_masked, AMAX only): rows whose bit in allow[] (bit i of word i / 64) is clear take no part in
+// the pick.  The mask is an argument of its own, so GemvArgs - and the kernels that do not mask - stay as they were.
+template <int NB, bool AMAX, bool MASK>
+__device__ __forceinline__ void gemv_bf16_body(GemvArgs p, const unsigned long long* __restrict__ allow) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* xs = (bf16_t*)smem;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -62,8 +64,14 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) {
       v0 = v0 * p.am_inv_temp + gumbel_noise(p.am_seed, am_step, (unsigned)o);
       v1 = v1 * p.am_inv_temp + gumbel_noise(p.am_seed, am_step, (unsigned)(o + 1));
     }
-    if (v0 > best || (v0 == best && o < bi)) { best = v0; bi = o; }
-    if (o + 1 < p.N && (v1 > best || (v1 == best && o + 1 < bi))) { best = v1; bi = o + 1; }
+    bool ok0 = true, ok1 = true;
+    if constexpr (MASK) {           // o is even: both rows' bits sit in one word
+      const unsigned long long m = allow[o >> 6];
+      ok0 = (m >> (o & 63)) & 1ull;
+      ok1 = (m >> ((o + 1) & 63)) & 1ull;
+    }
+    if (ok0 && (v0 > best || (v0 == best && o < bi))) { best = v0; bi = o; }
+    if (ok1 && o + 1 < p.N && (v1 > best || (v1 == best && o + 1 < bi))) { best = v1; bi = o + 1; }
   };
   int pair = p_begin, seg = 0;  // task being consumed
   for (int t = 0; t < n_tasks; t += 2) {
@@ -105,6 +113,13 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) {
       p.am_idx[blockIdx.x] = bi;
     }
   }
+}
+
+template <int NB, bool AMAX = false>
+__global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) { gemv_bf16_body<NB, AMAX, false>(p, nullptr); }
+
+__global__ __launch_bounds__(256) void gemv_bf16_argmax_masked_kernel(GemvArgs p, const unsigned long long* allow) {
+  gemv_bf16_body<1, true, true>(p, allow);
 }
 
 // LDS of a multi-row launch: nb rows of K bf16 (the attribute is raised once per kernel instance)
@@ -926,10 +941,13 @@ extern "C" int vis_decode_cross_attn_batch(const void* q, const void* q_norm_w, 
 // writes tokens[*step] = argmax, cur_token = argmax and then *step += 1.
 // temperature sampling = Gumbel-max: argmax(logit/T + g_i), g_i = -log(-log(u_i)), u_i from a counter hash of
 // (seed, step, i).  Exact categorical sampling, no softmax pass, no host round trip, graph-replayable.
-__global__ __launch_bounds__(256) void argmax_stage1_kernel(const float* __restrict__ logits, int V,
-                                                            float* __restrict__ bval, int* __restrict__ bidx,
-                                                            float inv_temp, unsigned seed,
-                                                            const int* __restrict__ step_ptr, int ld_logits) {
+// MASK (vis_argmax_masked_f32): sequence seq's ids whose bit in allow[seq * ld_allow + i / 64] is clear are skipped; the
+// allowed ones see exactly the comparisons and the noise of the unmasked pick.
+template <bool MASK>
+__device__ __forceinline__ void argmax_stage1_body(const float* __restrict__ logits, int V, float* __restrict__ bval,
+                                                   int* __restrict__ bidx, float inv_temp, unsigned seed,
+                                                   const int* __restrict__ step_ptr, int ld_logits,
+                                                   const unsigned long long* __restrict__ allow, int ld_allow) {
   const int tid = threadIdx.x, seq = blockIdx.y;
   logits += (size_t)seq * ld_logits;
   bval += seq * 256;
@@ -939,6 +957,9 @@ __global__ __launch_bounds__(256) void argmax_stage1_kernel(const float* __restr
   int bi = 0x7fffffff;
   const unsigned step = (unsigned)step_ptr[seq];
   for (int i = blockIdx.x * 256 + tid; i < V; i += gridDim.x * 256) {
+    if constexpr (MASK) {
+      if (!((allow[(size_t)seq * ld_allow + (i >> 6)] >> (i & 63)) & 1ull)) continue;
+    }
     float v = logits[i];
     if (inv_temp > 0.f) v = v * inv_temp + gumbel_noise(seed, step, (unsigned)i);
     if (v > best || (v == best && i < bi)) { best = v; bi = i; }
@@ -961,10 +982,28 @@ __global__ __launch_bounds__(256) void argmax_stage1_kernel(const float* __restr
   }
 }
 
-__global__ __launch_bounds__(64) void argmax_stage2_kernel(const float* __restrict__ bval,
-                                                           const int* __restrict__ bidx, int nb,
-                                                           int* __restrict__ tokens, int max_tokens,
-                                                           int* __restrict__ cur_token, int* __restrict__ step_ptr) {
+__global__ __launch_bounds__(256) void argmax_stage1_kernel(const float* __restrict__ logits, int V,
+                                                            float* __restrict__ bval, int* __restrict__ bidx,
+                                                            float inv_temp, unsigned seed,
+                                                            const int* __restrict__ step_ptr, int ld_logits) {
+  argmax_stage1_body<false>(logits, V, bval, bidx, inv_temp, seed, step_ptr, ld_logits, nullptr, 0);
+}
+
+__global__ __launch_bounds__(256) void argmax_stage1_masked_kernel(const float* __restrict__ logits, int V,
+                                                                   float* __restrict__ bval, int* __restrict__ bidx,
+                                                                   float inv_temp, unsigned seed,
+                                                                   const int* __restrict__ step_ptr, int ld_logits,
+                                                                   const unsigned long long* __restrict__ allow,
+                                                                   int ld_allow) {
+  argmax_stage1_body<true>(logits, V, bval, bidx, inv_temp, seed, step_ptr, ld_logits, allow, ld_allow);
+}
+
+// MASK: a row with no allowed id at all (a caller's empty mask; vis_json_mask never leaves one) stores id 0 rather than
+// the sentinel, so the next step's embedding gather stays inside the table.
+template <bool MASK>
+__device__ __forceinline__ void argmax_stage2_body(const float* __restrict__ bval, const int* __restrict__ bidx, int nb,
+                                                   int* __restrict__ tokens, int max_tokens, int* __restrict__ cur_token,
+                                                   int* __restrict__ step_ptr) {
   const int lane = threadIdx.x, seq = blockIdx.x;
   bval += seq * 256;
   bidx += seq * 256;
@@ -985,11 +1024,26 @@ __global__ __launch_bounds__(64) void argmax_stage2_kernel(const float* __restri
     if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
   }
   if (lane == 0) {
+    if (MASK && bi == 0x7fffffff) bi = 0;
     const int st = *step_ptr;
     if (st < max_tokens) tokens[st] = bi;
     *cur_token = bi;
     *step_ptr = st + 1;
   }
+}
+
+__global__ __launch_bounds__(64) void argmax_stage2_kernel(const float* __restrict__ bval,
+                                                           const int* __restrict__ bidx, int nb,
+                                                           int* __restrict__ tokens, int max_tokens,
+                                                           int* __restrict__ cur_token, int* __restrict__ step_ptr) {
+  argmax_stage2_body<false>(bval, bidx, nb, tokens, max_tokens, cur_token, step_ptr);
+}
+
+__global__ __launch_bounds__(64) void argmax_stage2_masked_kernel(const float* __restrict__ bval,
+                                                                  const int* __restrict__ bidx, int nb,
+                                                                  int* __restrict__ tokens, int max_tokens,
+                                                                  int* __restrict__ cur_token, int* __restrict__ step_ptr) {
+  argmax_stage2_body<true>(bval, bidx, nb, tokens, max_tokens, cur_token, step_ptr);
 }
 
 extern "C" int vis_argmax_f32(const void* logits, int V, void* ws_val, void* ws_idx, void* tokens, int max_tokens,
@@ -1006,11 +1060,30 @@ extern "C" int vis_argmax_f32(const void* logits, int V, void* ws_val, void* ws_
   return vis_check_launch();
 }
 
+// The same pick over the allowed ids only (vis_json_mask's bitmask rows).  With every bit set it is vis_argmax_f32 bit for
+// bit; at temperature > 0 the Gumbel-max over the allowed set samples the renormalised constrained distribution.
+extern "C" int vis_argmax_masked_f32(const void* logits, int V, void* ws_val, void* ws_idx, void* tokens, int max_tokens,
+                                     void* cur_token, void* step_ptr, float inv_temp, unsigned seed, int batch,
+                                     int ld_logits, const void* allow, int ld_allow, hipStream_t stream) {
+  if (!logits || V <= 0 || !ws_val || !ws_idx || !tokens || !cur_token || !step_ptr || !allow) return VIS_ERR_ARG;
+  if (!(inv_temp >= 0.f) || batch <= 0 || batch > 64 || (batch > 1 && ld_logits < V)) return VIS_ERR_ARG;
+  if (ld_allow < (V + 63) / 64 || (((uintptr_t)allow) & 7)) return VIS_ERR_ARG;
+  const int nb = min(256, (V + 255) / 256);
+  vis_clear_error();
+  hipLaunchKernelGGL(argmax_stage1_masked_kernel, dim3(nb, batch), dim3(256), 0, stream, (const float*)logits, V,
+                     (float*)ws_val, (int*)ws_idx, inv_temp, seed, (const int*)step_ptr, ld_logits,
+                     (const unsigned long long*)allow, ld_allow);
+  hipLaunchKernelGGL(argmax_stage2_masked_kernel, dim3(batch), dim3(64), 0, stream, (const float*)ws_val,
+                     (const int*)ws_idx, nb, (int*)tokens, max_tokens, (int*)cur_token, (int*)step_ptr);
+  return vis_check_launch();
+}
+
 // argmax_stage2_kernel for up to 2048 per-workgroup maxima (vis_gemv_bf16_argmax): 256 threads, every thread's eight
 // entries requested at once (the 64-thread form walks them in 32 dependent round trips: 11.5 us per token in the r04 trace)
-__global__ __launch_bounds__(256) void argmax_merge_kernel(const float* __restrict__ bval, const int* __restrict__ bidx, int nb,
-                                                           int* __restrict__ tokens, int max_tokens,
-                                                           int* __restrict__ cur_token, int* __restrict__ step_ptr) {
+template <bool MASK>
+__device__ __forceinline__ void argmax_merge_body(const float* __restrict__ bval, const int* __restrict__ bidx, int nb,
+                                                  int* __restrict__ tokens, int max_tokens, int* __restrict__ cur_token,
+                                                  int* __restrict__ step_ptr) {
   const int tid = threadIdx.x;
   float v[8];
   int ix[8];
@@ -1038,11 +1111,24 @@ __global__ __launch_bounds__(256) void argmax_merge_kernel(const float* __restri
   if (tid == 0) {
     for (int w = 1; w < 4; ++w)
       if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    if (MASK && bi == 0x7fffffff) bi = 0;
     const int st = *step_ptr;
     if (st < max_tokens) tokens[st] = bi;
     *cur_token = bi;
     *step_ptr = st + 1;
   }
+}
+
+__global__ __launch_bounds__(256) void argmax_merge_kernel(const float* __restrict__ bval, const int* __restrict__ bidx, int nb,
+                                                           int* __restrict__ tokens, int max_tokens,
+                                                           int* __restrict__ cur_token, int* __restrict__ step_ptr) {
+  argmax_merge_body<false>(bval, bidx, nb, tokens, max_tokens, cur_token, step_ptr);
+}
+
+__global__ __launch_bounds__(256) void argmax_merge_masked_kernel(const float* __restrict__ bval, const int* __restrict__ bidx,
+                                                                  int nb, int* __restrict__ tokens, int max_tokens,
+                                                                  int* __restrict__ cur_token, int* __restrict__ step_ptr) {
+  argmax_merge_body<true>(bval, bidx, nb, tokens, max_tokens, cur_token, step_ptr);
 }
 
 // K10 + K12 of the single-sequence step in two launches instead of three: logits = W rmsnorm(x) (f32, all N written, as
@@ -1070,5 +1156,33 @@ extern "C" int vis_gemv_bf16_argmax(const void* x, const void* W, const void* no
   hipLaunchKernelGGL((gemv_bf16_kernel<1, true>), dim3(blocks), dim3(256), (size_t)K * 2, stream, p);
   hipLaunchKernelGGL(argmax_merge_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx, blocks,
                      (int*)tokens, max_tokens, (int*)cur_token, (int*)step_ptr);
+  return vis_check_launch();
+}
+
+// vis_gemv_bf16_argmax with the allowed-token bitmask allow[ceil(N / 64)] (vis_json_mask's row): rows whose bit is clear
+// take no part in the pick; every logit is still written.  With every bit set the pick is vis_gemv_bf16_argmax's.
+extern "C" int vis_gemv_bf16_argmax_masked(const void* x, const void* W, const void* norm_w, void* logits, int N, int K,
+                                           int ldw, float eps, void* ws_val, void* ws_idx, void* tokens, int max_tokens,
+                                           void* cur_token, void* step_ptr, float inv_temp, unsigned seed,
+                                           const void* allow, hipStream_t stream) {
+  if (!x || !W || !logits || !ws_val || !ws_idx || !tokens || !cur_token || !step_ptr || !allow || N <= 0 || K <= 0)
+    return VIS_ERR_ARG;
+  if (K % 8 != 0 || ldw % 8 != 0 || K * 2 > 60 * 1024 || !(inv_temp >= 0.f)) return VIS_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)W | (uintptr_t)norm_w) & 15 || (((uintptr_t)allow) & 7)) return VIS_ERR_ARG;
+  GemvArgs p;
+  p.x = (const bf16_t*)x; p.W = (const bf16_t*)W; p.bias = nullptr; p.R = nullptr; p.norm_w = (const bf16_t*)norm_w;
+  p.y = logits; p.N = N; p.K = K; p.ldw = ldw; p.act = GV_ACT_NONE; p.out_f32 = 1; p.eps = eps; p.outs_per_block = 0;
+  p.nb = 1; p.ldx = 0; p.ldy = 0; p.ldr = 0;
+  p.am_val = (float*)ws_val; p.am_idx = (int*)ws_idx; p.am_step = (const int*)step_ptr; p.am_inv_temp = inv_temp;
+  p.am_seed = seed;
+  const int n_pairs = (N + 1) / 2;
+  int blocks = (n_pairs + 3) / 4;                     // the grid rule of gemv_bf16_launch
+  if (blocks > 1024) blocks = 1024 + (blocks - 1024) / 8;
+  if (blocks > 2048) blocks = 2048;
+  vis_clear_error();
+  hipLaunchKernelGGL(gemv_bf16_argmax_masked_kernel, dim3(blocks), dim3(256), (size_t)K * 2, stream, p,
+                     (const unsigned long long*)allow);
+  hipLaunchKernelGGL(argmax_merge_masked_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx,
+                     blocks, (int*)tokens, max_tokens, (int*)cur_token, (int*)step_ptr);
   return vis_check_launch();
 }

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .json_mode import JsonBuffers, JsonModeError, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
@@ -324,6 +325,11 @@ class Qwen2VLEngine:
         self.lp_k: Optional[int] = None
         self._lp: Optional[LogprobsBuffers] = None
         self.last_logprobs: Optional[list] = None
+        # JSON mode (generate(..., json_mode=True)): on while a request asks for it; token table and state on first use.
+        # tokenizer: the vocabulary's token_bytes (the client sets it when it loads the model)
+        self.json_on = False
+        self._json: Optional[JsonBuffers] = None
+        self.tokenizer = None
 
     # ------------------------------------------------------------------ vision tower
     def vision_forward(self, frames: Sequence[torch.Tensor], split_rows: bool = True) -> torch.Tensor:
@@ -657,8 +663,10 @@ class Qwen2VLEngine:
         if taps is not None:
             taps["first_logits"] = logits.clone()
         step.fill_(S - 1)
-        hip.argmax(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
-                   cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot)   # per-slot workspace: prefills
+        if self.json_on:
+            self._json.reset(slot)
+        self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
+                   cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot, slot)   # per-slot workspace: prefills
         # of different slots may run concurrently on different streams
         self._logprobs_after_pick(1, slot)
         self.slot_prompt_len[slot] = S
@@ -835,9 +843,11 @@ class Qwen2VLEngine:
             else:
                 hip.gemv(x[(j + 1) * n - 1], w.lm_head, logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
             self.step_b[slot:slot + 1].fill_(S - 1)
-            hip.argmax(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
+            if self.json_on:
+                self._json.reset(slot)
+            self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
                        self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
-                       self.seed + 0x9E3779B9 * slot)
+                       self.seed + 0x9E3779B9 * slot, slot)
             self._logprobs_after_pick(1, slot)
             self.slot_prompt_len[slot] = S
             if slot == 0:
@@ -1071,6 +1081,31 @@ class Qwen2VLEngine:
         if self.lp_k is not None:
             self._lp.launch(self.logits_b[slot:slot + B], self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], self.lp_k, slot)
 
+    # ------------------------------------------------------------------ JSON mode
+    def _begin_json(self, json_mode: bool) -> None:
+        """Switch the grammar mask of every pick on or off for the request about to run."""
+        if not isinstance(json_mode, bool):
+            raise ValueError("json_mode must be True or False")
+        if json_mode and self._json is None:
+            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device)
+        self.json_on = json_mode
+
+    def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
+        """The next-token pick of slots slot .. slot + B - 1: vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick."""
+        if not self.json_on:
+            hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
+            return
+        allow = self._json.mask(tokens, step, slot)
+        hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
+
+    def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
+        """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode."""
+        if not self.json_on:
+            hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
+            return
+        allow = self._json.mask(tokens, step, 0)
+        hip.gemv_argmax_masked(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, allow[0], **kw)
+
     # ------------------------------------------------------------------ decode
     def _decode_step(self, chained: Optional[bool] = None) -> None:
         cfg, w = self.cfg, self.w
@@ -1092,7 +1127,7 @@ class Qwen2VLEngine:
                 hip.gemv_fp8(x2[0], *q["gateup_w"], self.d_act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=cfg.rms_eps)
                 hip.gemv_fp8(self.d_act, *q["down_w"], x[0], residual=x2[0])
             hip.gemv_fp8(x[0], *self.q8_lm_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
-            hip.argmax(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
+            self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                        self.temperature, self.seed)
             self._logprobs_after_pick(1)
             return
@@ -1119,12 +1154,12 @@ class Qwen2VLEngine:
             hip.gemv(x2[0], lw.gateup_w, self.d_act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=cfg.rms_eps)
             hip.gemv(self.d_act, lw.down_w, x[0], residual=x2[0])
         if chained:     # the pick's first stage rides in the lm_head epilogue
-            hip.gemv_argmax(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
+            self._gemv_pick(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                             norm_w=w.final_norm_w, eps=cfg.rms_eps, temperature=self.temperature, seed=self.seed)
             self._logprobs_after_pick(1)
             return
         hip.gemv(x[0], w.lm_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
-        hip.argmax(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
+        self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                    self.temperature, self.seed)
         self._logprobs_after_pick(1)
 
@@ -1174,7 +1209,7 @@ class Qwen2VLEngine:
             next_norm = w.llm[li + 1].ln1_w if li + 1 < n_layers else w.final_norm_w
             hip.skinny_finalize(part, ks, x, cfg.hidden, residual=x2, norm_w=next_norm, yn=xn, eps=eps)
         hip.decode_gemm(xn, w.lm_head, out=self.logits_b[:B])
-        hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
+        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
 
@@ -1244,7 +1279,7 @@ class Qwen2VLEngine:
         else:
             hip.decode_proj(xw, w.lm_head, ws, hip.DP_PLAIN, out=self.logits_b[:B], ssq_in=s1_in, norm_dim=H, eps=eps)
         if not projections_only:
-            hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
+            self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                        self.temperature, self.seed)
             self._logprobs_after_pick(B)
         return 4 * n_layers + 1
@@ -1278,7 +1313,7 @@ class Qwen2VLEngine:
             proj(x2, pick("gateup_w"), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
             proj(act, pick("down_w"), x, residual=x2)
         proj(x, self.q8_lm_head if fp8 else w.lm_head, self.logits_b[:B], norm_w=w.final_norm_w, eps=eps)
-        hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
+        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
 
@@ -1322,13 +1357,14 @@ class Qwen2VLEngine:
             hip.skinny_finalize_fp8(part, ks, x, cfg.hidden, sx=saq, sw=dw[1], residual=x2, norm_w=next_norm, yn=xn,
                                     yq=xq, yq_scale=sxq, eps=eps)
         hip.decode_gemm_fp8(xq, sxq, *self.q8_lm_head, out=self.logits_b[:B])
-        hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
+        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
 
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
-        # sampling parameters, the batch size and the logprobs k are kernel arguments baked into the graph
-        key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch, self.lp_k)
+        # sampling parameters, the batch size, the logprobs k and JSON mode are kernel arguments baked into the graph
+        key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch, self.lp_k,
+               self.json_on)
         if key in self._graphs:
             return self._graphs[key]
         step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
@@ -1444,13 +1480,18 @@ class Qwen2VLEngine:
 
     def generate(self, input_ids: Sequence[int], frames: Sequence[torch.Tensor] = (), max_new_tokens: int = 128,
                  ignore_eos: bool = False, use_graph: bool = True, check_every: int = 16,
-                 temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None) -> List[int]:
+                 temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
+                 json_mode: bool = False) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
         (log-softmax of the raw logits - independent of temperature and seed - for every returned token, plus its k most
-        likely alternatives); None = off, no extra launch."""
+        likely alternatives); None = off, no extra launch.  ``json_mode``: every pick is restricted to the tokens that
+        continue a JSON object (json_grammar; needs ``self.tokenizer``): the reply is a prefix of one, complete when it
+        ended on EOS; JsonModeError when the vocabulary could not continue it.  Logprobs keep their meaning (raw logits),
+        so top_logprobs may list tokens the mask forbade."""
         self._begin_logprobs(logprobs)
+        self._begin_json(json_mode)
         room = self.max_ctx - len(input_ids) - 1
         if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
             self._warned_clamp = True          # said once per engine: the reply may end before the model is done
@@ -1473,6 +1514,7 @@ class Qwen2VLEngine:
             return self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
         finally:
             self.lp_k = None
+            self.json_on = False
 
     def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time (tracing)
@@ -1499,21 +1541,27 @@ class Qwen2VLEngine:
             toks = toks[:next((i for i, t in enumerate(toks) if t in eos), len(toks))]
         if self.lp_k is not None:
             self.last_logprobs = [self._lp.record(0, self.prompt_len - 1, len(toks), self.lp_k)]
+        if self.json_on and self._json.failed([0])[0]:
+            raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return toks
 
     # ------------------------------------------------------------------ batched generation
     def generate_batch(self, requests: Sequence,
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
-                       check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None) -> list:
+                       check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
+                       json_mode: bool = False) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
         Returns one token list per request; for a lazy request whose callable raised, the exception object instead.
-        ``logprobs``: as in generate; ``last_logprobs`` then holds one record per request (None for a failed one)."""
+        ``logprobs``: as in generate; ``last_logprobs`` then holds one record per request (None for a failed one).
+        ``json_mode``: as in generate; a request whose JSON text could not be continued gets a JsonModeError."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
         check_k(logprobs)
+        if not isinstance(json_mode, bool):
+            raise ValueError("json_mode must be True or False")
         if n_req == 1:
             r = requests[0]
             if callable(r):
@@ -1522,13 +1570,18 @@ class Qwen2VLEngine:
                 except Exception as e:      # noqa: BLE001
                     self.last_logprobs = [None] if logprobs is not None else None
                     return [e]
-            return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                                  logprobs=logprobs)]
+            try:
+                return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
+                                      logprobs=logprobs, json_mode=json_mode)]
+            except JsonModeError as e:
+                return [e]
         self._begin_logprobs(logprobs)
+        self._begin_json(json_mode)
         try:
             return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
         finally:
             self.lp_k = None
+            self.json_on = False
 
     def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> list:
         n_req = len(requests)
@@ -1575,4 +1628,8 @@ class Qwen2VLEngine:
         if self.lp_k is not None:
             self.last_logprobs = [self._lp.record(slots[b], starts[slots[b]], len(outs[slots[b]]), self.lp_k)
                                   if slots[b] is not None else None for b in range(n_req)]
+        if self.json_on:
+            for s, bad in enumerate(self._json.failed(range(B))):
+                if bad:
+                    outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]

@@ -55,6 +55,9 @@ _SIGS = {
     "vis_argmax_f32": "p" + "i" + "ppp" + "i" + "pp" + "fu" + "ii" + "p",
     "vis_logprobs_ws_bytes": "ii",
     "vis_logprobs_f32": "p" + "ii" + "p" + "i" + "p" + "i" + "ppp" + "l" + "i" + "p",
+    "vis_json_mask": "pp" + "i" + "p" * 5 + "iip" + "ii" + "p",
+    "vis_argmax_masked_f32": "p" + "i" + "ppp" + "i" + "pp" + "fu" + "ii" + "p" + "i" + "p",
+    "vis_gemv_bf16_argmax_masked": "pppp" + "iii" + "f" + "ppp" + "i" + "pp" + "fu" + "p" + "p",
     "vis_gemm_decode_ksplit": "ii",
     "vis_gemm_decode_bf16": "pppp" + "iiiiiiii" + "p",
     "vis_gemm_decode_fp8_ksplit": "ii",
@@ -1064,6 +1067,80 @@ def logprobs(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, top
     rc = load().vis_logprobs_f32(_ptr(logits), V, logits.stride(0) if logits.dim() == 2 else V, _ptr(tokens), T, _ptr(step),
                                  top_k, _ptr(lp), _ptr(top_ids), _ptr(ws), ws.numel() * 4, B, _stream())
     _check(rc, "vis_logprobs_f32")
+
+
+JSON_STATE_INTS = 32    # int32 words of one sequence's vis_json_mask state (json_grammar.STATE_INTS)
+
+
+def json_mask(state: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, tok_off: torch.Tensor, tok_bytes: torch.Tensor,
+              tok_flags: torch.Tensor, eos_ids: torch.Tensor, allow: torch.Tensor) -> None:
+    """Fold the tokens picked since the last call into the grammar state and write the allowed-token bitmask of the next pick.
+    state [B, 32] int32 (zeroed = fresh), tokens [B, T] int32, step [B] int32, allow [B, ceil(V / 64)] int64; the token table
+    (json_grammar.TokenTable) as device tensors: tok_off [V + 1] int32, tok_bytes uint8, tok_flags [V] uint8, eos_ids int32."""
+    if state.dim() != 2 or tokens.dim() != 2 or allow.dim() != 2:
+        raise HipLibraryError("json_mask: state / tokens / allow must be 2-D")
+    B = state.shape[0]
+    V = tok_flags.numel()
+    if state.dtype != torch.int32 or state.shape[1] != JSON_STATE_INTS or tokens.dtype != torch.int32 or step.dtype != torch.int32:
+        raise HipLibraryError("json_mask: int32 state [B, 32] / tokens / step required")
+    if tokens.shape[0] != B or step.numel() != B or allow.shape[0] != B or allow.dtype != torch.int64:
+        raise HipLibraryError("json_mask: bad batch shapes / int64 allow required")
+    if tok_off.dtype != torch.int32 or tok_off.numel() != V + 1 or tok_bytes.dtype != torch.uint8 \
+            or tok_flags.dtype != torch.uint8 or eos_ids.dtype != torch.int32:
+        raise HipLibraryError("json_mask: bad token table")
+    if allow.shape[1] < (V + 63) // 64 or allow.stride(1) != 1 or tokens.stride(1) != 1 or not (
+            state.is_contiguous() and step.is_contiguous() and tok_off.is_contiguous() and tok_bytes.is_contiguous()
+            and tok_flags.is_contiguous() and eos_ids.is_contiguous()):
+        raise HipLibraryError("json_mask: bad strides")
+    if B > 1 and (tokens.stride(0) != tokens.shape[1] or state.stride(0) != JSON_STATE_INTS):
+        raise HipLibraryError("json_mask: rows must be contiguous")
+    rc = load().vis_json_mask(_ptr(state), _ptr(tokens), tokens.shape[1], _ptr(step), _ptr(tok_off), _ptr(tok_bytes),
+                              _ptr(tok_flags), _ptr(eos_ids), eos_ids.numel(), V, _ptr(allow), allow.stride(0), B, _stream())
+    _check(rc, "vis_json_mask")
+
+
+def argmax_masked(logits: torch.Tensor, ws_val: torch.Tensor, ws_idx: torch.Tensor, tokens: torch.Tensor,
+                  cur_token: torch.Tensor, step: torch.Tensor, allow: torch.Tensor, temperature: float = 0.0,
+                  seed: int = 0) -> None:
+    """argmax over the ids allowed by ``allow`` (int64 [ceil(V / 64)] or [B, ceil(V / 64)], json_mask's rows); the same
+    comparison and noise as argmax, so an all-ones mask gives its pick bit for bit."""
+    if logits.dtype != torch.float32 or tokens.dtype != torch.int32 or cur_token.dtype != torch.int32:
+        raise HipLibraryError("argmax_masked: f32 logits / int32 tokens required")
+    B = logits.shape[0] if logits.dim() == 2 else 1
+    V = logits.shape[-1]
+    if ws_val.numel() < 256 * B or ws_idx.numel() < 256 * B or cur_token.numel() != B or step.numel() != B:
+        raise HipLibraryError("argmax_masked: workspace too small / bad state shapes")
+    if logits.stride(-1) != 1 or not tokens.is_contiguous() or tokens.numel() % B:
+        raise HipLibraryError("argmax_masked: bad strides")
+    a2 = allow if allow.dim() == 2 else allow.view(1, -1)
+    if allow.dtype != torch.int64 or a2.shape[0] != B or a2.shape[1] < (V + 63) // 64 or a2.stride(-1) != 1:
+        raise HipLibraryError("argmax_masked: allow must be int64 [B, ceil(V / 64)]")
+    rc = load().vis_argmax_masked_f32(_ptr(logits), V, _ptr(ws_val), _ptr(ws_idx), _ptr(tokens), tokens.numel() // B,
+                                      _ptr(cur_token), _ptr(step), (1.0 / temperature) if temperature > 0 else 0.0,
+                                      seed & 0xFFFFFFFF, B, logits.stride(0) if logits.dim() == 2 else V, _ptr(a2),
+                                      a2.stride(0) if B > 1 else a2.shape[1], _stream())
+    _check(rc, "vis_argmax_masked_f32")
+
+
+def gemv_argmax_masked(x: torch.Tensor, w: torch.Tensor, logits: torch.Tensor, ws_val: torch.Tensor, ws_idx: torch.Tensor,
+                       tokens: torch.Tensor, cur_token: torch.Tensor, step: torch.Tensor, allow: torch.Tensor,
+                       norm_w: Optional[torch.Tensor] = None, eps: float = 1e-6, temperature: float = 0.0,
+                       seed: int = 0) -> None:
+    """gemv_argmax with the pick restricted to the ids allowed by ``allow`` (int64 [ceil(N / 64)]).  Single sequence."""
+    _bf16(x, "gemv_argmax_masked x"); _bf16(w, "gemv_argmax_masked w")
+    N, K = w.shape
+    if x.numel() != K or w.stride(1) != 1 or logits.dtype != torch.float32 or logits.numel() != N:
+        raise HipLibraryError("gemv_argmax_masked: bad shapes")
+    if ws_val.dtype != torch.float32 or ws_idx.dtype != torch.int32 or ws_val.numel() < 2048 or ws_idx.numel() < 2048 \
+            or tokens.dtype != torch.int32 or cur_token.numel() != 1 or step.numel() != 1 or not tokens.is_contiguous():
+        raise HipLibraryError("gemv_argmax_masked: workspace too small / bad state shapes")
+    if allow.dtype != torch.int64 or allow.numel() < (N + 63) // 64 or not allow.is_contiguous():
+        raise HipLibraryError("gemv_argmax_masked: allow must be int64 [ceil(N / 64)]")
+    rc = load().vis_gemv_bf16_argmax_masked(_ptr(x), _ptr(w), _ptr(norm_w), _ptr(logits), N, K, w.stride(0), eps, _ptr(ws_val),
+                                            _ptr(ws_idx), _ptr(tokens), tokens.numel(), _ptr(cur_token), _ptr(step),
+                                            (1.0 / temperature) if temperature > 0 else 0.0, seed & 0xFFFFFFFF, _ptr(allow),
+                                            _stream())
+    _check(rc, "vis_gemv_bf16_argmax_masked")
 
 
 DP_PLAIN, DP_SWIGLU, DP_RESID_NORMW = 0, 1, 2

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .json_mode import JsonBuffers, JsonModeError, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
 
@@ -198,6 +199,10 @@ class MllamaEngine:
         self.lp_k: Optional[int] = None
         self._lp: Optional[LogprobsBuffers] = None
         self.last_logprobs: Optional[list] = None
+        # JSON mode (generate(..., json_mode=True)), as in Qwen2VLEngine; tokenizer: set by the client
+        self.json_on = False
+        self._json: Optional[JsonBuffers] = None
+        self.tokenizer = None
 
     # ------------------------------------------------------------------ preprocessing (geometry on host, pixels on GPU)
     def prepare_image(self, frame: torch.Tensor):
@@ -473,8 +478,10 @@ class MllamaEngine:
         if taps is not None:
             taps["first_logits"] = logits.clone()
         step.fill_(S - 1)
-        hip.argmax(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
-                   cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot)
+        if self.json_on:
+            self._json.reset(slot)
+        self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
+                   cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot, slot)
         self._logprobs_after_pick(1, slot)
         self.slot_prompt_len[slot] = S
         if slot == 0:
@@ -606,9 +613,11 @@ class MllamaEngine:
             else:
                 hip.gemv(x[(j + 1) * S - 1], w.lm_head, logits, norm_w=w.norm_w, eps=cfg.rms_eps)
             self.step_b[slot:slot + 1].fill_(S - 1)
-            hip.argmax(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
+            if self.json_on:
+                self._json.reset(slot)
+            self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
                        self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
-                       self.seed + 0x9E3779B9 * slot)
+                       self.seed + 0x9E3779B9 * slot, slot)
             self._logprobs_after_pick(1, slot)
             self.slot_prompt_len[slot] = S
             if slot == 0:
@@ -654,12 +663,12 @@ class MllamaEngine:
             hip.gemv(x2[0], lw.gateup_w, self.d_act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=cfg.rms_eps)
             hip.gemv(self.d_act, lw.down_w, x[0], residual=x2[0])
         if chained:     # the pick's first stage rides in the lm_head epilogue
-            hip.gemv_argmax(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
+            self._gemv_pick(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                             norm_w=w.norm_w, eps=cfg.rms_eps, temperature=self.temperature, seed=self.seed)
             self._logprobs_after_pick(1)
             return
         hip.gemv(x[0], w.lm_head, self.logits, norm_w=w.norm_w, eps=cfg.rms_eps)
-        hip.argmax(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step, self.temperature,
+        self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step, self.temperature,
                    self.seed)
         self._logprobs_after_pick(1)
 
@@ -675,9 +684,33 @@ class MllamaEngine:
         if self.lp_k is not None:
             self._lp.launch(self.logits_b[slot:slot + B], self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], self.lp_k, slot)
 
+    def _begin_json(self, json_mode: bool) -> None:
+        """Switch the grammar mask of every pick on or off for the request about to run (Qwen2VLEngine._begin_json)."""
+        if not isinstance(json_mode, bool):
+            raise ValueError("json_mode must be True or False")
+        if json_mode and self._json is None:
+            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device)
+        self.json_on = json_mode
+
+    def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
+        """vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick, for slots slot .. slot + B - 1."""
+        if not self.json_on:
+            hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
+            return
+        allow = self._json.mask(tokens, step, slot)
+        hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
+
+    def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
+        """The fused lm_head + pick of the single-sequence step, masked in JSON mode."""
+        if not self.json_on:
+            hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
+            return
+        allow = self._json.mask(tokens, step, 0)
+        hip.gemv_argmax_masked(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, allow[0], **kw)
+
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k)
+        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k, self.json_on)
         if key in self._graphs:
             return self._graphs[key]
         snap = (self.step.clone(), self.cur_token.clone())
@@ -787,7 +820,7 @@ class MllamaEngine:
             next_norm = w.layers[li + 1].ln1_w if li + 1 < n_layers else w.norm_w
             hip.skinny_finalize(part, ks, x, H, residual=x2, norm_w=next_norm, yn=xn, eps=eps)
         hip.decode_gemm(xn, w.lm_head, out=self.logits_b[:B])
-        hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
+        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
 
@@ -837,12 +870,12 @@ class MllamaEngine:
                 hip.decode_proj(act, lw.down_w, ws, hip.DP_RESID_NORMW, out=x, out_w=xw, residual=x2, norm_w=next_norm,
                                 ssq_out=s1)
         hip.decode_proj(xw, w.lm_head, ws, hip.DP_PLAIN, out=self.logits_b[:B], ssq_in=s1_in, norm_dim=H, eps=eps)
-        hip.argmax(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
+        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B, self.lp_k)
+        key = (self.temperature, self.seed, B, self.lp_k, self.json_on)
         if key in self._graphs_b:
             return self._graphs_b[key]
         snap = (self.step_b.clone(), self.cur_b.clone())
@@ -863,24 +896,28 @@ class MllamaEngine:
 
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                       chunk: int = 16, logprobs: Optional[int] = None) -> list:
+                       chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
         decode, so the prompt pass of image 0 runs while images 1.. are still being decoded); one that raises gets no
         slot and its exception takes its place in the returned list.  ``logprobs``: as in generate; ``last_logprobs`` then
-        holds one record per request (None for a failed one)."""
+        holds one record per request (None for a failed one).  ``json_mode``: as in generate; a request whose JSON text could
+        not be continued gets a JsonModeError."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
         check_k(logprobs)
+        if not isinstance(json_mode, bool):
+            raise ValueError("json_mode must be True or False")
         lazy = any(callable(r) for r in requests)
         if lazy and n_req == 1:
             # one lazy request (always the case with max_batch == 1, where the batched buffers do not even exist): the
             # single-sequence path; its failure stays its own, as in the batched form
             try:
                 ids, fr = requests[0]() if callable(requests[0]) else requests[0]
-                return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph, logprobs=logprobs)]
+                return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph, logprobs=logprobs,
+                                      json_mode=json_mode)]
             except Exception as e:      # noqa: BLE001
                 self.last_logprobs = [None] if logprobs is not None else None
                 return [e]
@@ -888,12 +925,18 @@ class MllamaEngine:
             if n_req > 1:
                 raise ValueError("generate_batch needs an image in every request (text-only prompts go through generate)")
             ids, fr = requests[0]
-            return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph, logprobs=logprobs)]
+            try:
+                return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph, logprobs=logprobs,
+                                      json_mode=json_mode)]
+            except JsonModeError as e:
+                return [e]
         self._begin_logprobs(logprobs)
+        self._begin_json(json_mode)
         try:
             return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
         finally:
             self.lp_k = None
+            self.json_on = False
 
     def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> list:
         n_req = len(requests)
@@ -1016,6 +1059,10 @@ class MllamaEngine:
         if self.lp_k is not None:
             self.last_logprobs = [self._lp.record(slots[b], starts[slots[b]], len(outs[slots[b]]), self.lp_k)
                                   if slots[b] is not None else None for b in range(n_req)]
+        if self.json_on:
+            for s, bad in enumerate(self._json.failed(range(B))):
+                if bad:
+                    outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]
 
     def generated(self, n: int) -> List[int]:
@@ -1026,11 +1073,13 @@ class MllamaEngine:
 
     def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                 chunk: int = 32, logprobs: Optional[int] = None) -> List[int]:
+                 chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False) -> List[int]:
         """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
         logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
-        None = off, no extra launch."""
+        None = off, no extra launch.  ``json_mode``: every pick restricted to the tokens that continue a JSON object, as in
+        Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it)."""
         self._begin_logprobs(logprobs)
+        self._begin_json(json_mode)
         try:
             return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
         except hip.ChainStalled as e:
@@ -1043,6 +1092,7 @@ class MllamaEngine:
             return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
         finally:
             self.lp_k = None
+            self.json_on = False
 
     def _generate(self, input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time, as in Qwen2VLEngine
@@ -1067,4 +1117,6 @@ class MllamaEngine:
             toks = toks[:next((i + 1 for i, t in enumerate(toks) if t in eos), len(toks))]
         if self.lp_k is not None:
             self.last_logprobs = [self._lp.record(0, self.prompt_len - 1, len(toks), self.lp_k)]
+        if self.json_on and self._json.failed([0])[0]:
+            raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return toks
