@@ -259,6 +259,22 @@ int vis_gemv_bf16_argmax_masked(const void* x, const void* W, const void* norm_w
                                 float eps, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
                                 void* step_ptr, float inv_temp, unsigned seed, const void* allow, vis_stream_t stream);
 
+/* Nucleus (top_p) sampling with per-row seeds (csrc/sampling.hip).  Row b < batch: logits + b * ld_logits (V f32), allowed
+ * set A = every id, or (allow non-null) the ids whose bit is set in allow + b * ld_allow (vis_json_mask's rows).  Order A by
+ * (logit desc, id asc); w_i = exp((l_i - max) * inv_temp); K = the shortest prefix whose mass >= top_p * sum(w), at least
+ * one token.  The pick is the argmax over K of l_i * inv_temp + gumbel_noise(seeds[b], step_ptr[b], i) - vis_argmax_f32's
+ * expression and tie rule, so top_p = 1 gives its pick bit for bit for the same row seed.  inv_temp = 0: greedy over A.
+ * Effects: tokens[b * max_tokens + step] = pick (step < max_tokens), cur_token[b] = pick, step_ptr[b] += 1; nothing allowed
+ * picks id 0.  nkeep (int32 [batch], may be null) = |K| (1 when inv_temp = 0).  seeds: uint32 [batch] in device memory.
+ * Masses are summed in fixed point, so a row's K and pick depend only on its own inputs.  Own workspace of
+ * vis_sample_ws_bytes(V, batch) bytes (row b uses bytes [b * ws_bytes(V, 1), (b + 1) * ws_bytes(V, 1))); one launch at a
+ * time per workspace.  VIS_ERR_ARG: null pointer, V <= 0, batch outside 1..64, ld_logits < V at batch > 1, top_p NaN or
+ * outside [0, 1], inv_temp < 0 or NaN, ld_allow < ceil(V / 64) or allow not 8-byte aligned. */
+long long vis_sample_ws_bytes(int V, int batch);
+int vis_sample_f32(const void* logits, int V, int ld_logits, const void* allow, int ld_allow, float inv_temp, float top_p,
+                   const void* seeds, void* tokens, int max_tokens, void* cur_token, void* step_ptr, int batch, void* ws,
+                   void* nkeep, vis_stream_t stream);
+
 /* K10 (batched decode), first half.  For up to 64 in-flight sequences the weight matrix is streamed from HBM
  * ONCE per step by <= 256 persistent workgroups (one per CU, 7-stage LDS-DMA ring, stream-K cut of the
  * (128-column tile, K-step) sequence).  part[slot][R][N] (f32), R = 16 / 32 / 64 for B <= 16 / 32 / 64 (one, two or four

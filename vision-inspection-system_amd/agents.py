@@ -30,6 +30,19 @@ def json_mode_kwargs() -> dict:
     return {"response_format": {"type": "json_object"}} if os.environ.get("VIS_JSON_MODE", "0") == "1" else {}
 
 
+def seed_kwargs() -> dict:
+    """VIS_SEED=<integer> (default unset): the analysis and verify requests pass seed=<integer>, so a sampled report depends
+    on the image and the prompt only, not on its place in a batch or on what shares the batch.  Unset: the calls are as
+    before."""
+    v = os.environ.get("VIS_SEED", "").strip()
+    if not v:
+        return {}
+    try:
+        return {"seed": int(v)}
+    except ValueError:
+        raise ValueError("VIS_SEED must be an integer") from None
+
+
 def _logger(name: str) -> logging.Logger:
     try:  # pragma: no cover - only inside the reference application
         from utils.logger import setup_logger  # type: ignore
@@ -56,7 +69,7 @@ class _BaseAgent:
             try:
                 completion = self.client.chat.completions.create(
                     model=self.model_id, messages=messages, temperature=self.temperature, max_tokens=self.max_tokens,
-                    **json_mode_kwargs())
+                    **json_mode_kwargs(), **seed_kwargs())
                 return completion.choices[0].message.content
             except Exception as e:
                 text = str(e)
@@ -295,13 +308,13 @@ def _many(agent, image_paths, contexts, prepared=None) -> list:
         try:
             if hasattr(agent.client, "complete_many"):
                 replies = agent.client.complete_many(agent.model_id, msgs, agent.temperature, agent.max_tokens,
-                                                     **json_mode_kwargs())
+                                                     **json_mode_kwargs(), **seed_kwargs())
                 texts = [r if isinstance(r, Exception) else r.choices[0].message.content for r in replies]
             else:
                 texts = [agent.client.chat.completions.create(model=agent.model_id, messages=m,
                                                               temperature=agent.temperature,
                                                               max_tokens=agent.max_tokens,
-                                                              **json_mode_kwargs()).choices[0].message.content
+                                                              **json_mode_kwargs(), **seed_kwargs()).choices[0].message.content
                          for m in msgs]
         except Exception as e:
             agent.logger.error(f"{agent.nickname}: batched call failed: {e}", exc_info=True)

@@ -75,9 +75,11 @@ class _Completions:
 
     def create(self, model: Optional[str] = None, messages: Optional[list] = None,
                temperature: Optional[float] = None, max_tokens: Optional[int] = None, logprobs: bool = False,
-               top_logprobs: Optional[int] = None, response_format: Optional[dict] = None, **kwargs) -> ChatCompletion:
+               top_logprobs: Optional[int] = None, response_format: Optional[dict] = None, top_p: Optional[float] = None,
+               seed: Optional[int] = None, **kwargs) -> ChatCompletion:
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
-                                     top_logprobs=top_logprobs, response_format=response_format, **kwargs)
+                                     top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
+                                     **kwargs)
 
 
 class _Chat:
@@ -366,12 +368,13 @@ class LocalVLMClient:
         return build_chat_ids(lm.tokenizer, messages, counts), frames
 
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
-                  **kwargs) -> ChatCompletion:
+                  top_p=None, seed=None, **kwargs) -> ChatCompletion:
         return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
-                                  response_format=response_format)[0]
+                                  response_format=response_format, top_p=top_p, seed=seed)[0]
 
     def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
-                      top_logprobs: Optional[int] = None, response_format: Optional[dict] = None) -> List[ChatCompletion]:
+                      top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
+                      top_p: Optional[float] = None, seed: Optional[int] = None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -383,10 +386,17 @@ class LocalVLMClient:
         ``response_format`` (OpenAI's): {"type": "json_object"} restricts every generated token to the ones that continue a
         JSON object (RFC 8259, strict UTF-8; the engines' json_mode): a reply that ended on EOS parses with json.loads, one cut
         by max_tokens is a prefix of a JSON object; a request the vocabulary could not continue fails with JsonModeError.
-        None or {"type": "text"}: unchanged.  Logprobs keep their meaning: top_logprobs may list tokens the mask forbade."""
+        None or {"type": "text"}: unchanged.  Logprobs keep their meaning: top_logprobs may list tokens the mask forbade.
+        ``top_p`` (OpenAI's / huggingface_hub's): nucleus sampling - each token is drawn from the shortest most-likely set
+        holding top_p of the temperature-scaled probability (sampling.py); None or 1 = the whole vocabulary.  ``seed``: every
+        request of the call samples with this seed, so its reply depends on its own messages only (not on its place in the
+        batch or what shares it); None = the client's seed, varied per batch slot as before."""
         import torch
+        from .sampling import check_seed, check_top_p
         k = logprobs_k(logprobs, top_logprobs)
         jm = json_mode_of(response_format)
+        top_p = check_top_p(top_p)
+        seed = check_seed(seed)
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
@@ -396,7 +406,7 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         out: List[ChatCompletion] = []
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -432,7 +442,9 @@ class LocalVLMClient:
                 idx = range(i, min(len(futs), i + eng.max_batch))
                 toks = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp, seed=self.seed,
                                           ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1",
-                                          **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}))
+                                          **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}),
+                                          **({"top_p": top_p} if top_p is not None else {}),
+                                          **({"seeds": [seed] * len(idx)} if seed is not None else {}))
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", {}))
                 if timing:
@@ -474,7 +486,8 @@ class LocalVLMClient:
         return build_llama_chat_ids(lm.tokenizer, messages, len(frames)), (frames[0] if frames else None)
 
     def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
-                              k: Optional[int] = None, jm: bool = False) -> List[ChatCompletion]:
+                              k: Optional[int] = None, jm: bool = False, top_p: Optional[float] = None,
+                              seed: Optional[int] = None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -486,6 +499,11 @@ class LocalVLMClient:
         lpk = {"logprobs": k} if k is not None else {}
         if jm:
             lpk["json_mode"] = True
+        if top_p is not None:
+            lpk["top_p"] = top_p
+
+        def seeds_of(n):
+            return {"seeds": [seed] * n} if seed is not None else {}
 
         def completion(n_ids, t, rec=None):
             lp = _choice_logprobs(tok, t, rec) if rec is not None else None
@@ -511,7 +529,7 @@ class LocalVLMClient:
                 for g0 in range(0, len(futs), eng.max_batch):
                     idx = range(g0, min(len(futs), g0 + eng.max_batch))
                     outs = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp,
-                                              seed=self.seed, stop_on_eos=not ignore_eos, **lpk)
+                                              seed=self.seed, stop_on_eos=not ignore_eos, **lpk, **seeds_of(len(idx)))
                     recs = eng.last_logprobs if k is not None else [None] * len(idx)
                     if getattr(eng, "last_timing", None):
                         TIMING_LOG.append({"model": lm.model_id, **eng.last_timing})
@@ -527,13 +545,14 @@ class LocalVLMClient:
                 grp = with_img[g0:g0 + eng.max_batch]
                 reqs = [(prepared[i][0], _frame_to_device(prepared[i][1], eng.device)) for i in grp]
                 outs = eng.generate_batch(reqs, max_new_tokens=max_new, temperature=temp, seed=self.seed,
-                                          stop_on_eos=not ignore_eos, **lpk)
+                                          stop_on_eos=not ignore_eos, **lpk, **seeds_of(len(reqs)))
                 for n, (i, t) in enumerate(zip(grp, outs)):
                     toks_out[i] = t
                     recs[i] = eng.last_logprobs[n] if k is not None else None
             for i, (ids, f) in enumerate(prepared):
                 if f is None:
-                    toks_out[i] = eng.generate(ids, None, max_new_tokens=max_new, temperature=temp, seed=self.seed,
+                    toks_out[i] = eng.generate(ids, None, max_new_tokens=max_new, temperature=temp,
+                                               seed=self.seed if seed is None else seed,
                                                stop_on_eos=not ignore_eos, **lpk)
                     recs[i] = eng.last_logprobs[0] if k is not None else None
         return [completion(len(ids), t, r) for (ids, _), t, r in zip(prepared, toks_out, recs)]
@@ -558,9 +577,10 @@ class CannedResponseClient:
         self.calls: List[dict] = []
         self.chat = _Chat(self)
 
-    def _complete(self, model, messages, temperature, max_tokens, response_format=None, **kwargs) -> ChatCompletion:
+    def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
+                  **kwargs) -> ChatCompletion:
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
-                           "response_format": response_format})
+                           "response_format": response_format, "top_p": top_p, "seed": seed})
         reply = self.reply(messages) if callable(self.reply) else self.reply
         return ChatCompletion([_Choice(_Message(reply))], model=model or "")
 

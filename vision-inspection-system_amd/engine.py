@@ -28,6 +28,7 @@ import torch
 from . import hip
 from .json_mode import JsonBuffers, JsonModeError, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
+from .sampling import SampleBuffers, check_seeds, check_top_p
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
 
@@ -330,6 +331,11 @@ class Qwen2VLEngine:
         self.json_on = False
         self._json: Optional[JsonBuffers] = None
         self.tokenizer = None
+        # nucleus sampling / per-request seeds (generate(..., top_p=), generate_batch(..., top_p=, seeds=)): while on, every
+        # pick is vis_sample_f32 with the row seeds of a device buffer; top_p None = 1; _slot_seed: slot -> request seed
+        self.smp_on, self.top_p, self.seeded = False, None, False
+        self._smp: Optional[SampleBuffers] = None
+        self._slot_seed: Dict[int, int] = {}
 
     # ------------------------------------------------------------------ vision tower
     def vision_forward(self, frames: Sequence[torch.Tensor], split_rows: bool = True) -> torch.Tensor:
@@ -665,6 +671,7 @@ class Qwen2VLEngine:
         step.fill_(S - 1)
         if self.json_on:
             self._json.reset(slot)
+        self._seed_slot(slot)
         self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
                    cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot, slot)   # per-slot workspace: prefills
         # of different slots may run concurrently on different streams
@@ -845,6 +852,7 @@ class Qwen2VLEngine:
             self.step_b[slot:slot + 1].fill_(S - 1)
             if self.json_on:
                 self._json.reset(slot)
+            self._seed_slot(slot)
             self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
                        self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
                        self.seed + 0x9E3779B9 * slot, slot)
@@ -878,7 +886,8 @@ class Qwen2VLEngine:
 
     def prefill_many(self, requests: Sequence, temperature: float = 0.0,
                      seed: int = 0, max_new_tokens: Optional[int] = None,
-                     ids_dev: Optional[Sequence[torch.Tensor]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
+                     ids_dev: Optional[Sequence[torch.Tensor]] = None,
+                     seeds: Optional[Sequence[int]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
         """Prefill the requests into consecutive slots.  The prefills are independent kernel chains: they are issued round-robin
         on a few HIP streams (VIS_PREFILL_STREAMS, default 2: 418 -> 381 ms for 8 images) so that the ragged last round of one image's GEMM /
         attention grids is filled by another image's workgroups.  Returns with the current stream ordered after
@@ -888,6 +897,7 @@ class Qwen2VLEngine:
         batch seam: the callable waits for the image's host decode and uploads it, so the GPU starts on image 0 while
         images 1.. are still being decoded).  Lazy requests are resolved in order, a ViT group at a time; one that
         raises gets no slot and its exception is returned instead of failing the batch.
+        ``seeds``: request b's own sampling seed (read by the picks while nucleus sampling / seeds are on).
         Returns (slot of request b or None, exception of request b or None)."""
         B = len(requests)
         lazy = any(callable(r) for r in requests)
@@ -937,6 +947,8 @@ class Qwen2VLEngine:
                 r = get(b)
                 if r is None:
                     continue
+                if seeds is not None:
+                    self._slot_seed[next_slot] = seeds[b]
                 self.prefill(r[0], r[1], ids_dev=ids_dev[b] if ids_dev else None, temperature=temperature, seed=seed,
                              max_new_tokens=max_new_tokens, slot=next_slot, prefix=prefix_for(r[0]))
                 slots[b] = next_slot
@@ -979,6 +991,8 @@ class Qwen2VLEngine:
                     if len(same) >= 2:
                         merged = same
             slot_of = {b: next_slot + i for i, b in enumerate(grp_all)}       # slots follow the request order
+            if seeds is not None:
+                self._slot_seed.update({slot_of[b]: seeds[b] for b in grp_all})
             next_slot += len(grp_all)
             if merged:
                 st = streams[(g0 // vb) % n_streams]         # consecutive groups alternate streams
@@ -1090,8 +1104,32 @@ class Qwen2VLEngine:
             self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device)
         self.json_on = json_mode
 
+    # ------------------------------------------------------------------ nucleus sampling / per-request seeds
+    def _begin_sampling(self, top_p, seeded: bool) -> None:
+        """Route every pick of the request about to run through vis_sample_f32 when top_p < 1 or it brings its own seeds."""
+        top_p = check_top_p(top_p)
+        self.top_p = top_p if top_p is not None and top_p < 1.0 else None
+        self.seeded = bool(seeded)
+        self.smp_on = self.seeded or self.top_p is not None
+        if self.smp_on and self._smp is None:
+            self._smp = SampleBuffers(self.max_batch, self.cfg.vocab, self.device)
+
+    def _end_sampling(self) -> None:
+        self.smp_on, self.top_p, self.seeded = False, None, False
+        self._slot_seed = {}
+
+    def _seed_slot(self, slot: int) -> None:
+        """Before a prompt pass's pick: the row seed of ``slot`` (the request's own, else the slot-derived one)."""
+        if self.smp_on:
+            self._smp.set_slot(slot, self._slot_seed.get(slot, self.seed + 0x9E3779B9 * slot))
+
     def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
-        """The next-token pick of slots slot .. slot + B - 1: vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick."""
+        """The next-token pick of slots slot .. slot + B - 1: vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick;
+        vis_sample_f32 (seeds from the device buffer, the JSON rows as its mask) while nucleus sampling / seeds are on."""
+        if self.smp_on:
+            allow = self._json.mask(tokens, step, slot) if self.json_on else None
+            self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
+            return
         if not self.json_on:
             hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
             return
@@ -1099,7 +1137,12 @@ class Qwen2VLEngine:
         hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
 
     def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
-        """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode."""
+        """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode; while nucleus sampling / seeds
+        are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
+        if self.smp_on:
+            hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
+            self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
+            return
         if not self.json_on:
             hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
             return
@@ -1362,9 +1405,10 @@ class Qwen2VLEngine:
         self._logprobs_after_pick(B)
 
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
-        # sampling parameters, the batch size, the logprobs k and JSON mode are kernel arguments baked into the graph
+        # sampling parameters, the batch size, the logprobs k, JSON mode and top_p are kernel arguments baked into the graph;
+        # the row seeds of vis_sample_f32 are read from device memory at replay, so only whether they are in use is part of it
         key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch, self.lp_k,
-               self.json_on)
+               self.json_on, self.top_p, self.seeded)
         if key in self._graphs:
             return self._graphs[key]
         step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
@@ -1481,7 +1525,7 @@ class Qwen2VLEngine:
     def generate(self, input_ids: Sequence[int], frames: Sequence[torch.Tensor] = (), max_new_tokens: int = 128,
                  ignore_eos: bool = False, use_graph: bool = True, check_every: int = 16,
                  temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
-                 json_mode: bool = False) -> List[int]:
+                 json_mode: bool = False, top_p: Optional[float] = None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
@@ -1489,9 +1533,12 @@ class Qwen2VLEngine:
         likely alternatives); None = off, no extra launch.  ``json_mode``: every pick is restricted to the tokens that
         continue a JSON object (json_grammar; needs ``self.tokenizer``): the reply is a prefix of one, complete when it
         ended on EOS; JsonModeError when the vocabulary could not continue it.  Logprobs keep their meaning (raw logits),
-        so top_logprobs may list tokens the mask forbade."""
+        so top_logprobs may list tokens the mask forbade.  ``top_p`` in [0, 1]: nucleus sampling (sampling.py) - each pick
+        draws from the shortest most-likely prefix holding top_p of the temperature-scaled mass; None or 1 = off."""
+        check_top_p(top_p)
         self._begin_logprobs(logprobs)
         self._begin_json(json_mode)
+        self._begin_sampling(top_p, False)
         room = self.max_ctx - len(input_ids) - 1
         if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
             self._warned_clamp = True          # said once per engine: the reply may end before the model is done
@@ -1515,6 +1562,7 @@ class Qwen2VLEngine:
         finally:
             self.lp_k = None
             self.json_on = False
+            self._end_sampling()
 
     def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time (tracing)
@@ -1549,19 +1597,23 @@ class Qwen2VLEngine:
     def generate_batch(self, requests: Sequence,
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
-                       json_mode: bool = False) -> list:
+                       json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
         Returns one token list per request; for a lazy request whose callable raised, the exception object instead.
         ``logprobs``: as in generate; ``last_logprobs`` then holds one record per request (None for a failed one).
-        ``json_mode``: as in generate; a request whose JSON text could not be continued gets a JsonModeError."""
+        ``json_mode``: as in generate; a request whose JSON text could not be continued gets a JsonModeError.
+        ``top_p``: as in generate.  ``seeds``: one integer per request, its own sampling seed in place of the slot-derived
+        one, so a request's sampled reply does not depend on its slot or on what shares the batch."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
         check_k(logprobs)
         if not isinstance(json_mode, bool):
             raise ValueError("json_mode must be True or False")
+        check_top_p(top_p)
+        seeds = check_seeds(seeds, n_req)
         if n_req == 1:
             r = requests[0]
             if callable(r):
@@ -1571,25 +1623,30 @@ class Qwen2VLEngine:
                     self.last_logprobs = [None] if logprobs is not None else None
                     return [e]
             try:
-                return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                                      logprobs=logprobs, json_mode=json_mode)]
+                return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature,
+                                      seed if seeds is None else seeds[0], logprobs=logprobs, json_mode=json_mode,
+                                      top_p=top_p)]
             except JsonModeError as e:
                 return [e]
         self._begin_logprobs(logprobs)
         self._begin_json(json_mode)
+        self._begin_sampling(top_p, seeds is not None)
         try:
-            return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
+            return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, seeds)
         finally:
             self.lp_k = None
             self.json_on = False
+            self._end_sampling()
 
-    def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> list:
+    def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
+                        seeds=None) -> list:
         n_req = len(requests)
         # every prompt's own limit (prompt + new tokens <= context) is applied by its prefill; the shared loop below
         # runs to the limit of the longest one
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
-        slots, errors = self.prefill_many(requests, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens)
+        slots, errors = self.prefill_many(requests, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens,
+                                          seeds=seeds)
         ev[1].record()
         live = [b for b in range(n_req) if slots[b] is not None]
         B = len(live)

@@ -58,6 +58,8 @@ _SIGS = {
     "vis_json_mask": "pp" + "i" + "p" * 5 + "iip" + "ii" + "p",
     "vis_argmax_masked_f32": "p" + "i" + "ppp" + "i" + "pp" + "fu" + "ii" + "p" + "i" + "p",
     "vis_gemv_bf16_argmax_masked": "pppp" + "iii" + "f" + "ppp" + "i" + "pp" + "fu" + "p" + "p",
+    "vis_sample_ws_bytes": "ii",
+    "vis_sample_f32": "p" + "ii" + "p" + "i" + "ff" + "pp" + "i" + "pp" + "i" + "pp" + "p",
     "vis_gemm_decode_ksplit": "ii",
     "vis_gemm_decode_bf16": "pppp" + "iiiiiiii" + "p",
     "vis_gemm_decode_fp8_ksplit": "ii",
@@ -201,6 +203,7 @@ def load() -> ctypes.CDLL:
     lib.vis_decode_chain_ws_bytes.restype = ctypes.c_longlong
     lib.vis_decode_proj_ws_bytes.restype = ctypes.c_longlong
     lib.vis_logprobs_ws_bytes.restype = ctypes.c_longlong
+    lib.vis_sample_ws_bytes.restype = ctypes.c_longlong
     _lib = _Lib(lib)
     return _lib
 
@@ -1141,6 +1144,46 @@ def gemv_argmax_masked(x: torch.Tensor, w: torch.Tensor, logits: torch.Tensor, w
                                             (1.0 / temperature) if temperature > 0 else 0.0, seed & 0xFFFFFFFF, _ptr(allow),
                                             _stream())
     _check(rc, "vis_gemv_bf16_argmax_masked")
+
+
+def sample_ws(V: int, batch: int, device) -> torch.Tensor:
+    """Workspace of vis_sample_f32 for up to ``batch`` rows of V logits, [batch, n] uint8 (row b's slice serves one row)."""
+    n = int(load().vis_sample_ws_bytes(V, batch))
+    if n <= 0:
+        raise HipLibraryError(f"sample_ws: unsupported V={V} batch={batch}")
+    return torch.empty((batch, n // batch), dtype=torch.uint8, device=device)
+
+
+def sample(logits: torch.Tensor, tokens: torch.Tensor, cur_token: torch.Tensor, step: torch.Tensor, seeds: torch.Tensor,
+           ws: torch.Tensor, temperature: float = 0.0, top_p: float = 1.0, allow: Optional[torch.Tensor] = None,
+           nkeep: Optional[torch.Tensor] = None) -> None:
+    """Nucleus pick (vis_sample_f32): the Gumbel-max over the shortest (logit desc, id asc) prefix holding top_p of the
+    temperature-scaled mass, with row b's seed read from seeds[b] (int32 / uint32 bits) at launch time, so a captured
+    launch serves any seeds.  logits [V] or [B, V]; tokens [T] / [B, T]; cur_token, step, seeds [B]; ws from sample_ws
+    (rows >= B); allow: vis_json_mask's int64 rows [B, ceil(V / 64)] or None; nkeep: int32 [B] receives |K| or None.
+    top_p = 1 picks what argmax(..., seed) does for the same row seed."""
+    if logits.dtype != torch.float32 or tokens.dtype != torch.int32 or cur_token.dtype != torch.int32 \
+            or step.dtype != torch.int32 or seeds.dtype not in (torch.int32, torch.uint32) or ws.dtype != torch.uint8:
+        raise HipLibraryError("sample: f32 logits / int32 tokens, step, seeds / uint8 workspace required")
+    B = logits.shape[0] if logits.dim() == 2 else 1
+    V = logits.shape[-1]
+    if cur_token.numel() != B or step.numel() != B or seeds.numel() < B or not seeds.is_contiguous():
+        raise HipLibraryError("sample: bad state shapes")
+    if logits.stride(-1) != 1 or not tokens.is_contiguous() or tokens.numel() % B or not ws.is_contiguous() \
+            or ws.numel() < int(load().vis_sample_ws_bytes(V, B)):
+        raise HipLibraryError("sample: bad strides / workspace too small")
+    if nkeep is not None and (nkeep.dtype != torch.int32 or nkeep.numel() < B or not nkeep.is_contiguous()):
+        raise HipLibraryError("sample: nkeep must be int32 [B]")
+    a2 = None
+    if allow is not None:
+        a2 = allow if allow.dim() == 2 else allow.view(1, -1)
+        if allow.dtype != torch.int64 or a2.shape[0] != B or a2.shape[1] < (V + 63) // 64 or a2.stride(-1) != 1:
+            raise HipLibraryError("sample: allow must be int64 [B, ceil(V / 64)]")
+    rc = load().vis_sample_f32(_ptr(logits), V, logits.stride(0) if logits.dim() == 2 else V, _ptr(a2),
+                               (a2.stride(0) if B > 1 else a2.shape[1]) if a2 is not None else 0,
+                               (1.0 / temperature) if temperature > 0 else 0.0, float(top_p), _ptr(seeds), _ptr(tokens),
+                               tokens.numel() // B, _ptr(cur_token), _ptr(step), B, _ptr(ws), _ptr(nkeep), _stream())
+    _check(rc, "vis_sample_f32")
 
 
 DP_PLAIN, DP_SWIGLU, DP_RESID_NORMW = 0, 1, 2

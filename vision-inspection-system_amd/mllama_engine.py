@@ -33,6 +33,7 @@ import torch
 from . import hip
 from .json_mode import JsonBuffers, JsonModeError, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
+from .sampling import SampleBuffers, check_seeds, check_top_p
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
 
 
@@ -203,6 +204,10 @@ class MllamaEngine:
         self.json_on = False
         self._json: Optional[JsonBuffers] = None
         self.tokenizer = None
+        # nucleus sampling / per-request seeds, as in Qwen2VLEngine
+        self.smp_on, self.top_p, self.seeded = False, None, False
+        self._smp: Optional[SampleBuffers] = None
+        self._slot_seed: Dict[int, int] = {}
 
     # ------------------------------------------------------------------ preprocessing (geometry on host, pixels on GPU)
     def prepare_image(self, frame: torch.Tensor):
@@ -480,6 +485,7 @@ class MllamaEngine:
         step.fill_(S - 1)
         if self.json_on:
             self._json.reset(slot)
+        self._seed_slot(slot)
         self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
                    cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot, slot)
         self._logprobs_after_pick(1, slot)
@@ -615,6 +621,7 @@ class MllamaEngine:
             self.step_b[slot:slot + 1].fill_(S - 1)
             if self.json_on:
                 self._json.reset(slot)
+            self._seed_slot(slot)
             self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
                        self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
                        self.seed + 0x9E3779B9 * slot, slot)
@@ -692,8 +699,31 @@ class MllamaEngine:
             self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device)
         self.json_on = json_mode
 
+    def _begin_sampling(self, top_p, seeded: bool) -> None:
+        """Route every pick through vis_sample_f32 for this request (Qwen2VLEngine._begin_sampling)."""
+        top_p = check_top_p(top_p)
+        self.top_p = top_p if top_p is not None and top_p < 1.0 else None
+        self.seeded = bool(seeded)
+        self.smp_on = self.seeded or self.top_p is not None
+        if self.smp_on and self._smp is None:
+            self._smp = SampleBuffers(self.max_batch, self.cfg.vocab, self.device)
+
+    def _end_sampling(self) -> None:
+        self.smp_on, self.top_p, self.seeded = False, None, False
+        self._slot_seed = {}
+
+    def _seed_slot(self, slot: int) -> None:
+        """Before a prompt pass's pick: the row seed of ``slot`` (the request's own, else the slot-derived one)."""
+        if self.smp_on:
+            self._smp.set_slot(slot, self._slot_seed.get(slot, self.seed + 0x9E3779B9 * slot))
+
     def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
-        """vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick, for slots slot .. slot + B - 1."""
+        """vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick, for slots slot .. slot + B - 1; vis_sample_f32
+        while nucleus sampling / seeds are on."""
+        if self.smp_on:
+            allow = self._json.mask(tokens, step, slot) if self.json_on else None
+            self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
+            return
         if not self.json_on:
             hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
             return
@@ -701,7 +731,12 @@ class MllamaEngine:
         hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
 
     def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
-        """The fused lm_head + pick of the single-sequence step, masked in JSON mode."""
+        """The fused lm_head + pick of the single-sequence step, masked in JSON mode; the plain lm_head GEMV + _pick while
+        nucleus sampling / seeds are on."""
+        if self.smp_on:
+            hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
+            self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
+            return
         if not self.json_on:
             hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
             return
@@ -710,7 +745,7 @@ class MllamaEngine:
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k, self.json_on)
+        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k, self.json_on, self.top_p, self.seeded)
         if key in self._graphs:
             return self._graphs[key]
         snap = (self.step.clone(), self.cur_token.clone())
@@ -875,7 +910,7 @@ class MllamaEngine:
         self._logprobs_after_pick(B)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B, self.lp_k, self.json_on)
+        key = (self.temperature, self.seed, B, self.lp_k, self.json_on, self.top_p, self.seeded)
         if key in self._graphs_b:
             return self._graphs_b[key]
         snap = (self.step_b.clone(), self.cur_b.clone())
@@ -896,28 +931,32 @@ class MllamaEngine:
 
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                       chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False) -> list:
+                       chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
+                       top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
         decode, so the prompt pass of image 0 runs while images 1.. are still being decoded); one that raises gets no
         slot and its exception takes its place in the returned list.  ``logprobs``: as in generate; ``last_logprobs`` then
         holds one record per request (None for a failed one).  ``json_mode``: as in generate; a request whose JSON text could
-        not be continued gets a JsonModeError."""
+        not be continued gets a JsonModeError.  ``top_p`` / ``seeds``: as in Qwen2VLEngine.generate_batch."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
         check_k(logprobs)
         if not isinstance(json_mode, bool):
             raise ValueError("json_mode must be True or False")
+        check_top_p(top_p)
+        seeds = check_seeds(seeds, n_req)
+        seed0 = seed if seeds is None else seeds[0]
         lazy = any(callable(r) for r in requests)
         if lazy and n_req == 1:
             # one lazy request (always the case with max_batch == 1, where the batched buffers do not even exist): the
             # single-sequence path; its failure stays its own, as in the batched form
             try:
                 ids, fr = requests[0]() if callable(requests[0]) else requests[0]
-                return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode)]
+                return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
+                                      json_mode=json_mode, top_p=top_p)]
             except Exception as e:      # noqa: BLE001
                 self.last_logprobs = [None] if logprobs is not None else None
                 return [e]
@@ -926,19 +965,21 @@ class MllamaEngine:
                 raise ValueError("generate_batch needs an image in every request (text-only prompts go through generate)")
             ids, fr = requests[0]
             try:
-                return [self.generate(ids, fr, max_new_tokens, temperature, seed, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode)]
+                return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
+                                      json_mode=json_mode, top_p=top_p)]
             except JsonModeError as e:
                 return [e]
         self._begin_logprobs(logprobs)
         self._begin_json(json_mode)
+        self._begin_sampling(top_p, seeds is not None)
         try:
-            return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
+            return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds)
         finally:
             self.lp_k = None
             self.json_on = False
+            self._end_sampling()
 
-    def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> list:
+    def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds=None) -> list:
         n_req = len(requests)
         lazy = any(callable(r) for r in requests)
         slots: List[Optional[int]] = [None] * n_req
@@ -991,6 +1032,8 @@ class MllamaEngine:
                         items = []
                         for (b, ids, fr), cs in zip(grp, crosses):
                             cs[0].record_stream(st)
+                            if seeds is not None:
+                                self._slot_seed[B + len(items)] = seeds[b]
                             items.append((B + len(items), ids, cs[0], cs[1]))
                         self._prefill_group(items, temperature, seed)
                     for (b, _, _) in grp:
@@ -1003,6 +1046,8 @@ class MllamaEngine:
                         errors[b] = e
                 continue
             for (b, ids, fr), cs in zip(grp, crosses):
+                if seeds is not None:
+                    self._slot_seed[B] = seeds[b]
                 try:
                     if n_streams > 1:
                         st = self._prefill_streams[B % n_streams]
@@ -1073,13 +1118,17 @@ class MllamaEngine:
 
     def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                 chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False) -> List[int]:
+                 chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False,
+                 top_p: Optional[float] = None) -> List[int]:
         """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
         logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
         None = off, no extra launch.  ``json_mode``: every pick restricted to the tokens that continue a JSON object, as in
-        Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it)."""
+        Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it).  ``top_p``: nucleus sampling, as in
+        Qwen2VLEngine.generate."""
+        check_top_p(top_p)
         self._begin_logprobs(logprobs)
         self._begin_json(json_mode)
+        self._begin_sampling(top_p, False)
         try:
             return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
         except hip.ChainStalled as e:
@@ -1093,6 +1142,7 @@ class MllamaEngine:
         finally:
             self.lp_k = None
             self.json_on = False
+            self._end_sampling()
 
     def _generate(self, input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time, as in Qwen2VLEngine
