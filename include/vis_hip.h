@@ -275,6 +275,23 @@ int vis_sample_f32(const void* logits, int V, int ld_logits, const void* allow, 
                    const void* seeds, void* tokens, int max_tokens, void* cur_token, void* step_ptr, int batch, void* ws,
                    void* nkeep, vis_stream_t stream);
 
+/* Logit penalties ahead of the pick (csrc/penalty.hip): repetition penalty r (transformers' RepetitionPenaltyLogitsProcessor,
+ * over prompt and generated ids), then frequency penalty f and presence penalty q (OpenAI's, over generated ids only):
+ *   seen = v in the prompt or c[v] > 0;  y = seen && r != 1 ? (x < 0 ? x * r : x / r) : x;  y -= f * c[v] + q * (c[v] > 0)
+ * state: vis_penalty_state_bytes(V, batch) bytes, 16-byte aligned, row b at b * vis_penalty_state_bytes(V, 1); a zeroed row is
+ * a fresh sequence (a 16-byte head, then one 16-bit word per id: prompt flag + saturating count of generated occurrences).
+ * vis_penalty_prompt marks ids[0 .. n) (int32, device memory) as prompt members of ONE row; ids outside [0, V) are skipped.
+ * vis_penalize_f32, one launch per pick: for every row b < batch folds the tokens picked since the row's state was advanced
+ * (positions [pos, step[b]) of tokens[b][max_tokens]; none on the first launch after a reset) into the counts and writes
+ * out[b][v] for all v; logits are left intact (out != logits).  params: f32 [batch][3] = (r, f, q) in device memory, read at
+ * run time.  A launch repeated at the same step changes nothing.  A row's result depends on that row alone.
+ * VIS_ERR_ARG: null pointer, V outside 1..262144, batch outside 1..64, max_tokens <= 0, ld_logits / ld_out < V at batch > 1,
+ * state not 16-byte aligned, out == logits. */
+long long vis_penalty_state_bytes(int V, int batch);
+int vis_penalty_prompt(void* state_row, int V, const void* ids, int n, vis_stream_t stream);
+int vis_penalize_f32(const void* logits, int V, int ld_logits, void* state, const void* params, const void* tokens,
+                     int max_tokens, const void* step_ptr, void* out, int ld_out, int batch, vis_stream_t stream);
+
 /* K10 (batched decode), first half.  For up to 64 in-flight sequences the weight matrix is streamed from HBM
  * ONCE per step by <= 256 persistent workgroups (one per CU, 7-stage LDS-DMA ring, stream-K cut of the
  * (128-column tile, K-step) sequence).  part[slot][R][N] (f32), R = 16 / 32 / 64 for B <= 16 / 32 / 64 (one, two or four

@@ -43,6 +43,19 @@ def seed_kwargs() -> dict:
         raise ValueError("VIS_SEED must be an integer") from None
 
 
+def penalty_kwargs() -> dict:
+    """VIS_REPETITION_PENALTY=<number> (default unset): the analysis and verify requests pass repetition_penalty=<number>
+    (transformers' meaning; the published generation_config.json of Qwen2-VL-7B-Instruct carries 1.05), which keeps a
+    near-greedy reply from repeating an entry until max_tokens cuts it.  Unset: the calls are as before."""
+    v = os.environ.get("VIS_REPETITION_PENALTY", "").strip()
+    if not v:
+        return {}
+    try:
+        return {"repetition_penalty": float(v)}
+    except ValueError:
+        raise ValueError("VIS_REPETITION_PENALTY must be a number") from None
+
+
 def _logger(name: str) -> logging.Logger:
     try:  # pragma: no cover - only inside the reference application
         from utils.logger import setup_logger  # type: ignore
@@ -69,7 +82,7 @@ class _BaseAgent:
             try:
                 completion = self.client.chat.completions.create(
                     model=self.model_id, messages=messages, temperature=self.temperature, max_tokens=self.max_tokens,
-                    **json_mode_kwargs(), **seed_kwargs())
+                    **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs())
                 return completion.choices[0].message.content
             except Exception as e:
                 text = str(e)
@@ -308,13 +321,14 @@ def _many(agent, image_paths, contexts, prepared=None) -> list:
         try:
             if hasattr(agent.client, "complete_many"):
                 replies = agent.client.complete_many(agent.model_id, msgs, agent.temperature, agent.max_tokens,
-                                                     **json_mode_kwargs(), **seed_kwargs())
+                                                     **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs())
                 texts = [r if isinstance(r, Exception) else r.choices[0].message.content for r in replies]
             else:
                 texts = [agent.client.chat.completions.create(model=agent.model_id, messages=m,
                                                               temperature=agent.temperature,
                                                               max_tokens=agent.max_tokens,
-                                                              **json_mode_kwargs(), **seed_kwargs()).choices[0].message.content
+                                                              **json_mode_kwargs(), **seed_kwargs(),
+                                                              **penalty_kwargs()).choices[0].message.content
                          for m in msgs]
         except Exception as e:
             agent.logger.error(f"{agent.nickname}: batched call failed: {e}", exc_info=True)

@@ -76,7 +76,12 @@ class _Completions:
     def create(self, model: Optional[str] = None, messages: Optional[list] = None,
                temperature: Optional[float] = None, max_tokens: Optional[int] = None, logprobs: bool = False,
                top_logprobs: Optional[int] = None, response_format: Optional[dict] = None, top_p: Optional[float] = None,
-               seed: Optional[int] = None, **kwargs) -> ChatCompletion:
+               seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
+               presence_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
+               **kwargs) -> ChatCompletion:
+        given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
+                 "repetition_penalty": repetition_penalty}
+        kwargs.update({name: v for name, v in given.items() if v is not None})
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
                                      top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
                                      **kwargs)
@@ -368,13 +373,17 @@ class LocalVLMClient:
         return build_chat_ids(lm.tokenizer, messages, counts), frames
 
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
-                  top_p=None, seed=None, **kwargs) -> ChatCompletion:
+                  top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
+                  **kwargs) -> ChatCompletion:
         return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
-                                  response_format=response_format, top_p=top_p, seed=seed)[0]
+                                  response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
+                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty)[0]
 
     def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
                       top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
-                      top_p: Optional[float] = None, seed: Optional[int] = None) -> List[ChatCompletion]:
+                      top_p: Optional[float] = None, seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
+                      presence_penalty: Optional[float] = None,
+                      repetition_penalty: Optional[float] = None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -390,13 +399,21 @@ class LocalVLMClient:
         ``top_p`` (OpenAI's / huggingface_hub's): nucleus sampling - each token is drawn from the shortest most-likely set
         holding top_p of the temperature-scaled probability (sampling.py); None or 1 = the whole vocabulary.  ``seed``: every
         request of the call samples with this seed, so its reply depends on its own messages only (not on its place in the
-        batch or what shares it); None = the client's seed, varied per batch slot as before."""
+        batch or what shares it); None = the client's seed, varied per batch slot as before.
+        ``frequency_penalty`` / ``presence_penalty`` (OpenAI's / huggingface_hub's, in [-2, 2]): every logit is lowered by
+        frequency_penalty times the number of times its token was generated so far, and by presence_penalty when it was
+        generated at all.  ``repetition_penalty`` (extension, transformers' meaning, > 0): the logit of every token of the
+        prompt or the reply so far is divided by it when positive, multiplied when negative.  Applied to the raw logits
+        ahead of temperature, the JSON mask and top_p (penalties.py); None or 0 / 0 / 1 = off.  Logprobs keep their meaning."""
         import torch
+        from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
         k = logprobs_k(logprobs, top_logprobs)
         jm = json_mode_of(response_format)
         top_p = check_top_p(top_p)
         seed = check_seed(seed)
+        pen = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
+        pen = {} if pen is None else dict(zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), pen[0]))
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
@@ -406,7 +423,7 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         out: List[ChatCompletion] = []
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -444,7 +461,7 @@ class LocalVLMClient:
                                           ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1",
                                           **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}),
                                           **({"top_p": top_p} if top_p is not None else {}),
-                                          **({"seeds": [seed] * len(idx)} if seed is not None else {}))
+                                          **({"seeds": [seed] * len(idx)} if seed is not None else {}), **pen)
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", {}))
                 if timing:
@@ -487,7 +504,7 @@ class LocalVLMClient:
 
     def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
                               k: Optional[int] = None, jm: bool = False, top_p: Optional[float] = None,
-                              seed: Optional[int] = None) -> List[ChatCompletion]:
+                              seed: Optional[int] = None, pen: Optional[dict] = None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -501,6 +518,7 @@ class LocalVLMClient:
             lpk["json_mode"] = True
         if top_p is not None:
             lpk["top_p"] = top_p
+        lpk.update(pen or {})
 
         def seeds_of(n):
             return {"seeds": [seed] * n} if seed is not None else {}
@@ -578,9 +596,12 @@ class CannedResponseClient:
         self.chat = _Chat(self)
 
     def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
-                  **kwargs) -> ChatCompletion:
+                  frequency_penalty=None, presence_penalty=None, repetition_penalty=None, **kwargs) -> ChatCompletion:
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
                            "response_format": response_format, "top_p": top_p, "seed": seed})
+        given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
+                 "repetition_penalty": repetition_penalty}
+        self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
         reply = self.reply(messages) if callable(self.reply) else self.reply
         return ChatCompletion([_Choice(_Message(reply))], model=model or "")
 

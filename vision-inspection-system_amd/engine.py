@@ -28,6 +28,7 @@ import torch
 from . import hip
 from .json_mode import JsonBuffers, JsonModeError, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
+from .penalties import NEUTRAL, PenaltyBuffers, check_penalties
 from .sampling import SampleBuffers, check_seeds, check_top_p
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
@@ -336,6 +337,11 @@ class Qwen2VLEngine:
         self.smp_on, self.top_p, self.seeded = False, None, False
         self._smp: Optional[SampleBuffers] = None
         self._slot_seed: Dict[int, int] = {}
+        # logit penalties (generate(..., repetition_penalty=, frequency_penalty=, presence_penalty=)): while on, every pick
+        # reads the row vis_penalize_f32 wrote instead of the raw logits; _slot_pen: slot -> the request's (r, f, q)
+        self.pen_on = False
+        self._pen: Optional[PenaltyBuffers] = None
+        self._slot_pen: Dict[int, tuple] = {}
 
     # ------------------------------------------------------------------ vision tower
     def vision_forward(self, frames: Sequence[torch.Tensor], split_rows: bool = True) -> torch.Tensor:
@@ -672,6 +678,7 @@ class Qwen2VLEngine:
         if self.json_on:
             self._json.reset(slot)
         self._seed_slot(slot)
+        self._penalty_slot(slot, ids_dev)
         self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
                    cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot, slot)   # per-slot workspace: prefills
         # of different slots may run concurrently on different streams
@@ -742,6 +749,7 @@ class Qwen2VLEngine:
         nq = (Hq + 2 * Hkv) * D
         x = torch.empty((k * n, H), dtype=bf, device=dev)
         tabs = None
+        ids_devs = []
         for j, (slot, ids, ids_dev, img) in enumerate(items):
             ids_np = np.asarray(list(ids), dtype=np.int64)
             if len(ids_np) != S or not np.array_equal(ids_np == cfg.image_token_id, is_img) or \
@@ -758,6 +766,7 @@ class Qwen2VLEngine:
             self.sin_b[slot][:S + n_dec].copy_(tabs[1], non_blocking=True)
             if ids_dev is None:
                 ids_dev = hip.upload(ids_np.astype(np.int32), dev)
+            ids_devs.append(ids_dev)
             xj = x[j * n:(j + 1) * n]
             hip.gather_rows(w.embed, ids_dev[P:], xj)
             hip.scatter_rows(img, tabs[2] - P, xj)
@@ -853,6 +862,7 @@ class Qwen2VLEngine:
             if self.json_on:
                 self._json.reset(slot)
             self._seed_slot(slot)
+            self._penalty_slot(slot, ids_devs[j])
             self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
                        self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
                        self.seed + 0x9E3779B9 * slot, slot)
@@ -887,7 +897,8 @@ class Qwen2VLEngine:
     def prefill_many(self, requests: Sequence, temperature: float = 0.0,
                      seed: int = 0, max_new_tokens: Optional[int] = None,
                      ids_dev: Optional[Sequence[torch.Tensor]] = None,
-                     seeds: Optional[Sequence[int]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
+                     seeds: Optional[Sequence[int]] = None,
+                     penalties: Optional[Sequence[tuple]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
         """Prefill the requests into consecutive slots.  The prefills are independent kernel chains: they are issued round-robin
         on a few HIP streams (VIS_PREFILL_STREAMS, default 2: 418 -> 381 ms for 8 images) so that the ragged last round of one image's GEMM /
         attention grids is filled by another image's workgroups.  Returns with the current stream ordered after
@@ -898,6 +909,7 @@ class Qwen2VLEngine:
         images 1.. are still being decoded).  Lazy requests are resolved in order, a ViT group at a time; one that
         raises gets no slot and its exception is returned instead of failing the batch.
         ``seeds``: request b's own sampling seed (read by the picks while nucleus sampling / seeds are on).
+        ``penalties``: request b's (repetition, frequency, presence) penalties (read by the picks while penalties are on).
         Returns (slot of request b or None, exception of request b or None)."""
         B = len(requests)
         lazy = any(callable(r) for r in requests)
@@ -949,6 +961,8 @@ class Qwen2VLEngine:
                     continue
                 if seeds is not None:
                     self._slot_seed[next_slot] = seeds[b]
+                if penalties is not None:
+                    self._slot_pen[next_slot] = penalties[b]
                 self.prefill(r[0], r[1], ids_dev=ids_dev[b] if ids_dev else None, temperature=temperature, seed=seed,
                              max_new_tokens=max_new_tokens, slot=next_slot, prefix=prefix_for(r[0]))
                 slots[b] = next_slot
@@ -993,6 +1007,8 @@ class Qwen2VLEngine:
             slot_of = {b: next_slot + i for i, b in enumerate(grp_all)}       # slots follow the request order
             if seeds is not None:
                 self._slot_seed.update({slot_of[b]: seeds[b] for b in grp_all})
+            if penalties is not None:
+                self._slot_pen.update({slot_of[b]: penalties[b] for b in grp_all})
             next_slot += len(grp_all)
             if merged:
                 st = streams[(g0 // vb) % n_streams]         # consecutive groups alternate streams
@@ -1123,9 +1139,30 @@ class Qwen2VLEngine:
         if self.smp_on:
             self._smp.set_slot(slot, self._slot_seed.get(slot, self.seed + 0x9E3779B9 * slot))
 
+    # ------------------------------------------------------------------ logit penalties
+    def _begin_penalties(self, penalties: Optional[Sequence[tuple]]) -> None:
+        """Route every pick of the request about to run through vis_penalize_f32 when some request of it carries a penalty
+        (penalties: check_penalties' result - one (r, f, q) per request, or None = off)."""
+        self.pen_on = penalties is not None
+        self._slot_pen = {}
+        if self.pen_on and self._pen is None:
+            self._pen = PenaltyBuffers(self.max_batch, self.cfg.vocab, self.device)
+
+    def _end_penalties(self) -> None:
+        self.pen_on = False
+        self._slot_pen = {}
+
+    def _penalty_slot(self, slot: int, ids_dev: torch.Tensor) -> None:
+        """Before a prompt pass's pick: fresh token statistics of ``slot``, the request's triple and its prompt ids."""
+        if self.pen_on:
+            self._pen.begin(slot, ids_dev, *self._slot_pen.get(slot, NEUTRAL))
+
     def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
         """The next-token pick of slots slot .. slot + B - 1: vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick;
-        vis_sample_f32 (seeds from the device buffer, the JSON rows as its mask) while nucleus sampling / seeds are on."""
+        vis_sample_f32 (seeds from the device buffer, the JSON rows as its mask) while nucleus sampling / seeds are on.  While
+        penalties are on, all of them read the penalised copy of the rows (vis_penalize_f32); the raw rows stay intact."""
+        if self.pen_on:
+            logits = self._pen.apply(logits, tokens, step, slot)
         if self.smp_on:
             allow = self._json.mask(tokens, step, slot) if self.json_on else None
             self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
@@ -1138,8 +1175,8 @@ class Qwen2VLEngine:
 
     def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
         """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode; while nucleus sampling / seeds
-        are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
-        if self.smp_on:
+        or penalties are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
+        if self.smp_on or self.pen_on:
             hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
             self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
             return
@@ -1406,9 +1443,10 @@ class Qwen2VLEngine:
 
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
         # sampling parameters, the batch size, the logprobs k, JSON mode and top_p are kernel arguments baked into the graph;
-        # the row seeds of vis_sample_f32 are read from device memory at replay, so only whether they are in use is part of it
+        # the row seeds of vis_sample_f32 and the penalty values of vis_penalize_f32 are read from device memory at replay, so
+        # only whether they are in use is part of it
         key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch, self.lp_k,
-               self.json_on, self.top_p, self.seeded)
+               self.json_on, self.top_p, self.seeded, self.pen_on)
         if key in self._graphs:
             return self._graphs[key]
         step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
@@ -1525,7 +1563,8 @@ class Qwen2VLEngine:
     def generate(self, input_ids: Sequence[int], frames: Sequence[torch.Tensor] = (), max_new_tokens: int = 128,
                  ignore_eos: bool = False, use_graph: bool = True, check_every: int = 16,
                  temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
-                 json_mode: bool = False, top_p: Optional[float] = None) -> List[int]:
+                 json_mode: bool = False, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
@@ -1534,11 +1573,18 @@ class Qwen2VLEngine:
         continue a JSON object (json_grammar; needs ``self.tokenizer``): the reply is a prefix of one, complete when it
         ended on EOS; JsonModeError when the vocabulary could not continue it.  Logprobs keep their meaning (raw logits),
         so top_logprobs may list tokens the mask forbade.  ``top_p`` in [0, 1]: nucleus sampling (sampling.py) - each pick
-        draws from the shortest most-likely prefix holding top_p of the temperature-scaled mass; None or 1 = off."""
+        draws from the shortest most-likely prefix holding top_p of the temperature-scaled mass; None or 1 = off.
+        ``repetition_penalty`` > 0 (transformers' meaning: over prompt and generated ids), ``frequency_penalty`` /
+        ``presence_penalty`` in [-2, 2] (OpenAI's: over generated ids): penalties.py - applied to the raw logits ahead of
+        everything above; None or 1 / 0 / 0 = off.  Logprobs keep their meaning (raw logits)."""
         check_top_p(top_p)
+        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         self._begin_logprobs(logprobs)
         self._begin_json(json_mode)
         self._begin_sampling(top_p, False)
+        self._begin_penalties(penalties)
+        if penalties is not None:
+            self._slot_pen[0] = penalties[0]
         room = self.max_ctx - len(input_ids) - 1
         if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
             self._warned_clamp = True          # said once per engine: the reply may end before the model is done
@@ -1563,6 +1609,7 @@ class Qwen2VLEngine:
             self.lp_k = None
             self.json_on = False
             self._end_sampling()
+            self._end_penalties()
 
     def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time (tracing)
@@ -1597,7 +1644,8 @@ class Qwen2VLEngine:
     def generate_batch(self, requests: Sequence,
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
-                       json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None) -> list:
+                       json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
+                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
@@ -1605,7 +1653,9 @@ class Qwen2VLEngine:
         ``logprobs``: as in generate; ``last_logprobs`` then holds one record per request (None for a failed one).
         ``json_mode``: as in generate; a request whose JSON text could not be continued gets a JsonModeError.
         ``top_p``: as in generate.  ``seeds``: one integer per request, its own sampling seed in place of the slot-derived
-        one, so a request's sampled reply does not depend on its slot or on what shares the batch."""
+        one, so a request's sampled reply does not depend on its slot or on what shares the batch.
+        ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty``: as in generate, each a number or a sequence
+        with one value per request."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -1614,6 +1664,7 @@ class Qwen2VLEngine:
             raise ValueError("json_mode must be True or False")
         check_top_p(top_p)
         seeds = check_seeds(seeds, n_req)
+        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
         if n_req == 1:
             r = requests[0]
             if callable(r):
@@ -1625,28 +1676,32 @@ class Qwen2VLEngine:
             try:
                 return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature,
                                       seed if seeds is None else seeds[0], logprobs=logprobs, json_mode=json_mode,
-                                      top_p=top_p)]
+                                      top_p=top_p, **({} if penalties is None else dict(
+                                          zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))))]
             except JsonModeError as e:
                 return [e]
         self._begin_logprobs(logprobs)
         self._begin_json(json_mode)
         self._begin_sampling(top_p, seeds is not None)
+        self._begin_penalties(penalties)
         try:
-            return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, seeds)
+            return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, seeds,
+                                        penalties)
         finally:
             self.lp_k = None
             self.json_on = False
             self._end_sampling()
+            self._end_penalties()
 
     def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                        seeds=None) -> list:
+                        seeds=None, penalties=None) -> list:
         n_req = len(requests)
         # every prompt's own limit (prompt + new tokens <= context) is applied by its prefill; the shared loop below
         # runs to the limit of the longest one
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
         slots, errors = self.prefill_many(requests, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens,
-                                          seeds=seeds)
+                                          seeds=seeds, penalties=penalties)
         ev[1].record()
         live = [b for b in range(n_req) if slots[b] is not None]
         B = len(live)

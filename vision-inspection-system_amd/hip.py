@@ -60,6 +60,9 @@ _SIGS = {
     "vis_gemv_bf16_argmax_masked": "pppp" + "iii" + "f" + "ppp" + "i" + "pp" + "fu" + "p" + "p",
     "vis_sample_ws_bytes": "ii",
     "vis_sample_f32": "p" + "ii" + "p" + "i" + "ff" + "pp" + "i" + "pp" + "i" + "pp" + "p",
+    "vis_penalty_state_bytes": "ii",
+    "vis_penalty_prompt": "pi" + "pi" + "p",
+    "vis_penalize_f32": "p" + "ii" + "ppp" + "i" + "pp" + "ii" + "p",
     "vis_gemm_decode_ksplit": "ii",
     "vis_gemm_decode_bf16": "pppp" + "iiiiiiii" + "p",
     "vis_gemm_decode_fp8_ksplit": "ii",
@@ -204,6 +207,7 @@ def load() -> ctypes.CDLL:
     lib.vis_decode_proj_ws_bytes.restype = ctypes.c_longlong
     lib.vis_logprobs_ws_bytes.restype = ctypes.c_longlong
     lib.vis_sample_ws_bytes.restype = ctypes.c_longlong
+    lib.vis_penalty_state_bytes.restype = ctypes.c_longlong
     _lib = _Lib(lib)
     return _lib
 
@@ -1184,6 +1188,46 @@ def sample(logits: torch.Tensor, tokens: torch.Tensor, cur_token: torch.Tensor, 
                                (1.0 / temperature) if temperature > 0 else 0.0, float(top_p), _ptr(seeds), _ptr(tokens),
                                tokens.numel() // B, _ptr(cur_token), _ptr(step), B, _ptr(ws), _ptr(nkeep), _stream())
     _check(rc, "vis_sample_f32")
+
+
+def penalty_state(V: int, batch: int, device) -> torch.Tensor:
+    """Zeroed token statistics of vis_penalize_f32 for ``batch`` rows of V ids, [batch, n] uint8 (a zeroed row = a fresh
+    sequence; row b's slice serves one row)."""
+    n = int(load().vis_penalty_state_bytes(V, batch))
+    if n <= 0:
+        raise HipLibraryError(f"penalty_state: unsupported V={V} batch={batch}")
+    return torch.zeros((batch, n // batch), dtype=torch.uint8, device=device)
+
+
+def penalty_prompt(state_row: torch.Tensor, V: int, ids: torch.Tensor) -> None:
+    """Mark the prompt ids (int32, device) of ONE row of penalty_state; ids outside [0, V) are skipped."""
+    if state_row.dtype != torch.uint8 or not state_row.is_contiguous() or ids.dtype != torch.int32 or not ids.is_contiguous() \
+            or state_row.numel() != int(load().vis_penalty_state_bytes(V, 1)):
+        raise HipLibraryError("penalty_prompt: one uint8 row of penalty_state / contiguous int32 ids required")
+    rc = load().vis_penalty_prompt(_ptr(state_row), V, _ptr(ids), ids.numel(), _stream())
+    _check(rc, "vis_penalty_prompt")
+
+
+def penalize(logits: torch.Tensor, state: torch.Tensor, params: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor,
+             out: torch.Tensor) -> None:
+    """Penalised copy of the raw logits (vis_penalize_f32): folds the tokens picked since the last call into the rows' counts,
+    then out = repetition / frequency / presence penalties applied to logits, which stay intact.  logits, out [V] or [B, V]
+    f32; state: B rows of penalty_state; params [B, 3] f32 = (r, f, q) in device memory; tokens [T] / [B, T], step [B]."""
+    if logits.dtype != torch.float32 or out.dtype != torch.float32 or params.dtype != torch.float32 \
+            or tokens.dtype != torch.int32 or step.dtype != torch.int32 or state.dtype != torch.uint8:
+        raise HipLibraryError("penalize: f32 logits, out, params / int32 tokens, step / uint8 state required")
+    B = logits.shape[0] if logits.dim() == 2 else 1
+    V = logits.shape[-1]
+    if out.shape != logits.shape or step.numel() != B or params.numel() != 3 * B or tokens.numel() % B:
+        raise HipLibraryError("penalize: bad state shapes")
+    if logits.stride(-1) != 1 or out.stride(-1) != 1 or not (tokens.is_contiguous() and step.is_contiguous()
+                                                             and params.is_contiguous() and state.is_contiguous()) \
+            or state.numel() != int(load().vis_penalty_state_bytes(V, B)):
+        raise HipLibraryError("penalize: bad strides / state is not B rows of penalty_state")
+    rc = load().vis_penalize_f32(_ptr(logits), V, logits.stride(0) if logits.dim() == 2 else V, _ptr(state), _ptr(params),
+                                 _ptr(tokens), tokens.numel() // B, _ptr(step), _ptr(out),
+                                 out.stride(0) if out.dim() == 2 else V, B, _stream())
+    _check(rc, "vis_penalize_f32")
 
 
 DP_PLAIN, DP_SWIGLU, DP_RESID_NORMW = 0, 1, 2

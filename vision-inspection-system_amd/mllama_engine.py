@@ -33,6 +33,7 @@ import torch
 from . import hip
 from .json_mode import JsonBuffers, JsonModeError, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
+from .penalties import NEUTRAL, PenaltyBuffers, check_penalties
 from .sampling import SampleBuffers, check_seeds, check_top_p
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
 
@@ -208,6 +209,10 @@ class MllamaEngine:
         self.smp_on, self.top_p, self.seeded = False, None, False
         self._smp: Optional[SampleBuffers] = None
         self._slot_seed: Dict[int, int] = {}
+        # logit penalties, as in Qwen2VLEngine
+        self.pen_on = False
+        self._pen: Optional[PenaltyBuffers] = None
+        self._slot_pen: Dict[int, tuple] = {}
 
     # ------------------------------------------------------------------ preprocessing (geometry on host, pixels on GPU)
     def prepare_image(self, frame: torch.Tensor):
@@ -415,7 +420,8 @@ class MllamaEngine:
             xvt = torch.empty((Hkv, D, self.Tk), dtype=bf, device=dev)
             q2 = torch.empty((S, Hq * D), dtype=bf, device=dev)
         x = torch.empty((S, H), dtype=bf, device=dev)
-        hip.gather_rows(w.embed, hip.upload(ids_np.astype(np.int32), dev), x)
+        ids_dev = hip.upload(ids_np.astype(np.int32), dev)
+        hip.gather_rows(w.embed, ids_dev, x)
         cos, sin = self.cos_t[:S], self.sin_t[:S]
         work = hip.make_attn_pairs(0, S, dev)        # causal self-attention: paired query blocks (hip.attn_prefill_pairs)
         ld = _round_up(S, 64)
@@ -486,6 +492,7 @@ class MllamaEngine:
         if self.json_on:
             self._json.reset(slot)
         self._seed_slot(slot)
+        self._penalty_slot(slot, ids_dev)
         self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
                    cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot, slot)
         self._logprobs_after_pick(1, slot)
@@ -512,7 +519,7 @@ class MllamaEngine:
         nm = int(np.nonzero(ids0 == cfg.image_token_id)[0][0])
         M = k * S
         x = torch.empty((M, H), dtype=bf, device=dev)
-        xworks, xvts = [], []
+        xworks, xvts, ids_devs = [], [], []
         for j, (slot, ids, cross, n_tiles) in enumerate(items):
             ids_np = np.asarray(list(ids), dtype=np.int64)
             locs = np.nonzero(ids_np == cfg.image_token_id)[0]
@@ -520,7 +527,8 @@ class MllamaEngine:
                 raise ValueError("_prefill_group: the prompts of a group must share length and image-token position")
             if ids_np.min() < 0 or ids_np.max() >= cfg.vocab + 8:
                 raise ValueError("token id out of range")
-            hip.gather_rows(w.embed, hip.upload(ids_np.astype(np.int32), dev), x[j * S:(j + 1) * S])
+            ids_devs.append(hip.upload(ids_np.astype(np.int32), dev))
+            hip.gather_rows(w.embed, ids_devs[j], x[j * S:(j + 1) * S])
             nR = n_tiles * P
             self.nkeys_b[slot:slot + 1].fill_(nR - 1)
             xitems = [(q0, min(128, nm - q0), 0, TP) for q0 in range(0, nm, 128)] + \
@@ -622,6 +630,7 @@ class MllamaEngine:
             if self.json_on:
                 self._json.reset(slot)
             self._seed_slot(slot)
+            self._penalty_slot(slot, ids_devs[j])
             self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
                        self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
                        self.seed + 0x9E3779B9 * slot, slot)
@@ -717,9 +726,28 @@ class MllamaEngine:
         if self.smp_on:
             self._smp.set_slot(slot, self._slot_seed.get(slot, self.seed + 0x9E3779B9 * slot))
 
+    def _begin_penalties(self, penalties: Optional[Sequence[tuple]]) -> None:
+        """Route every pick through vis_penalize_f32 for this request (Qwen2VLEngine._begin_penalties)."""
+        self.pen_on = penalties is not None
+        self._slot_pen = {}
+        if self.pen_on and self._pen is None:
+            self._pen = PenaltyBuffers(self.max_batch, self.cfg.vocab, self.device)
+
+    def _end_penalties(self) -> None:
+        self.pen_on = False
+        self._slot_pen = {}
+
+    def _penalty_slot(self, slot: int, ids_dev: torch.Tensor) -> None:
+        """Before a prompt pass's pick: fresh token statistics of ``slot``, the request's triple and its prompt ids (the image
+        token's id equals the vocabulary size: the kernel skips it)."""
+        if self.pen_on:
+            self._pen.begin(slot, ids_dev, *self._slot_pen.get(slot, NEUTRAL))
+
     def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
         """vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick, for slots slot .. slot + B - 1; vis_sample_f32
-        while nucleus sampling / seeds are on."""
+        while nucleus sampling / seeds are on.  While penalties are on, all of them read the penalised copy of the rows."""
+        if self.pen_on:
+            logits = self._pen.apply(logits, tokens, step, slot)
         if self.smp_on:
             allow = self._json.mask(tokens, step, slot) if self.json_on else None
             self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
@@ -732,8 +760,8 @@ class MllamaEngine:
 
     def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
         """The fused lm_head + pick of the single-sequence step, masked in JSON mode; the plain lm_head GEMV + _pick while
-        nucleus sampling / seeds are on."""
-        if self.smp_on:
+        nucleus sampling / seeds or penalties are on."""
+        if self.smp_on or self.pen_on:
             hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
             self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
             return
@@ -745,7 +773,8 @@ class MllamaEngine:
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k, self.json_on, self.top_p, self.seeded)
+        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k, self.json_on, self.top_p, self.seeded,
+               self.pen_on)
         if key in self._graphs:
             return self._graphs[key]
         snap = (self.step.clone(), self.cur_token.clone())
@@ -910,7 +939,7 @@ class MllamaEngine:
         self._logprobs_after_pick(B)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B, self.lp_k, self.json_on, self.top_p, self.seeded)
+        key = (self.temperature, self.seed, B, self.lp_k, self.json_on, self.top_p, self.seeded, self.pen_on)
         if key in self._graphs_b:
             return self._graphs_b[key]
         snap = (self.step_b.clone(), self.cur_b.clone())
@@ -932,14 +961,16 @@ class MllamaEngine:
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
                        chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
-                       top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None) -> list:
+                       top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
+                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
         decode, so the prompt pass of image 0 runs while images 1.. are still being decoded); one that raises gets no
         slot and its exception takes its place in the returned list.  ``logprobs``: as in generate; ``last_logprobs`` then
         holds one record per request (None for a failed one).  ``json_mode``: as in generate; a request whose JSON text could
-        not be continued gets a JsonModeError.  ``top_p`` / ``seeds``: as in Qwen2VLEngine.generate_batch."""
+        not be continued gets a JsonModeError.  ``top_p`` / ``seeds`` and the three penalties (a number or one value per request): as in
+        Qwen2VLEngine.generate_batch."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -949,6 +980,8 @@ class MllamaEngine:
         check_top_p(top_p)
         seeds = check_seeds(seeds, n_req)
         seed0 = seed if seeds is None else seeds[0]
+        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
+        pen0 = {} if penalties is None else dict(zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))
         lazy = any(callable(r) for r in requests)
         if lazy and n_req == 1:
             # one lazy request (always the case with max_batch == 1, where the batched buffers do not even exist): the
@@ -956,7 +989,7 @@ class MllamaEngine:
             try:
                 ids, fr = requests[0]() if callable(requests[0]) else requests[0]
                 return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, top_p=top_p)]
+                                      json_mode=json_mode, top_p=top_p, **pen0)]
             except Exception as e:      # noqa: BLE001
                 self.last_logprobs = [None] if logprobs is not None else None
                 return [e]
@@ -966,20 +999,24 @@ class MllamaEngine:
             ids, fr = requests[0]
             try:
                 return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, top_p=top_p)]
+                                      json_mode=json_mode, top_p=top_p, **pen0)]
             except JsonModeError as e:
                 return [e]
         self._begin_logprobs(logprobs)
         self._begin_json(json_mode)
         self._begin_sampling(top_p, seeds is not None)
+        self._begin_penalties(penalties)
         try:
-            return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds)
+            return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds,
+                                        penalties)
         finally:
             self.lp_k = None
             self.json_on = False
             self._end_sampling()
+            self._end_penalties()
 
-    def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds=None) -> list:
+    def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds=None,
+                        penalties=None) -> list:
         n_req = len(requests)
         lazy = any(callable(r) for r in requests)
         slots: List[Optional[int]] = [None] * n_req
@@ -1034,6 +1071,8 @@ class MllamaEngine:
                             cs[0].record_stream(st)
                             if seeds is not None:
                                 self._slot_seed[B + len(items)] = seeds[b]
+                            if penalties is not None:
+                                self._slot_pen[B + len(items)] = penalties[b]
                             items.append((B + len(items), ids, cs[0], cs[1]))
                         self._prefill_group(items, temperature, seed)
                     for (b, _, _) in grp:
@@ -1048,6 +1087,8 @@ class MllamaEngine:
             for (b, ids, fr), cs in zip(grp, crosses):
                 if seeds is not None:
                     self._slot_seed[B] = seeds[b]
+                if penalties is not None:
+                    self._slot_pen[B] = penalties[b]
                 try:
                     if n_streams > 1:
                         st = self._prefill_streams[B % n_streams]
@@ -1119,16 +1160,21 @@ class MllamaEngine:
     def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
                  chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False,
-                 top_p: Optional[float] = None) -> List[int]:
+                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None) -> List[int]:
         """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
         logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
         None = off, no extra launch.  ``json_mode``: every pick restricted to the tokens that continue a JSON object, as in
         Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it).  ``top_p``: nucleus sampling, as in
-        Qwen2VLEngine.generate."""
+        Qwen2VLEngine.generate; so are ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty`` (penalties.py)."""
         check_top_p(top_p)
+        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         self._begin_logprobs(logprobs)
         self._begin_json(json_mode)
         self._begin_sampling(top_p, False)
+        self._begin_penalties(penalties)
+        if penalties is not None:
+            self._slot_pen[0] = penalties[0]
         try:
             return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
         except hip.ChainStalled as e:
@@ -1143,6 +1189,7 @@ class MllamaEngine:
             self.lp_k = None
             self.json_on = False
             self._end_sampling()
+            self._end_penalties()
 
     def _generate(self, input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time, as in Qwen2VLEngine
