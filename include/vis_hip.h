@@ -444,6 +444,20 @@ int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, const void* sw,
                  void* C, void* work, int ksplit, int M, int N, int K, int lda, int ldw, int ldc, int ldr, int act,
                  vis_stream_t stream);
 
+/* Host-only (no HIP call, callable without a GPU): what vis_gemm_bf16 / vis_gemm_fp8 would launch for this problem,
+ * honouring the VIS_GEMM_* A/B variables exactly as the launchers do (both launch FROM this plan).  aligned16: C and R
+ * (if any) are 16-byte aligned; split: a split-K call of vis_gemm_fp8 (work != NULL).  Writes plan[0] = launches,
+ * plan[1] = LDS-staged "wide" epilogue (else direct), plan[2] = non-temporal C stores, then per launch five ints
+ * {kernel id, first W row, W rows, tiles_m, tiles_n}.  Kernel ids: 1 = 128x128, 2 = 3-stage 256x128, 4 = 2-phase
+ * 256x256, 5 / 6 = 2-phase 256x128 / 256x192, 7 = 256x256 ping-pong, 8 = 128x256 ping-pong half-tiles.  Returns the
+ * number of launches (<= 4), or 0 for arguments the launcher rejects by shape or when plan_ints < 3 + 5 * launches.
+ * The queries see no pointers: what the launchers reject by pointer (null, misaligned operands) or by the presence of a
+ * bias (vis_gemm_fp8 takes none with SwiGLU) still gets a plan. */
+int vis_gemm_bf16_plan(int M, int N, int K, int ldc, int ldr, int act, int has_residual, int aligned16, int* plan,
+                       int plan_ints);
+int vis_gemm_fp8_plan(int M, int N, int K, int ldc, int ldr, int act, int has_residual, int aligned16, int split,
+                      int* plan, int plan_ints);
+
 /* Per-row dynamic quantisation of bf16 activations to e4m3: scale[m] = amax(row)/448, q = rne(x * (1/scale)); with
  * norm_w != NULL the row is normalised first (K <= 4096): RMSNorm when norm_b == NULL, LayerNorm otherwise - the
  * same bf16 values vis_rmsnorm_bf16 / vis_layernorm_bf16 write. */

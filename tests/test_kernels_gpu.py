@@ -55,18 +55,19 @@ def test_gemm_plain(hip, device, M, N, K):
 
 
 @pytest.mark.parametrize("M,N,K,kind", [
-    (2249, 4608, 3584, "bias"),        # LLM qkv       -> 256x192 tiles (one round)
-    (2249, 3584, 3584, "residual"),    # LLM o         -> 256x128 pipelined tiles
-    (2249, 37888, 3584, "swiglu"),     # LLM gate/up   -> 256x256 whole rounds + 128x128 remainder columns
-    (4900, 5120, 1280, "quickgelu"),   # ViT fc1       -> 256x256
-    (4900, 1280, 5120, "residual"),    # ViT fc2       -> 256x128
-    (4900, 3840, 1280, "bias"),        # ViT qkv       -> 128x128
-    (2300, 768, 1024, "bias"),         # ragged M and N tails on the 256-row kernels
+    (2249, 4608, 3584, "bias"),        # LLM qkv       -> 256x256 ping-pong, 162 tiles
+    (2249, 3584, 3584, "residual"),    # LLM o         -> 128x256 ping-pong half-tiles (252 = one round)
+    (2249, 37888, 3584, "swiglu"),     # LLM gate/up   -> 256x256 whole rounds (142 columns) + half-tiles on the 6 remainder columns
+    (4900, 5120, 1280, "quickgelu"),   # ViT fc1       -> 256x256 ping-pong
+    (4900, 1280, 5120, "residual"),    # ViT fc2       -> 128x256 half-tiles
+    (4900, 3840, 1280, "bias"),        # ViT qkv       -> 256x256 one whole round (12 columns) + half-tiles on the last 3
+    (2300, 768, 1024, "bias"),         # ragged M and N tails on the half-tile kernel
     (2049, 12296, 1088, "bias"),       # ping-pong 256x256: odd K-tile count (17), ragged M and N edges
     (4096, 6144, 1024, "residual"),    # ping-pong 256x256: exactly full tiles, even K-tile count
 ])
 def test_gemm_production_shapes(hip, device, M, N, K, kind):
-    """The shapes the 7B prefill actually runs, so that every tile kernel and dispatch branch is parity-checked."""
+    """The shapes the 7B prefill actually runs, so that every tile kernel and dispatch branch is parity-checked.  The kernel
+    each comment names is asserted through the plan query in tests/test_gemm_exact.py (PRODUCTION)."""
     from vision_inspection_system_amd.weights import interleave_gate_up
     a = _randn((M, K), device, 11)
     w = _randn((N, K), device, 12, 1.0 / math.sqrt(K))
@@ -97,13 +98,14 @@ def test_gemm_pingpong_exact_integers(hip, device, K):
     single stale or early LDS half-tile (a staging race in the ping-pong schedule) shows as a wrong integer.  Run
     several times: a race would come and go."""
     M, N = 2048 + 40, 12288 + 24          # 9 x 49 tiles of 256 x 256 -> the ping-pong kernel, ragged edges
+    from gemm_exact import assert_live_k, draw_w
     g = torch.Generator(device="cpu").manual_seed(K)
     a = torch.randint(-2, 3, (M, K), generator=g).to(torch.bfloat16).to(device)
-    w = torch.randint(-1, 2, (N, K), generator=g).to(torch.bfloat16).to(device)
-    # keep |sum| < 256 so that the bf16 output is exact: zero out all but 120 columns of k per row of w
-    keep = torch.zeros(K, dtype=torch.bool)
-    keep[torch.randperm(K, generator=g)[:120]] = True
-    w = w * keep.to(device).to(torch.bfloat16)
+    # keep |sum| < 256 so that the bf16 output is exact: 120 non-zero columns of k per row of w, each row its OWN support,
+    # so that every k index contributes to every 128-column block (one mask for all rows left 88 % of them dead)
+    w = draw_w(N, K, 64, np.random.default_rng(K))
+    assert_live_k(w, 64)
+    w = w.to(torch.bfloat16).to(device)
     ref = (a.float() @ w.float().t())
     assert float(ref.abs().max()) <= 256
     for _ in range(5):
@@ -508,10 +510,9 @@ def test_gemm_fp8_pingpong_exact_integers(hip, device, K):
     M, N = 2048 + 40, 12288 + 24
     g = torch.Generator(device="cpu").manual_seed(K)
     a = torch.randint(-2, 3, (M, K), generator=g).float()
-    w = torch.randint(-1, 2, (N, K), generator=g).float()
-    keep = torch.zeros(K)
-    keep[torch.randperm(K, generator=g)[:120]] = 1.0
-    w = w * keep
+    from gemm_exact import assert_live_k, draw_w
+    w = draw_w(N, K, 128, np.random.default_rng(K))      # each row of w its own 120 non-zero columns: every k index is live
+    assert_live_k(w, 128)
     aq = a.to(torch.float8_e4m3fn).view(torch.uint8).to(device)
     wq = w.to(torch.float8_e4m3fn).view(torch.uint8).to(device)
     sa = torch.ones(M, dtype=torch.float32, device=device)

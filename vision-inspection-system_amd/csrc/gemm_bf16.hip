@@ -1416,124 +1416,184 @@ __global__ __launch_bounds__(256) void gemm_splitk_finalize_kernel(GemmArgs p) {
 //  * 128x256 ping-pong half-tiles (1 WG/CU): what would otherwise go to 128x128 tiles, when the half-tile grid needs
 //    no more rounds (LLM o, ViT proj, the gate/up remainder columns, the merger);
 //  * 128x128 (2 WG/CU): everything else.
-static int gemm_dispatch(GemmArgs p, hipStream_t stream) {
+// The choice is host arithmetic on (M, N, K) alone and lives in gemm_plan(); gemm_dispatch() launches FROM that plan and
+// vis_gemm_bf16_plan() exports it, so what a test asks about and what runs cannot drift apart.
+// Kernel ids (the VIS_GEMM_TILE values where one exists): 1 = 128x128, 2 = 3-stage 256x128, 4 = 2-phase 256x256,
+// 5 / 6 = 2-phase 256x128 / 256x192, 7 = 256x256 ping-pong, 8 = 128x256 ping-pong half-tiles.
+#define GEMM_PLAN_MAX 4
+struct GemmLaunch { int kernel, n0, ncols, tiles_m, tiles_n; };   // covers W rows [n0, n0 + ncols)
+struct GemmPlan { int n; GemmLaunch l[GEMM_PLAN_MAX]; };
+
+static void gemm_plan(int M, int Ntot, int K, GemmPlan* plan) {
   static const int forced = [] { const char* e = getenv("VIS_GEMM_TILE"); return e ? atoi(e) : 0; }();
-  const int M = p.M, N = p.N, K = p.K;
-  const int tn1 = (N + GEMM_BN - 1) / GEMM_BN;
-  const int t2 = ((M + GEMM2_BM - 1) / GEMM2_BM) * tn1;
-  const int tm4 = (M + GEMM4_B - 1) / GEMM4_B, tn4 = (N + GEMM4_B - 1) / GEMM4_B;
-  const int t4 = tm4 * tn4, last = t4 % 256;
-  const bool big = forced == 2;   // the 3-stage 256x128 kernel: A/B only
   static const int pp_env = [] { const char* e = getenv("VIS_GEMM_PP"); return e ? atoi(e) : 1; }();   // 0: the 2-phase kernel (A/B)
-  const bool use_pp = (pp_env != 0 && forced != 4) || forced == 7;
-  // Kernel choice by a two-line cost model fitted to cold-cache timings of the production shapes (tools/gemm_tiles_ab.py,
-  // r02): a 256x256 ping-pong tile costs ~1.41 us per 64-wide K-step + 4.3 us (prologue + epilogue), one per CU; a
-  // 128x128 tile ~1.2 us per K-step + 3 us with two per CU.  Rounds are what ragged grids pay for:
-  //   ViT qkv  4900x3840x1280: 300 tiles of 256^2 = 2 rounds (66 us) beat 1170 of 128^2 = 3 rounds (78 us);
-  //   LLM qkv  2249x4608x3584: 162 tiles of 256^2 on 63 % of the CUs (83 us) still beat 216 tiles of 256x192 (90 us);
-  //   LLM o    2249x3584x3584: 504 tiles of 128^2 = one full round of two per CU (75 us) beat 252 of 256x128 (85 us).
-  // Every kernel accumulates K in the same order, so the choice (which depends on M) never changes a result bit.
-  const int nk64 = K / GEMM_BK;
-  const int t1 = ((M + GEMM_BM - 1) / GEMM_BM) * tn1;
-  const float cost1 = (float)((t1 + 511) / 512) * (1.2f * nk64 + 3.0f);
-  const float cost4 = (float)((t4 + 255) / 256) * (1.41f * nk64 + 4.3f);
-  bool huge = forced ? (forced == 4 || forced == 7) : (K >= 256 && M > 128 && N > 128 && cost4 < cost1);
-  int cols4 = tn4;  // 256-wide tile columns given to the 256x256 kernel
-  // ... and (r05) ONE whole round + a remainder of fewer than 64 tiles: the second round of a 294-tile grid (LLM o at four images)
-  // or a 264-tile one (the Auditor's qkv) costs almost a full round for 15 % / 3 % of the tiles - 155 -> 141 us and 162 -> 141 us
-  // with the remainder columns on half-tiles (tools/probes/gemm_mix_probe.py, launches alone; inside `dual` at 32 per step the
-  // difference is within run-to-run noise, 9.93 vs 9.93 images/s; VIS_GEMM_MIX1=0: off, A/B)
   static const int mix1 = [] { const char* e = getenv("VIS_GEMM_MIX1"); return e ? atoi(e) : 64; }();
-  if (!forced && K >= 1024 && M >= 1024 && last != 0 && ((t4 >= 512 && last < 128) || (t4 > 256 && t4 < 512 && last < mix1))) {   // whole rounds + a thin remainder
-    cols4 = (t4 / 256) * 256 / tm4;  // whole rounds only; the ragged remainder columns go through this function again
-    huge = cols4 > 0;
-  }
-  // 256 x 192 / 256 x 128 forms of the 2-phase pipelined kernel: A/B only (r02: never the fastest on a production shape)
-  const bool nt3 = forced == 6;
-  const bool nt2 = forced == 5;
-  if (nt3 || nt2) {
-    static const bool attr_ok = [] {
-      return hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 GEMM4_LDS_BYTES) == hipSuccess &&
-             hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 GEMM4_LDS_BYTES) == hipSuccess;
-    }();
-    if (!attr_ok) return VIS_ERR_LAUNCH;
-    p.tiles_m = tm4;
-    if (nt3) {
-      p.tiles_n = (N + 191) / 192;
-      hipLaunchKernelGGL(gemm_bf16_256xN_kernel<3>, dim3(p.tiles_m * p.tiles_n), dim3(512), GEMM4_LDS_BYTES, stream, p);
-    } else {
-      p.tiles_n = tn1;
-      hipLaunchKernelGGL(gemm_bf16_256xN_kernel<2>, dim3(p.tiles_m * p.tiles_n), dim3(512), GEMM4_LDS_BYTES, stream, p);
-    }
-    return VIS_OK;
-  }
-  // 128 x 256 ping-pong half-tiles wherever the 128 x 128 kernel would run and the half-tile grid needs no more rounds
-  // than its grid does (LLM o: 252 half-tiles = one round, 74.9 -> 68.0 us; ViT proj 195: 36.4 -> 33.6; the gate/up
-  // remainder 108: 62.0 -> 56.6 - tools/gemm_tiles_ab.py, cold caches).  Its K-tile costs 1.14 us against the 128 x 128
-  // tile's 1.2 us for HALF the work: both sit at the CU's LDS bandwidth (176 KiB of fragment reads + LDS-DMA writes per
-  // K-tile here), which is why the gain is 9 % and not the 40 % the MFMA count alone would give.  VIS_GEMM_HALF=0: off.
   static const bool half_ok = [] { const char* e = getenv("VIS_GEMM_HALF"); return !(e && atoi(e) == 0); }();
-  const int t6 = ((M + 127) / 128) * tn4;
-  const bool half = forced == 8 || (!forced && half_ok && !huge && M > 128 && N >= 256 && K >= 512 &&
-                                    (t6 + 255) / 256 <= (t1 + 511) / 512);
-  if (half) {
-    static const bool attr6_ok = [] {
-      return hipFuncSetAttribute((const void*)gemm_bf16_128x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 GEMM6_LDS_BYTES) == hipSuccess;
-    }();
-    if (!attr6_ok) return VIS_ERR_LAUNCH;
-    p.tiles_m = (M + 127) / 128;
-    p.tiles_n = tn4;
-    hipLaunchKernelGGL(gemm_bf16_128x256_pp_kernel, dim3(p.tiles_m * p.tiles_n), dim3(512), GEMM6_LDS_BYTES, stream, p);
-    return VIS_OK;
-  }
-  if (huge) {
-    static const bool attr4_ok = [] {
-      return hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 GEMM4_LDS_BYTES) == hipSuccess;
-    }();
-    if (!attr4_ok) return VIS_ERR_LAUNCH;
-    GemmArgs q = p;
-    if (cols4 < tn4) q.N = cols4 * GEMM4_B;
-    q.tiles_m = tm4;
-    q.tiles_n = cols4;
-    if (use_pp) {
-      static const bool attr5_ok = [] {
-        return hipFuncSetAttribute((const void*)gemm_bf16_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   GEMM5_LDS_BYTES) == hipSuccess;
-      }();
-      if (!attr5_ok) return VIS_ERR_LAUNCH;
-      hipLaunchKernelGGL(gemm_bf16_256x256_pp_kernel, dim3(q.tiles_m * q.tiles_n), dim3(512), GEMM5_LDS_BYTES, stream, q);
-    } else {
-      hipLaunchKernelGGL(gemm_bf16_256xN_kernel<4>, dim3(q.tiles_m * q.tiles_n), dim3(512), GEMM4_LDS_BYTES, stream, q);
+  plan->n = 0;
+  int n0 = 0;
+  for (;;) {
+    const int N = Ntot - n0;
+    const int tn1 = (N + GEMM_BN - 1) / GEMM_BN;
+    const int tm4 = (M + GEMM4_B - 1) / GEMM4_B, tn4 = (N + GEMM4_B - 1) / GEMM4_B;
+    const int t4 = tm4 * tn4, last = t4 % 256;
+    const bool big = forced == 2;   // the 3-stage 256x128 kernel: A/B only
+    const bool use_pp = (pp_env != 0 && forced != 4) || forced == 7;
+    // Kernel choice by a two-line cost model fitted to cold-cache timings of the production shapes (tools/gemm_tiles_ab.py,
+    // r02): a 256x256 ping-pong tile costs ~1.41 us per 64-wide K-step + 4.3 us (prologue + epilogue), one per CU; a
+    // 128x128 tile ~1.2 us per K-step + 3 us with two per CU.  Rounds are what ragged grids pay for:
+    //   ViT qkv  4900x3840x1280: 300 tiles of 256^2 = 2 rounds (66 us) beat 1170 of 128^2 = 3 rounds (78 us);
+    //   LLM qkv  2249x4608x3584: 162 tiles of 256^2 on 63 % of the CUs (83 us) still beat 216 tiles of 256x192 (90 us);
+    //   LLM o    2249x3584x3584: 504 tiles of 128^2 = one full round of two per CU (75 us) beat 252 of 256x128 (85 us).
+    // Every kernel accumulates K in the same order, so the choice (which depends on M) never changes a result bit
+    // (tests/test_gemm_exact_gpu.py::test_row_count_invariance_*).
+    const int nk64 = K / GEMM_BK;
+    const int t1 = ((M + GEMM_BM - 1) / GEMM_BM) * tn1;
+    const float cost1 = (float)((t1 + 511) / 512) * (1.2f * nk64 + 3.0f);
+    const float cost4 = (float)((t4 + 255) / 256) * (1.41f * nk64 + 4.3f);
+    bool huge = forced ? (forced == 4 || forced == 7) : (K >= 256 && M > 128 && N > 128 && cost4 < cost1);
+    int cols4 = tn4;  // 256-wide tile columns given to the 256x256 kernel
+    // ... and (r05) ONE whole round + a remainder of fewer than 64 tiles: the second round of a 294-tile grid (LLM o at four images)
+    // or a 264-tile one (the Auditor's qkv) costs almost a full round for 15 % / 3 % of the tiles - 155 -> 141 us and 162 -> 141 us
+    // with the remainder columns on half-tiles (tools/probes/gemm_mix_probe.py, launches alone; inside `dual` at 32 per step the
+    // difference is within run-to-run noise, 9.93 vs 9.93 images/s; VIS_GEMM_MIX1=0: off, A/B)
+    // (the last plan slot takes what is left whole: a fourth cut would need a remainder of more than 256 tiles three times
+    // over, i.e. M > 32768 - the recursion this loop replaced had no such cap; only the kernel choice there differs)
+    if (!forced && plan->n < GEMM_PLAN_MAX - 1 && K >= 1024 && M >= 1024 && last != 0 &&
+        ((t4 >= 512 && last < 128) || (t4 > 256 && t4 < 512 && last < mix1))) {   // whole rounds + a thin remainder
+      cols4 = (t4 / 256) * 256 / tm4;  // whole rounds only; the ragged remainder columns go through this loop again
+      huge = cols4 > 0;
     }
-    if (cols4 == tn4) return VIS_OK;
-    // remainder columns [n_off, N): same problem, shifted operands
-    const int n_off = cols4 * GEMM4_B;
-    const int c_off = (p.act == ACT_SWIGLU) ? n_off / 2 : n_off;
-    p.W += (size_t)n_off * p.ldw;
-    if (p.bias) p.bias += n_off;
-    if (p.R) p.R += c_off;
-    p.C += c_off;
-    p.N = N - n_off;
-    return gemm_dispatch(p, stream);
+    GemmLaunch& L = plan->l[plan->n++];
+    L.n0 = n0;
+    L.ncols = N;
+    // 256 x 192 / 256 x 128 forms of the 2-phase pipelined kernel: A/B only (r02: never the fastest on a production shape)
+    if (forced == 6 || forced == 5) {
+      L.kernel = forced;
+      L.tiles_m = tm4;
+      L.tiles_n = forced == 6 ? (N + 191) / 192 : tn1;
+      return;
+    }
+    // 128 x 256 ping-pong half-tiles wherever the 128 x 128 kernel would run and the half-tile grid needs no more rounds
+    // than its grid does (LLM o: 252 half-tiles = one round, 74.9 -> 68.0 us; ViT proj 195: 36.4 -> 33.6; the gate/up
+    // remainder 108: 62.0 -> 56.6 - tools/gemm_tiles_ab.py, cold caches).  Its K-tile costs 1.14 us against the 128 x 128
+    // tile's 1.2 us for HALF the work: both sit at the CU's LDS bandwidth (176 KiB of fragment reads + LDS-DMA writes per
+    // K-tile here), which is why the gain is 9 % and not the 40 % the MFMA count alone would give.  VIS_GEMM_HALF=0: off.
+    const int t6 = ((M + 127) / 128) * tn4;
+    const bool half = forced == 8 || (!forced && half_ok && !huge && M > 128 && N >= 256 && K >= 512 &&
+                                      (t6 + 255) / 256 <= (t1 + 511) / 512);
+    if (half) {
+      L.kernel = 8;
+      L.tiles_m = (M + 127) / 128;
+      L.tiles_n = tn4;
+      return;
+    }
+    if (huge) {
+      L.kernel = use_pp ? 7 : 4;
+      if (cols4 < tn4) L.ncols = cols4 * GEMM4_B;
+      L.tiles_m = tm4;
+      L.tiles_n = cols4;
+      if (cols4 == tn4) return;
+      n0 += cols4 * GEMM4_B;   // remainder columns [n0, Ntot): same problem, shifted operands
+      continue;
+    }
+    L.kernel = big ? 2 : 1;
+    L.tiles_m = big ? (M + GEMM2_BM - 1) / GEMM2_BM : (M + GEMM_BM - 1) / GEMM_BM;
+    L.tiles_n = tn1;
+    return;
   }
-  p.tiles_n = tn1;
-  if (big) {
-    static const bool attr_ok = [] {
-      return hipFuncSetAttribute((const void*)gemm_bf16_256x128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 GEMM2_LDS_BYTES) == hipSuccess;
-    }();
-    if (!attr_ok) return VIS_ERR_LAUNCH;
-    p.tiles_m = (M + GEMM2_BM - 1) / GEMM2_BM;
-    hipLaunchKernelGGL(gemm_bf16_256x128_kernel, dim3(p.tiles_m * p.tiles_n), dim3(512), GEMM2_LDS_BYTES, stream, p);
-  } else {
-    p.tiles_m = (M + GEMM_BM - 1) / GEMM_BM;
-    hipLaunchKernelGGL(gemm_bf16_128x128_kernel, dim3(p.tiles_m * p.tiles_n), dim3(256), 0, stream, p);
+}
+
+static int gemm_dispatch(GemmArgs p, hipStream_t stream) {
+  GemmPlan plan;
+  gemm_plan(p.M, p.N, p.K, &plan);
+  for (int i = 0; i < plan.n; ++i) {
+    const GemmLaunch& L = plan.l[i];
+    GemmArgs q = p;
+    const int c_off = (p.act == ACT_SWIGLU) ? L.n0 / 2 : L.n0;
+    q.W += (size_t)L.n0 * p.ldw;
+    if (q.bias) q.bias += L.n0;
+    if (q.R) q.R += c_off;
+    q.C += c_off;
+    q.N = L.ncols;
+    q.tiles_m = L.tiles_m;
+    q.tiles_n = L.tiles_n;
+    const dim3 grid(q.tiles_m * q.tiles_n);
+    switch (L.kernel) {
+      case 5:
+      case 6: {
+        static const bool attr_ok = [] {
+          return hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     GEMM4_LDS_BYTES) == hipSuccess &&
+                 hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     GEMM4_LDS_BYTES) == hipSuccess;
+        }();
+        if (!attr_ok) return VIS_ERR_LAUNCH;
+        if (L.kernel == 6) hipLaunchKernelGGL(gemm_bf16_256xN_kernel<3>, grid, dim3(512), GEMM4_LDS_BYTES, stream, q);
+        else hipLaunchKernelGGL(gemm_bf16_256xN_kernel<2>, grid, dim3(512), GEMM4_LDS_BYTES, stream, q);
+        break;
+      }
+      case 8: {
+        static const bool attr6_ok = [] {
+          return hipFuncSetAttribute((const void*)gemm_bf16_128x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     GEMM6_LDS_BYTES) == hipSuccess;
+        }();
+        if (!attr6_ok) return VIS_ERR_LAUNCH;
+        hipLaunchKernelGGL(gemm_bf16_128x256_pp_kernel, grid, dim3(512), GEMM6_LDS_BYTES, stream, q);
+        break;
+      }
+      case 4:
+      case 7: {
+        static const bool attr4_ok = [] {
+          return hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     GEMM4_LDS_BYTES) == hipSuccess;
+        }();
+        if (!attr4_ok) return VIS_ERR_LAUNCH;
+        if (L.kernel == 7) {
+          static const bool attr5_ok = [] {
+            return hipFuncSetAttribute((const void*)gemm_bf16_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       GEMM5_LDS_BYTES) == hipSuccess;
+          }();
+          if (!attr5_ok) return VIS_ERR_LAUNCH;
+          hipLaunchKernelGGL(gemm_bf16_256x256_pp_kernel, grid, dim3(512), GEMM5_LDS_BYTES, stream, q);
+        } else {
+          hipLaunchKernelGGL(gemm_bf16_256xN_kernel<4>, grid, dim3(512), GEMM4_LDS_BYTES, stream, q);
+        }
+        break;
+      }
+      case 2: {
+        static const bool attr_ok = [] {
+          return hipFuncSetAttribute((const void*)gemm_bf16_256x128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     GEMM2_LDS_BYTES) == hipSuccess;
+        }();
+        if (!attr_ok) return VIS_ERR_LAUNCH;
+        hipLaunchKernelGGL(gemm_bf16_256x128_kernel, grid, dim3(512), GEMM2_LDS_BYTES, stream, q);
+        break;
+      }
+      default:
+        hipLaunchKernelGGL(gemm_bf16_128x128_kernel, grid, dim3(256), 0, stream, q);
+    }
   }
   return VIS_OK;
+}
+
+// Host-only: what vis_gemm_bf16 would launch (no HIP call).  plan[0] = launches, plan[1] = wide epilogue, plan[2] =
+// non-temporal stores, then per launch {kernel id, first W row, W rows, tiles_m, tiles_n}.
+extern "C" int vis_gemm_bf16_plan(int M, int N, int K, int ldc, int ldr, int act, int has_residual, int aligned16,
+                                  int* plan, int plan_ints) {
+  if (!plan || M <= 0 || N <= 0 || K <= 0 || K % GEMM_BK != 0 || N % 4 != 0) return 0;
+  if (ldc % 4 != 0 || (has_residual && ldr % 4 != 0) || act < ACT_NONE || act > ACT_SWIGLU) return 0;
+  if (act == ACT_SWIGLU && (N % 32 != 0 || has_residual)) return 0;
+  GemmPlan g;
+  gemm_plan(M, N, K, &g);
+  if (plan_ints < 3 + 5 * g.n) return 0;
+  plan[0] = g.n;
+  plan[1] = gemm_wide_ok(N, ldc, has_residual, ldr, aligned16, act);
+  plan[2] = gemm_nt_on(M, N, act);
+  for (int i = 0; i < g.n; ++i) {
+    int* o = plan + 3 + 5 * i;
+    o[0] = g.l[i].kernel; o[1] = g.l[i].n0; o[2] = g.l[i].ncols; o[3] = g.l[i].tiles_m; o[4] = g.l[i].tiles_n;
+  }
+  return g.n;
 }
 
 // C-ABI launcher (declared in include/vis_hip.h)
@@ -1557,11 +1617,8 @@ extern "C" int vis_gemm_bf16(const void* A, const void* W, const void* bias, con
   p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
   p.act = act;
   p.part = nullptr; p.ksplit = 1; p.out_f32 = 0;
-  static const int wide_env = [] { const char* e = getenv("VIS_GEMM_WIDE"); return e ? atoi(e) : 1; }();   // 0: direct epilogue (A/B)
-  p.wide = wide_env && N % 8 == 0 && ldc % 8 == 0 && (!R || ldr % 8 == 0) && !(((uintptr_t)C | (uintptr_t)R) & 15) &&
-           !(act == ACT_SWIGLU && N % 16 != 0);
-  static const int nt_env = [] { const char* e = getenv("VIS_GEMM_NT"); return e ? atoi(e) : 1; }();   // 0 never, 1 by size, 2 always (A/B)
-  p.nt = nt_env == 2 || (nt_env == 1 && (size_t)M * (act == ACT_SWIGLU ? N / 2 : N) * 2 >= ((size_t)64 << 20));
+  p.wide = gemm_wide_ok(N, ldc, R != nullptr, ldr, !(((uintptr_t)C | (uintptr_t)R) & 15), act);
+  p.nt = gemm_nt_on(M, N, act);
   vis_clear_error();
   const int st = gemm_dispatch(p, stream);
   return st != VIS_OK ? st : vis_check_launch();

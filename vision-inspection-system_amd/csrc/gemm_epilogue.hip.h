@@ -27,6 +27,18 @@ __device__ __forceinline__ float act_apply(float x, int act) {
   return x;
 }
 
+// Epilogue form and store policy of one call, from what the caller passes (host; shared by the bf16 and fp8 launchers and
+// their plan queries).  aligned16: C and R (if any) are 16-byte aligned.
+#include <stdlib.h>
+static inline int gemm_wide_ok(int N, int ldc, int has_r, int ldr, int aligned16, int act) {
+  static const int wide_env = [] { const char* e = getenv("VIS_GEMM_WIDE"); return e ? atoi(e) : 1; }();   // 0: direct epilogue (A/B)
+  return wide_env && N % 8 == 0 && ldc % 8 == 0 && (!has_r || ldr % 8 == 0) && aligned16 && !(act == ACT_SWIGLU && N % 16 != 0);
+}
+static inline int gemm_nt_on(int M, int N, int act) {
+  static const int nt_env = [] { const char* e = getenv("VIS_GEMM_NT"); return e ? atoi(e) : 1; }();   // 0 never, 1 by size, 2 always (A/B)
+  return nt_env == 2 || (nt_env == 1 && (size_t)M * (act == ACT_SWIGLU ? N / 2 : N) * 2 >= ((size_t)64 << 20));
+}
+
 // ---------------------------------------------------------------------------
 // Wide epilogue: the wave's accumulator tile goes through a wave-private 16 KiB LDS region and leaves as whole
 // 16-byte chunks of C rows (8 lanes cover one 128-byte row segment), instead of 8-byte stores at a row stride

@@ -609,6 +609,71 @@ __global__ __launch_bounds__(256) void gemm_fp8_splitk_finalize_kernel(GemmF8Arg
   }
 }
 
+// Tile choice by a cost model in us, fitted to tools/gemm_kscan.py KS_FP8=1 on the r05 kernels (VIS_GEMM8_TILE=1|4 forces):
+//   256 x 256 ping-pong, one workgroup per CU : a round of 256 tiles costs 8.2 + 1.27 per 128-wide K-step
+//   128 x 128, two workgroups per CU          : a round of 512 tiles costs 4.5 + 1.06 per K-step
+// candidates: everything on one kernel, or whole rounds of the big tile + the remaining columns on the small one (a
+// second launch: + 2 us).  r04's rule ("256 only when the last round is at least half full") sent the LLM's qkv / o
+// projections at 4 images (378 / 294 big tiles) to the small kernel: 121 / 118 us where two big rounds take ~88.
+// Host arithmetic only: vis_gemm_fp8 launches from this plan and vis_gemm_fp8_plan exports it.
+// Kernel ids: 1 = 128x128, 4 = 2-phase 256x256, 7 = 256x256 ping-pong.
+struct GemmF8Launch { int kernel, n0, ncols, tiles_m, tiles_n; };   // covers W rows [n0, n0 + ncols)
+struct GemmF8Plan { int n; GemmF8Launch l[2]; };
+
+static void gemm_fp8_plan(int M, int N, int K, bool split, GemmF8Plan* plan) {
+  static const int pp_env = [] { const char* e = getenv("VIS_GEMM_PP"); return e ? atoi(e) : 1; }();   // 0: 2-phase kernel (A/B)
+  static const int forced = [] { const char* e = getenv("VIS_GEMM8_TILE"); return e ? atoi(e) : 0; }();
+  const int k256 = pp_env ? 7 : 4;
+  const int tiles_m = (M + F8_B - 1) / F8_B, tiles_n = (N + F8_B - 1) / F8_B;
+  const int t4 = tiles_m * tiles_n;
+  const int nk = K / F8_BK;
+  const float c256 = 8.2f + 1.27f * nk, c128 = 4.5f + 1.06f * nk;
+  auto rounds = [](long long tiles, int per) { return (float)((tiles + per - 1) / per); };
+  auto tiles128 = [&](int n) { return (long long)((M + 127) / 128) * ((n + 127) / 128); };
+  const float cost_big = rounds(t4, 256) * c256, cost_small = rounds(tiles128(N), 512) * c128;
+  const int cols4 = (t4 / 256) * 256 / tiles_m;  // columns of big tiles in whole rounds only
+  const int n_off = cols4 * F8_B;
+  const float cost_mixed = (cols4 > 0 && n_off < N)
+                               ? rounds((long long)cols4 * tiles_m, 256) * c256 + rounds(tiles128(N - n_off), 512) * c128 + 2.f
+                               : 1e30f;
+  int choice;   // 4: big, 1: small, 5: mixed
+  if (split || forced == 4) choice = 4;
+  else if (forced == 1 || M < 1024) choice = 1;
+  else choice = (cost_big <= cost_small && cost_big <= cost_mixed) ? 4 : (cost_mixed < cost_small ? 5 : 1);
+  if (choice == 4) {
+    plan->n = 1;
+    plan->l[0] = {k256, 0, N, tiles_m, tiles_n};
+  } else if (choice == 5) {
+    plan->n = 2;
+    plan->l[0] = {k256, 0, n_off, tiles_m, cols4};
+    plan->l[1] = {1, n_off, N - n_off, (M + 127) / 128, (N - n_off + 127) / 128};
+  } else {
+    plan->n = 1;
+    plan->l[0] = {1, 0, N, (M + 127) / 128, (N + 127) / 128};
+  }
+}
+
+// Host-only: what vis_gemm_fp8 would launch (no HIP call); `split` = a split-K call (work != NULL).  plan[] as for
+// vis_gemm_bf16_plan.
+extern "C" int vis_gemm_fp8_plan(int M, int N, int K, int ldc, int ldr, int act, int has_residual, int aligned16,
+                                 int split, int* plan, int plan_ints) {
+  if (!plan || M <= 0 || N <= 0 || K <= 0 || K % F8_BK != 0 || N % 4 != 0) return 0;
+  if (ldc % 4 != 0 || (has_residual && ldr % 4 != 0) || act < F8_ACT_NONE || act > F8_ACT_SWIGLU) return 0;
+  if (act == F8_ACT_SWIGLU && (N % 32 != 0 || has_residual)) return 0;
+  if (split && (N % 8 != 0 || ldc % 8 != 0 || (has_residual && ldr % 8 != 0) || act == F8_ACT_SWIGLU || !aligned16)) return 0;
+  GemmF8Plan g;
+  gemm_fp8_plan(M, N, K, split != 0, &g);
+  if (plan_ints < 3 + 5 * g.n) return 0;
+  plan[0] = g.n;
+  plan[1] = gemm_wide_ok(N, ldc, has_residual, ldr, aligned16, act);
+  plan[2] = gemm_nt_on(M, N, act);
+  for (int i = 0; i < g.n; ++i) {
+    int* o = plan + 3 + 5 * i;
+    o[0] = g.l[i].kernel; o[1] = g.l[i].n0; o[2] = g.l[i].ncols; o[3] = g.l[i].tiles_m; o[4] = g.l[i].tiles_n;
+  }
+  return g.n;
+}
+
 // work != NULL with ksplit in 2..8: split-K (f32 partials in `work`, ksplit*M*N floats; needs N % 8 == 0, no SwiGLU)
 extern "C" int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, const void* sw, const void* bias,
                             const void* R, void* C, void* work, int ksplit, int M, int N, int K, int lda, int ldw,
@@ -626,8 +691,6 @@ extern "C" int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, cons
            hipFuncSetAttribute((const void*)gemm_fp8_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                F8_LDS_BYTES) == hipSuccess;
   }();
-  static const int pp_env = [] { const char* e = getenv("VIS_GEMM_PP"); return e ? atoi(e) : 1; }();   // 0: 2-phase kernel (A/B)
-  auto* const k256 = pp_env ? gemm_fp8_256x256_pp_kernel : gemm_fp8_256x256_kernel;
   if (!attr_ok) return VIS_ERR_LAUNCH;
   GemmF8Args p;
   p.A = (const uint8_t*)Aq; p.W = (const uint8_t*)Wq; p.sa = (const float*)sa; p.sw = (const float*)sw;
@@ -636,11 +699,8 @@ extern "C" int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, cons
   p.tiles_m = (M + F8_B - 1) / F8_B;
   p.tiles_n = (N + F8_B - 1) / F8_B;
   p.part = nullptr; p.ksplit = 1;
-  static const int wide_env = [] { const char* e = getenv("VIS_GEMM_WIDE"); return e ? atoi(e) : 1; }();   // 0: direct epilogue (A/B)
-  p.wide = wide_env && N % 8 == 0 && ldc % 8 == 0 && (!R || ldr % 8 == 0) && !(((uintptr_t)C | (uintptr_t)R) & 15) &&
-           !(act == F8_ACT_SWIGLU && N % 16 != 0);
-  static const int nt_env = [] { const char* e = getenv("VIS_GEMM_NT"); return e ? atoi(e) : 1; }();
-  p.nt = nt_env == 2 || (nt_env == 1 && (size_t)M * (act == F8_ACT_SWIGLU ? N / 2 : N) * 2 >= ((size_t)64 << 20));
+  p.wide = gemm_wide_ok(N, ldc, R != nullptr, ldr, !(((uintptr_t)C | (uintptr_t)R) & 15), act);
+  p.nt = gemm_nt_on(M, N, act);
   if (work) {
     if (ksplit < 2 || ksplit > 8 || K / F8_BK < 2 * ksplit || N % 8 != 0 || ldc % 8 != 0 || (R && ldr % 8 != 0) ||
         act == F8_ACT_SWIGLU || ((uintptr_t)work & 15) || (((uintptr_t)C | (uintptr_t)bias | (uintptr_t)R) & 15))
@@ -648,51 +708,24 @@ extern "C" int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, cons
     p.part = (float*)work; p.ksplit = ksplit;
   }
   vis_clear_error();
-  // tile choice by a cost model in us, fitted to tools/gemm_kscan.py KS_FP8=1 on the r05 kernels (VIS_GEMM8_TILE=1|4 forces):
-  //   256 x 256 ping-pong, one workgroup per CU : a round of 256 tiles costs 8.2 + 1.27 per 128-wide K-step
-  //   128 x 128, two workgroups per CU          : a round of 512 tiles costs 4.5 + 1.06 per K-step
-  // candidates: everything on one kernel, or whole rounds of the big tile + the remaining columns on the small one (a
-  // second launch: + 2 us).  r04's rule ("256 only when the last round is at least half full") sent the LLM's qkv / o
-  // projections at 4 images (378 / 294 big tiles) to the small kernel: 121 / 118 us where two big rounds take ~88.
-  static const int forced = [] { const char* e = getenv("VIS_GEMM8_TILE"); return e ? atoi(e) : 0; }();
-  const int t4 = p.tiles_m * p.tiles_n;
-  const int nk = K / F8_BK;
-  const float c256 = 8.2f + 1.27f * nk, c128 = 4.5f + 1.06f * nk;
-  auto rounds = [](long long tiles, int per) { return (float)((tiles + per - 1) / per); };
-  auto tiles128 = [&](int n) { return (long long)((M + 127) / 128) * ((n + 127) / 128); };
-  const float cost_big = rounds(t4, 256) * c256, cost_small = rounds(tiles128(N), 512) * c128;
-  const int cols4 = (t4 / 256) * 256 / p.tiles_m;  // columns of big tiles in whole rounds only
-  const int n_off = cols4 * F8_B;
-  const float cost_mixed = (cols4 > 0 && n_off < N)
-                               ? rounds((long long)cols4 * p.tiles_m, 256) * c256 + rounds(tiles128(N - n_off), 512) * c128 + 2.f
-                               : 1e30f;
-  int choice;   // 4: big, 1: small, 5: mixed
-  if (work || forced == 4) choice = 4;
-  else if (forced == 1 || M < 1024) choice = 1;
-  else choice = (cost_big <= cost_small && cost_big <= cost_mixed) ? 4 : (cost_mixed < cost_small ? 5 : 1);
-  auto launch128 = [&](GemmF8Args q) {
-    q.tiles_m = (q.M + 127) / 128;
-    q.tiles_n = (q.N + 127) / 128;
-    hipLaunchKernelGGL(gemm_fp8_128x128_kernel, dim3(q.tiles_m * q.tiles_n), dim3(256), 0, stream, q);
-  };
-  if (choice == 4) {
-    hipLaunchKernelGGL(k256, dim3(t4, p.ksplit), dim3(512), F8_LDS_BYTES, stream, p);
-  } else if (choice == 5) {
+  GemmF8Plan plan;
+  gemm_fp8_plan(M, N, K, work != nullptr, &plan);
+  for (int i = 0; i < plan.n; ++i) {
+    const GemmF8Launch& L = plan.l[i];
     GemmF8Args q = p;
-    q.N = cols4 * F8_B;
-    q.tiles_n = cols4;
-    hipLaunchKernelGGL(k256, dim3(q.tiles_m * q.tiles_n, 1), dim3(512), F8_LDS_BYTES, stream, q);
-    const int c_off = (act == F8_ACT_SWIGLU) ? n_off / 2 : n_off;
-    GemmF8Args r = p;
-    r.W += (size_t)n_off * ldw;
-    r.sw += n_off;
-    if (r.bias) r.bias += n_off;
-    if (r.R) r.R += c_off;
-    r.C += c_off;
-    r.N = N - n_off;
-    launch128(r);
-  } else {
-    launch128(p);
+    const int c_off = (act == F8_ACT_SWIGLU) ? L.n0 / 2 : L.n0;
+    q.W += (size_t)L.n0 * ldw;
+    q.sw += L.n0;
+    if (q.bias) q.bias += L.n0;
+    if (q.R) q.R += c_off;
+    q.C += c_off;
+    q.N = L.ncols;
+    q.tiles_m = L.tiles_m;
+    q.tiles_n = L.tiles_n;
+    const dim3 grid(q.tiles_m * q.tiles_n, L.kernel == 1 ? 1 : p.ksplit);
+    if (L.kernel == 7) hipLaunchKernelGGL(gemm_fp8_256x256_pp_kernel, grid, dim3(512), F8_LDS_BYTES, stream, q);
+    else if (L.kernel == 4) hipLaunchKernelGGL(gemm_fp8_256x256_kernel, grid, dim3(512), F8_LDS_BYTES, stream, q);
+    else hipLaunchKernelGGL(gemm_fp8_128x128_kernel, grid, dim3(256), 0, stream, q);
   }
   if (work) {
     const long long total = (long long)M * (N / 8);

@@ -27,6 +27,8 @@ _SIGS = {
     "vis_gemm_bf16_splitk_part": "ppp" + "iiiiii" + "p",
     "vis_splitk_finalize_norm": "p" + "i" + "pppppp" + "iiiii" + "f" + "p",
     "vis_gemm_fp8": "pppppppp" + "iiiiiiiii" + "p",
+    "vis_gemm_bf16_plan": "iiiiiiii" + "p" + "i",
+    "vis_gemm_fp8_plan": "iiiiiiiii" + "p" + "i",
     "vis_quant_rows_fp8": "ppppp" + "iiii" + "f" + "p",
     "vis_rmsnorm_bf16": "ppp" + "iiii" + "f" + "p",
     "vis_rmsnorm_heads_bf16": "ppp" + "iiiii" + "f" + "p",
@@ -357,6 +359,40 @@ def gemm_fp8(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.Ten
                              residual.stride(0) if residual is not None else 0, act, _stream())
     _check(rc, "vis_gemm_fp8")
     return out
+
+
+GEMM_KERNEL_NAMES = {1: "128x128", 2: "256x128_3stage", 4: "256x256_2phase", 5: "256x128_2phase", 6: "256x192_2phase",
+                     7: "256x256_pp", 8: "128x256_pp"}
+
+
+def _gemm_plan(fn, args) -> dict:
+    import ctypes
+    buf = (ctypes.c_int * 23)()
+    n = fn(*args, ctypes.cast(buf, ctypes.c_void_p), 23)
+    if n <= 0:
+        raise HipLibraryError(f"gemm plan: arguments rejected {args}")
+    launches = [dict(kernel=GEMM_KERNEL_NAMES[buf[3 + 5 * i]], n0=buf[4 + 5 * i], ncols=buf[5 + 5 * i],
+                     tiles_m=buf[6 + 5 * i], tiles_n=buf[7 + 5 * i]) for i in range(n)]
+    return dict(wide=bool(buf[1]), nt=bool(buf[2]), launches=launches, kernels=tuple(l["kernel"] for l in launches))
+
+
+def gemm_plan(M: int, N: int, K: int, act: int = ACT_NONE, ldc: Optional[int] = None, ldr: Optional[int] = None,
+              residual: bool = False, aligned16: bool = True) -> dict:
+    """Host-only: the launches vis_gemm_bf16 makes for this problem (kernel per column range), its epilogue form and
+    store policy.  Needs no GPU."""
+    n_out = N // 2 if act == ACT_SWIGLU else N
+    ldc = n_out if ldc is None else ldc
+    ldr = (ldc if ldr is None else ldr) if residual else 0
+    return _gemm_plan(load().vis_gemm_bf16_plan, (M, N, K, ldc, ldr, act, int(residual), int(aligned16)))
+
+
+def gemm_fp8_plan(M: int, N: int, K: int, act: int = ACT_NONE, ldc: Optional[int] = None, ldr: Optional[int] = None,
+                  residual: bool = False, aligned16: bool = True, split: bool = False) -> dict:
+    """Host-only: the launches vis_gemm_fp8 makes for this problem.  Needs no GPU."""
+    n_out = N // 2 if act == ACT_SWIGLU else N
+    ldc = n_out if ldc is None else ldc
+    ldr = (ldc if ldr is None else ldr) if residual else 0
+    return _gemm_plan(load().vis_gemm_fp8_plan, (M, N, K, ldc, ldr, act, int(residual), int(aligned16), int(split)))
 
 
 # --------------------------------------------------------------------------- K3 / K5
