@@ -247,6 +247,22 @@ int vis_logprobs_f32(const void* logits, int V, int ld_logits, const void* token
 int vis_json_mask(void* state, const void* tokens, int max_tokens, const void* step_ptr, const void* tok_off,
                   const void* tok_bytes, const void* tok_flags, const void* eos_ids, int n_eos, int V, void* allow,
                   int ld_allow, int batch, vis_stream_t stream);
+/* Schema-constrained decoding (csrc/schema_mask.hip; json_schema.py compiles the tables and is the reference): vis_json_mask
+ * with a byte-level DFA in place of the JSON grammar - same state pitch (32 int32 per sequence: two slots of 12 words chosen
+ * by the parity of step_ptr[b], slot words DFA state / error bit / position / anchored, counters at words 24 / 25; all zero =
+ * a fresh sequence in the DFA's start state), same folding of the tokens picked since the last launch, same token table,
+ * same allow rows, same "no token allowed -> EOS ids + error bit".  The DFA: header int32 [4] = {n_states, n_classes, start,
+ * 0}, READ BY THE KERNEL (a captured launch serves whatever schema the buffers hold when it is replayed); trans u16
+ * [n_states][n_classes] packed at the front of a buffer of cap_states * cap_classes entries, 65535 = no transition;
+ * byte_class u8 [256]; state_flags u8 [cap_states], bit 0 = accepting (EOS ids allowed here only), bit 1 = every printable
+ * ASCII byte but '"' and '\' loops (tokens with flag bit 1 are accepted without a walk).  next = trans[s * n_classes +
+ * byte_class[byte]].  A header outside the capacities or a state outside the header puts the row in the error state.
+ * VIS_ERR_ARG: as vis_json_mask, and null DFA pointer, cap_states outside 1..4096, cap_classes outside 1..256,
+ * cap_states * cap_classes * 2 not a multiple of 16, trans not 16-byte aligned, header not 4-byte aligned. */
+int vis_schema_mask(void* state, const void* tokens, int max_tokens, const void* step_ptr, const void* tok_off,
+                    const void* tok_bytes, const void* tok_flags, const void* eos_ids, int n_eos, int V, void* allow,
+                    int ld_allow, const void* header, const void* trans, const void* byte_class, const void* state_flags,
+                    int cap_states, int cap_classes, int batch, vis_stream_t stream);
 /* vis_argmax_f32 over the allowed ids only: sequence b skips id i unless bit i of allow + b * ld_allow is set.  The
  * comparison (ties to the lower index) and the Gumbel noise are vis_argmax_f32's, so with every bit set the pick is the
  * same bit for bit, and at temperature > 0 it samples the renormalised distribution over the allowed ids.  A row with no

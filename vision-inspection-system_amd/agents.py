@@ -21,12 +21,17 @@ from .config import LOCAL_PROVIDER, get_config
 from .image_processing import direct_frames_enabled, encode_image_optimized, frame_url_for, release_frames
 from .prompts import AUDITOR_PROMPT, INSPECTOR_PROMPT
 from .response_parsing import parse_json_robust, validate_and_fix_result
-from .schemas import InspectionContext, VLMAnalysisResult
+from .schemas import REPORT_RESPONSE_FORMAT, InspectionContext, VLMAnalysisResult
 
 
 def json_mode_kwargs() -> dict:
     """VIS_JSON_MODE=1 (default 0): the analysis requests ask for response_format={"type": "json_object"} - the engine then
-    only generates JSON objects (json_grammar).  The health check's one-word ping never does.  Off: the calls are as before."""
+    only generates JSON objects (json_grammar).  VIS_JSON_SCHEMA=1 (default 0) takes precedence: the analysis and verify
+    requests send the schema of the report they parse (schemas.REPORT_SCHEMA) as response_format json_schema, so keys, types
+    and literals are the ones response_parsing expects.  The health check's one-word ping sends neither.  Off: the calls are
+    as before."""
+    if os.environ.get("VIS_JSON_SCHEMA", "0") == "1":
+        return {"response_format": REPORT_RESPONSE_FORMAT}
     return {"response_format": {"type": "json_object"}} if os.environ.get("VIS_JSON_MODE", "0") == "1" else {}
 
 

@@ -263,8 +263,43 @@ def json_mode_of(response_format) -> bool:
         return False
     if kind == "json_object":
         return True
-    raise ValueError("response_format: only {'type': 'text'} and {'type': 'json_object'} are supported "
-                     "(json_schema and other grammars are not)")
+    raise ValueError("response_format: only {'type': 'text'} and {'type': 'json_object'} turn JSON mode on or off "
+                     "(json_schema goes through schema_of; other grammars are unsupported)")
+
+
+_SCHEMA_CACHE: dict = {}
+_SCHEMA_CACHE_MAX = 64
+
+
+def schema_of(response_format):
+    """OpenAI's response_format -> the compiled SchemaDFA of {"type": "json_schema", "json_schema": {"name": ..., "schema":
+    {...}, "strict": ...}}, or None for every other form (json_mode_of judges those).  The schema is compiled here, before
+    any model is loaded: what json_schema.compile_schema does not support is a ValueError naming the cause.  ``strict`` may be
+    true, false or absent - the reply always conforms.  Compiled DFAs are cached by the schema's canonical JSON text."""
+    if not isinstance(response_format, dict) or response_format.get("type") != "json_schema":
+        return None
+    from . import json_schema
+    spec = response_format.get("json_schema")
+    if not isinstance(spec, dict) or not isinstance(spec.get("schema"), dict):
+        raise ValueError("response_format json_schema: needs {'json_schema': {'name': ..., 'schema': {...}}}")
+    extra = set(response_format) - {"type", "json_schema"} | set(spec) - {"name", "schema", "strict", "description"}
+    if extra:
+        raise ValueError(f"response_format json_schema: unknown field(s) {sorted(extra)}")
+    if "name" in spec and not isinstance(spec["name"], str) or not isinstance(spec.get("strict", True), bool):
+        raise ValueError("response_format json_schema: 'name' must be a string and 'strict' true or false")
+    try:
+        key = json_schema.canonical(spec["schema"])
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"response_format json_schema: the schema is not JSON ({e})") from None
+    with _ENGINES_LOCK:
+        dfa = _SCHEMA_CACHE.get(key)
+    if dfa is None:
+        dfa = json_schema.compile_schema(spec["schema"])
+        with _ENGINES_LOCK:
+            if len(_SCHEMA_CACHE) >= _SCHEMA_CACHE_MAX:
+                _SCHEMA_CACHE.pop(next(iter(_SCHEMA_CACHE)))
+            dfa = _SCHEMA_CACHE.setdefault(key, dfa)
+    return dfa
 
 
 def _choice_logprobs(tok, toks: List[int], rec) -> ChoiceLogprobs:
@@ -395,6 +430,10 @@ class LocalVLMClient:
         ``response_format`` (OpenAI's): {"type": "json_object"} restricts every generated token to the ones that continue a
         JSON object (RFC 8259, strict UTF-8; the engines' json_mode): a reply that ended on EOS parses with json.loads, one cut
         by max_tokens is a prefix of a JSON object; a request the vocabulary could not continue fails with JsonModeError.
+        {"type": "json_schema", "json_schema": {"name": ..., "schema": {...}, "strict": ...}}: the same with the schema as the
+        grammar (json_schema.py: fixed keys in ``properties`` order, types, enum / const literals, nested objects and arrays,
+        Optional as anyOf with null): a reply that ended on EOS is a document of the schema.  An unsupported schema is a
+        ValueError before any model is loaded.
         None or {"type": "text"}: unchanged.  Logprobs keep their meaning: top_logprobs may list tokens the mask forbade.
         ``top_p`` (OpenAI's / huggingface_hub's): nucleus sampling - each token is drawn from the shortest most-likely set
         holding top_p of the temperature-scaled probability (sampling.py); None or 1 = the whole vocabulary.  ``seed``: every
@@ -409,7 +448,8 @@ class LocalVLMClient:
         from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
         k = logprobs_k(logprobs, top_logprobs)
-        jm = json_mode_of(response_format)
+        dfa = schema_of(response_format)
+        jm = json_mode_of(response_format) if dfa is None else False
         top_p = check_top_p(top_p)
         seed = check_seed(seed)
         pen = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
@@ -423,7 +463,7 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         out: List[ChatCompletion] = []
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -460,6 +500,7 @@ class LocalVLMClient:
                 toks = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp, seed=self.seed,
                                           ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1",
                                           **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}),
+                                          **({"json_schema": dfa} if dfa is not None else {}),
                                           **({"top_p": top_p} if top_p is not None else {}),
                                           **({"seeds": [seed] * len(idx)} if seed is not None else {}), **pen)
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
@@ -504,7 +545,7 @@ class LocalVLMClient:
 
     def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
                               k: Optional[int] = None, jm: bool = False, top_p: Optional[float] = None,
-                              seed: Optional[int] = None, pen: Optional[dict] = None) -> List[ChatCompletion]:
+                              seed: Optional[int] = None, pen: Optional[dict] = None, dfa=None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -516,6 +557,8 @@ class LocalVLMClient:
         lpk = {"logprobs": k} if k is not None else {}
         if jm:
             lpk["json_mode"] = True
+        if dfa is not None:
+            lpk["json_schema"] = dfa
         if top_p is not None:
             lpk["top_p"] = top_p
         lpk.update(pen or {})

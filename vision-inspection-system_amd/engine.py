@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .json_mode import JsonBuffers, JsonModeError, engine_tokenizer
+from .json_mode import JsonBuffers, JsonModeError, SchemaBuffers, begin_schema, check_schema, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
 from .penalties import NEUTRAL, PenaltyBuffers, check_penalties
 from .sampling import SampleBuffers, check_seeds, check_top_p
@@ -331,6 +331,9 @@ class Qwen2VLEngine:
         # tokenizer: the vocabulary's token_bytes (the client sets it when it loads the model)
         self.json_on = False
         self._json: Optional[JsonBuffers] = None
+        # schema-constrained decoding (generate(..., json_schema=SchemaDFA)): the same pick with vis_schema_mask's rows
+        self.schema_on = False
+        self._schema: Optional[SchemaBuffers] = None
         self.tokenizer = None
         # nucleus sampling / per-request seeds (generate(..., top_p=), generate_batch(..., top_p=, seeds=)): while on, every
         # pick is vis_sample_f32 with the row seeds of a device buffer; top_p None = 1; _slot_seed: slot -> request seed
@@ -675,8 +678,8 @@ class Qwen2VLEngine:
         if taps is not None:
             taps["first_logits"] = logits.clone()
         step.fill_(S - 1)
-        if self.json_on:
-            self._json.reset(slot)
+        if self._mask is not None:
+            self._mask.reset(slot)
         self._seed_slot(slot)
         self._penalty_slot(slot, ids_dev)
         self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
@@ -859,8 +862,8 @@ class Qwen2VLEngine:
             else:
                 hip.gemv(x[(j + 1) * n - 1], w.lm_head, logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
             self.step_b[slot:slot + 1].fill_(S - 1)
-            if self.json_on:
-                self._json.reset(slot)
+            if self._mask is not None:
+                self._mask.reset(slot)
             self._seed_slot(slot)
             self._penalty_slot(slot, ids_devs[j])
             self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
@@ -1117,8 +1120,14 @@ class Qwen2VLEngine:
         if not isinstance(json_mode, bool):
             raise ValueError("json_mode must be True or False")
         if json_mode and self._json is None:
-            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device)
+            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
+                                     share=self._schema)
         self.json_on = json_mode
+
+    @property
+    def _mask(self):
+        """The buffers of the grammar mask that is on (JSON mode or a schema), or None."""
+        return self._schema if self.schema_on else (self._json if self.json_on else None)
 
     # ------------------------------------------------------------------ nucleus sampling / per-request seeds
     def _begin_sampling(self, top_p, seeded: bool) -> None:
@@ -1164,13 +1173,13 @@ class Qwen2VLEngine:
         if self.pen_on:
             logits = self._pen.apply(logits, tokens, step, slot)
         if self.smp_on:
-            allow = self._json.mask(tokens, step, slot) if self.json_on else None
+            allow = self._mask.mask(tokens, step, slot) if self._mask is not None else None
             self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
             return
-        if not self.json_on:
+        if self._mask is None:
             hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
             return
-        allow = self._json.mask(tokens, step, slot)
+        allow = self._mask.mask(tokens, step, slot)
         hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
 
     def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
@@ -1180,10 +1189,10 @@ class Qwen2VLEngine:
             hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
             self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
             return
-        if not self.json_on:
+        if self._mask is None:
             hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
             return
-        allow = self._json.mask(tokens, step, 0)
+        allow = self._mask.mask(tokens, step, 0)
         hip.gemv_argmax_masked(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, allow[0], **kw)
 
     # ------------------------------------------------------------------ decode
@@ -1446,7 +1455,7 @@ class Qwen2VLEngine:
         # the row seeds of vis_sample_f32 and the penalty values of vis_penalize_f32 are read from device memory at replay, so
         # only whether they are in use is part of it
         key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch, self.lp_k,
-               self.json_on, self.top_p, self.seeded, self.pen_on)
+               self.json_on, self.schema_on, self.top_p, self.seeded, self.pen_on)
         if key in self._graphs:
             return self._graphs[key]
         step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
@@ -1564,7 +1573,7 @@ class Qwen2VLEngine:
                  ignore_eos: bool = False, use_graph: bool = True, check_every: int = 16,
                  temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                  json_mode: bool = False, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None) -> List[int]:
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
@@ -1576,10 +1585,13 @@ class Qwen2VLEngine:
         draws from the shortest most-likely prefix holding top_p of the temperature-scaled mass; None or 1 = off.
         ``repetition_penalty`` > 0 (transformers' meaning: over prompt and generated ids), ``frequency_penalty`` /
         ``presence_penalty`` in [-2, 2] (OpenAI's: over generated ids): penalties.py - applied to the raw logits ahead of
-        everything above; None or 1 / 0 / 0 = off.  Logprobs keep their meaning (raw logits)."""
+        everything above; None or 1 / 0 / 0 = off.  Logprobs keep their meaning (raw logits).
+        ``json_schema`` (a json_schema.SchemaDFA): as ``json_mode``, with the schema's compiled DFA as the grammar
+        (vis_schema_mask): a reply that ended on EOS is a document of the schema.  Not together with ``json_mode``."""
         check_top_p(top_p)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         self._begin_logprobs(logprobs)
+        begin_schema(self, json_mode, json_schema)
         self._begin_json(json_mode)
         self._begin_sampling(top_p, False)
         self._begin_penalties(penalties)
@@ -1608,6 +1620,7 @@ class Qwen2VLEngine:
         finally:
             self.lp_k = None
             self.json_on = False
+            self.schema_on = False
             self._end_sampling()
             self._end_penalties()
 
@@ -1636,7 +1649,7 @@ class Qwen2VLEngine:
             toks = toks[:next((i for i, t in enumerate(toks) if t in eos), len(toks))]
         if self.lp_k is not None:
             self.last_logprobs = [self._lp.record(0, self.prompt_len - 1, len(toks), self.lp_k)]
-        if self.json_on and self._json.failed([0])[0]:
+        if self._mask is not None and self._mask.failed([0])[0]:
             raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return toks
 
@@ -1645,7 +1658,7 @@ class Qwen2VLEngine:
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                        json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
-                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None) -> list:
+                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
@@ -1655,13 +1668,14 @@ class Qwen2VLEngine:
         ``top_p``: as in generate.  ``seeds``: one integer per request, its own sampling seed in place of the slot-derived
         one, so a request's sampled reply does not depend on its slot or on what shares the batch.
         ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty``: as in generate, each a number or a sequence
-        with one value per request."""
+        with one value per request.  ``json_schema``: as in generate, one schema for the whole group."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
         check_k(logprobs)
         if not isinstance(json_mode, bool):
             raise ValueError("json_mode must be True or False")
+        check_schema(json_mode, json_schema)
         check_top_p(top_p)
         seeds = check_seeds(seeds, n_req)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
@@ -1675,12 +1689,13 @@ class Qwen2VLEngine:
                     return [e]
             try:
                 return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature,
-                                      seed if seeds is None else seeds[0], logprobs=logprobs, json_mode=json_mode,
+                                      seed if seeds is None else seeds[0], logprobs=logprobs, json_mode=json_mode, json_schema=json_schema,
                                       top_p=top_p, **({} if penalties is None else dict(
                                           zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))))]
             except JsonModeError as e:
                 return [e]
         self._begin_logprobs(logprobs)
+        begin_schema(self, json_mode, json_schema)
         self._begin_json(json_mode)
         self._begin_sampling(top_p, seeds is not None)
         self._begin_penalties(penalties)
@@ -1690,6 +1705,7 @@ class Qwen2VLEngine:
         finally:
             self.lp_k = None
             self.json_on = False
+            self.schema_on = False
             self._end_sampling()
             self._end_penalties()
 
@@ -1740,8 +1756,8 @@ class Qwen2VLEngine:
         if self.lp_k is not None:
             self.last_logprobs = [self._lp.record(slots[b], starts[slots[b]], len(outs[slots[b]]), self.lp_k)
                                   if slots[b] is not None else None for b in range(n_req)]
-        if self.json_on:
-            for s, bad in enumerate(self._json.failed(range(B))):
+        if self._mask is not None:
+            for s, bad in enumerate(self._mask.failed(range(B))):
                 if bad:
                     outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]

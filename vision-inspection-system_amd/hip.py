@@ -58,6 +58,7 @@ _SIGS = {
     "vis_logprobs_ws_bytes": "ii",
     "vis_logprobs_f32": "p" + "ii" + "p" + "i" + "p" + "i" + "ppp" + "l" + "i" + "p",
     "vis_json_mask": "pp" + "i" + "p" * 5 + "iip" + "ii" + "p",
+    "vis_schema_mask": "pp" + "i" + "p" * 5 + "iip" + "i" + "pppp" + "iii" + "p",
     "vis_argmax_masked_f32": "p" + "i" + "ppp" + "i" + "pp" + "fu" + "ii" + "p" + "i" + "p",
     "vis_gemv_bf16_argmax_masked": "pppp" + "iii" + "f" + "ppp" + "i" + "pp" + "fu" + "p" + "p",
     "vis_sample_ws_bytes": "ii",
@@ -1140,6 +1141,42 @@ def json_mask(state: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, tok
     rc = load().vis_json_mask(_ptr(state), _ptr(tokens), tokens.shape[1], _ptr(step), _ptr(tok_off), _ptr(tok_bytes),
                               _ptr(tok_flags), _ptr(eos_ids), eos_ids.numel(), V, _ptr(allow), allow.stride(0), B, _stream())
     _check(rc, "vis_json_mask")
+
+
+def schema_mask(state: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, tok_off: torch.Tensor, tok_bytes: torch.Tensor,
+                tok_flags: torch.Tensor, eos_ids: torch.Tensor, allow: torch.Tensor, header: torch.Tensor, trans: torch.Tensor,
+                byte_class: torch.Tensor, state_flags: torch.Tensor) -> None:
+    """json_mask with a compiled schema (json_schema.SchemaDFA) in place of the JSON grammar: fold the tokens picked since
+    the last call into the DFA state, write the allowed-token bitmask of the next pick.  state / tokens / step / allow and the
+    token table as in json_mask.  The DFA in fixed-capacity device tensors the kernel sizes from ``header`` (int32 [4]:
+    n_states, n_classes, start, 0): trans [cap_states, cap_classes] int16 (the u16 bits) holding the live [n_states, n_classes] table
+    packed at its front, byte_class [256] uint8, state_flags [cap_states] uint8."""
+    if state.dim() != 2 or tokens.dim() != 2 or allow.dim() != 2:
+        raise HipLibraryError("schema_mask: state / tokens / allow must be 2-D")
+    B = state.shape[0]
+    V = tok_flags.numel()
+    if state.dtype != torch.int32 or state.shape[1] != JSON_STATE_INTS or tokens.dtype != torch.int32 or step.dtype != torch.int32:
+        raise HipLibraryError("schema_mask: int32 state [B, 32] / tokens / step required")
+    if tokens.shape[0] != B or step.numel() != B or allow.shape[0] != B or allow.dtype != torch.int64:
+        raise HipLibraryError("schema_mask: bad batch shapes / int64 allow required")
+    if tok_off.dtype != torch.int32 or tok_off.numel() != V + 1 or tok_bytes.dtype != torch.uint8 \
+            or tok_flags.dtype != torch.uint8 or eos_ids.dtype != torch.int32:
+        raise HipLibraryError("schema_mask: bad token table")
+    if header.dtype != torch.int32 or header.numel() != 4 or trans.dtype != torch.int16 or trans.dim() != 2 \
+            or byte_class.dtype != torch.uint8 or byte_class.numel() != 256 or state_flags.dtype != torch.uint8 \
+            or state_flags.numel() != trans.shape[0]:
+        raise HipLibraryError("schema_mask: bad DFA tables")
+    if allow.shape[1] < (V + 63) // 64 or allow.stride(1) != 1 or tokens.stride(1) != 1 or not (
+            state.is_contiguous() and step.is_contiguous() and tok_off.is_contiguous() and tok_bytes.is_contiguous()
+            and tok_flags.is_contiguous() and eos_ids.is_contiguous() and header.is_contiguous() and trans.is_contiguous()
+            and byte_class.is_contiguous() and state_flags.is_contiguous()):
+        raise HipLibraryError("schema_mask: bad strides")
+    if B > 1 and (tokens.stride(0) != tokens.shape[1] or state.stride(0) != JSON_STATE_INTS):
+        raise HipLibraryError("schema_mask: rows must be contiguous")
+    rc = load().vis_schema_mask(_ptr(state), _ptr(tokens), tokens.shape[1], _ptr(step), _ptr(tok_off), _ptr(tok_bytes),
+                                _ptr(tok_flags), _ptr(eos_ids), eos_ids.numel(), V, _ptr(allow), allow.stride(0), _ptr(header),
+                                _ptr(trans), _ptr(byte_class), _ptr(state_flags), trans.shape[0], trans.shape[1], B, _stream())
+    _check(rc, "vis_schema_mask")
 
 
 def argmax_masked(logits: torch.Tensor, ws_val: torch.Tensor, ws_idx: torch.Tensor, tokens: torch.Tensor,

@@ -13,9 +13,10 @@ import time
 import torch
 
 from . import hip
+from . import json_schema as schema
 from .json_grammar import ERR, SLOT_INTS, STATE_INTS, TokenTable, build_token_table
 
-assert STATE_INTS == hip.JSON_STATE_INTS
+assert STATE_INTS == hip.JSON_STATE_INTS == schema.STATE_INTS
 
 
 class JsonModeError(RuntimeError):
@@ -27,15 +28,19 @@ class JsonBuffers:
     """One engine's device token table (built on its first JSON-mode request), grammar states [slots, 32] int32 and allowed-
     token masks [slots, ceil(V / 64)] int64."""
 
-    def __init__(self, tokenizer, vocab: int, eos_ids, slots: int, device):
-        t0 = time.perf_counter()
-        table = build_token_table(tokenizer, vocab, eos_ids)
-        self.table_build_s = time.perf_counter() - t0      # host side; reported by tools/json_mode_bench.py
-        self.table: TokenTable = table
-        self.off = torch.from_numpy(table.off).to(device)
-        self.data = torch.from_numpy(table.data).to(device)
-        self.flags = torch.from_numpy(table.flags).to(device)
-        self.eos = torch.from_numpy(table.eos_ids).to(device)
+    def __init__(self, tokenizer, vocab: int, eos_ids, slots: int, device, share=None):
+        if share is not None:       # the engine's other mask already built the token table: one table, host and device
+            self.table_build_s = 0.0
+            self.table, self.off, self.data, self.flags, self.eos = share.table, share.off, share.data, share.flags, share.eos
+        else:
+            t0 = time.perf_counter()
+            table = build_token_table(tokenizer, vocab, eos_ids)
+            self.table_build_s = time.perf_counter() - t0      # host side; reported by tools/json_mode_bench.py
+            self.table: TokenTable = table
+            self.off = torch.from_numpy(table.off).to(device)
+            self.data = torch.from_numpy(table.data).to(device)
+            self.flags = torch.from_numpy(table.flags).to(device)
+            self.eos = torch.from_numpy(table.eos_ids).to(device)
         self.state = torch.zeros((slots, STATE_INTS), dtype=torch.int32, device=device)
         self.allow = torch.zeros((slots, (vocab + 63) // 64), dtype=torch.int64, device=device)
 
@@ -57,9 +62,89 @@ class JsonBuffers:
         return [bool(st[s, ERR] or st[s, SLOT_INTS + ERR]) for s in slots]
 
 
+class SchemaBuffers(JsonBuffers):
+    """JsonBuffers for a compiled schema (the ``json_schema=`` keyword): the same token table (shared with the engine's
+    JsonBuffers, whichever came first), states and mask rows, plus the DFA in device tables of fixed capacity
+    (SCHEMA_MAX_STATES x SCHEMA_MAX_CLASSES) and the header vis_schema_mask sizes them from.  ``load`` overwrites them per
+    request group; a captured decode graph holds only their addresses, so it serves every schema."""
+
+    def __init__(self, tokenizer, vocab: int, eos_ids, slots: int, device, share=None):
+        super().__init__(tokenizer, vocab, eos_ids, slots, device, share)
+        self.header = torch.zeros(schema.HEADER_INTS, dtype=torch.int32, device=device)
+        # u16 bits in an int16 tensor (-1 = DEAD)
+        self.trans = torch.full((schema.SCHEMA_MAX_STATES, schema.SCHEMA_MAX_CLASSES), -1, dtype=torch.int16, device=device)
+        self.byte_class = torch.zeros(256, dtype=torch.uint8, device=device)
+        self.state_flags = torch.zeros(schema.SCHEMA_MAX_STATES, dtype=torch.uint8, device=device)
+        self.dfa = None
+
+    def load(self, dfa, streams=()) -> None:
+        """Make ``dfa`` the schema of the launches that follow.  Called before a request group's first prompt pass, outside
+        any captured graph: the copies run on the current stream once everything queued on ``streams`` (the streams that
+        launched masks for the previous group) has finished, and those streams then wait for the copies."""
+        if not isinstance(dfa, schema.SchemaDFA):
+            raise ValueError("json_schema must be a SchemaDFA (json_schema.compile_schema)")
+        n, c = dfa.trans.shape
+        if not (1 <= n <= schema.SCHEMA_MAX_STATES and 1 <= c <= schema.SCHEMA_MAX_CLASSES and 0 <= dfa.start < n):
+            raise ValueError(f"json_schema: {n} states x {c} classes exceed the device tables "
+                             f"({schema.SCHEMA_MAX_STATES} x {schema.SCHEMA_MAX_CLASSES})")
+        if dfa.trans.dtype != schema.np.uint16 or dfa.byte_class.shape != (256,) or dfa.state_flags.shape != (n,) \
+                or int(dfa.byte_class.max()) >= c or bool(((dfa.trans >= n) & (dfa.trans != schema.DEAD)).any()):
+            raise ValueError("json_schema: inconsistent DFA tables")
+        if dfa is self.dfa:
+            return
+        cur = torch.cuda.current_stream(self.header.device)
+        for s in streams:
+            cur.wait_stream(s)
+        packed = torch.from_numpy(schema.np.ascontiguousarray(dfa.trans).reshape(-1).view(schema.np.int16))
+        self.trans.view(-1)[:n * c].copy_(packed)
+        self.byte_class.copy_(torch.from_numpy(schema.np.ascontiguousarray(dfa.byte_class)))
+        self.state_flags[:n].copy_(torch.from_numpy(schema.np.ascontiguousarray(dfa.state_flags)))
+        self.header.copy_(torch.tensor([n, c, dfa.start, 0], dtype=torch.int32))
+        for s in streams:
+            s.wait_stream(cur)
+        self.dfa = dfa
+
+    def mask(self, tokens: torch.Tensor, step: torch.Tensor, slot: int = 0) -> torch.Tensor:
+        """vis_schema_mask for slots slot .. slot + B - 1 (tokens [B, T] or [T], step [B]); returns their mask rows."""
+        t2 = tokens if tokens.dim() == 2 else tokens.view(1, -1)
+        B = t2.shape[0]
+        hip.schema_mask(self.state[slot:slot + B], t2, step, self.off, self.data, self.flags, self.eos,
+                        self.allow[slot:slot + B], self.header, self.trans, self.byte_class, self.state_flags)
+        return self.allow[slot:slot + B]
+
+    def failed(self, slots) -> list:
+        st = self.state.cpu()
+        return [bool(st[s, schema.ERR] or st[s, schema.SLOT_INTS + schema.ERR]) for s in slots]
+
+
 def engine_tokenizer(engine):
     tok = getattr(engine, "tokenizer", None)
     if tok is None or not hasattr(tok, "token_bytes"):
         raise ValueError("json_mode needs the engine's tokenizer (engine.tokenizer with token_bytes); "
                          "the client sets it when it loads a model")
     return tok
+
+
+def check_schema(json_mode, json_schema) -> None:
+    """Argument check of the engines' ``json_schema=`` keyword (None = off)."""
+    if json_schema is None:
+        return
+    if not isinstance(json_schema, schema.SchemaDFA):
+        raise ValueError("json_schema must be a SchemaDFA (json_schema.compile_schema) or None")
+    if json_mode:
+        raise ValueError("json_mode and json_schema are two grammars for one reply: give one of them")
+
+
+def begin_schema(engine, json_mode, json_schema) -> None:
+    """Switch vis_schema_mask on (with ``json_schema``'s tables on the device) or off for the request group about to run.
+    Runs before the group's first prompt pass and outside any captured graph; the engine's prompt-pass streams are ordered
+    around the table upload."""
+    check_schema(json_mode, json_schema)
+    if json_schema is None:
+        engine.schema_on = False
+        return
+    if engine._schema is None:
+        engine._schema = SchemaBuffers(engine_tokenizer(engine), engine.cfg.vocab, engine.cfg.eos_ids, engine.max_batch,
+                                       engine.device, share=engine._json)
+    engine._schema.load(json_schema, getattr(engine, "_prefill_streams", ()))
+    engine.schema_on = True

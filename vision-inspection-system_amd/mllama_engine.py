@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .json_mode import JsonBuffers, JsonModeError, engine_tokenizer
+from .json_mode import JsonBuffers, JsonModeError, SchemaBuffers, begin_schema, check_schema, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
 from .penalties import NEUTRAL, PenaltyBuffers, check_penalties
 from .sampling import SampleBuffers, check_seeds, check_top_p
@@ -204,6 +204,9 @@ class MllamaEngine:
         # JSON mode (generate(..., json_mode=True)), as in Qwen2VLEngine; tokenizer: set by the client
         self.json_on = False
         self._json: Optional[JsonBuffers] = None
+        # schema-constrained decoding (generate(..., json_schema=SchemaDFA)): the same pick with vis_schema_mask's rows
+        self.schema_on = False
+        self._schema: Optional[SchemaBuffers] = None
         self.tokenizer = None
         # nucleus sampling / per-request seeds, as in Qwen2VLEngine
         self.smp_on, self.top_p, self.seeded = False, None, False
@@ -489,8 +492,8 @@ class MllamaEngine:
         if taps is not None:
             taps["first_logits"] = logits.clone()
         step.fill_(S - 1)
-        if self.json_on:
-            self._json.reset(slot)
+        if self._mask is not None:
+            self._mask.reset(slot)
         self._seed_slot(slot)
         self._penalty_slot(slot, ids_dev)
         self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
@@ -627,8 +630,8 @@ class MllamaEngine:
             else:
                 hip.gemv(x[(j + 1) * S - 1], w.lm_head, logits, norm_w=w.norm_w, eps=cfg.rms_eps)
             self.step_b[slot:slot + 1].fill_(S - 1)
-            if self.json_on:
-                self._json.reset(slot)
+            if self._mask is not None:
+                self._mask.reset(slot)
             self._seed_slot(slot)
             self._penalty_slot(slot, ids_devs[j])
             self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
@@ -705,8 +708,14 @@ class MllamaEngine:
         if not isinstance(json_mode, bool):
             raise ValueError("json_mode must be True or False")
         if json_mode and self._json is None:
-            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device)
+            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
+                                     share=self._schema)
         self.json_on = json_mode
+
+    @property
+    def _mask(self):
+        """The buffers of the grammar mask that is on (JSON mode or a schema), or None."""
+        return self._schema if self.schema_on else (self._json if self.json_on else None)
 
     def _begin_sampling(self, top_p, seeded: bool) -> None:
         """Route every pick through vis_sample_f32 for this request (Qwen2VLEngine._begin_sampling)."""
@@ -749,13 +758,13 @@ class MllamaEngine:
         if self.pen_on:
             logits = self._pen.apply(logits, tokens, step, slot)
         if self.smp_on:
-            allow = self._json.mask(tokens, step, slot) if self.json_on else None
+            allow = self._mask.mask(tokens, step, slot) if self._mask is not None else None
             self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
             return
-        if not self.json_on:
+        if self._mask is None:
             hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
             return
-        allow = self._json.mask(tokens, step, slot)
+        allow = self._mask.mask(tokens, step, slot)
         hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
 
     def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
@@ -765,15 +774,15 @@ class MllamaEngine:
             hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
             self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
             return
-        if not self.json_on:
+        if self._mask is None:
             hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
             return
-        allow = self._json.mask(tokens, step, 0)
+        allow = self._mask.mask(tokens, step, 0)
         hip.gemv_argmax_masked(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, allow[0], **kw)
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k, self.json_on, self.top_p, self.seeded,
+        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k, self.json_on, self.schema_on, self.top_p, self.seeded,
                self.pen_on)
         if key in self._graphs:
             return self._graphs[key]
@@ -939,7 +948,7 @@ class MllamaEngine:
         self._logprobs_after_pick(B)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B, self.lp_k, self.json_on, self.top_p, self.seeded, self.pen_on)
+        key = (self.temperature, self.seed, B, self.lp_k, self.json_on, self.schema_on, self.top_p, self.seeded, self.pen_on)
         if key in self._graphs_b:
             return self._graphs_b[key]
         snap = (self.step_b.clone(), self.cur_b.clone())
@@ -962,7 +971,7 @@ class MllamaEngine:
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
                        chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
                        top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
-                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None) -> list:
+                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
@@ -970,13 +979,14 @@ class MllamaEngine:
         slot and its exception takes its place in the returned list.  ``logprobs``: as in generate; ``last_logprobs`` then
         holds one record per request (None for a failed one).  ``json_mode``: as in generate; a request whose JSON text could
         not be continued gets a JsonModeError.  ``top_p`` / ``seeds`` and the three penalties (a number or one value per request): as in
-        Qwen2VLEngine.generate_batch."""
+        Qwen2VLEngine.generate_batch; so is ``json_schema`` (one schema for the whole group)."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
         check_k(logprobs)
         if not isinstance(json_mode, bool):
             raise ValueError("json_mode must be True or False")
+        check_schema(json_mode, json_schema)
         check_top_p(top_p)
         seeds = check_seeds(seeds, n_req)
         seed0 = seed if seeds is None else seeds[0]
@@ -989,7 +999,7 @@ class MllamaEngine:
             try:
                 ids, fr = requests[0]() if callable(requests[0]) else requests[0]
                 return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, top_p=top_p, **pen0)]
+                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, **pen0)]
             except Exception as e:      # noqa: BLE001
                 self.last_logprobs = [None] if logprobs is not None else None
                 return [e]
@@ -999,10 +1009,11 @@ class MllamaEngine:
             ids, fr = requests[0]
             try:
                 return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, top_p=top_p, **pen0)]
+                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, **pen0)]
             except JsonModeError as e:
                 return [e]
         self._begin_logprobs(logprobs)
+        begin_schema(self, json_mode, json_schema)
         self._begin_json(json_mode)
         self._begin_sampling(top_p, seeds is not None)
         self._begin_penalties(penalties)
@@ -1012,6 +1023,7 @@ class MllamaEngine:
         finally:
             self.lp_k = None
             self.json_on = False
+            self.schema_on = False
             self._end_sampling()
             self._end_penalties()
 
@@ -1145,8 +1157,8 @@ class MllamaEngine:
         if self.lp_k is not None:
             self.last_logprobs = [self._lp.record(slots[b], starts[slots[b]], len(outs[slots[b]]), self.lp_k)
                                   if slots[b] is not None else None for b in range(n_req)]
-        if self.json_on:
-            for s, bad in enumerate(self._json.failed(range(B))):
+        if self._mask is not None:
+            for s, bad in enumerate(self._mask.failed(range(B))):
                 if bad:
                     outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]
@@ -1161,15 +1173,17 @@ class MllamaEngine:
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
                  chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False,
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None) -> List[int]:
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None) -> List[int]:
         """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
         logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
         None = off, no extra launch.  ``json_mode``: every pick restricted to the tokens that continue a JSON object, as in
         Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it).  ``top_p``: nucleus sampling, as in
-        Qwen2VLEngine.generate; so are ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty`` (penalties.py)."""
+        Qwen2VLEngine.generate; so are ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty`` (penalties.py)
+        and ``json_schema`` (a compiled json_schema.SchemaDFA as the grammar; not together with ``json_mode``)."""
         check_top_p(top_p)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         self._begin_logprobs(logprobs)
+        begin_schema(self, json_mode, json_schema)
         self._begin_json(json_mode)
         self._begin_sampling(top_p, False)
         self._begin_penalties(penalties)
@@ -1188,6 +1202,7 @@ class MllamaEngine:
         finally:
             self.lp_k = None
             self.json_on = False
+            self.schema_on = False
             self._end_sampling()
             self._end_penalties()
 
@@ -1214,6 +1229,6 @@ class MllamaEngine:
             toks = toks[:next((i + 1 for i, t in enumerate(toks) if t in eos), len(toks))]
         if self.lp_k is not None:
             self.last_logprobs = [self._lp.record(0, self.prompt_len - 1, len(toks), self.lp_k)]
-        if self.json_on and self._json.failed([0])[0]:
+        if self._mask is not None and self._mask.failed([0])[0]:
             raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return toks

@@ -169,5 +169,43 @@ if not HOST_SCHEMAS:
         user_notes: Optional[str] = None
 
 
+# JSON Schema of the report the agents' prompts ask the model to write (prompts._SCHEMA, the reference's prompt shape) and
+# response_parsing turns into a VLMAnalysisResult: the keys in the prompt's order with VLMAnalysisResult's / DefectInfo's
+# literals.  Written out, not derived from model_json_schema(): timestamp, analysis_failed, failure_reason and defect_id are
+# filled in by this side, never by the model.  Sent as response_format json_schema when VIS_JSON_SCHEMA=1 (agents.py); it
+# pins keys, types and literals, not BoundingBox's range validators.
+_STR = {"type": "string"}
+_NUM = {"type": "number"}
+_LEVEL = {"enum": ["high", "medium", "low"]}
+REPORT_SCHEMA: Dict[str, Any] = {
+    "type": "object",
+    "properties": {
+        "object_identified": _STR,
+        "overall_condition": {"enum": ["damaged", "good", "uncertain"]},
+        "defects": {"type": "array", "items": {
+            "type": "object",
+            "properties": {
+                "type": _STR,
+                "location": _STR,
+                "bbox": {"anyOf": [{"type": "object",
+                                    "properties": {"x": _NUM, "y": _NUM, "width": _NUM, "height": _NUM},
+                                    "required": ["x", "y", "width", "height"], "additionalProperties": False},
+                                   {"type": "null"}]},
+                "safety_impact": {"enum": ["CRITICAL", "MODERATE", "COSMETIC"]},
+                "reasoning": _STR,
+                "confidence": _LEVEL,
+                "recommended_action": _STR,
+            },
+            "required": ["type", "location", "safety_impact", "reasoning", "confidence", "recommended_action"],
+            "additionalProperties": False}},
+        "overall_confidence": _LEVEL,
+        "analysis_reasoning": _STR,
+    },
+    "required": ["object_identified", "overall_condition", "defects", "overall_confidence"],
+    "additionalProperties": False,
+}
+REPORT_RESPONSE_FORMAT: Dict[str, Any] = {"type": "json_schema",
+                                          "json_schema": {"name": "inspection_report", "schema": REPORT_SCHEMA, "strict": True}}
+
 __all__ = ["BoundingBox", "DefectInfo", "VLMAnalysisResult", "ConsensusResult", "SafetyVerdict",
-           "InspectionContext", "HOST_SCHEMAS"]
+           "InspectionContext", "HOST_SCHEMAS", "REPORT_SCHEMA", "REPORT_RESPONSE_FORMAT"]

@@ -177,19 +177,23 @@ class LlamaByteTokenizer:
         self.bos_id, self.start_header_id, self.end_header_id, self.eot_id = 256, 257, 258, 259
         self.image_token_id = image_token_id
         self.eos_ids = tuple(eos_ids) + (self.eot_id,)
+        # a configured EOS id may lie below 256 (the tiny model's is 2): it is a special like the others, so it ends a
+        # reply without adding a byte to its text (the real vocabulary's decode skips specials the same way)
+        self._eos = frozenset(self.eos_ids)
 
     def encode(self, text: str) -> List[int]:
         return list(text.encode("utf-8"))
 
     def decode(self, ids: Sequence[int]) -> str:
-        return bytes(i for i in ids if 0 <= i < 256).decode("utf-8", errors="replace")
+        return bytes(i for i in ids if 0 <= i < 256 and i not in self._eos).decode("utf-8", errors="replace")
 
     def token_bytes(self, token_id: int) -> bytes:
-        return bytes([token_id]) if 0 <= token_id < 256 else b""
+        return bytes([token_id]) if 0 <= token_id < 256 and token_id not in self._eos else b""
 
     def token_text(self, token_id: int) -> str:
-        names = {self.bos_id: "<|begin_of_text|>", self.start_header_id: "<|start_header_id|>",
-                 self.end_header_id: "<|end_header_id|>", self.eot_id: "<|eot_id|>", self.image_token_id: "<|image|>"}
+        names = {e: "<|end_of_text|>" for e in self._eos}
+        names.update({self.bos_id: "<|begin_of_text|>", self.start_header_id: "<|start_header_id|>",
+                      self.end_header_id: "<|end_header_id|>", self.eot_id: "<|eot_id|>", self.image_token_id: "<|image|>"})
         if token_id in names:
             return names[token_id]
         return self.token_bytes(token_id).decode("utf-8", errors="replace")
