@@ -82,14 +82,13 @@ def kernel_times() -> list:
 
 def step_times() -> list:
     from vision_inspection_system_amd.client import get_model
-    from vision_inspection_system_amd.json_mode import begin_schema
     eng = get_model("synthetic:7b", "cuda:0").engine
     dfa = S.compile_schema(REPORT_SCHEMA)
     rng = np.random.default_rng(0)
     modes = ["off", "json_object", "json_schema"]
 
     def begin(m):
-        begin_schema(eng, False, dfa if m == "json_schema" else None)
+        eng._begin_schema(False, dfa if m == "json_schema" else None)
         eng._begin_json(m == "json_object")
 
     out = []

@@ -26,10 +26,11 @@ import numpy as np
 import torch
 
 from . import hip
-from .json_mode import JsonBuffers, JsonModeError, SchemaBuffers, begin_schema, check_schema, engine_tokenizer
-from .logprobs import LogprobsBuffers, check_k
-from .penalties import NEUTRAL, PenaltyBuffers, check_penalties
-from .sampling import SampleBuffers, check_seeds, check_top_p
+from .json_mode import JsonModeError, check_schema
+from .logprobs import check_k
+from .penalties import check_penalties
+from .pick import PickStage
+from .sampling import check_seeds, check_top_p
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
 
@@ -148,7 +149,7 @@ def _chain_order_lock(index: Optional[int]) -> threading.Lock:
 
 
 # ----------------------------------------------------------------------------- engine
-class Qwen2VLEngine:
+class Qwen2VLEngine(PickStage):
     """One model replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
     def __init__(self, cfg: Qwen2VLConfig, weights: DeviceWeights, device, max_ctx: int = 4096,
@@ -323,28 +324,8 @@ class Qwen2VLEngine:
         self._decoded = 0
         self.decode_limit = 0
         self.last_first_logits: Optional[torch.Tensor] = None
-        # token log-probabilities (generate(..., logprobs=k)): k while a request asks for them, else None; buffers on first use
-        self.lp_k: Optional[int] = None
-        self._lp: Optional[LogprobsBuffers] = None
-        self.last_logprobs: Optional[list] = None
-        # JSON mode (generate(..., json_mode=True)): on while a request asks for it; token table and state on first use.
-        # tokenizer: the vocabulary's token_bytes (the client sets it when it loads the model)
-        self.json_on = False
-        self._json: Optional[JsonBuffers] = None
-        # schema-constrained decoding (generate(..., json_schema=SchemaDFA)): the same pick with vis_schema_mask's rows
-        self.schema_on = False
-        self._schema: Optional[SchemaBuffers] = None
         self.tokenizer = None
-        # nucleus sampling / per-request seeds (generate(..., top_p=), generate_batch(..., top_p=, seeds=)): while on, every
-        # pick is vis_sample_f32 with the row seeds of a device buffer; top_p None = 1; _slot_seed: slot -> request seed
-        self.smp_on, self.top_p, self.seeded = False, None, False
-        self._smp: Optional[SampleBuffers] = None
-        self._slot_seed: Dict[int, int] = {}
-        # logit penalties (generate(..., repetition_penalty=, frequency_penalty=, presence_penalty=)): while on, every pick
-        # reads the row vis_penalize_f32 wrote instead of the raw logits; _slot_pen: slot -> the request's (r, f, q)
-        self.pen_on = False
-        self._pen: Optional[PenaltyBuffers] = None
-        self._slot_pen: Dict[int, tuple] = {}
+        self._init_pick_stage()      # the request switches of the next-token pick (pick.py)
 
     # ------------------------------------------------------------------ vision tower
     def vision_forward(self, frames: Sequence[torch.Tensor], split_rows: bool = True) -> torch.Tensor:
@@ -678,14 +659,7 @@ class Qwen2VLEngine:
         if taps is not None:
             taps["first_logits"] = logits.clone()
         step.fill_(S - 1)
-        if self._mask is not None:
-            self._mask.reset(slot)
-        self._seed_slot(slot)
-        self._penalty_slot(slot, ids_dev)
-        self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
-                   cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot, slot)   # per-slot workspace: prefills
-        # of different slots may run concurrently on different streams
-        self._logprobs_after_pick(1, slot)
+        self._prompt_pick(slot, ids_dev, logits, tokens, cur_token, step)
         self.slot_prompt_len[slot] = S
         if slot == 0:
             self.prompt_len = S
@@ -862,14 +836,7 @@ class Qwen2VLEngine:
             else:
                 hip.gemv(x[(j + 1) * n - 1], w.lm_head, logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
             self.step_b[slot:slot + 1].fill_(S - 1)
-            if self._mask is not None:
-                self._mask.reset(slot)
-            self._seed_slot(slot)
-            self._penalty_slot(slot, ids_devs[j])
-            self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
-                       self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
-                       self.seed + 0x9E3779B9 * slot, slot)
-            self._logprobs_after_pick(1, slot)
+            self._prompt_pick(slot, ids_devs[j], logits, self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1])
             self.slot_prompt_len[slot] = S
             if slot == 0:
                 self.prompt_len = S
@@ -1100,100 +1067,6 @@ class Qwen2VLEngine:
             P = int(special[0])
         P = (P // 64) * 64
         return P if P >= self.min_shared_prefix else 0
-
-    # ------------------------------------------------------------------ token log-probabilities
-    def _begin_logprobs(self, logprobs: Optional[int]) -> None:
-        """Switch the per-pick logprobs launch on (k alternatives) or off (None) for the request about to run."""
-        self.lp_k = check_k(logprobs)
-        self.last_logprobs = None
-        if self.lp_k is not None and self._lp is None:
-            self._lp = LogprobsBuffers(self.max_batch, self.tokens_b.shape[1], self.cfg.vocab, self.device)
-
-    def _logprobs_after_pick(self, B: int, slot: int = 0) -> None:
-        """vis_logprobs_f32 on the logits of slots slot .. slot + B - 1, right after their pick (nothing when off)."""
-        if self.lp_k is not None:
-            self._lp.launch(self.logits_b[slot:slot + B], self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], self.lp_k, slot)
-
-    # ------------------------------------------------------------------ JSON mode
-    def _begin_json(self, json_mode: bool) -> None:
-        """Switch the grammar mask of every pick on or off for the request about to run."""
-        if not isinstance(json_mode, bool):
-            raise ValueError("json_mode must be True or False")
-        if json_mode and self._json is None:
-            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
-                                     share=self._schema)
-        self.json_on = json_mode
-
-    @property
-    def _mask(self):
-        """The buffers of the grammar mask that is on (JSON mode or a schema), or None."""
-        return self._schema if self.schema_on else (self._json if self.json_on else None)
-
-    # ------------------------------------------------------------------ nucleus sampling / per-request seeds
-    def _begin_sampling(self, top_p, seeded: bool) -> None:
-        """Route every pick of the request about to run through vis_sample_f32 when top_p < 1 or it brings its own seeds."""
-        top_p = check_top_p(top_p)
-        self.top_p = top_p if top_p is not None and top_p < 1.0 else None
-        self.seeded = bool(seeded)
-        self.smp_on = self.seeded or self.top_p is not None
-        if self.smp_on and self._smp is None:
-            self._smp = SampleBuffers(self.max_batch, self.cfg.vocab, self.device)
-
-    def _end_sampling(self) -> None:
-        self.smp_on, self.top_p, self.seeded = False, None, False
-        self._slot_seed = {}
-
-    def _seed_slot(self, slot: int) -> None:
-        """Before a prompt pass's pick: the row seed of ``slot`` (the request's own, else the slot-derived one)."""
-        if self.smp_on:
-            self._smp.set_slot(slot, self._slot_seed.get(slot, self.seed + 0x9E3779B9 * slot))
-
-    # ------------------------------------------------------------------ logit penalties
-    def _begin_penalties(self, penalties: Optional[Sequence[tuple]]) -> None:
-        """Route every pick of the request about to run through vis_penalize_f32 when some request of it carries a penalty
-        (penalties: check_penalties' result - one (r, f, q) per request, or None = off)."""
-        self.pen_on = penalties is not None
-        self._slot_pen = {}
-        if self.pen_on and self._pen is None:
-            self._pen = PenaltyBuffers(self.max_batch, self.cfg.vocab, self.device)
-
-    def _end_penalties(self) -> None:
-        self.pen_on = False
-        self._slot_pen = {}
-
-    def _penalty_slot(self, slot: int, ids_dev: torch.Tensor) -> None:
-        """Before a prompt pass's pick: fresh token statistics of ``slot``, the request's triple and its prompt ids."""
-        if self.pen_on:
-            self._pen.begin(slot, ids_dev, *self._slot_pen.get(slot, NEUTRAL))
-
-    def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
-        """The next-token pick of slots slot .. slot + B - 1: vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick;
-        vis_sample_f32 (seeds from the device buffer, the JSON rows as its mask) while nucleus sampling / seeds are on.  While
-        penalties are on, all of them read the penalised copy of the rows (vis_penalize_f32); the raw rows stay intact."""
-        if self.pen_on:
-            logits = self._pen.apply(logits, tokens, step, slot)
-        if self.smp_on:
-            allow = self._mask.mask(tokens, step, slot) if self._mask is not None else None
-            self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
-            return
-        if self._mask is None:
-            hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
-            return
-        allow = self._mask.mask(tokens, step, slot)
-        hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
-
-    def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
-        """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode; while nucleus sampling / seeds
-        or penalties are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
-        if self.smp_on or self.pen_on:
-            hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
-            self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
-            return
-        if self._mask is None:
-            hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
-            return
-        allow = self._mask.mask(tokens, step, 0)
-        hip.gemv_argmax_masked(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, allow[0], **kw)
 
     # ------------------------------------------------------------------ decode
     def _decode_step(self, chained: Optional[bool] = None) -> None:
@@ -1451,11 +1324,9 @@ class Qwen2VLEngine:
         self._logprobs_after_pick(B)
 
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
-        # sampling parameters, the batch size, the logprobs k, JSON mode and top_p are kernel arguments baked into the graph;
-        # the row seeds of vis_sample_f32 and the penalty values of vis_penalize_f32 are read from device memory at replay, so
-        # only whether they are in use is part of it
-        key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch, self.lp_k,
-               self.json_on, self.schema_on, self.top_p, self.seeded, self.pen_on)
+        # temperature, seed and the batch size are kernel arguments baked into the graph; so is what _pick_key() names
+        key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch) \
+            + self._pick_key()
         if key in self._graphs:
             return self._graphs[key]
         step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
@@ -1588,41 +1459,28 @@ class Qwen2VLEngine:
         everything above; None or 1 / 0 / 0 = off.  Logprobs keep their meaning (raw logits).
         ``json_schema`` (a json_schema.SchemaDFA): as ``json_mode``, with the schema's compiled DFA as the grammar
         (vis_schema_mask): a reply that ended on EOS is a document of the schema.  Not together with ``json_mode``."""
-        check_top_p(top_p)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        self._begin_logprobs(logprobs)
-        begin_schema(self, json_mode, json_schema)
-        self._begin_json(json_mode)
-        self._begin_sampling(top_p, False)
-        self._begin_penalties(penalties)
-        if penalties is not None:
-            self._slot_pen[0] = penalties[0]
-        room = self.max_ctx - len(input_ids) - 1
-        if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
-            self._warned_clamp = True          # said once per engine: the reply may end before the model is done
-            _LOG.warning("max_tokens=%d does not fit the context (prompt %d + reply <= VIS_MAX_CTX=%d): generating at most %d",
-                         max_new_tokens, len(input_ids), self.max_ctx, max(1, room))
-        max_new_tokens = max(1, min(max_new_tokens, room))
-        try:
-            out = self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
-            self._maybe_reenable_chain()
-            return out
-        except hip.ChainStalled as e:
-            # Something else held CU slots this launch's producers needed (another PROCESS sharing the GPU, or other work of
-            # this process on another stream: chained launches of this process are ordered, Qwen2VLEngine.decode, everything
-            # else is covered by the bounded wait only).  From the launch after the stall on every chained launch of the
-            # request returned at once (status word read at kernel entry), so what was lost is one wait bound.  The request is
-            # served again on the unchained launches - the same HIP kernels' arithmetic, identical tokens - and the engine
-            # stays on them for the next VIS_CHAIN_RETRY_AFTER requests.
-            _LOG.warning("%s - continuing on the unchained decode step", e)
-            self.disable_chain()
-            return self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
-        finally:
-            self.lp_k = None
-            self.json_on = False
-            self.schema_on = False
-            self._end_sampling()
-            self._end_penalties()
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties):
+            room = self.max_ctx - len(input_ids) - 1
+            if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
+                self._warned_clamp = True          # said once per engine: the reply may end before the model is done
+                _LOG.warning("max_tokens=%d does not fit the context (prompt %d + reply <= VIS_MAX_CTX=%d): generating at most %d",
+                             max_new_tokens, len(input_ids), self.max_ctx, max(1, room))
+            max_new_tokens = max(1, min(max_new_tokens, room))
+            try:
+                out = self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
+                self._maybe_reenable_chain()
+                return out
+            except hip.ChainStalled as e:
+                # Something else held CU slots this launch's producers needed (another PROCESS sharing the GPU, or other work
+                # of this process on another stream: chained launches of this process are ordered, Qwen2VLEngine.decode,
+                # everything else is covered by the bounded wait only).  From the launch after the stall on every chained
+                # launch of the request returned at once (status word read at kernel entry), so what was lost is one wait
+                # bound.  The request is served again on the unchained launches - the same HIP kernels' arithmetic, identical
+                # tokens - and the engine stays on them for the next VIS_CHAIN_RETRY_AFTER requests.
+                _LOG.warning("%s - continuing on the unchained decode step", e)
+                self.disable_chain()
+                return self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
 
     def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time (SURVEY section 5: tracing)
@@ -1647,9 +1505,8 @@ class Qwen2VLEngine:
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": 1}
         if not ignore_eos:
             toks = toks[:next((i for i, t in enumerate(toks) if t in eos), len(toks))]
-        if self.lp_k is not None:
-            self.last_logprobs = [self._lp.record(0, self.prompt_len - 1, len(toks), self.lp_k)]
-        if self._mask is not None and self._mask.failed([0])[0]:
+        self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
+        if self._mask_failed([0]):
             raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return toks
 
@@ -1694,20 +1551,9 @@ class Qwen2VLEngine:
                                           zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))))]
             except JsonModeError as e:
                 return [e]
-        self._begin_logprobs(logprobs)
-        begin_schema(self, json_mode, json_schema)
-        self._begin_json(json_mode)
-        self._begin_sampling(top_p, seeds is not None)
-        self._begin_penalties(penalties)
-        try:
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties):
             return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, seeds,
                                         penalties)
-        finally:
-            self.lp_k = None
-            self.json_on = False
-            self.schema_on = False
-            self._end_sampling()
-            self._end_penalties()
 
     def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
                         seeds=None, penalties=None) -> list:
@@ -1722,8 +1568,7 @@ class Qwen2VLEngine:
         live = [b for b in range(n_req) if slots[b] is not None]
         B = len(live)
         if B == 0:
-            if self.lp_k is not None:
-                self.last_logprobs = [None] * n_req
+            self._record_logprobs([None] * n_req)
             return list(errors)
         longest = max(self.slot_prompt_len[slots[b]] for b in live)
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
@@ -1753,11 +1598,8 @@ class Qwen2VLEngine:
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
         if not ignore_eos:
             outs = [seq[:next((i for i, t in enumerate(seq) if t in eos), len(seq))] for seq in outs]
-        if self.lp_k is not None:
-            self.last_logprobs = [self._lp.record(slots[b], starts[slots[b]], len(outs[slots[b]]), self.lp_k)
-                                  if slots[b] is not None else None for b in range(n_req)]
-        if self._mask is not None:
-            for s, bad in enumerate(self._mask.failed(range(B))):
-                if bad:
-                    outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
+        self._record_logprobs([(slots[b], starts[slots[b]], len(outs[slots[b]])) if slots[b] is not None else None
+                               for b in range(n_req)])
+        for s in self._mask_failed(range(B)):
+            outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]

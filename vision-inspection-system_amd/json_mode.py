@@ -134,17 +134,3 @@ def check_schema(json_mode, json_schema) -> None:
     if json_mode:
         raise ValueError("json_mode and json_schema are two grammars for one reply: give one of them")
 
-
-def begin_schema(engine, json_mode, json_schema) -> None:
-    """Switch vis_schema_mask on (with ``json_schema``'s tables on the device) or off for the request group about to run.
-    Runs before the group's first prompt pass and outside any captured graph; the engine's prompt-pass streams are ordered
-    around the table upload."""
-    check_schema(json_mode, json_schema)
-    if json_schema is None:
-        engine.schema_on = False
-        return
-    if engine._schema is None:
-        engine._schema = SchemaBuffers(engine_tokenizer(engine), engine.cfg.vocab, engine.cfg.eos_ids, engine.max_batch,
-                                       engine.device, share=engine._json)
-    engine._schema.load(json_schema, getattr(engine, "_prefill_streams", ()))
-    engine.schema_on = True

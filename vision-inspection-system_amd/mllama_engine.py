@@ -31,10 +31,11 @@ import numpy as np
 import torch
 
 from . import hip
-from .json_mode import JsonBuffers, JsonModeError, SchemaBuffers, begin_schema, check_schema, engine_tokenizer
-from .logprobs import LogprobsBuffers, check_k
-from .penalties import NEUTRAL, PenaltyBuffers, check_penalties
-from .sampling import SampleBuffers, check_seeds, check_top_p
+from .json_mode import JsonModeError, check_schema
+from .logprobs import check_k
+from .penalties import check_penalties
+from .pick import PickStage
+from .sampling import check_seeds, check_top_p
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
 
 
@@ -95,7 +96,7 @@ def llama3_rope_tables(cfg: MllamaConfig, n: int) -> Tuple[np.ndarray, np.ndarra
     return np.cos(emb).astype(np.float32), np.sin(emb).astype(np.float32)
 
 
-class MllamaEngine:
+class MllamaEngine(PickStage):
     """One mllama replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
     def __init__(self, cfg: MllamaConfig, weights: MllamaDeviceWeights, device, max_ctx: int = 4096, max_batch: int = 1):
@@ -197,25 +198,8 @@ class MllamaEngine:
         self._decoded = 0
         self.has_image = False
         self.decode_limit = 0
-        # token log-probabilities (generate(..., logprobs=k)), as in Qwen2VLEngine: k while a request asks for them, else None
-        self.lp_k: Optional[int] = None
-        self._lp: Optional[LogprobsBuffers] = None
-        self.last_logprobs: Optional[list] = None
-        # JSON mode (generate(..., json_mode=True)), as in Qwen2VLEngine; tokenizer: set by the client
-        self.json_on = False
-        self._json: Optional[JsonBuffers] = None
-        # schema-constrained decoding (generate(..., json_schema=SchemaDFA)): the same pick with vis_schema_mask's rows
-        self.schema_on = False
-        self._schema: Optional[SchemaBuffers] = None
         self.tokenizer = None
-        # nucleus sampling / per-request seeds, as in Qwen2VLEngine
-        self.smp_on, self.top_p, self.seeded = False, None, False
-        self._smp: Optional[SampleBuffers] = None
-        self._slot_seed: Dict[int, int] = {}
-        # logit penalties, as in Qwen2VLEngine
-        self.pen_on = False
-        self._pen: Optional[PenaltyBuffers] = None
-        self._slot_pen: Dict[int, tuple] = {}
+        self._init_pick_stage()      # the request switches of the next-token pick (pick.py)
 
     # ------------------------------------------------------------------ preprocessing (geometry on host, pixels on GPU)
     def prepare_image(self, frame: torch.Tensor):
@@ -492,13 +476,7 @@ class MllamaEngine:
         if taps is not None:
             taps["first_logits"] = logits.clone()
         step.fill_(S - 1)
-        if self._mask is not None:
-            self._mask.reset(slot)
-        self._seed_slot(slot)
-        self._penalty_slot(slot, ids_dev)
-        self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)], tokens,
-                   cur_token, step, self.temperature, self.seed + 0x9E3779B9 * slot, slot)
-        self._logprobs_after_pick(1, slot)
+        self._prompt_pick(slot, ids_dev, logits, tokens, cur_token, step)
         self.slot_prompt_len[slot] = S
         if slot == 0:
             self.prompt_len, self._decoded = S, 0
@@ -630,14 +608,7 @@ class MllamaEngine:
             else:
                 hip.gemv(x[(j + 1) * S - 1], w.lm_head, logits, norm_w=w.norm_w, eps=cfg.rms_eps)
             self.step_b[slot:slot + 1].fill_(S - 1)
-            if self._mask is not None:
-                self._mask.reset(slot)
-            self._seed_slot(slot)
-            self._penalty_slot(slot, ids_devs[j])
-            self._pick(logits, self.ws_val[256 * slot:256 * (slot + 1)], self.ws_idx[256 * slot:256 * (slot + 1)],
-                       self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1], self.temperature,
-                       self.seed + 0x9E3779B9 * slot, slot)
-            self._logprobs_after_pick(1, slot)
+            self._prompt_pick(slot, ids_devs[j], logits, self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1])
             self.slot_prompt_len[slot] = S
             if slot == 0:
                 self.has_image = True
@@ -691,99 +662,9 @@ class MllamaEngine:
                    self.seed)
         self._logprobs_after_pick(1)
 
-    def _begin_logprobs(self, logprobs: Optional[int]) -> None:
-        """Switch the per-pick logprobs launch on (k alternatives) or off (None) for the request about to run."""
-        self.lp_k = check_k(logprobs)
-        self.last_logprobs = None
-        if self.lp_k is not None and self._lp is None:
-            self._lp = LogprobsBuffers(self.max_batch, self.tokens_b.shape[1], self.cfg.vocab, self.device)
-
-    def _logprobs_after_pick(self, B: int, slot: int = 0) -> None:
-        """vis_logprobs_f32 on the logits of slots slot .. slot + B - 1, right after their pick (nothing when off)."""
-        if self.lp_k is not None:
-            self._lp.launch(self.logits_b[slot:slot + B], self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], self.lp_k, slot)
-
-    def _begin_json(self, json_mode: bool) -> None:
-        """Switch the grammar mask of every pick on or off for the request about to run (Qwen2VLEngine._begin_json)."""
-        if not isinstance(json_mode, bool):
-            raise ValueError("json_mode must be True or False")
-        if json_mode and self._json is None:
-            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
-                                     share=self._schema)
-        self.json_on = json_mode
-
-    @property
-    def _mask(self):
-        """The buffers of the grammar mask that is on (JSON mode or a schema), or None."""
-        return self._schema if self.schema_on else (self._json if self.json_on else None)
-
-    def _begin_sampling(self, top_p, seeded: bool) -> None:
-        """Route every pick through vis_sample_f32 for this request (Qwen2VLEngine._begin_sampling)."""
-        top_p = check_top_p(top_p)
-        self.top_p = top_p if top_p is not None and top_p < 1.0 else None
-        self.seeded = bool(seeded)
-        self.smp_on = self.seeded or self.top_p is not None
-        if self.smp_on and self._smp is None:
-            self._smp = SampleBuffers(self.max_batch, self.cfg.vocab, self.device)
-
-    def _end_sampling(self) -> None:
-        self.smp_on, self.top_p, self.seeded = False, None, False
-        self._slot_seed = {}
-
-    def _seed_slot(self, slot: int) -> None:
-        """Before a prompt pass's pick: the row seed of ``slot`` (the request's own, else the slot-derived one)."""
-        if self.smp_on:
-            self._smp.set_slot(slot, self._slot_seed.get(slot, self.seed + 0x9E3779B9 * slot))
-
-    def _begin_penalties(self, penalties: Optional[Sequence[tuple]]) -> None:
-        """Route every pick through vis_penalize_f32 for this request (Qwen2VLEngine._begin_penalties)."""
-        self.pen_on = penalties is not None
-        self._slot_pen = {}
-        if self.pen_on and self._pen is None:
-            self._pen = PenaltyBuffers(self.max_batch, self.cfg.vocab, self.device)
-
-    def _end_penalties(self) -> None:
-        self.pen_on = False
-        self._slot_pen = {}
-
-    def _penalty_slot(self, slot: int, ids_dev: torch.Tensor) -> None:
-        """Before a prompt pass's pick: fresh token statistics of ``slot``, the request's triple and its prompt ids (the image
-        token's id equals the vocabulary size: the kernel skips it)."""
-        if self.pen_on:
-            self._pen.begin(slot, ids_dev, *self._slot_pen.get(slot, NEUTRAL))
-
-    def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
-        """vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick, for slots slot .. slot + B - 1; vis_sample_f32
-        while nucleus sampling / seeds are on.  While penalties are on, all of them read the penalised copy of the rows."""
-        if self.pen_on:
-            logits = self._pen.apply(logits, tokens, step, slot)
-        if self.smp_on:
-            allow = self._mask.mask(tokens, step, slot) if self._mask is not None else None
-            self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
-            return
-        if self._mask is None:
-            hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
-            return
-        allow = self._mask.mask(tokens, step, slot)
-        hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
-
-    def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
-        """The fused lm_head + pick of the single-sequence step, masked in JSON mode; the plain lm_head GEMV + _pick while
-        nucleus sampling / seeds or penalties are on."""
-        if self.smp_on or self.pen_on:
-            hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
-            self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
-            return
-        if self._mask is None:
-            hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
-            return
-        allow = self._mask.mask(tokens, step, 0)
-        hip.gemv_argmax_masked(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, allow[0], **kw)
-
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained, self.lp_k, self.json_on, self.schema_on, self.top_p, self.seeded,
-               self.pen_on)
+        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key()
         if key in self._graphs:
             return self._graphs[key]
         snap = (self.step.clone(), self.cur_token.clone())
@@ -948,7 +829,7 @@ class MllamaEngine:
         self._logprobs_after_pick(B)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B, self.lp_k, self.json_on, self.schema_on, self.top_p, self.seeded, self.pen_on)
+        key = (self.temperature, self.seed, B) + self._pick_key()
         if key in self._graphs_b:
             return self._graphs_b[key]
         snap = (self.step_b.clone(), self.cur_b.clone())
@@ -1012,20 +893,9 @@ class MllamaEngine:
                                       json_mode=json_mode, json_schema=json_schema, top_p=top_p, **pen0)]
             except JsonModeError as e:
                 return [e]
-        self._begin_logprobs(logprobs)
-        begin_schema(self, json_mode, json_schema)
-        self._begin_json(json_mode)
-        self._begin_sampling(top_p, seeds is not None)
-        self._begin_penalties(penalties)
-        try:
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties):
             return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds,
                                         penalties)
-        finally:
-            self.lp_k = None
-            self.json_on = False
-            self.schema_on = False
-            self._end_sampling()
-            self._end_penalties()
 
     def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds=None,
                         penalties=None) -> list:
@@ -1124,8 +994,7 @@ class MllamaEngine:
                 cur.wait_stream(st)
         ev[1].record()
         if B == 0:
-            if self.lp_k is not None:
-                self.last_logprobs = [None] * n_req
+            self._record_logprobs([None] * n_req)
             return list(errors)
         longest = max(self.slot_prompt_len[s] for s in range(B))
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
@@ -1154,13 +1023,10 @@ class MllamaEngine:
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
         if stop_on_eos:
             outs = [seq[:next((i + 1 for i, t in enumerate(seq) if t in eos), len(seq))] for seq in outs]
-        if self.lp_k is not None:
-            self.last_logprobs = [self._lp.record(slots[b], starts[slots[b]], len(outs[slots[b]]), self.lp_k)
-                                  if slots[b] is not None else None for b in range(n_req)]
-        if self._mask is not None:
-            for s, bad in enumerate(self._mask.failed(range(B))):
-                if bad:
-                    outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
+        self._record_logprobs([(slots[b], starts[slots[b]], len(outs[slots[b]])) if slots[b] is not None else None
+                               for b in range(n_req)])
+        for s in self._mask_failed(range(B)):
+            outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]
 
     def generated(self, n: int) -> List[int]:
@@ -1180,31 +1046,18 @@ class MllamaEngine:
         Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it).  ``top_p``: nucleus sampling, as in
         Qwen2VLEngine.generate; so are ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty`` (penalties.py)
         and ``json_schema`` (a compiled json_schema.SchemaDFA as the grammar; not together with ``json_mode``)."""
-        check_top_p(top_p)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        self._begin_logprobs(logprobs)
-        begin_schema(self, json_mode, json_schema)
-        self._begin_json(json_mode)
-        self._begin_sampling(top_p, False)
-        self._begin_penalties(penalties)
-        if penalties is not None:
-            self._slot_pen[0] = penalties[0]
-        try:
-            return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
-        except hip.ChainStalled as e:
-            # a chained launch could not get its waiting workgroups resident (another process on the GPU): the request is served
-            # again on the separate launches - identical tokens - and this engine stays on them
-            import logging
-            logging.getLogger("vision_inspection_system_amd.engine").warning("%s - continuing on the unchained decode step", e)
-            self.chain_sync = None
-            self._graphs.clear()
-            return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
-        finally:
-            self.lp_k = None
-            self.json_on = False
-            self.schema_on = False
-            self._end_sampling()
-            self._end_penalties()
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties):
+            try:
+                return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
+            except hip.ChainStalled as e:
+                # a chained launch could not get its waiting workgroups resident (another process on the GPU): the request is
+                # served again on the separate launches - identical tokens - and this engine stays on them
+                import logging
+                logging.getLogger("vision_inspection_system_amd.engine").warning("%s - continuing on the unchained decode step", e)
+                self.chain_sync = None
+                self._graphs.clear()
+                return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
 
     def _generate(self, input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> List[int]:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time, as in Qwen2VLEngine
@@ -1227,8 +1080,7 @@ class MllamaEngine:
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": 1}
         if stop_on_eos:
             toks = toks[:next((i + 1 for i, t in enumerate(toks) if t in eos), len(toks))]
-        if self.lp_k is not None:
-            self.last_logprobs = [self._lp.record(0, self.prompt_len - 1, len(toks), self.lp_k)]
-        if self._mask is not None and self._mask.failed([0])[0]:
+        self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
+        if self._mask_failed([0]):
             raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return toks

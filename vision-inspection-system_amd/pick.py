@@ -1,0 +1,217 @@
+"""The next-token pick and the request switches that steer it (logprobs, JSON mode, a JSON Schema, nucleus sampling /
+seeds, penalties): which launches turn a row of logits into a token, the state behind each switch, and the part of the
+decode-graph key that depends on them.  Both engines derive from ``PickStage``; nothing else knows this policy."""
+from __future__ import annotations
+
+import contextlib
+from typing import Dict, Iterable, List, Optional, Sequence
+
+import torch
+
+from . import hip
+from .json_mode import JsonBuffers, SchemaBuffers, check_schema, engine_tokenizer
+from .logprobs import LogprobsBuffers, check_k
+from .penalties import NEUTRAL, PenaltyBuffers
+from .sampling import SLOT_SEED_STRIDE, SampleBuffers, check_top_p
+
+
+class PickStage:
+    """Base class of the engines: works on ``self``, holds no model knowledge.
+
+    Contract - what it reads of the engine, all present before ``_init_pick_stage()`` runs: ``cfg.vocab``, ``cfg.eos_ids``,
+    ``max_batch``, ``device``, the per-slot rows ``tokens_b`` [slots, T] / ``logits_b`` [slots, V] / ``step_b`` [slots], the
+    pick workspace ``ws_val`` / ``ws_idx`` (>= 256 entries per slot), ``temperature`` and ``seed`` of the request running,
+    and ``tokenizer`` (the vocabulary's token_bytes; the client sets it when it loads the model).  The streams of an
+    engine's ``_prefill_streams``, where it has any, are ordered around a schema's table upload."""
+
+    def _init_pick_stage(self) -> None:
+        # token log-probabilities (generate(..., logprobs=k)): k while a request asks for them, else None; buffers on first use
+        self.lp_k: Optional[int] = None
+        self._lp: Optional[LogprobsBuffers] = None
+        self.last_logprobs: Optional[list] = None
+        # JSON mode (generate(..., json_mode=True)): on while a request asks for it; token table and state on first use.
+        self.json_on = False
+        self._json: Optional[JsonBuffers] = None
+        # schema-constrained decoding (generate(..., json_schema=SchemaDFA)): the same pick with vis_schema_mask's rows
+        self.schema_on = False
+        self._schema: Optional[SchemaBuffers] = None
+        # nucleus sampling / per-request seeds (generate(..., top_p=), generate_batch(..., top_p=, seeds=)): while on, every
+        # pick is vis_sample_f32 with the row seeds of a device buffer; top_p None = 1; _slot_seed: slot -> request seed
+        self.smp_on, self.top_p, self.seeded = False, None, False
+        self._smp: Optional[SampleBuffers] = None
+        self._slot_seed: Dict[int, int] = {}
+        # logit penalties (generate(..., repetition_penalty=, frequency_penalty=, presence_penalty=)): while on, every pick
+        # reads the row vis_penalize_f32 wrote instead of the raw logits; _slot_pen: slot -> the request's (r, f, q)
+        self.pen_on = False
+        self._pen: Optional[PenaltyBuffers] = None
+        self._slot_pen: Dict[int, tuple] = {}
+
+    # ------------------------------------------------------------------ one request's switches
+    @contextlib.contextmanager
+    def _pick_request(self, logprobs, json_mode, json_schema, top_p, seeded: bool, penalties: Optional[Sequence[tuple]]):
+        """The switches of one request (or one batch of them) on for the body, and all off again afterwards - also when the
+        body, or switching on itself (no tokenizer, a schema the device tables cannot hold), raises.  ``penalties``:
+        check_penalties' result; a single request runs in slot 0 and its triple is placed there."""
+        check_k(logprobs)
+        check_schema(json_mode, json_schema)
+        if not isinstance(json_mode, bool):
+            raise ValueError("json_mode must be True or False")
+        check_top_p(top_p)
+        try:
+            self._begin_logprobs(logprobs)
+            self._begin_schema(json_mode, json_schema)
+            self._begin_json(json_mode)
+            self._begin_sampling(top_p, seeded)
+            self._begin_penalties(penalties)
+            if penalties is not None and len(penalties) == 1:
+                self._slot_pen[0] = penalties[0]
+            yield
+        finally:
+            self.lp_k = None
+            self.json_on = False
+            self.schema_on = False
+            self._end_sampling()
+            self._end_penalties()
+
+    def _pick_key(self) -> tuple:
+        """The switches' part of a decode-graph key.  The logprobs k, the masks and top_p are kernel arguments or launches
+        baked into a captured step; the row seeds of vis_sample_f32 and the penalty values of vis_penalize_f32 are read from
+        device memory at replay, so only whether they are in use is part of it."""
+        return (self.lp_k, self.json_on, self.schema_on, self.top_p, self.seeded, self.pen_on)
+
+    # ------------------------------------------------------------------ token log-probabilities
+    def _begin_logprobs(self, logprobs: Optional[int]) -> None:
+        """Switch the per-pick logprobs launch on (k alternatives) or off (None) for the request about to run."""
+        self.lp_k = check_k(logprobs)
+        self.last_logprobs = None
+        if self.lp_k is not None and self._lp is None:
+            self._lp = LogprobsBuffers(self.max_batch, self.tokens_b.shape[1], self.cfg.vocab, self.device)
+
+    def _logprobs_after_pick(self, B: int, slot: int = 0) -> None:
+        """vis_logprobs_f32 on the logits of slots slot .. slot + B - 1, right after their pick (nothing when off)."""
+        if self.lp_k is not None:
+            self._lp.launch(self.logits_b[slot:slot + B], self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], self.lp_k, slot)
+
+    def _record_logprobs(self, rows: Iterable[Optional[tuple]]) -> None:
+        """After the run (the stream has drained): ``last_logprobs`` = one record per request from its (slot, start, length)
+        row, None for a request that failed (nothing when off)."""
+        if self.lp_k is not None:
+            self.last_logprobs = [self._lp.record(*r, self.lp_k) if r is not None else None for r in rows]
+
+    # ------------------------------------------------------------------ JSON mode / JSON Schema
+    def _begin_schema(self, json_mode: bool, json_schema) -> None:
+        """Switch vis_schema_mask on (with ``json_schema``'s tables on the device) or off for the request group about to run.
+        Runs before the group's first prompt pass and outside any captured graph; the engine's prompt-pass streams are ordered
+        around the table upload."""
+        check_schema(json_mode, json_schema)
+        if json_schema is None:
+            self.schema_on = False
+            return
+        if self._schema is None:
+            self._schema = SchemaBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
+                                         share=self._json)
+        self._schema.load(json_schema, getattr(self, "_prefill_streams", ()))
+        self.schema_on = True
+
+    def _begin_json(self, json_mode: bool) -> None:
+        """Switch the grammar mask of every pick on or off for the request about to run."""
+        if not isinstance(json_mode, bool):
+            raise ValueError("json_mode must be True or False")
+        if json_mode and self._json is None:
+            self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
+                                     share=self._schema)
+        self.json_on = json_mode
+
+    @property
+    def _mask(self):
+        """The buffers of the grammar mask that is on (JSON mode or a schema), or None."""
+        return self._schema if self.schema_on else (self._json if self.json_on else None)
+
+    def _mask_failed(self, slots: Iterable[int]) -> List[int]:
+        """After the run: those of ``slots`` whose grammar could not be continued by any token (none when no mask is on);
+        synchronises."""
+        slots = list(slots)
+        if self._mask is None:
+            return []
+        return [s for s, bad in zip(slots, self._mask.failed(slots)) if bad]
+
+    # ------------------------------------------------------------------ nucleus sampling / per-request seeds
+    def _begin_sampling(self, top_p, seeded: bool) -> None:
+        """Route every pick of the request about to run through vis_sample_f32 when top_p < 1 or it brings its own seeds."""
+        top_p = check_top_p(top_p)
+        self.top_p = top_p if top_p is not None and top_p < 1.0 else None
+        self.seeded = bool(seeded)
+        self.smp_on = self.seeded or self.top_p is not None
+        if self.smp_on and self._smp is None:
+            self._smp = SampleBuffers(self.max_batch, self.cfg.vocab, self.device)
+
+    def _end_sampling(self) -> None:
+        self.smp_on, self.top_p, self.seeded = False, None, False
+        self._slot_seed = {}
+
+    def _seed_slot(self, slot: int) -> None:
+        """Before a prompt pass's pick: the row seed of ``slot`` (the request's own, else the slot-derived one)."""
+        if self.smp_on:
+            self._smp.set_slot(slot, self._slot_seed.get(slot, self.seed + SLOT_SEED_STRIDE * slot))
+
+    # ------------------------------------------------------------------ logit penalties
+    def _begin_penalties(self, penalties: Optional[Sequence[tuple]]) -> None:
+        """Route every pick of the request about to run through vis_penalize_f32 when some request of it carries a penalty
+        (penalties: check_penalties' result - one (r, f, q) per request, or None = off)."""
+        self.pen_on = penalties is not None
+        self._slot_pen = {}
+        if self.pen_on and self._pen is None:
+            self._pen = PenaltyBuffers(self.max_batch, self.cfg.vocab, self.device)
+
+    def _end_penalties(self) -> None:
+        self.pen_on = False
+        self._slot_pen = {}
+
+    def _penalty_slot(self, slot: int, ids_dev: torch.Tensor) -> None:
+        """Before a prompt pass's pick: fresh token statistics of ``slot``, the request's triple and its prompt ids (mllama's
+        image token has the id of the vocabulary size: the kernel skips it)."""
+        if self.pen_on:
+            self._pen.begin(slot, ids_dev, *self._slot_pen.get(slot, NEUTRAL))
+
+    # ------------------------------------------------------------------ the pick
+    def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
+        """The next-token pick of slots slot .. slot + B - 1: vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick;
+        vis_sample_f32 (seeds from the device buffer, the JSON rows as its mask) while nucleus sampling / seeds are on.  While
+        penalties are on, all of them read the penalised copy of the rows (vis_penalize_f32); the raw rows stay intact."""
+        if self.pen_on:
+            logits = self._pen.apply(logits, tokens, step, slot)
+        if self.smp_on:
+            allow = self._mask.mask(tokens, step, slot) if self._mask is not None else None
+            self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
+            return
+        if self._mask is None:
+            hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
+            return
+        allow = self._mask.mask(tokens, step, slot)
+        hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
+
+    def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
+        """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode; while nucleus sampling / seeds
+        or penalties are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
+        if self.smp_on or self.pen_on:
+            hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
+            self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
+            return
+        if self._mask is None:
+            hip.gemv_argmax(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw)
+            return
+        allow = self._mask.mask(tokens, step, 0)
+        hip.gemv_argmax_masked(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, allow[0], **kw)
+
+    def _prompt_pick(self, slot: int, ids_dev: torch.Tensor, logits, tokens, cur_token, step) -> None:
+        """The first token of ``slot``, from the logits of its prompt's last row: a fresh grammar state, row seed and token
+        statistics, then the pick and its logprobs."""
+        if self._mask is not None:
+            self._mask.reset(slot)
+        self._seed_slot(slot)
+        self._penalty_slot(slot, ids_dev)
+        ws = slice(256 * slot, 256 * (slot + 1))    # per-slot workspace: prefills of different slots may run concurrently
+        # on different streams
+        self._pick(logits, self.ws_val[ws], self.ws_idx[ws], tokens, cur_token, step, self.temperature,
+                   self.seed + SLOT_SEED_STRIDE * slot, slot)
+        self._logprobs_after_pick(1, slot)
