@@ -308,6 +308,26 @@ int vis_penalty_prompt(void* state_row, int V, const void* ids, int n, vis_strea
 int vis_penalize_f32(const void* logits, int V, int ld_logits, void* state, const void* params, const void* tokens,
                      int max_tokens, const void* step_ptr, void* out, int ld_out, int batch, vis_stream_t stream);
 
+/* Stop sequences and how a reply ended (csrc/stop_scan.hip; stop.py compiles the tables and is the reference).  One launch
+ * AFTER each pick: for every row b < batch folds the tokens picked since the row's last launch (positions [pos, step[b]) of
+ * tokens[b][max_tokens]; on the first launch after a reset the one at step[b] - 1) byte by byte - token table as
+ * vis_json_mask's - through the Aho-Corasick automaton of the request's stop strings.  state: int32 [batch][8], 16-byte
+ * aligned, all zero = a fresh sequence: DFA state, pos, bytes so far, reason (0 open, 1 EOS, 2 stop), tokens kept (EOS:
+ * exclusive; stop: through the token that completed the match), cut (byte offset in the generated stream where the match
+ * starts; EOS: bytes so far), index of the stop string, anchored.  A row with reason != 0 is never written again; a launch
+ * repeated at the same step changes nothing.  The automaton: header int32 [4] = {n_states, n_classes, 0, 0}, READ BY THE
+ * KERNEL (a captured launch serves whatever stop set the buffers hold when it is replayed); trans u16 [n_states][n_classes]
+ * packed at the front of a buffer of cap_states * cap_classes entries, failure links resolved, bit 15 = the target state
+ * ends a stop string; byte_class u8 [256]; hits u8 [cap_states][2] = (length of the longest stop string that is a suffix at
+ * the state, its index).  eos_on = 0: tokens flagged EOS are folded as tokens without bytes.  A header outside the
+ * capacities switches the walk off; states and classes outside the header are clamped.
+ * VIS_ERR_ARG: null pointer, V outside 1..262144, batch outside 1..64, max_tokens <= 0, eos_on not 0 / 1, cap_states outside
+ * 1..257, cap_classes outside 1..256, state not 16-byte aligned, tok_bytes / header not 4-byte aligned. */
+int vis_stop_scan(void* state, const void* tokens, int max_tokens, const void* step_ptr, const void* tok_off,
+                  const void* tok_bytes, const void* tok_flags, int V, const void* header, const void* trans,
+                  const void* byte_class, const void* hits, int cap_states, int cap_classes, int eos_on, int batch,
+                  vis_stream_t stream);
+
 /* K10 (batched decode), first half.  For up to 64 in-flight sequences the weight matrix is streamed from HBM
  * ONCE per step by <= 256 persistent workgroups (one per CU, 7-stage LDS-DMA ring, stream-K cut of the
  * (128-column tile, K-step) sequence).  part[slot][R][N] (f32), R = 16 / 32 / 64 for B <= 16 / 32 / 64 (one, two or four

@@ -61,6 +61,25 @@ def penalty_kwargs() -> dict:
         raise ValueError("VIS_REPETITION_PENALTY must be a number") from None
 
 
+def stop_kwargs() -> dict:
+    """VIS_STOP=<JSON string or list of up to 4 strings> (default unset): the analysis and verify requests pass it as stop=,
+    so a report ends in front of the first of them (VIS_STOP='["```"]': at the fence that closes its JSON block) instead of
+    running on to max_tokens.  Unset: the calls are as before."""
+    v = os.environ.get("VIS_STOP", "").strip()
+    if not v:
+        return {}
+    import json
+    from .stop import check_stop
+    try:
+        stop = json.loads(v)
+    except ValueError:
+        raise ValueError("VIS_STOP must be a JSON string or a JSON list of strings") from None
+    if not isinstance(stop, (str, list)):
+        raise ValueError("VIS_STOP must be a JSON string or a JSON list of strings")
+    check_stop(stop)
+    return {"stop": stop}
+
+
 def _logger(name: str) -> logging.Logger:
     try:  # pragma: no cover - only inside the reference application
         from utils.logger import setup_logger  # type: ignore
@@ -87,7 +106,7 @@ class _BaseAgent:
             try:
                 completion = self.client.chat.completions.create(
                     model=self.model_id, messages=messages, temperature=self.temperature, max_tokens=self.max_tokens,
-                    **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs())
+                    **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs())
                 return completion.choices[0].message.content
             except Exception as e:
                 text = str(e)
@@ -326,14 +345,14 @@ def _many(agent, image_paths, contexts, prepared=None) -> list:
         try:
             if hasattr(agent.client, "complete_many"):
                 replies = agent.client.complete_many(agent.model_id, msgs, agent.temperature, agent.max_tokens,
-                                                     **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs())
+                                                     **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs())
                 texts = [r if isinstance(r, Exception) else r.choices[0].message.content for r in replies]
             else:
                 texts = [agent.client.chat.completions.create(model=agent.model_id, messages=m,
                                                               temperature=agent.temperature,
                                                               max_tokens=agent.max_tokens,
                                                               **json_mode_kwargs(), **seed_kwargs(),
-                                                              **penalty_kwargs()).choices[0].message.content
+                                                              **penalty_kwargs(), **stop_kwargs()).choices[0].message.content
                          for m in msgs]
         except Exception as e:
             agent.logger.error(f"{agent.nickname}: batched call failed: {e}", exc_info=True)

@@ -78,9 +78,9 @@ class _Completions:
                top_logprobs: Optional[int] = None, response_format: Optional[dict] = None, top_p: Optional[float] = None,
                seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
                presence_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
-               **kwargs) -> ChatCompletion:
+               stop=None, **kwargs) -> ChatCompletion:
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
-                 "repetition_penalty": repetition_penalty}
+                 "repetition_penalty": repetition_penalty, "stop": stop}
         kwargs.update({name: v for name, v in given.items() if v is not None})
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
                                      top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
@@ -236,6 +236,20 @@ def _reply_text(model_id: str, decoded: str) -> str:
         if fixed:
             return fixed
     return decoded
+
+
+def _finish_reason(fin) -> str:
+    """An engine's ``last_finish`` entry as OpenAI's finish_reason: "stop" for EOS or a stop string, "length" for a reply
+    that max_tokens or the context cut off (an engine stand-in without the record: "stop", as before)."""
+    return "length" if fin is not None and fin[0] == "length" else "stop"
+
+
+def _finished_text(tok, toks: List[int], fin) -> str:
+    """The reply text of the returned tokens: on a stop match their bytes up to where the stop string starts (UTF-8, a
+    sequence the cut split is replaced), else what the tokenizer decodes."""
+    if fin is not None and fin[0] == "stop":
+        return b"".join(tok.token_bytes(t) for t in toks)[:fin[1]].decode("utf-8", errors="replace")
+    return tok.decode(toks)
 
 
 def logprobs_k(logprobs, top_logprobs) -> Optional[int]:
@@ -409,16 +423,16 @@ class LocalVLMClient:
 
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
                   top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
-                  **kwargs) -> ChatCompletion:
+                  stop=None, **kwargs) -> ChatCompletion:
         return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
                                   response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
-                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty)[0]
+                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop)[0]
 
     def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
                       top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
                       top_p: Optional[float] = None, seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
                       presence_penalty: Optional[float] = None,
-                      repetition_penalty: Optional[float] = None) -> List[ChatCompletion]:
+                      repetition_penalty: Optional[float] = None, stop=None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -443,14 +457,20 @@ class LocalVLMClient:
         frequency_penalty times the number of times its token was generated so far, and by presence_penalty when it was
         generated at all.  ``repetition_penalty`` (extension, transformers' meaning, > 0): the logit of every token of the
         prompt or the reply so far is divided by it when positive, multiplied when negative.  Applied to the raw logits
-        ahead of temperature, the JSON mask and top_p (penalties.py); None or 0 / 0 / 1 = off.  Logprobs keep their meaning."""
+        ahead of temperature, the JSON mask and top_p (penalties.py); None or 0 / 0 / 1 = off.  Logprobs keep their meaning.
+        ``stop`` (OpenAI's): a string or up to 4 of them, each 1..64 bytes of UTF-8; the reply ends in front of the first
+        occurrence of one in its bytes (stop.py, matched on the GPU) and never contains it; tokens, usage and logprobs run
+        through the token that completed the match.  Every choice's ``finish_reason`` is "stop" when the reply ended on EOS
+        or a stop string and "length" when max_tokens or the context cut it off."""
         import torch
         from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
+        from .stop import check_stop
         k = logprobs_k(logprobs, top_logprobs)
         dfa = schema_of(response_format)
         jm = json_mode_of(response_format) if dfa is None else False
         top_p = check_top_p(top_p)
+        stop = check_stop(stop)
         seed = check_seed(seed)
         pen = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         pen = {} if pen is None else dict(zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), pen[0]))
@@ -463,7 +483,7 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         out: List[ChatCompletion] = []
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa, stop)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -502,22 +522,25 @@ class LocalVLMClient:
                                           **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}),
                                           **({"json_schema": dfa} if dfa is not None else {}),
                                           **({"top_p": top_p} if top_p is not None else {}),
-                                          **({"seeds": [seed] * len(idx)} if seed is not None else {}), **pen)
+                                          **({"seeds": [seed] * len(idx)} if seed is not None else {}),
+                                          **({"stop": stop} if stop is not None else {}), **pen)
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
+                fins = getattr(eng, "last_finish", None) or [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", {}))
                 if timing:
                     TIMING_LOG.append({"model": model_id, **timing})
                     del TIMING_LOG[:-4096]
                     logger.debug("%s: %d request(s): prompt pass %.1f ms, %d decode steps in %.1f ms (device time)", model_id,
                                  len(idx), timing["prefill_ms"], timing["decode_steps"], timing["decode_ms"])
-                for j, t, rec in zip(idx, toks, recs):
+                for j, t, rec, fin in zip(idx, toks, recs, fins):
                     if isinstance(t, Exception):
                         if not lazy:
                             raise t
                         out.append(t)
                         continue
                     lp = _choice_logprobs(tok, t, rec) if rec is not None else None
-                    out.append(ChatCompletion([_Choice(_Message(_reply_text(model_id, tok.decode(t))), logprobs=lp)], model=model_id,
+                    out.append(ChatCompletion([_Choice(_Message(_reply_text(model_id, _finished_text(tok, t, fin))),
+                                                       finish_reason=_finish_reason(fin), logprobs=lp)], model=model_id,
                                               usage={"prompt_tokens": n_ids[j], "completion_tokens": len(t),
                                                      "total_tokens": n_ids[j] + len(t)}, timings=timing))
         return out
@@ -545,7 +568,8 @@ class LocalVLMClient:
 
     def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
                               k: Optional[int] = None, jm: bool = False, top_p: Optional[float] = None,
-                              seed: Optional[int] = None, pen: Optional[dict] = None, dfa=None) -> List[ChatCompletion]:
+                              seed: Optional[int] = None, pen: Optional[dict] = None, dfa=None,
+                              stop=None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -561,14 +585,17 @@ class LocalVLMClient:
             lpk["json_schema"] = dfa
         if top_p is not None:
             lpk["top_p"] = top_p
+        if stop is not None:
+            lpk["stop"] = stop
         lpk.update(pen or {})
 
         def seeds_of(n):
             return {"seeds": [seed] * n} if seed is not None else {}
 
-        def completion(n_ids, t, rec=None):
+        def completion(n_ids, t, rec=None, fin=None):
             lp = _choice_logprobs(tok, t, rec) if rec is not None else None
-            return ChatCompletion([_Choice(_Message(_reply_text(lm.model_id, tok.decode(t))), logprobs=lp)], model=lm.model_id,
+            return ChatCompletion([_Choice(_Message(_reply_text(lm.model_id, _finished_text(tok, t, fin))),
+                                           finish_reason=_finish_reason(fin), logprobs=lp)], model=lm.model_id,
                                   usage={"prompt_tokens": n_ids, "completion_tokens": len(t), "total_tokens": n_ids + len(t)},
                                   timings=dict(getattr(eng, "last_timing", {})))
 
@@ -592,14 +619,17 @@ class LocalVLMClient:
                     outs = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp,
                                               seed=self.seed, stop_on_eos=not ignore_eos, **lpk, **seeds_of(len(idx)))
                     recs = eng.last_logprobs if k is not None else [None] * len(idx)
+                    fins = eng.last_finish
                     if getattr(eng, "last_timing", None):
                         TIMING_LOG.append({"model": lm.model_id, **eng.last_timing})
                         del TIMING_LOG[:-4096]
-                    out.extend(t if isinstance(t, Exception) else completion(n_ids[j], t, r) for j, t, r in zip(idx, outs, recs))
+                    out.extend(t if isinstance(t, Exception) else completion(n_ids[j], t, r, f)
+                               for j, t, r, f in zip(idx, outs, recs, fins))
             return out
         prepared = [f.result() for f in futs]
         toks_out: List[Optional[List[int]]] = [None] * len(prepared)
         recs: list = [None] * len(prepared)
+        fins: list = [None] * len(prepared)
         with eng.lock:
             with_img = [i for i, (_, f) in enumerate(prepared) if f is not None]
             for g0 in range(0, len(with_img), eng.max_batch):
@@ -610,13 +640,15 @@ class LocalVLMClient:
                 for n, (i, t) in enumerate(zip(grp, outs)):
                     toks_out[i] = t
                     recs[i] = eng.last_logprobs[n] if k is not None else None
+                    fins[i] = eng.last_finish[n]
             for i, (ids, f) in enumerate(prepared):
                 if f is None:
                     toks_out[i] = eng.generate(ids, None, max_new_tokens=max_new, temperature=temp,
                                                seed=self.seed if seed is None else seed,
                                                stop_on_eos=not ignore_eos, **lpk)
                     recs[i] = eng.last_logprobs[0] if k is not None else None
-        return [completion(len(ids), t, r) for (ids, _), t, r in zip(prepared, toks_out, recs)]
+                    fins[i] = eng.last_finish[0]
+        return [completion(len(ids), t, r, f) for (ids, _), t, r, f in zip(prepared, toks_out, recs, fins)]
 
 
 _MOCK_REPLY: List[Optional[Any]] = [None]
@@ -639,11 +671,12 @@ class CannedResponseClient:
         self.chat = _Chat(self)
 
     def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
-                  frequency_penalty=None, presence_penalty=None, repetition_penalty=None, **kwargs) -> ChatCompletion:
+                  frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None,
+                  **kwargs) -> ChatCompletion:
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
                            "response_format": response_format, "top_p": top_p, "seed": seed})
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
-                 "repetition_penalty": repetition_penalty}
+                 "repetition_penalty": repetition_penalty, "stop": stop}
         self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
         reply = self.reply(messages) if callable(self.reply) else self.reply
         return ChatCompletion([_Choice(_Message(reply))], model=model or "")

@@ -31,6 +31,7 @@ from .logprobs import check_k
 from .penalties import check_penalties
 from .pick import PickStage
 from .sampling import check_seeds, check_top_p
+from .stop import check_stop
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
 
@@ -1092,6 +1093,7 @@ class Qwen2VLEngine(PickStage):
             self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                        self.temperature, self.seed)
             self._logprobs_after_pick(1)
+            self._stop_after_pick(1)
             return
         for li, lw in enumerate(w.llm):
             if chained:
@@ -1119,11 +1121,13 @@ class Qwen2VLEngine(PickStage):
             self._gemv_pick(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                             norm_w=w.final_norm_w, eps=cfg.rms_eps, temperature=self.temperature, seed=self.seed)
             self._logprobs_after_pick(1)
+            self._stop_after_pick(1)
             return
         hip.gemv(x[0], w.lm_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
         self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                    self.temperature, self.seed)
         self._logprobs_after_pick(1)
+        self._stop_after_pick(1)
 
     # ---- batched decode: B in-flight sequences (slots 0..B-1) share every weight read of a step
     def _decode_step_batched(self, B: int) -> None:
@@ -1174,6 +1178,7 @@ class Qwen2VLEngine(PickStage):
         self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
+        self._stop_after_pick(B)
 
     def _decode_step_fused(self, B: int, projections_only: bool = False) -> int:
         """One decode step for B in-flight sequences, every projection ONE launch (r05, csrc/decode_stream.hip): the stream-K
@@ -1244,6 +1249,7 @@ class Qwen2VLEngine(PickStage):
             self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                        self.temperature, self.seed)
             self._logprobs_after_pick(B)
+            self._stop_after_pick(B)
         return 4 * n_layers + 1
 
     def _decode_step_rows(self, B: int) -> None:
@@ -1278,6 +1284,7 @@ class Qwen2VLEngine(PickStage):
         self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
+        self._stop_after_pick(B)
 
     def _decode_step_batched_fp8(self, B: int) -> None:
         """Batched decode on e4m3 weights AND activations (BASELINE configs[4]): qkv, gate/up, down and the lm_head run
@@ -1322,11 +1329,12 @@ class Qwen2VLEngine(PickStage):
         self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
+        self._stop_after_pick(B)
 
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
         # temperature, seed and the batch size are kernel arguments baked into the graph; so is what _pick_key() names
         key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch) \
-            + self._pick_key()
+            + self._pick_key() + self._stop_key()
         if key in self._graphs:
             return self._graphs[key]
         step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
@@ -1444,7 +1452,8 @@ class Qwen2VLEngine(PickStage):
                  ignore_eos: bool = False, use_graph: bool = True, check_every: int = 16,
                  temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                  json_mode: bool = False, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None) -> List[int]:
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
+                 stop=None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
@@ -1458,9 +1467,15 @@ class Qwen2VLEngine(PickStage):
         ``presence_penalty`` in [-2, 2] (OpenAI's: over generated ids): penalties.py - applied to the raw logits ahead of
         everything above; None or 1 / 0 / 0 = off.  Logprobs keep their meaning (raw logits).
         ``json_schema`` (a json_schema.SchemaDFA): as ``json_mode``, with the schema's compiled DFA as the grammar
-        (vis_schema_mask): a reply that ended on EOS is a document of the schema.  Not together with ``json_mode``."""
+        (vis_schema_mask): a reply that ended on EOS is a document of the schema.  Not together with ``json_mode``.
+        ``stop``: a string or 1..4 of them (stop.py): the reply ends with the token that completes the first occurrence of
+        one in its bytes (vis_stop_scan after every pick; the poll then reads its records, not the token row), also in an
+        ``ignore_eos`` run.  Afterwards, always, ``last_finish`` = [(reason, cut)]: "eos", "stop" (cut = the byte offset in
+        the returned tokens' bytes where the stop string starts) or "length" (max_new_tokens, the context clamp, or an
+        ``ignore_eos`` run that matched nothing)."""
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties):
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop):
+            self.stop_eos = not ignore_eos
             room = self.max_ctx - len(input_ids) - 1
             if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
                 self._warned_clamp = True          # said once per engine: the reply may end before the model is done
@@ -1492,21 +1507,24 @@ class Qwen2VLEngine(PickStage):
         ev[1].record()
         done, eos = 1, set(self.cfg.eos_ids)
         while done < max_new_tokens:
-            if not ignore_eos:
+            if self.stop_on:
+                if self._stop_done([0]):
+                    break
+            elif not ignore_eos:
                 toks = self.generated(done)
                 if any(t in eos for t in toks):
                     break
-            n = min(check_every if not ignore_eos else max_new_tokens, max_new_tokens - done)
+            n = min(check_every if not ignore_eos or self.stop_on else max_new_tokens, max_new_tokens - done)
             self.decode(n, use_graph=use_graph)
             done += n
         ev[2].record()
         toks = self.generated(done)                                         # D2H: synchronises, the events have completed
         self.last_timing = {"prompt_tokens": len(input_ids), "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": 1}
-        if not ignore_eos:
-            toks = toks[:next((i for i, t in enumerate(toks) if t in eos), len(toks))]
+        toks = self._finish([(0, toks)], eos, ignore_eos)[0]
         self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
         if self._mask_failed([0]):
+            self.last_finish = [None]
             raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return toks
 
@@ -1515,7 +1533,8 @@ class Qwen2VLEngine(PickStage):
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                        json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
-                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None) -> list:
+                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
+                       stop=None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
@@ -1525,7 +1544,9 @@ class Qwen2VLEngine(PickStage):
         ``top_p``: as in generate.  ``seeds``: one integer per request, its own sampling seed in place of the slot-derived
         one, so a request's sampled reply does not depend on its slot or on what shares the batch.
         ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty``: as in generate, each a number or a sequence
-        with one value per request.  ``json_schema``: as in generate, one schema for the whole group."""
+        with one value per request.  ``json_schema``: as in generate, one schema for the whole group.  ``stop``: as in
+        generate, one set for the whole group; the shared loop ends when every row has ended.  ``last_finish`` holds one
+        (reason, cut) per request, None for a failed one."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -1536,6 +1557,7 @@ class Qwen2VLEngine(PickStage):
         check_top_p(top_p)
         seeds = check_seeds(seeds, n_req)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
+        check_stop(stop)
         if n_req == 1:
             r = requests[0]
             if callable(r):
@@ -1543,15 +1565,17 @@ class Qwen2VLEngine(PickStage):
                     r = r()
                 except Exception as e:      # noqa: BLE001
                     self.last_logprobs = [None] if logprobs is not None else None
+                    self.last_finish = [None]
                     return [e]
             try:
                 return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature,
                                       seed if seeds is None else seeds[0], logprobs=logprobs, json_mode=json_mode, json_schema=json_schema,
-                                      top_p=top_p, **({} if penalties is None else dict(
+                                      top_p=top_p, stop=stop, **({} if penalties is None else dict(
                                           zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))))]
             except JsonModeError as e:
                 return [e]
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties):
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop):
+            self.stop_eos = not ignore_eos
             return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, seeds,
                                         penalties)
 
@@ -1569,6 +1593,7 @@ class Qwen2VLEngine(PickStage):
         B = len(live)
         if B == 0:
             self._record_logprobs([None] * n_req)
+            self.last_finish = [None] * n_req
             return list(errors)
         longest = max(self.slot_prompt_len[slots[b]] for b in live)
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
@@ -1582,9 +1607,12 @@ class Qwen2VLEngine(PickStage):
         done = 1
         g = self._ensure_graph(B) if use_graph else None
         while done < max_new_tokens:
-            if not ignore_eos and all(any(t in eos for t in seq) for seq in collect(done)):
+            if self.stop_on:
+                if self._stop_done(range(B)):
+                    break
+            elif not ignore_eos and all(any(t in eos for t in seq) for seq in collect(done)):
                 break
-            n = min(check_every if not ignore_eos else max_new_tokens, max_new_tokens - done)
+            n = min(check_every if not ignore_eos or self.stop_on else max_new_tokens, max_new_tokens - done)
             for _ in range(n):
                 if g is not None:
                     g.replay()
@@ -1596,10 +1624,14 @@ class Qwen2VLEngine(PickStage):
         # host waiting for the lazy requests' decodes is inside prefill_ms here: it is the time until all prompts are in
         self.last_timing = {"prompt_tokens": longest, "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
-        if not ignore_eos:
-            outs = [seq[:next((i for i, t in enumerate(seq) if t in eos), len(seq))] for seq in outs]
-        self._record_logprobs([(slots[b], starts[slots[b]], len(outs[slots[b]])) if slots[b] is not None else None
+        outs = self._finish([(slots[b], outs[slots[b]]) if slots[b] is not None else None for b in range(n_req)], eos, ignore_eos)
+        self._record_logprobs([(slots[b], starts[slots[b]], len(outs[b])) if slots[b] is not None else None
                                for b in range(n_req)])
-        for s in self._mask_failed(range(B)):
-            outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
-        return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]
+        failed = set(self._mask_failed(range(B)))
+        for b in range(n_req):
+            if slots[b] is None:
+                outs[b] = errors[b]
+            elif slots[b] in failed:
+                outs[b] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
+                self.last_finish[b] = None
+        return outs

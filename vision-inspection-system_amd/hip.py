@@ -66,6 +66,7 @@ _SIGS = {
     "vis_penalty_state_bytes": "ii",
     "vis_penalty_prompt": "pi" + "pi" + "p",
     "vis_penalize_f32": "p" + "ii" + "ppp" + "i" + "pp" + "ii" + "p",
+    "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
     "vis_gemm_decode_ksplit": "ii",
     "vis_gemm_decode_bf16": "pppp" + "iiiiiiii" + "p",
     "vis_gemm_decode_fp8_ksplit": "ii",
@@ -1301,6 +1302,43 @@ def penalize(logits: torch.Tensor, state: torch.Tensor, params: torch.Tensor, to
                                  _ptr(tokens), tokens.numel() // B, _ptr(step), _ptr(out),
                                  out.stride(0) if out.dim() == 2 else V, B, _stream())
     _check(rc, "vis_penalize_f32")
+
+
+STOP_STATE_INTS = 8     # int32 words of one sequence's vis_stop_scan record (stop.STATE_INTS)
+
+
+def stop_scan(state: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, tok_off: torch.Tensor, tok_bytes: torch.Tensor,
+              tok_flags: torch.Tensor, header: torch.Tensor, trans: torch.Tensor, byte_class: torch.Tensor,
+              hits: torch.Tensor, eos_on: bool = True) -> None:
+    """Fold the tokens picked since the last call through the stop strings' automaton (stop.StopDFA) and keep each row's
+    sticky finish record.  Runs AFTER the pick.  state [B, 8] int32 (zeroed = fresh), tokens [B, T] int32, step [B] int32; the
+    token table as in json_mask; header int32 [4] = (n_states, n_classes, 0, 0), trans [cap_states, cap_classes] int16 (the
+    u16 bits, bit 15 = the target state ends a stop string) holding the live table packed at its front, byte_class [256]
+    uint8, hits [cap_states, 2] uint8 = (hit_len, hit_id)."""
+    if state.dim() != 2 or tokens.dim() != 2:
+        raise HipLibraryError("stop_scan: state / tokens must be 2-D")
+    B = state.shape[0]
+    V = tok_flags.numel()
+    if state.dtype != torch.int32 or state.shape[1] != STOP_STATE_INTS or tokens.dtype != torch.int32 or step.dtype != torch.int32:
+        raise HipLibraryError("stop_scan: int32 state [B, 8] / tokens / step required")
+    if tokens.shape[0] != B or step.numel() != B:
+        raise HipLibraryError("stop_scan: bad batch shapes")
+    if tok_off.dtype != torch.int32 or tok_off.numel() != V + 1 or tok_bytes.dtype != torch.uint8 or tok_flags.dtype != torch.uint8:
+        raise HipLibraryError("stop_scan: bad token table")
+    if header.dtype != torch.int32 or header.numel() != 4 or trans.dtype != torch.int16 or trans.dim() != 2 \
+            or byte_class.dtype != torch.uint8 or byte_class.numel() != 256 or hits.dtype != torch.uint8 \
+            or hits.shape != (trans.shape[0], 2):
+        raise HipLibraryError("stop_scan: bad automaton tables")
+    if tokens.stride(1) != 1 or not (state.is_contiguous() and step.is_contiguous() and tok_off.is_contiguous()
+                                     and tok_bytes.is_contiguous() and tok_flags.is_contiguous() and header.is_contiguous()
+                                     and trans.is_contiguous() and byte_class.is_contiguous() and hits.is_contiguous()):
+        raise HipLibraryError("stop_scan: bad strides")
+    if B > 1 and tokens.stride(0) != tokens.shape[1]:
+        raise HipLibraryError("stop_scan: rows must be contiguous")
+    rc = load().vis_stop_scan(_ptr(state), _ptr(tokens), tokens.shape[1], _ptr(step), _ptr(tok_off), _ptr(tok_bytes),
+                              _ptr(tok_flags), V, _ptr(header), _ptr(trans), _ptr(byte_class), _ptr(hits), trans.shape[0],
+                              trans.shape[1], int(bool(eos_on)), B, _stream())
+    _check(rc, "vis_stop_scan")
 
 
 DP_PLAIN, DP_SWIGLU, DP_RESID_NORMW = 0, 1, 2

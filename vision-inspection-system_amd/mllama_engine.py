@@ -36,6 +36,7 @@ from .logprobs import check_k
 from .penalties import check_penalties
 from .pick import PickStage
 from .sampling import check_seeds, check_top_p
+from .stop import check_stop
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
 
 
@@ -656,15 +657,17 @@ class MllamaEngine(PickStage):
             self._gemv_pick(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                             norm_w=w.norm_w, eps=cfg.rms_eps, temperature=self.temperature, seed=self.seed)
             self._logprobs_after_pick(1)
+            self._stop_after_pick(1)
             return
         hip.gemv(x[0], w.lm_head, self.logits, norm_w=w.norm_w, eps=cfg.rms_eps)
         self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step, self.temperature,
                    self.seed)
         self._logprobs_after_pick(1)
+        self._stop_after_pick(1)
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key()
+        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key()
         if key in self._graphs:
             return self._graphs[key]
         snap = (self.step.clone(), self.cur_token.clone())
@@ -777,6 +780,7 @@ class MllamaEngine(PickStage):
         self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
+        self._stop_after_pick(B)
 
     def _decode_step_fused(self, B: int) -> None:
         """The batched step with every projection as ONE launch (r05, csrc/decode_stream.hip; see Qwen2VLEngine._decode_step_fused):
@@ -827,9 +831,10 @@ class MllamaEngine(PickStage):
         self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)
+        self._stop_after_pick(B)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B) + self._pick_key()
+        key = (self.temperature, self.seed, B) + self._pick_key() + self._stop_key()
         if key in self._graphs_b:
             return self._graphs_b[key]
         snap = (self.step_b.clone(), self.cur_b.clone())
@@ -852,7 +857,8 @@ class MllamaEngine(PickStage):
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
                        chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
                        top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
-                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None) -> list:
+                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
+                       stop=None) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
@@ -860,7 +866,8 @@ class MllamaEngine(PickStage):
         slot and its exception takes its place in the returned list.  ``logprobs``: as in generate; ``last_logprobs`` then
         holds one record per request (None for a failed one).  ``json_mode``: as in generate; a request whose JSON text could
         not be continued gets a JsonModeError.  ``top_p`` / ``seeds`` and the three penalties (a number or one value per request): as in
-        Qwen2VLEngine.generate_batch; so is ``json_schema`` (one schema for the whole group)."""
+        Qwen2VLEngine.generate_batch; so are ``json_schema`` and ``stop`` (one schema, one stop set for the whole group) and
+        ``last_finish``.  A reply that ended on EOS keeps its EOS token here, with or without stop strings."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -873,6 +880,7 @@ class MllamaEngine(PickStage):
         seed0 = seed if seeds is None else seeds[0]
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
         pen0 = {} if penalties is None else dict(zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))
+        check_stop(stop)
         lazy = any(callable(r) for r in requests)
         if lazy and n_req == 1:
             # one lazy request (always the case with max_batch == 1, where the batched buffers do not even exist): the
@@ -880,9 +888,10 @@ class MllamaEngine(PickStage):
             try:
                 ids, fr = requests[0]() if callable(requests[0]) else requests[0]
                 return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, **pen0)]
+                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, **pen0)]
             except Exception as e:      # noqa: BLE001
                 self.last_logprobs = [None] if logprobs is not None else None
+                self.last_finish = [None]
                 return [e]
         if not lazy and (n_req == 1 or any(fr is None for _, fr in requests)):
             if n_req > 1:
@@ -890,10 +899,11 @@ class MllamaEngine(PickStage):
             ids, fr = requests[0]
             try:
                 return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, **pen0)]
+                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, **pen0)]
             except JsonModeError as e:
                 return [e]
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties):
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop):
+            self.stop_eos = bool(stop_on_eos)
             return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds,
                                         penalties)
 
@@ -995,6 +1005,7 @@ class MllamaEngine(PickStage):
         ev[1].record()
         if B == 0:
             self._record_logprobs([None] * n_req)
+            self.last_finish = [None] * n_req
             return list(errors)
         longest = max(self.slot_prompt_len[s] for s in range(B))
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
@@ -1008,9 +1019,12 @@ class MllamaEngine(PickStage):
         done = 1
         g = self._ensure_graph_batched(B) if use_graph else None
         while done < max_new_tokens:
-            if stop_on_eos and all(any(t in eos for t in seq) for seq in collect(done)):
+            if self.stop_on:
+                if self._stop_done(range(B)):
+                    break
+            elif stop_on_eos and all(any(t in eos for t in seq) for seq in collect(done)):
                 break
-            n = min(chunk if stop_on_eos else max_new_tokens, max_new_tokens - done)
+            n = min(chunk if stop_on_eos or self.stop_on else max_new_tokens, max_new_tokens - done)
             for _ in range(n):
                 if g is not None:
                     g.replay()
@@ -1021,13 +1035,18 @@ class MllamaEngine(PickStage):
         outs = collect(done)
         self.last_timing = {"prompt_tokens": longest, "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
-        if stop_on_eos:
-            outs = [seq[:next((i + 1 for i, t in enumerate(seq) if t in eos), len(seq))] for seq in outs]
-        self._record_logprobs([(slots[b], starts[slots[b]], len(outs[slots[b]])) if slots[b] is not None else None
+        outs = self._finish([(slots[b], outs[slots[b]]) if slots[b] is not None else None for b in range(n_req)], eos,
+                            not stop_on_eos, keep_eos=True)
+        self._record_logprobs([(slots[b], starts[slots[b]], len(outs[b])) if slots[b] is not None else None
                                for b in range(n_req)])
-        for s in self._mask_failed(range(B)):
-            outs[s] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
-        return [outs[slots[b]] if slots[b] is not None else errors[b] for b in range(n_req)]
+        failed = set(self._mask_failed(range(B)))
+        for b in range(n_req):
+            if slots[b] is None:
+                outs[b] = errors[b]
+            elif slots[b] in failed:
+                outs[b] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
+                self.last_finish[b] = None
+        return outs
 
     def generated(self, n: int) -> List[int]:
         s = self.prompt_len - 1          # the token generated at step i is stored at index (its position - 1)
@@ -1039,15 +1058,18 @@ class MllamaEngine(PickStage):
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
                  chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False,
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None) -> List[int]:
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
+                 stop=None) -> List[int]:
         """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
         logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
         None = off, no extra launch.  ``json_mode``: every pick restricted to the tokens that continue a JSON object, as in
         Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it).  ``top_p``: nucleus sampling, as in
         Qwen2VLEngine.generate; so are ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty`` (penalties.py)
-        and ``json_schema`` (a compiled json_schema.SchemaDFA as the grammar; not together with ``json_mode``)."""
+        and ``json_schema`` (a compiled json_schema.SchemaDFA as the grammar; not together with ``json_mode``).  ``stop`` and
+        ``last_finish``: as in Qwen2VLEngine.generate; a reply that ended on EOS keeps its EOS token here."""
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties):
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop):
+            self.stop_eos = bool(stop_on_eos)
             try:
                 return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
             except hip.ChainStalled as e:
@@ -1068,9 +1090,13 @@ class MllamaEngine(PickStage):
         eos = set(self.cfg.eos_ids)
         done = 1
         while done < max_new_tokens:
-            toks = self.generated(done)
-            if stop_on_eos and any(t in eos for t in toks):
-                break
+            if self.stop_on:
+                if self._stop_done([0]):
+                    break
+            else:
+                toks = self.generated(done)
+                if stop_on_eos and any(t in eos for t in toks):
+                    break
             n = min(chunk, max_new_tokens - done)
             self.decode(n, use_graph)
             done += n
@@ -1078,9 +1104,9 @@ class MllamaEngine(PickStage):
         toks = self.generated(done)                      # D2H: synchronises, the events have completed
         self.last_timing = {"prompt_tokens": len(input_ids), "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": 1}
-        if stop_on_eos:
-            toks = toks[:next((i + 1 for i, t in enumerate(toks) if t in eos), len(toks))]
+        toks = self._finish([(0, toks)], eos, not stop_on_eos, keep_eos=True)[0]
         self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
         if self._mask_failed([0]):
+            self.last_finish = [None]
             raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
         return toks

@@ -1,6 +1,6 @@
 """The next-token pick and the request switches that steer it (logprobs, JSON mode, a JSON Schema, nucleus sampling /
-seeds, penalties): which launches turn a row of logits into a token, the state behind each switch, and the part of the
-decode-graph key that depends on them.  Both engines derive from ``PickStage``; nothing else knows this policy."""
+seeds, penalties) or watch it (stop strings): which launches turn a row of logits into a token, the state behind each
+switch, and the part of the decode-graph key that depends on them.  Both engines derive from ``PickStage``; nothing else knows this policy."""
 from __future__ import annotations
 
 import contextlib
@@ -13,6 +13,7 @@ from .json_mode import JsonBuffers, SchemaBuffers, check_schema, engine_tokenize
 from .logprobs import LogprobsBuffers, check_k
 from .penalties import NEUTRAL, PenaltyBuffers
 from .sampling import SLOT_SEED_STRIDE, SampleBuffers, check_top_p
+from .stop import StopBuffers, check_stop, finish_of, host_finish
 
 
 class PickStage:
@@ -45,18 +46,27 @@ class PickStage:
         self.pen_on = False
         self._pen: Optional[PenaltyBuffers] = None
         self._slot_pen: Dict[int, tuple] = {}
+        # stop strings (generate(..., stop=)): while on, vis_stop_scan follows every pick and the engines poll its records
+        # instead of the token rows; stop_eos: whether an EOS id ends a row too (off in a run that ignores EOS)
+        self.stop_on, self.stop_eos = False, True
+        self._stop: Optional[StopBuffers] = None
+        # how each request of the last run ended: (reason, cut) with reason "eos" / "stop" / "length", None for a failed one
+        self.last_finish: Optional[list] = None
 
     # ------------------------------------------------------------------ one request's switches
     @contextlib.contextmanager
-    def _pick_request(self, logprobs, json_mode, json_schema, top_p, seeded: bool, penalties: Optional[Sequence[tuple]]):
+    def _pick_request(self, logprobs, json_mode, json_schema, top_p, seeded: bool, penalties: Optional[Sequence[tuple]],
+                      stop=None):
         """The switches of one request (or one batch of them) on for the body, and all off again afterwards - also when the
         body, or switching on itself (no tokenizer, a schema the device tables cannot hold), raises.  ``penalties``:
-        check_penalties' result; a single request runs in slot 0 and its triple is placed there."""
+        check_penalties' result; a single request runs in slot 0 and its triple is placed there.  ``stop``: None, a string or
+        1..4 of them (check_stop), one set for the whole group."""
         check_k(logprobs)
         check_schema(json_mode, json_schema)
         if not isinstance(json_mode, bool):
             raise ValueError("json_mode must be True or False")
         check_top_p(top_p)
+        stop = check_stop(stop)
         try:
             self._begin_logprobs(logprobs)
             self._begin_schema(json_mode, json_schema)
@@ -65,6 +75,7 @@ class PickStage:
             self._begin_penalties(penalties)
             if penalties is not None and len(penalties) == 1:
                 self._slot_pen[0] = penalties[0]
+            self._begin_stop(stop)
             yield
         finally:
             self.lp_k = None
@@ -72,12 +83,18 @@ class PickStage:
             self.schema_on = False
             self._end_sampling()
             self._end_penalties()
+            self.stop_on, self.stop_eos = False, True
 
     def _pick_key(self) -> tuple:
         """The switches' part of a decode-graph key.  The logprobs k, the masks and top_p are kernel arguments or launches
         baked into a captured step; the row seeds of vis_sample_f32 and the penalty values of vis_penalize_f32 are read from
         device memory at replay, so only whether they are in use is part of it."""
         return (self.lp_k, self.json_on, self.schema_on, self.top_p, self.seeded, self.pen_on)
+
+    def _stop_key(self) -> tuple:
+        """The stop scan's part of a decode-graph key, appended by the engines next to _pick_key(): whether the launch is in
+        the step and its one switch that is a kernel argument.  The stop strings themselves are read from device tables."""
+        return (self.stop_on, self.stop_eos)
 
     # ------------------------------------------------------------------ token log-probabilities
     def _begin_logprobs(self, logprobs: Optional[int]) -> None:
@@ -109,7 +126,7 @@ class PickStage:
             return
         if self._schema is None:
             self._schema = SchemaBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
-                                         share=self._json)
+                                         share=self._json or self._stop)
         self._schema.load(json_schema, getattr(self, "_prefill_streams", ()))
         self.schema_on = True
 
@@ -119,7 +136,7 @@ class PickStage:
             raise ValueError("json_mode must be True or False")
         if json_mode and self._json is None:
             self._json = JsonBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
-                                     share=self._schema)
+                                     share=self._schema or self._stop)
         self.json_on = json_mode
 
     @property
@@ -173,6 +190,62 @@ class PickStage:
         if self.pen_on:
             self._pen.begin(slot, ids_dev, *self._slot_pen.get(slot, NEUTRAL))
 
+    # ------------------------------------------------------------------ stop strings / how a reply ended
+    def _begin_stop(self, stop: Optional[tuple]) -> None:
+        """Switch vis_stop_scan on (with the automaton of ``stop``, check_stop's result, on the device) or off for the request
+        group about to run.  Runs before the group's first prompt pass and outside any captured graph; the engine's
+        prompt-pass streams are ordered around the table upload."""
+        self.last_finish = None
+        if stop is None:
+            self.stop_on = False
+            return
+        if self._stop is None:
+            self._stop = StopBuffers(engine_tokenizer(self), self.cfg.vocab, self.cfg.eos_ids, self.max_batch, self.device,
+                                     share=self._json or self._schema)
+        self._stop.load(stop, getattr(self, "_prefill_streams", ()))
+        self.stop_on = True
+
+    def _stop_after_pick(self, B: int, slot: int = 0) -> None:
+        """vis_stop_scan on the token rows of slots slot .. slot + B - 1, right after their pick (nothing when off)."""
+        if self.stop_on:
+            self._stop.scan(self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], slot, self.stop_eos)
+
+    def _stop_done(self, slots: Iterable[int]) -> bool:
+        """The poll while stop strings are on: True when every one of ``slots`` has ended (EOS or a stop string);
+        one small D2H, synchronises."""
+        return all(r[3] != 0 for r in self._stop.records(slots))
+
+    def _finish(self, rows: Sequence[Optional[tuple]], eos_ids, ignore_eos: bool, keep_eos: bool = False) -> list:
+        """After the run: ``last_finish`` = one (reason, cut) per request and the token lists cut where each reply ended.
+        ``rows``: per request (slot, tokens generated) or None for a failed one.  With stop strings on, the device records
+        say where (an EOS token itself is kept only for ``keep_eos``); off, the host finds the first EOS id in the tokens as
+        it always did.  Returns the cut lists (None for a failed request)."""
+        eos = set(eos_ids)
+        recs = {}
+        if self.stop_on:
+            slots = [r[0] for r in rows if r is not None]
+            recs = dict(zip(slots, self._stop.records(slots))) if slots else {}
+        outs, fin = [], []
+        for r in rows:
+            if r is None:
+                outs.append(None)
+                fin.append(None)
+                continue
+            slot, toks = r
+            if self.stop_on:
+                rec = recs[slot]
+                f = finish_of(rec)
+                if f[0] != "length":
+                    toks = toks[:rec[4] + (1 if keep_eos and f[0] == "eos" else 0)]
+            else:
+                f = host_finish(toks, eos, ignore_eos)
+                if not ignore_eos:
+                    toks = toks[:next((i + (1 if keep_eos else 0) for i, t in enumerate(toks) if t in eos), len(toks))]
+            outs.append(toks)
+            fin.append(f)
+        self.last_finish = fin
+        return outs
+
     # ------------------------------------------------------------------ the pick
     def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
         """The next-token pick of slots slot .. slot + B - 1: vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick;
@@ -215,3 +288,6 @@ class PickStage:
         self._pick(logits, self.ws_val[ws], self.ws_idx[ws], tokens, cur_token, step, self.temperature,
                    self.seed + SLOT_SEED_STRIDE * slot, slot)
         self._logprobs_after_pick(1, slot)
+        if self.stop_on:
+            self._stop.reset(slot)
+            self._stop_after_pick(1, slot)
