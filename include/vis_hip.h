@@ -471,6 +471,23 @@ int vis_gemv_fp8w_rows(const void* x, const void* Wq, const void* scale, const v
                        const void* norm_w, void* y, int B, int N, int K, int ldw, int ldx, int ldy, int ldr, int act,
                        int out_f32, float eps, vis_stream_t stream);
 
+/* Decode projections on OCP Microscaling FP4 weights ("W4A16", csrc/decode_fp4.hip):
+ * y = act(sum_k deq(Wq, Ws)[n][k] * x[k] + bias) + R, f32 accumulation, x bf16 with the options of vis_gemv_fp8w
+ * (fused RMSNorm prologue, bias / residual, SwiGLU on the 16-row interleaved gate/up with N % 64 == 0, bf16 or f32 y).
+ * Wq uint8 [N][ldq]: byte j of a row holds the E2M1 codes (sign << 3 | exp << 1 | man: +-{0, .5, 1, 1.5, 2, 3, 4, 6})
+ * of element 2j in its low and 2j+1 in its high nibble; ldq >= K/2, ldq % 16 == 0.  Ws uint8 [N][lds], lds >= K/32: one
+ * E8M0 byte b per 32 consecutive K-elements of a row, scale 2^(b-127), b in 3..250 (every product then is a normal bf16);
+ * no second-level scale.  K % 32 == 0, K * 2 <= 60 KiB.  A quarter of the bf16 bytes per generated token plus 1/16 for
+ * the scales (14.14 GB -> 3.76 GB at 7B).
+ * _rows: 1 <= B <= 4 input rows as vis_gemv_fp8w_rows (x [B][ldx], y [B][ldy], R [B][ldr]); every row bit-identical to
+ * the single-row call. */
+int vis_gemv_mxfp4w(const void* x, const void* Wq, const void* Ws, const void* bias, const void* R,
+                    const void* norm_w, void* y, int N, int K, int ldq, int lds, int act, int out_f32, float eps,
+                    vis_stream_t stream);
+int vis_gemv_mxfp4w_rows(const void* x, const void* Wq, const void* Ws, const void* bias, const void* R,
+                         const void* norm_w, void* y, int B, int N, int K, int ldq, int lds, int ldx, int ldy, int ldr,
+                         int act, int out_f32, float eps, vis_stream_t stream);
+
 /* BASELINE configs[4]: GEMM on the CDNA4 block-scaled fp8 MFMA (v_mfma_scale_f32_16x16x128_f8f6f4, unit block scales).
  * C[M, N(/2)] = act((Aq Wq^T) * sa[m] * sw[n] + bias) + R with Aq [M][lda] / Wq [N][ldw] OCP e4m3 bytes, per-row f32
  * scales sa [M] (per token, vis_quant_rows_fp8) and sw [N] (per output channel); act as vis_gemm_bf16; K % 128 == 0.

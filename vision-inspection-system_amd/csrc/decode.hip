@@ -122,9 +122,6 @@ __global__ __launch_bounds__(256) void gemv_bf16_argmax_masked_kernel(GemvArgs p
   gemv_bf16_body<1, true, true>(p, allow);
 }
 
-// LDS of a multi-row launch: nb rows of K bf16 (the attribute is raised once per kernel instance)
-#define GV_ROWS_LDS_MAX (152 * 1024)
-
 static int gemv_bf16_launch(GemvArgs p, hipStream_t stream) {
   const int n_pairs = (p.act == GV_ACT_SWIGLU) ? p.N / 2 : (p.N + 1) / 2;
   // one row pair per wave until the grid reaches ~4096 waves, then several pairs per wave

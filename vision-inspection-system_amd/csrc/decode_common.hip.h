@@ -139,9 +139,19 @@ __device__ __forceinline__ void gv_finish(const GemvArgs& p, bool swiglu, int pa
   }
 }
 
+// LDS position (16-byte chunk index) of chunk c of a staged x row.  SWZ (the MXFP4 GEMV, decode_fp4.hip: every lane reads
+// the FOUR chunks of one 32-element block, a 64-byte lane stride): chunk j of block c / 4 sits at j ^ ((c / 16) & 3), so the
+// 16 lanes a ds_read_b128 serves per cycle touch 16 different 16-byte slots of the bank row.
+template <bool SWZ>
+__device__ __forceinline__ int gv_slot(int c) { return SWZ ? (c ^ ((c >> 4) & 3)) : c; }
+
+// LDS of a multi-row launch: nb rows of K bf16 (the attribute is raised once per kernel instance)
+#define GV_ROWS_LDS_MAX (152 * 1024)
+
 // x -> rmsnorm(x) * w -> LDS (bf16, HF rounding order).  x and w are loaded ONCE (both loads issued before the
 // reduction) and normalised from registers: hidden sizes <= 4096 give at most two 16-byte chunks per thread; the
 // re-reading loop of the first version put a second L2 round trip into every norm-fused GEMV's prologue.
+template <bool SWZ = false>
 __device__ __forceinline__ void gv_stage_x_rmsnorm(const bf16_t* __restrict__ x, const bf16_t* __restrict__ nw, bf16_t* xs,
                                                    int nch, int K, float eps, int tid, int lane, int wave) {
   __shared__ float red[4];
@@ -163,12 +173,12 @@ __device__ __forceinline__ void gv_stage_x_rmsnorm(const bf16_t* __restrict__ x,
     if (c0 < nch) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = bf2f(f2bf(f0[e] * rstd)) * w0[e];
-      *(u32x4*)(xs + c0 * 8) = pack8(o);
+      *(u32x4*)(xs + gv_slot<SWZ>(c0) * 8) = pack8(o);
     }
     if (c1 < nch) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = bf2f(f2bf(f1[e] * rstd)) * w1[e];
-      *(u32x4*)(xs + c1 * 8) = pack8(o);
+      *(u32x4*)(xs + gv_slot<SWZ>(c1) * 8) = pack8(o);
     }
     return;
   }
@@ -189,7 +199,7 @@ __device__ __forceinline__ void gv_stage_x_rmsnorm(const bf16_t* __restrict__ x,
     unpack8(*(const u32x4*)(nw + c * 8), w);
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = bf2f(f2bf(f[e] * rstd)) * w[e];
-    *(u32x4*)(xs + c * 8) = pack8(o);
+    *(u32x4*)(xs + gv_slot<SWZ>(c) * 8) = pack8(o);
   }
 }
 
@@ -197,6 +207,7 @@ __device__ __forceinline__ void gv_stage_x_rmsnorm(const bf16_t* __restrict__ x,
 // 10 chunks per thread; a plain load/store loop serialises ~10 L2 round trips in front of the weight stream).  Unconditional clamped
 // loads (a predicated load makes hipcc drain vmcnt per branch); chunks past the end are simply not stored.
 #define GV_STAGE_MAX 15  // 15 x 256 x 8 = 30720 elements >= the 60 KiB LDS limit of the launchers
+template <bool SWZ = false>
 __device__ __forceinline__ void gv_stage_x(const bf16_t* __restrict__ x, bf16_t* xs, int nch, int tid) {
   u32x4 v[GV_STAGE_MAX];
 #pragma unroll
@@ -204,23 +215,24 @@ __device__ __forceinline__ void gv_stage_x(const bf16_t* __restrict__ x, bf16_t*
 #pragma unroll
   for (int i = 0; i < GV_STAGE_MAX; ++i) {
     const int c = tid + i * 256;
-    if (c < nch) *(u32x4*)(xs + c * 8) = v[i];
+    if (c < nch) *(u32x4*)(xs + gv_slot<SWZ>(c) * 8) = v[i];
   }
 }
 
 // stage one row of x (optionally RMS-normalised) into LDS; called once per input row
+template <bool SWZ = false>
 __device__ __forceinline__ void gv_stage_row(const bf16_t* __restrict__ x, const bf16_t* __restrict__ norm_w, bf16_t* xs, int nch,
                                              int K, float eps, int tid, int lane, int wave) {
   if (norm_w) {
-    gv_stage_x_rmsnorm(x, norm_w, xs, nch, K, eps, tid, lane, wave);
+    gv_stage_x_rmsnorm<SWZ>(x, norm_w, xs, nch, K, eps, tid, lane, wave);
   } else if (nch > 1024) {
-    gv_stage_x(x, xs, nch, tid);
+    gv_stage_x<SWZ>(x, xs, nch, tid);
   } else if (nch <= 512) {   // both loads in flight before the first store (one L2 round trip, not two)
     const u32x4 r0 = *(const u32x4*)(x + min(tid, nch - 1) * 8), r1 = *(const u32x4*)(x + min(tid + 256, nch - 1) * 8);
-    if (tid < nch) *(u32x4*)(xs + tid * 8) = r0;
-    if (tid + 256 < nch) *(u32x4*)(xs + (tid + 256) * 8) = r1;
+    if (tid < nch) *(u32x4*)(xs + gv_slot<SWZ>(tid) * 8) = r0;
+    if (tid + 256 < nch) *(u32x4*)(xs + gv_slot<SWZ>(tid + 256) * 8) = r1;
   } else {
-    for (int c = tid; c < nch; c += 256) *(u32x4*)(xs + c * 8) = *(const u32x4*)(x + c * 8);
+    for (int c = tid; c < nch; c += 256) *(u32x4*)(xs + gv_slot<SWZ>(c) * 8) = *(const u32x4*)(x + c * 8);
   }
 }
 

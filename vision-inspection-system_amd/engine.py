@@ -153,13 +153,31 @@ def _chain_order_lock(index: Optional[int]) -> threading.Lock:
 class Qwen2VLEngine(PickStage):
     """One model replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
+    @staticmethod
+    def check_decode_weights(cfg: Qwen2VLConfig, decode_weights: str) -> None:
+        """Refuse an unknown decode precision, or one the model's shapes do not fit (needs no GPU)."""
+        if decode_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError("decode_weights must be 'bf16', 'fp8' or 'mxfp4'")
+        if decode_weights == "mxfp4":
+            dims = {"hidden": cfg.hidden, "heads*head_dim": cfg.heads * cfg.head_dim, "intermediate": cfg.intermediate}
+            bad = [f"{n}={v}" for n, v in dims.items() if v % 32]
+            if bad:
+                raise ValueError("decode_weights='mxfp4' needs MX blocks of 32 inputs: " + ", ".join(bad)
+                                 + " must be multiples of 32")
+
     def __init__(self, cfg: Qwen2VLConfig, weights: DeviceWeights, device, max_ctx: int = 4096,
                  decode_splits: int = 0, max_batch: int = 1, decode_weights: str = "bf16",
                  prefill_dtype: str = "bf16"):
         """decode_weights="fp8" (BASELINE configs[4] slice, also VIS_DECODE_WEIGHTS=fp8): the single-sequence decode
         step streams OCP-e4m3 copies of the LLM projections and the lm_head (per-output-row f32 scales,
-        hip.quantize_fp8_rows at load time) through vis_gemv_fp8w; prefill and the batched decode keep bf16."""
+        hip.quantize_fp8_rows at load time) through vis_gemv_fp8w; prefill and the batched decode keep bf16.
+        decode_weights="mxfp4" (VIS_DECODE_WEIGHTS=mxfp4): the same projections as OCP Microscaling FP4 (E2M1 codes, one
+        E8M0 scale per 32 inputs, hip.quantize_mxfp4_rows at load time) through vis_gemv_mxfp4w at EVERY batch size: 2..4
+        sequences share one pass over the weights (vis_gemv_mxfp4w_rows), larger batches issue each projection once per
+        group of 4 rows, so a sequence decodes bit-identically alone or in any batch.  Embedding, norms, biases, the KV
+        cache and the prompt pass stay bf16."""
         cfg.validate_for_kernels()
+        self.check_decode_weights(cfg, decode_weights)
         hip.load()  # fail loudly when the gfx950 library is missing: there is no other path
         if not torch.cuda.is_available():
             raise hip.HipLibraryError("Qwen2VLEngine needs a ROCm GPU (no CPU fallback exists)")
@@ -222,14 +240,12 @@ class Qwen2VLEngine(PickStage):
             self.b_x2w = torch.empty((Bm, H), dtype=bf, device=dev)       # x2 * ln2_w (A operand of gate/up)
             self.b_ssq1 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
             self.b_ssq2 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
-        if Bm > 1 and not (self.fused_proj and decode_weights == "fp8"):
+        if Bm > 1 and not (self.fused_proj and decode_weights == "fp8") and decode_weights != "mxfp4":
             # split-K slabs of the r02-r04 pair of launches: the whole step with VIS_DECODE_FUSED=0, and the bf16 down
             # projection at many sequences in the fused step (_decode_step_fused)
             self.b_part = torch.empty(16 * hip.part_rows(Bm) * max(nq, H, 2 * cfg.intermediate), dtype=torch.float32,
                                       device=dev)   # 16 stream-K slots x (16 or 32) rows
         self.decode_weights = decode_weights
-        if decode_weights not in ("bf16", "fp8"):
-            raise ValueError("decode_weights must be 'bf16' or 'fp8'")
         # Single-sequence decode: the head of every layer (qkv projection -> rope / append / attention -> o projection) as ONE
         # launch whose stages hand over inside the grid (csrc/decode_chain.hip; bit-identical to the four launches it
         # replaces).  VIS_DECODE_CHAIN=0 keeps the four launches (A/B).
@@ -254,6 +270,11 @@ class Qwen2VLEngine(PickStage):
             for lw in weights.llm:
                 self.q8.append({n: hip.quantize_fp8_rows(getattr(lw, n)) for n in ("qkv_w", "o_w", "gateup_w", "down_w")})
             self.q8_lm_head = hip.quantize_fp8_rows(weights.lm_head)
+        self.q4: List[dict] = []
+        if decode_weights == "mxfp4":
+            for lw in weights.llm:
+                self.q4.append({n: hip.quantize_mxfp4_rows(getattr(lw, n)) for n in ("qkv_w", "o_w", "gateup_w", "down_w")})
+            self.q4_lm_head = hip.quantize_mxfp4_rows(weights.lm_head)
         self.fp8_batched = False
         if decode_weights == "fp8" and Bm > 1 and cfg.hidden % 128 == 0:
             self.fp8_batched = True
@@ -1080,16 +1101,18 @@ class Qwen2VLEngine(PickStage):
         if not chained:
             hip.gather_rows(w.embed, self.cur_token, self.d_x)
         x, x2 = self.d_x, self.d_x2
-        if self.decode_weights == "fp8":
+        if self.decode_weights in ("fp8", "mxfp4"):    # quantised weights: separate launches, no chained head
+            gemv_q, qw, q_head = (hip.gemv_fp8, self.q8, self.q8_lm_head) if self.decode_weights == "fp8" \
+                else (hip.gemv_mxfp4, self.q4, self.q4_lm_head)
             for li, lw in enumerate(w.llm):
-                q = self.q8[li]
-                hip.gemv_fp8(x[0], *q["qkv_w"], self.d_qkv, bias=lw.qkv_b, norm_w=lw.ln1_w, eps=cfg.rms_eps)
+                q = qw[li]
+                gemv_q(x[0], *q["qkv_w"], self.d_qkv, bias=lw.qkv_b, norm_w=lw.ln1_w, eps=cfg.rms_eps)
                 hip.decode_attn(self.d_qkv, self.cos_t, self.sin_t, self.kcache[li], self.vcache[li], self.step,
                                 self.part_o, self.part_ml, self.d_attn, Hq, Hkv, D, self.nsplit, scale)
-                hip.gemv_fp8(self.d_attn, *q["o_w"], x2[0], residual=x[0])
-                hip.gemv_fp8(x2[0], *q["gateup_w"], self.d_act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=cfg.rms_eps)
-                hip.gemv_fp8(self.d_act, *q["down_w"], x[0], residual=x2[0])
-            hip.gemv_fp8(x[0], *self.q8_lm_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
+                gemv_q(self.d_attn, *q["o_w"], x2[0], residual=x[0])
+                gemv_q(x2[0], *q["gateup_w"], self.d_act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=cfg.rms_eps)
+                gemv_q(self.d_act, *q["down_w"], x[0], residual=x2[0])
+            gemv_q(x[0], *q_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
             self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
                        self.temperature, self.seed)
             self._logprobs_after_pick(1)
@@ -1140,6 +1163,8 @@ class Qwen2VLEngine(PickStage):
         # default because it trades an invariant for those 6-13 %: a sequence decoded in a batch of 2 would then follow the
         # single-sequence arithmetic and in a batch of 3+ the stream-K arithmetic - its tokens could depend on the batch size
         # at near-ties (tests/test_fullsize_gpu.py::test_7b_batch_invariance_and_reproducibility).
+        if self.decode_weights == "mxfp4":     # MXFP4 has no MFMA projection: the multi-row GEMV at every batch size
+            return self._decode_step_rows(B)
         rows_max = int(os.environ.get("VIS_ROWS_GEMV", "0"))
         if 2 <= B <= min(rows_max, 4) and max(self.cfg.intermediate, self.cfg.hidden) * 2 * (2 if B <= 2 else 4) <= 152 * 1024:
             return self._decode_step_rows(B)
@@ -1256,23 +1281,30 @@ class Qwen2VLEngine(PickStage):
         """A couple of in-flight sequences: the single-sequence step with the multi-row GEMV (vis_gemv_*_rows) - one pass
         over the weights for all rows, norm / bias / residual / SwiGLU fused as at B = 1, no partial buffers and no
         finalisation launches (the stream-K projection pays four of those per layer); bf16 or e4m3 weights with bf16
-        activations, every sequence bit-identical to decoding alone.  Chosen by _decode_step_batched (VIS_ROWS_GEMV)."""
+        activations, every sequence bit-identical to decoding alone.  Chosen by _decode_step_batched (VIS_ROWS_GEMV).
+        MXFP4 weights take this step at EVERY batch size: more than 4 sequences issue each projection once per group of 4
+        rows (the weights are then read ceil(B / 4) times per step: slower than the bf16 stream-K step above ~16
+        sequences); attention, pick and the request switches stay one batched launch each."""
         cfg, w = self.cfg, self.w
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
         scale, eps = D ** -0.5, cfg.rms_eps
         x, x2, qkv, att, act = self.b_x[:B], self.b_x2[:B], self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
-        fp8 = self.decode_weights == "fp8"
+        fp8, fp4 = self.decode_weights == "fp8", self.decode_weights == "mxfp4"
 
-        def proj(inp, wt, out, **kw):
-            if fp8:
-                hip.gemv_fp8_rows(inp, *wt, out, **kw)
+        def proj(inp, wt, out, residual=None, **kw):
+            if fp4:
+                for b0 in range(0, B, 4):
+                    rows = slice(b0, min(b0 + 4, B))
+                    hip.gemv_mxfp4_rows(inp[rows], *wt, out[rows], residual=None if residual is None else residual[rows], **kw)
+            elif fp8:
+                hip.gemv_fp8_rows(inp, *wt, out, residual=residual, **kw)
             else:
-                hip.gemv_rows(inp, wt, out, **kw)
+                hip.gemv_rows(inp, wt, out, residual=residual, **kw)
 
         hip.gather_rows(w.embed, self.cur_b[:B], x)
         for li, lw in enumerate(w.llm):
-            q8 = self.q8[li] if fp8 else None
-            pick = (lambda n: q8[n]) if fp8 else (lambda n: getattr(lw, n))
+            q8 = self.q8[li] if fp8 else (self.q4[li] if fp4 else None)
+            pick = (lambda n: q8[n]) if q8 is not None else (lambda n: getattr(lw, n))
             proj(x, pick("qkv_w"), qkv, bias=lw.qkv_b, norm_w=lw.ln1_w, eps=eps)
             hip.decode_attn(qkv, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
                             self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
@@ -1280,7 +1312,8 @@ class Qwen2VLEngine(PickStage):
             proj(att, pick("o_w"), x2, residual=x)
             proj(x2, pick("gateup_w"), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
             proj(act, pick("down_w"), x, residual=x2)
-        proj(x, self.q8_lm_head if fp8 else w.lm_head, self.logits_b[:B], norm_w=w.final_norm_w, eps=eps)
+        proj(x, self.q8_lm_head if fp8 else (self.q4_lm_head if fp4 else w.lm_head), self.logits_b[:B],
+             norm_w=w.final_norm_w, eps=eps)
         self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)

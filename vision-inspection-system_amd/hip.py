@@ -46,6 +46,8 @@ _SIGS = {
     "vis_gemv_fp8w": "ppppppp" + "iiiii" + "f" + "p",
     "vis_gemv_bf16_rows": "pppppp" + "iiiiiiiii" + "f" + "p",
     "vis_gemv_fp8w_rows": "ppppppp" + "iiiiiiiii" + "f" + "p",
+    "vis_gemv_mxfp4w": "ppppppp" + "iiiiii" + "f" + "p",
+    "vis_gemv_mxfp4w_rows": "ppppppp" + "iiiiiiiiii" + "f" + "p",
     "vis_decode_attn": "ppppppppp" + "iiiii" + "f" + "i" + "lll" + "p",
     "vis_decode_attn_shared": "ppppppppp" + "iiiii" + "f" + "i" + "lll" + "i" + "p",
     "vis_decode_attn_parts": "p" + "ii" + "p" * 11 + "iiiii" + "f" + "i" + "ll" + "i" + "p",
@@ -873,6 +875,86 @@ def gemv_fp8_rows(x: torch.Tensor, wq: torch.Tensor, scale: torch.Tensor, out: t
                                    residual.stride(0) if residual is not None else 0, act,
                                    1 if out.dtype == torch.float32 else 0, eps, _stream())
     _check(rc, "vis_gemv_fp8w_rows")
+    return out
+
+
+# --------------------------------------------------------------------------- K10 on MXFP4 weights (W4A16)
+# OCP Microscaling FP4: E2M1 codes (sign << 3 | exp << 1 | man), one E8M0 scale byte per 32 consecutive K-elements of a row
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mxfp4_rows(w: torch.Tensor):
+    """bf16/f32 [N, K] (K % 32 == 0) -> (Wq uint8 [N, K/2], Ws uint8 [N, K/32]): byte j of a row holds element 2j in its low
+    and 2j+1 in its high nibble; Ws is the E8M0 byte b of each block of 32, X = 2^(b-127) the SMALLEST power of two with
+    block_amax / X <= 6 (amax = m 2^E, m in [1, 2): b = E + 125 when m <= 1.5, else E + 126), clamped to 3..250; an all-zero
+    block gets b = 127.  Elements round to the nearest E2M1 value, ties to the even mantissa bit.  Every step is exact
+    integer / power-of-two arithmetic, so CPU and GPU tensors give identical bytes.  Load-time plumbing (torch)."""
+    if w.dim() != 2 or w.shape[1] % 32 != 0:
+        raise HipLibraryError("quantize_mxfp4_rows: [N, K] with K % 32 == 0 required")
+    N, K = w.shape
+    blk = w.float().reshape(N, K // 32, 32)
+    amax = blk.abs().amax(-1)
+    bits = amax.contiguous().view(torch.int32)
+    e, man = (bits >> 23) & 0xFF, bits & 0x7FFFFF
+    b = (e - torch.where(man <= 0x400000, 2, 1)).clamp(3, 250)
+    b = torch.where(amax == 0, torch.full_like(b, 127), b)
+    a = torch.ldexp(blk.abs(), (127 - b)[..., None]).clamp_max(6.0)     # |w| / X, exact
+    # grid steps 0.5 below 2, 1 below 4, 2 up to 6; torch.round is half-to-even, and an even multiple of the step is the
+    # code with mantissa bit 0
+    code = torch.where(a < 2, torch.round(a * 2), torch.where(a < 4, torch.round(a) + 2, torch.round(a * 0.5) + 4))
+    code = code.to(torch.uint8) | (torch.signbit(blk).to(torch.uint8) << 3)
+    code = code.reshape(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), b.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(wq: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """(Wq uint8 [N, K/2], Ws uint8 [N, >= K/32]) -> f32 [N, K], exactly what vis_gemv_mxfp4w multiplies with."""
+    if wq.dtype != torch.uint8 or ws.dtype != torch.uint8 or wq.dim() != 2 or ws.dim() != 2 or wq.shape[1] % 16 != 0 \
+            or ws.shape[0] != wq.shape[0] or ws.shape[1] < wq.shape[1] // 16:
+        raise HipLibraryError("dequantize_mxfp4: bad shapes / dtypes")
+    N, K = wq.shape[0], wq.shape[1] * 2
+    code = torch.stack((wq & 15, wq >> 4), dim=-1).reshape(N, K).long()
+    table = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=wq.device)
+    v = table[code].reshape(N, K // 32, 32)
+    return torch.ldexp(v, (ws[:, :K // 32].to(torch.int32) - 127)[..., None]).reshape(N, K)
+
+
+def _mxfp4_check(name, wq, ws):
+    if wq.dtype != torch.uint8 or ws.dtype != torch.uint8 or wq.dim() != 2 or ws.dim() != 2 or wq.stride(1) != 1 \
+            or ws.stride(1) != 1 or ws.shape[0] != wq.shape[0]:
+        raise HipLibraryError(f"{name}: bad shapes / dtypes")
+    return wq.shape[0], wq.shape[1] * 2
+
+
+def gemv_mxfp4(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, out: torch.Tensor,
+               bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+               norm_w: Optional[torch.Tensor] = None, act: int = ACT_NONE, eps: float = 1e-6) -> torch.Tensor:
+    """gemv with MXFP4 weights (quantize_mxfp4_rows); same options as gemv."""
+    _bf16(x, "gemv_mxfp4 x")
+    N, K = _mxfp4_check("gemv_mxfp4", wq, ws)
+    if x.numel() != K:
+        raise HipLibraryError("gemv_mxfp4: bad shapes / dtypes")
+    n_out = N // 2 if act == ACT_SWIGLU else N
+    if out.numel() != n_out or out.dtype not in (torch.bfloat16, torch.float32):
+        raise HipLibraryError("gemv_mxfp4: bad output")
+    rc = load().vis_gemv_mxfp4w(_ptr(x), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(residual), _ptr(norm_w), _ptr(out), N, K,
+                                wq.stride(0), ws.stride(0), act, 1 if out.dtype == torch.float32 else 0, eps, _stream())
+    _check(rc, "vis_gemv_mxfp4w")
+    return out
+
+
+def gemv_mxfp4_rows(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, out: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
+                    norm_w: Optional[torch.Tensor] = None, act: int = ACT_NONE, eps: float = 1e-6) -> torch.Tensor:
+    """gemv_mxfp4 for 1..4 input rows (W4A16), every row bit-identical to ``gemv_mxfp4`` on it."""
+    _bf16(x, "gemv_mxfp4_rows x")
+    N, K = _mxfp4_check("gemv_mxfp4_rows", wq, ws)
+    B = _rows_check("gemv_mxfp4_rows", x, K, out, N // 2 if act == ACT_SWIGLU else N, residual)
+    rc = load().vis_gemv_mxfp4w_rows(_ptr(x), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(residual), _ptr(norm_w), _ptr(out), B,
+                                     N, K, wq.stride(0), ws.stride(0), x.stride(0), out.stride(0),
+                                     residual.stride(0) if residual is not None else 0, act,
+                                     1 if out.dtype == torch.float32 else 0, eps, _stream())
+    _check(rc, "vis_gemv_mxfp4w_rows")
     return out
 
 
