@@ -488,6 +488,21 @@ int vis_gemv_mxfp4w_rows(const void* x, const void* Wq, const void* Ws, const vo
                          const void* norm_w, void* y, int B, int N, int K, int ldq, int lds, int ldx, int ldy, int ldr,
                          int act, int out_f32, float eps, vis_stream_t stream);
 
+/* Batched decode projection on the same MXFP4 weights (csrc/decode_fp4_batched.hip): vis_gemm_decode_bf16 on
+ * deq(Wq, Ws) with the codes and scales streamed ONCE for 5 <= B <= 64 sequences (persistent stream-K workgroups, LDS-DMA
+ * ring, codes de-quantised in registers into exact bf16 MFMA fragments, f32 accumulation).  x bf16 [B][ldx], ldx % 8 == 0,
+ * ldx >= K; Wq / Ws as above (padded ldq / lds allowed); K % 64 == 0, N % 4 == 0; x, Wq, part and C 16-byte aligned.
+ * Output contract of vis_gemm_decode_bf16: part[slot][R][N] f32 with R = 16 / 32 / 64 for B <= 16 / 32 / 64, `ksplit`
+ * slots ALL written (unused ones zero-filled) whose sum is the projection; ksplit <= 0 means
+ * vis_gemm_decode_mxfp4_ksplit(N, K) (<= 16, fixed by (N, K) alone; 0 for N <= 0 or K < 64), a smaller value is an
+ * argument error, a larger one (<= 16) only adds zero slots.  part == NULL: C [B][ldc] is written directly (bf16, or
+ * f32 when out_f32; ldc % 4 == 0, ldc >= N).  The K order and the stream-K cut do not depend on B or on a row's position:
+ * a row's result is bit-identical in every batch of 5..64.  It is NOT the summation order of vis_gemv_mxfp4w[_rows].
+ * Anything else returns VIS_ERR_ARG and launches nothing. */
+int vis_gemm_decode_mxfp4_ksplit(int N, int K);
+int vis_gemm_decode_mxfp4(const void* x, const void* Wq, const void* Ws, void* part, void* C, int B, int N, int K,
+                          int ldx, int ldq, int lds, int ldc, int ksplit, int out_f32, vis_stream_t stream);
+
 /* BASELINE configs[4]: GEMM on the CDNA4 block-scaled fp8 MFMA (v_mfma_scale_f32_16x16x128_f8f6f4, unit block scales).
  * C[M, N(/2)] = act((Aq Wq^T) * sa[m] * sw[n] + bias) + R with Aq [M][lda] / Wq [N][ldw] OCP e4m3 bytes, per-row f32
  * scales sa [M] (per token, vis_quant_rows_fp8) and sw [N] (per output channel); act as vis_gemm_bf16; K % 128 == 0.

@@ -1,15 +1,20 @@
 """MXFP4 decode weights on the MI355X: the W4A16 GEMV next to the bf16 and e4m3 ones, and the decode step on each.
 
     python tools/mxfp4_bench.py kernel [out.json]   # vis_gemv_mxfp4w per call at the five 7B decode shapes, next to
-                                                    # vis_gemv_bf16 and vis_gemv_fp8w on the same shapes
-    python tools/mxfp4_bench.py step [out.json]     # synthetic:7b decode step, bf16 / fp8 / mxfp4 weights, 1 / 4 / 16 sequences
+                                                    # vis_gemv_bf16 and vis_gemv_fp8w on the same shapes; then the batched
+                                                    # projection vis_gemm_decode_mxfp4 at 8 / 16 / 32 / 64 rows next to
+                                                    # vis_gemm_decode_bf16 on the de-quantised weights
+    python tools/mxfp4_bench.py step [out.json]     # synthetic:7b decode step at 1 / 4 / 16 / 32 / 64 sequences: bf16, fp8 (up
+                                                    # to 16), mxfp4 on the rows step, mxfp4 with mxfp4_gemm_from=5
     python tools/mxfp4_bench.py all [out.json]      # both, each in a child process under its own timeout
 
 kernel: 20 launches captured in one graph, replayed 10 times after a warm-up, device events, median.  Every launch of a graph
 reads its OWN copy of the weights (20 copies, 0.3-5.4 GB per format and shape), so no byte comes from the 256 MB MALL.  GB/s
-on algorithmic bytes: N K 2 (bf16), N K + 4 N (fp8), N K / 2 + N K / 32 (mxfp4); frac_8TBps = GB/s / 8000.
+on algorithmic bytes: N K 2 (bf16), N K + 4 N (fp8), N K / 2 + N K / 32 (mxfp4), plus B K 2 of activations for the batched
+projections (the partial slabs are not counted); frac_8TBps = GB/s / 8000.
 step: one engine per precision in one process (the 7B weights are random; contexts of 1289 prompt tokens), the engine's own
-graph-replayed step (1 sequence: the single-sequence step; 4 and 16: the batched step), 5 rounds alternated, median ms."""
+graph-replayed step (1 sequence: the single-sequence step; more: the batched step), 5 rounds alternated, median ms.
+"mxfp4_mfma" is decode_weights="mxfp4" with mxfp4_gemm_from=5: at 1 and 4 sequences it runs the same launches as "mxfp4"."""
 import json
 import os
 import subprocess
@@ -26,7 +31,8 @@ DEV = torch.device("cuda:0")
 SHAPES = [("qkv", 4608, 3584, True, 0), ("o", 3584, 3584, False, 0), ("gate_up", 37888, 3584, True, 3),
           ("down", 3584, 18944, False, 0), ("lm_head", 152064, 3584, True, 0)]
 COPIES = 20
-TIMEOUTS = {"kernel": 420, "step": 900}
+GEMM_ROWS = (8, 16, 32, 64)
+TIMEOUTS = {"kernel": 600, "step": 900}
 
 
 def _time(run, reps=10) -> float:
@@ -81,19 +87,55 @@ def kernel_times() -> list:
     return rows
 
 
+def gemm_times() -> list:
+    """The batched decode projection: vis_gemm_decode_mxfp4 next to vis_gemm_decode_bf16 on the same (de-quantised) weights;
+    partial slabs for the layer projections, direct f32 logits for the lm_head, as the engine issues them."""
+    rows = []
+    for name, N, K, _, _ in SHAPES:
+        g = torch.Generator(device=DEV).manual_seed(N + K)
+        w = (torch.randn((N, K), generator=g, device=DEV) / K ** 0.5).to(torch.bfloat16)
+        q4, s4 = hip.quantize_mxfp4_rows(w)
+        w = hip.dequantize_mxfp4(q4, s4).to(torch.bfloat16)
+        w16 = [w.clone() for _ in range(COPIES)]
+        w4 = [(q4.clone(), s4.clone()) for _ in range(COPIES)]
+        del w, q4
+        direct = name == "lm_head"
+        for B in GEMM_ROWS:
+            x = torch.randn((B, K), generator=g, device=DEV).to(torch.bfloat16)
+            if direct:
+                kw = {"out": torch.empty((B, N), dtype=torch.float32, device=DEV)}
+            else:
+                kw = {"part": torch.empty(16 * hip.part_rows(B) * N, dtype=torch.float32, device=DEV)}
+            res = {
+                "bf16": (_time(lambda i: hip.decode_gemm(x, w16[i], **kw)), N * K * 2 + B * K * 2),
+                "mxfp4": (_time(lambda i: hip.decode_gemm_mxfp4(x, *w4[i], **kw)), N * K // 2 + N * K // 32 + B * K * 2),
+            }
+            row = {"shape": name, "N": N, "K": K, "rows": B, "kernel": "gemm_decode"}
+            for k, (us, nbytes) in res.items():
+                row[k] = {"us_per_call": round(us, 2), "bytes": nbytes, "GBps": round(nbytes / us / 1e3, 1),
+                          "frac_8TBps": round(nbytes / us / 1e3 / 8000, 3)}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del w16, w4
+        torch.cuda.empty_cache()
+    return rows
+
+
 def step_times() -> list:
     from vision_inspection_system_amd import weights as W
     from vision_inspection_system_amd.config import Qwen2VLConfig
     from vision_inspection_system_amd.engine import Qwen2VLEngine
     cfg = Qwen2VLConfig.qwen2_vl_7b()
     w = W.random_device_weights(cfg, DEV, 0)
-    engines = {p: Qwen2VLEngine(cfg, w, DEV, max_ctx=2048, max_batch=16, decode_weights=p) for p in ("bf16", "fp8", "mxfp4")}
+    engines = {p: Qwen2VLEngine(cfg, w, DEV, max_ctx=2048, max_batch=64, decode_weights=p) for p in ("bf16", "fp8", "mxfp4")}
+    engines["mxfp4_mfma"] = Qwen2VLEngine(cfg, w, DEV, max_ctx=2048, max_batch=64, decode_weights="mxfp4", mxfp4_gemm_from=5)
     rng = np.random.default_rng(0)
     out = []
-    for B in (1, 4, 16):
+    for B in (1, 4, 16, 32, 64):
         reqs = [(rng.integers(0, 150000, 1289).tolist(), []) for _ in range(B)]
         steps = {}
-        for p, eng in engines.items():
+        live = {p: e for p, e in engines.items() if p != "fp8" or B <= 16}
+        for p, eng in live.items():
             if B == 1:
                 eng.prefill(reqs[0][0], [], max_new_tokens=400)
                 steps[p] = lambda eng=eng: eng.decode(16)
@@ -101,16 +143,16 @@ def step_times() -> list:
                 eng.prefill_many(reqs, max_new_tokens=400)
                 steps[p] = lambda g=eng._ensure_graph(B): [g.replay() for _ in range(16)]
             steps[p]()
-        res = {p: [] for p in engines}
+        res = {p: [] for p in live}
         for _ in range(5):
-            for p in engines:
+            for p in live:
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 s.record()
                 steps[p]()
                 e.record()
                 torch.cuda.synchronize()
                 res[p].append(s.elapsed_time(e) / 16)
-        for p in engines:
+        for p in live:
             out.append({"sequences": B, "decode_weights": p, "ms_per_step": round(float(np.median(res[p])), 4)})
             print(json.dumps(out[-1]), flush=True)
     return out
@@ -138,7 +180,7 @@ if __name__ == "__main__":
         rows = run_all(path)
     else:
         hip.load()
-        rows = kernel_times() if what == "kernel" else step_times()
+        rows = kernel_times() + gemm_times() if what == "kernel" else step_times()
     if path:
         with open(path, "w") as f:
             json.dump(rows, f, indent=1)

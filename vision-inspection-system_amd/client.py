@@ -188,9 +188,16 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
             tok = HFTokenizer(path, cfg.image_token_id, cfg.vision_start_id, cfg.vision_end_id, cfg.eos_ids)
         lm = LoadedModel(Qwen2VLEngine(cfg, w, device, max_ctx=max_ctx, max_batch=max_batch,
                                        decode_weights=os.environ.get("VIS_DECODE_WEIGHTS", "bf16"),
-                                       prefill_dtype=os.environ.get("VIS_PREFILL_DTYPE", "bf16")), tok, cfg, model_id)
+                                       prefill_dtype=os.environ.get("VIS_PREFILL_DTYPE", "bf16"),
+                                       mxfp4_gemm_from=_env_int_or_none("VIS_MXFP4_GEMM_FROM")), tok, cfg, model_id)
         _ENGINES[key] = lm
         return lm
+
+
+def _env_int_or_none(name: str) -> Optional[int]:
+    """An integer switch from the environment; unset or empty means None, anything but an integer is a ValueError."""
+    v = os.environ.get(name, "").strip()
+    return int(v) if v else None
 
 
 def _load_mllama(model_id: str, device, max_ctx: int, max_batch: int = 1) -> Optional[LoadedModel]:

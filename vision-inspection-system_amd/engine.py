@@ -165,9 +165,24 @@ class Qwen2VLEngine(PickStage):
                 raise ValueError("decode_weights='mxfp4' needs MX blocks of 32 inputs: " + ", ".join(bad)
                                  + " must be multiples of 32")
 
+    @staticmethod
+    def check_mxfp4_gemm_from(cfg: Qwen2VLConfig, decode_weights: str, mxfp4_gemm_from) -> None:
+        """Refuse a threshold for the MXFP4 MFMA projection that is no integer in 5..64, that comes without
+        decode_weights='mxfp4', or that the model's shapes do not fit (needs no GPU)."""
+        if mxfp4_gemm_from is None:
+            return
+        if isinstance(mxfp4_gemm_from, bool) or not isinstance(mxfp4_gemm_from, int) or not 5 <= mxfp4_gemm_from <= 64:
+            raise ValueError("mxfp4_gemm_from must be None or an integer in 5..64 (smaller batches are the multi-row GEMV's)")
+        if decode_weights != "mxfp4":
+            raise ValueError("mxfp4_gemm_from needs decode_weights='mxfp4'")
+        dims = {"hidden": cfg.hidden, "heads*head_dim": cfg.heads * cfg.head_dim, "intermediate": cfg.intermediate}
+        bad = [f"{n}={v}" for n, v in dims.items() if v % 64]
+        if bad:
+            raise ValueError("mxfp4_gemm_from needs K-steps of 64 inputs: " + ", ".join(bad) + " must be multiples of 64")
+
     def __init__(self, cfg: Qwen2VLConfig, weights: DeviceWeights, device, max_ctx: int = 4096,
                  decode_splits: int = 0, max_batch: int = 1, decode_weights: str = "bf16",
-                 prefill_dtype: str = "bf16"):
+                 prefill_dtype: str = "bf16", mxfp4_gemm_from: Optional[int] = None):
         """decode_weights="fp8" (BASELINE configs[4] slice, also VIS_DECODE_WEIGHTS=fp8): the single-sequence decode
         step streams OCP-e4m3 copies of the LLM projections and the lm_head (per-output-row f32 scales,
         hip.quantize_fp8_rows at load time) through vis_gemv_fp8w; prefill and the batched decode keep bf16.
@@ -175,9 +190,16 @@ class Qwen2VLEngine(PickStage):
         E8M0 scale per 32 inputs, hip.quantize_mxfp4_rows at load time) through vis_gemv_mxfp4w at EVERY batch size: 2..4
         sequences share one pass over the weights (vis_gemv_mxfp4w_rows), larger batches issue each projection once per
         group of 4 rows, so a sequence decodes bit-identically alone or in any batch.  Embedding, norms, biases, the KV
-        cache and the prompt pass stay bf16."""
+        cache and the prompt pass stay bf16.
+        mxfp4_gemm_from=n (5..64, VIS_MXFP4_GEMM_FROM, default None = off; mxfp4 only): steps with n or more sequences run the
+        bf16 batched step's launches with every projection on vis_gemm_decode_mxfp4, which streams the FP4 weights ONCE
+        for up to 64 sequences.  That makes TWO arithmetic families: the GEMV summation order below n, the MFMA stream-K
+        order from n on.  Each is bit-invariant inside itself to batch size and row position; a request whose batch
+        crosses n may differ at near-ties (the trade VIS_ROWS_GEMV makes), which is why it is off by default."""
         cfg.validate_for_kernels()
         self.check_decode_weights(cfg, decode_weights)
+        self.check_mxfp4_gemm_from(cfg, decode_weights, mxfp4_gemm_from)
+        self.mxfp4_gemm_from = mxfp4_gemm_from
         hip.load()  # fail loudly when the gfx950 library is missing: there is no other path
         if not torch.cuda.is_available():
             raise hip.HipLibraryError("Qwen2VLEngine needs a ROCm GPU (no CPU fallback exists)")
@@ -240,7 +262,8 @@ class Qwen2VLEngine(PickStage):
             self.b_x2w = torch.empty((Bm, H), dtype=bf, device=dev)       # x2 * ln2_w (A operand of gate/up)
             self.b_ssq1 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
             self.b_ssq2 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
-        if Bm > 1 and not (self.fused_proj and decode_weights == "fp8") and decode_weights != "mxfp4":
+        if Bm > 1 and not (self.fused_proj and decode_weights == "fp8") and \
+                (decode_weights != "mxfp4" or mxfp4_gemm_from is not None):
             # split-K slabs of the r02-r04 pair of launches: the whole step with VIS_DECODE_FUSED=0, and the bf16 down
             # projection at many sequences in the fused step (_decode_step_fused)
             self.b_part = torch.empty(16 * hip.part_rows(Bm) * max(nq, H, 2 * cfg.intermediate), dtype=torch.float32,
@@ -1163,8 +1186,14 @@ class Qwen2VLEngine(PickStage):
         # default because it trades an invariant for those 6-13 %: a sequence decoded in a batch of 2 would then follow the
         # single-sequence arithmetic and in a batch of 3+ the stream-K arithmetic - its tokens could depend on the batch size
         # at near-ties (tests/test_fullsize_gpu.py::test_7b_batch_invariance_and_reproducibility).
-        if self.decode_weights == "mxfp4":     # MXFP4 has no MFMA projection: the multi-row GEMV at every batch size
-            return self._decode_step_rows(B)
+        if self.decode_weights == "mxfp4":
+            # the multi-row GEMV at every batch size, unless mxfp4_gemm_from hands the larger ones to the MFMA projection
+            # (the other arithmetic family, see __init__)
+            if self.mxfp4_gemm_from is None or B < self.mxfp4_gemm_from:
+                return self._decode_step_rows(B)
+            q4 = self.q4
+            return self._decode_step_streamk(B, lambda a, li, n, **kw: hip.decode_gemm_mxfp4(a, *q4[li][n], **kw),
+                                             lambda a, **kw: hip.decode_gemm_mxfp4(a, *self.q4_lm_head, **kw))
         rows_max = int(os.environ.get("VIS_ROWS_GEMV", "0"))
         if 2 <= B <= min(rows_max, 4) and max(self.cfg.intermediate, self.cfg.hidden) * 2 * (2 if B <= 2 else 4) <= 152 * 1024:
             return self._decode_step_rows(B)
@@ -1172,6 +1201,13 @@ class Qwen2VLEngine(PickStage):
             return self._decode_step_fused(B)
         if self.decode_weights == "fp8" and self.fp8_batched:
             return self._decode_step_batched_fp8(B)
+        llm = self.w.llm
+        self._decode_step_streamk(B, lambda a, li, n, **kw: hip.decode_gemm(a, getattr(llm[li], n), **kw),
+                                  lambda a, **kw: hip.decode_gemm(a, self.w.lm_head, **kw))
+
+    def _decode_step_streamk(self, B: int, gemm, gemm_head) -> None:
+        """The stream-K batched step: ``gemm(a, layer, name, part=)`` is the first half of a layer projection (hip.decode_gemm on
+        the bf16 weights, or hip.decode_gemm_mxfp4 on the FP4 codes - same partial slabs), ``gemm_head(a, out=)`` the lm_head."""
         cfg, w = self.cfg, self.w
         Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
         scale, eps = D ** -0.5, cfg.rms_eps
@@ -1182,7 +1218,7 @@ class Qwen2VLEngine(PickStage):
         hip.rmsnorm(x, w.llm[0].ln1_w, eps, out=xn)
         n_layers = len(w.llm)
         for li, lw in enumerate(w.llm):
-            ks = hip.decode_gemm(xn, lw.qkv_w, part=part)
+            ks = gemm(xn, li, "qkv_w", part=part)
             if self.fold_qkv:     # the attention workgroups finalise the qkv columns they read (same bits, one launch less)
                 hip.decode_attn_parts(part, ks, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
                                       self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
@@ -1192,14 +1228,14 @@ class Qwen2VLEngine(PickStage):
                 hip.decode_attn(qkv, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
                                 self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
                                 shared_len=self.batch_shared_len)
-            ks = hip.decode_gemm(att, lw.o_w, part=part)
+            ks = gemm(att, li, "o_w", part=part)
             hip.skinny_finalize(part, ks, x2, cfg.hidden, residual=x, norm_w=lw.ln2_w, yn=xn2, eps=eps)
-            ks = hip.decode_gemm(xn2, lw.gateup_w, part=part)
+            ks = gemm(xn2, li, "gateup_w", part=part)
             hip.skinny_finalize(part, ks, act, 2 * cfg.intermediate, swiglu=True, eps=eps)
-            ks = hip.decode_gemm(act, lw.down_w, part=part)
+            ks = gemm(act, li, "down_w", part=part)
             next_norm = w.llm[li + 1].ln1_w if li + 1 < n_layers else w.final_norm_w
             hip.skinny_finalize(part, ks, x, cfg.hidden, residual=x2, norm_w=next_norm, yn=xn, eps=eps)
-        hip.decode_gemm(xn, w.lm_head, out=self.logits_b[:B])
+        gemm_head(xn, out=self.logits_b[:B])
         self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
                    self.temperature, self.seed)
         self._logprobs_after_pick(B)

@@ -48,6 +48,8 @@ _SIGS = {
     "vis_gemv_fp8w_rows": "ppppppp" + "iiiiiiiii" + "f" + "p",
     "vis_gemv_mxfp4w": "ppppppp" + "iiiiii" + "f" + "p",
     "vis_gemv_mxfp4w_rows": "ppppppp" + "iiiiiiiiii" + "f" + "p",
+    "vis_gemm_decode_mxfp4_ksplit": "ii",
+    "vis_gemm_decode_mxfp4": "ppppp" + "iiiiiiiii" + "p",
     "vis_decode_attn": "ppppppppp" + "iiiii" + "f" + "i" + "lll" + "p",
     "vis_decode_attn_shared": "ppppppppp" + "iiiii" + "f" + "i" + "lll" + "i" + "p",
     "vis_decode_attn_parts": "p" + "ii" + "p" * 11 + "iiiii" + "f" + "i" + "ll" + "i" + "p",
@@ -956,6 +958,38 @@ def gemv_mxfp4_rows(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, out: to
                                      1 if out.dtype == torch.float32 else 0, eps, _stream())
     _check(rc, "vis_gemv_mxfp4w_rows")
     return out
+
+
+def decode_gemm_mxfp4_ksplit(N: int, K: int) -> int:
+    """Partial slots ``decode_gemm_mxfp4`` writes for (N, K): 1..16, fixed by the shape alone (0: shape not covered)."""
+    return load().vis_gemm_decode_mxfp4_ksplit(int(N), int(K))
+
+
+def decode_gemm_mxfp4(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, part: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None, ksplit: int = 0) -> int:
+    """``decode_gemm`` on MXFP4 weights (quantize_mxfp4_rows) for 5..64 rows: f32 partials part[slot][part_rows(B)][N] whose
+    sum over the returned number of slots is x[B,K] @ dequantize_mxfp4(wq, ws).T (every slot is written), or - with ``out``
+    instead of ``part`` - a direct bf16 / f32 result.  The codes and scales are streamed once for all rows."""
+    _bf16(x, "decode_gemm_mxfp4 x")
+    N, K = _mxfp4_check("decode_gemm_mxfp4", wq, ws)
+    if x.dim() != 2 or x.shape[1] != K or x.stride(1) != 1 or ws.shape[1] * 32 < K or (part is None) == (out is None):
+        raise HipLibraryError("decode_gemm_mxfp4: bad shapes (give exactly one of part / out)")
+    B = x.shape[0]
+    lib = load()
+    if part is not None:
+        ks = ksplit or lib.vis_gemm_decode_mxfp4_ksplit(N, K)
+        if part.dtype != torch.float32 or part.numel() < ks * part_rows(B) * N:
+            raise HipLibraryError("decode_gemm_mxfp4: partial workspace too small")
+        rc = lib.vis_gemm_decode_mxfp4(_ptr(x), _ptr(wq), _ptr(ws), _ptr(part), None, B, N, K, x.stride(0), wq.stride(0),
+                                       ws.stride(0), 0, ks, 0, _stream())
+    else:
+        ks = 1
+        if out.shape != (B, N) or out.stride(1) != 1 or out.dtype not in (torch.bfloat16, torch.float32):
+            raise HipLibraryError("decode_gemm_mxfp4: bad output")
+        rc = lib.vis_gemm_decode_mxfp4(_ptr(x), _ptr(wq), _ptr(ws), None, _ptr(out), B, N, K, x.stride(0), wq.stride(0),
+                                       ws.stride(0), out.stride(0), 1, 1 if out.dtype == torch.float32 else 0, _stream())
+    _check(rc, "vis_gemm_decode_mxfp4")
+    return ks
 
 
 def decode_attn_parts(part: torch.Tensor, ksplit: int, cos_t: torch.Tensor, sin_t: torch.Tensor, k_cache: torch.Tensor,
