@@ -767,6 +767,8 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
   if (nch <= 64 * QCH) {  // the row lives in registers (uniform branch)
     float v[QCH][8];
     float ss = 0.f;
+    const float inv_n = 1.0f / (float)K;   // the statistics in norm_rows_kernel's own expressions (sum * inv_n, not sum / K:
+                                           // they differ in the last f32 bit when K is no power of two, which flips a bf16 now and then)
     {   // r05: every load unconditional (clamped chunk) and issued before the first use - a guarded load drains the queue
       u32x4 raw[QCH];
 #pragma unroll
@@ -790,7 +792,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
           for (int e = 0; e < 8; ++e) sm += v[i][e];
         }
       }
-      const float mean = wave_sum(sm) / (float)K;
+      const float mean = wave_sum(sm) * inv_n;
       float d2 = 0.f;
 #pragma unroll
       for (int i = 0; i < QCH; ++i) {
@@ -800,7 +802,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
           for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mean; d2 += d * d; }
         }
       }
-      const float rstd = rsqrtf(wave_sum(d2) / (float)K + eps);
+      const float rstd = rsqrtf(wave_sum(d2) * inv_n + eps);
 #pragma unroll
       for (int i = 0; i < QCH; ++i) {
         const int c = lane + i * 64;
@@ -814,7 +816,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
       }
     } else if (nw) {  // RMSNorm (LLM)
       ss = wave_sum(ss);
-      const float rstd = rsqrtf(ss / (float)K + eps);
+      const float rstd = rsqrtf(ss * inv_n + eps);
 #pragma unroll
       for (int i = 0; i < QCH; ++i) {
         const int c = lane + i * 64;
