@@ -260,6 +260,10 @@ static inline int ds_check_common(const DsArgs& p, int B, int K, const void* ws,
     return VIS_ERR_ARG;
   if ((p.Cq != nullptr) != (p.Cqs != nullptr) || (p.Cq && (p.ldcq % 4 != 0 || ((uintptr_t)p.Cq & 3)))) return VIS_ERR_ARG;
   if (p.Cq && mode == DS_PLAIN) return VIS_ERR_ARG;
+  // row strides shorter than a row: the epilogue would write (R: read) into the next row and past the last one
+  const int n_out = mode == DS_SWIGLU ? p.N / 2 : p.N;
+  if (((p.C || p.Cw) && p.ldc < n_out) || (p.R && p.ldr < p.N)) return VIS_ERR_ARG;
+  if (p.Cq && (p.ldcq < n_out || p.ldcqs < (n_out + 31) / 32)) return VIS_ERR_ARG;
   if (((uintptr_t)p.C | (uintptr_t)p.Cw | (uintptr_t)p.bias | (uintptr_t)p.R | (uintptr_t)p.nw) & 7) return VIS_ERR_ARG;
   if (p.out_f32 && ((uintptr_t)p.C & 15)) return VIS_ERR_ARG;
   if (p.ssq_in && (p.tiles_in <= 0 || p.tiles_in > 128)) return VIS_ERR_ARG;
