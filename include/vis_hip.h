@@ -308,6 +308,28 @@ int vis_penalty_prompt(void* state_row, int V, const void* ids, int n, vis_strea
 int vis_penalize_f32(const void* logits, int V, int ld_logits, void* state, const void* params, const void* tokens,
                      int max_tokens, const void* step_ptr, void* out, int ld_out, int batch, vis_stream_t stream);
 
+/* Logit shaping ahead of the pick (csrc/shape.hip): logit_bias (OpenAI's), then top_k and min_p (transformers'
+ * TopKLogitsWarper / MinPLogitsWarper).  Row b < batch, allowed set A = every id, or (allow non-null) the ids whose bit is set
+ * in allow + b * ld_allow (vis_json_mask's rows, as vis_sample_f32 takes them):
+ *   y[v] = x[v] + bias_vals[b][j] where bias_ids[b][j] == v for some j < nbias[b] (one f32 add; the first such j counts; ids
+ *   outside [0, V) are skipped), y[v] = x[v] otherwise;  m = max y over A;
+ *   t = the k[b]-th largest y over A when 0 < k[b] < |A| (ties at t all stay), no rank cut otherwise;
+ *   v survives when it is in A, y[v] >= t and not (y[v] - m) < delta[b] (f32 subtraction and compare; delta = ln(min_p) /
+ *   inv_temp from the host, -inf = off; the row's maximum always survives);
+ *   out[b][v] = y[v] for survivors, -inf for every other id (ids outside A included); nkept[b] = the number of survivors.
+ * Comparisons are float comparisons (-0.0 == +0.0); inputs are finite.  k int32 [batch], delta f32 [batch], nbias int32
+ * [batch] (clamped to 0..300), bias_ids int32 [batch][300], bias_vals f32 [batch][300]: device memory, read at run time, so a
+ * captured launch serves any values.  logits are left intact (out != logits).  A row's result depends on that row alone; a
+ * repeated launch changes nothing.  ws: vis_shape_ws_bytes(V, batch) bytes, row b receives {f32 t, f32 m, int32 |A|, int32
+ * path} (path: 0 no rank cut, 1 cut found by rank counting in LDS, 2 by the radix select; m and |A| are 0 when neither top_k
+ * nor min_p is on).  VIS_ERR_ARG and nothing launched: null pointer (allow may be null), V outside 1..262144, batch outside
+ * 1..64, ld_logits / ld_out < V at batch > 1, ld_allow < ceil(V / 64) or allow not 8-byte aligned, a pointer not 4-byte
+ * aligned, out == logits. */
+long long vis_shape_ws_bytes(int V, int batch);
+int vis_shape_f32(const void* logits, int V, int ld_logits, const void* allow, int ld_allow, const void* k, const void* delta,
+                  const void* nbias, const void* bias_ids, const void* bias_vals, void* out, int ld_out, void* nkept,
+                  void* ws, int batch, vis_stream_t stream);
+
 /* Stop sequences and how a reply ended (csrc/stop_scan.hip; stop.py compiles the tables and is the reference).  One launch
  * AFTER each pick: for every row b < batch folds the tokens picked since the row's last launch (positions [pos, step[b]) of
  * tokens[b][max_tokens]; on the first launch after a reset the one at step[b] - 1) byte by byte - token table as

@@ -61,6 +61,38 @@ def penalty_kwargs() -> dict:
         raise ValueError("VIS_REPETITION_PENALTY must be a number") from None
 
 
+def shaping_kwargs() -> dict:
+    """VIS_TOP_K=<integer >= 1>, VIS_MIN_P=<number in [0, 1]>, VIS_LOGIT_BIAS=<JSON object {"token id": bias}> (default
+    unset): the analysis and verify requests pass top_k= / min_p= / logit_bias= with them (VIS_LOGIT_BIAS='{"<id>": -100}'
+    with the tokenizer's id of the code-fence token keeps a report from opening with three backticks).  Unset: the calls are as before."""
+    from .shaping import check_logit_bias, check_min_p, check_top_k
+    out = {}
+    v = os.environ.get("VIS_TOP_K", "").strip()
+    if v:
+        try:
+            out["top_k"] = check_top_k(int(v))
+        except ValueError:
+            raise ValueError("VIS_TOP_K must be an integer >= 1") from None
+    v = os.environ.get("VIS_MIN_P", "").strip()
+    if v:
+        try:
+            out["min_p"] = check_min_p(float(v))
+        except ValueError:
+            raise ValueError("VIS_MIN_P must be a number in [0, 1]") from None
+    v = os.environ.get("VIS_LOGIT_BIAS", "").strip()
+    if v:
+        import json
+        try:
+            bias = json.loads(v)
+        except ValueError:
+            raise ValueError("VIS_LOGIT_BIAS must be a JSON object {token id: bias}") from None
+        if not isinstance(bias, dict):
+            raise ValueError("VIS_LOGIT_BIAS must be a JSON object {token id: bias}")
+        check_logit_bias(bias)
+        out["logit_bias"] = bias
+    return out
+
+
 def stop_kwargs() -> dict:
     """VIS_STOP=<JSON string or list of up to 4 strings> (default unset): the analysis and verify requests pass it as stop=,
     so a report ends in front of the first of them (VIS_STOP='["```"]': at the fence that closes its JSON block) instead of
@@ -106,7 +138,8 @@ class _BaseAgent:
             try:
                 completion = self.client.chat.completions.create(
                     model=self.model_id, messages=messages, temperature=self.temperature, max_tokens=self.max_tokens,
-                    **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs())
+                    **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs(),
+                    **shaping_kwargs())
                 return completion.choices[0].message.content
             except Exception as e:
                 text = str(e)
@@ -345,14 +378,16 @@ def _many(agent, image_paths, contexts, prepared=None) -> list:
         try:
             if hasattr(agent.client, "complete_many"):
                 replies = agent.client.complete_many(agent.model_id, msgs, agent.temperature, agent.max_tokens,
-                                                     **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs())
+                                                     **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs(),
+                                                     **shaping_kwargs())
                 texts = [r if isinstance(r, Exception) else r.choices[0].message.content for r in replies]
             else:
                 texts = [agent.client.chat.completions.create(model=agent.model_id, messages=m,
                                                               temperature=agent.temperature,
                                                               max_tokens=agent.max_tokens,
                                                               **json_mode_kwargs(), **seed_kwargs(),
-                                                              **penalty_kwargs(), **stop_kwargs()).choices[0].message.content
+                                                              **penalty_kwargs(), **stop_kwargs(),
+                                                              **shaping_kwargs()).choices[0].message.content
                          for m in msgs]
         except Exception as e:
             agent.logger.error(f"{agent.nickname}: batched call failed: {e}", exc_info=True)

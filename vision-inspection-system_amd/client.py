@@ -78,9 +78,11 @@ class _Completions:
                top_logprobs: Optional[int] = None, response_format: Optional[dict] = None, top_p: Optional[float] = None,
                seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
                presence_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
-               stop=None, **kwargs) -> ChatCompletion:
+               stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
+               logit_bias: Optional[dict] = None, **kwargs) -> ChatCompletion:
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
-                 "repetition_penalty": repetition_penalty, "stop": stop}
+                 "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
+                 "logit_bias": logit_bias}
         kwargs.update({name: v for name, v in given.items() if v is not None})
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
                                      top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
@@ -430,16 +432,18 @@ class LocalVLMClient:
 
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
                   top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
-                  stop=None, **kwargs) -> ChatCompletion:
+                  stop=None, top_k=None, min_p=None, logit_bias=None, **kwargs) -> ChatCompletion:
         return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
                                   response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
-                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop)[0]
+                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop,
+                                  top_k=top_k, min_p=min_p, logit_bias=logit_bias)[0]
 
     def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
                       top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
                       top_p: Optional[float] = None, seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
                       presence_penalty: Optional[float] = None,
-                      repetition_penalty: Optional[float] = None, stop=None) -> List[ChatCompletion]:
+                      repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
+                      min_p: Optional[float] = None, logit_bias: Optional[dict] = None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -468,10 +472,17 @@ class LocalVLMClient:
         ``stop`` (OpenAI's): a string or up to 4 of them, each 1..64 bytes of UTF-8; the reply ends in front of the first
         occurrence of one in its bytes (stop.py, matched on the GPU) and never contains it; tokens, usage and logprobs run
         through the token that completed the match.  Every choice's ``finish_reason`` is "stop" when the reply ended on EOS
-        or a stop string and "length" when max_tokens or the context cut it off."""
+        or a stop string and "length" when max_tokens or the context cut it off.
+        ``logit_bias`` (OpenAI's): {token id: bias in [-100, 100]}, at most 300 entries, ids as integers or decimal strings;
+        the bias is added to the token's logit ahead of temperature: -100 bans a token, +100 all but forces it.  ``top_k``
+        (vLLM's / huggingface_hub's, an integer >= 1): only the k most likely allowed tokens stay, ties at the k-th place
+        included.  ``min_p`` (vLLM's, in [0, 1]): only tokens at least min_p times as likely as the most likely one stay.
+        One launch ahead of the pick (shaping.py), after the penalties and the JSON mask, before top_p and the draw; a
+        greedy request (temperature 0) is affected by logit_bias only.  None / 0 / {} = off.  Logprobs keep their meaning."""
         import torch
         from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
+        from .shaping import check_shaping, shaping_kwargs
         from .stop import check_stop
         k = logprobs_k(logprobs, top_logprobs)
         dfa = schema_of(response_format)
@@ -481,6 +492,7 @@ class LocalVLMClient:
         seed = check_seed(seed)
         pen = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         pen = {} if pen is None else dict(zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), pen[0]))
+        shp = {name: v for name, v in shaping_kwargs(check_shaping(top_k, min_p, logit_bias, 1)).items() if v is not None}
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
@@ -490,7 +502,7 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         out: List[ChatCompletion] = []
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa, stop)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa, stop, shp)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -530,7 +542,7 @@ class LocalVLMClient:
                                           **({"json_schema": dfa} if dfa is not None else {}),
                                           **({"top_p": top_p} if top_p is not None else {}),
                                           **({"seeds": [seed] * len(idx)} if seed is not None else {}),
-                                          **({"stop": stop} if stop is not None else {}), **pen)
+                                          **({"stop": stop} if stop is not None else {}), **pen, **shp)
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
                 fins = getattr(eng, "last_finish", None) or [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", {}))
@@ -576,7 +588,7 @@ class LocalVLMClient:
     def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
                               k: Optional[int] = None, jm: bool = False, top_p: Optional[float] = None,
                               seed: Optional[int] = None, pen: Optional[dict] = None, dfa=None,
-                              stop=None) -> List[ChatCompletion]:
+                              stop=None, shp: Optional[dict] = None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -595,6 +607,7 @@ class LocalVLMClient:
         if stop is not None:
             lpk["stop"] = stop
         lpk.update(pen or {})
+        lpk.update(shp or {})
 
         def seeds_of(n):
             return {"seeds": [seed] * n} if seed is not None else {}
@@ -678,12 +691,13 @@ class CannedResponseClient:
         self.chat = _Chat(self)
 
     def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
-                  frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None,
-                  **kwargs) -> ChatCompletion:
+                  frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None, top_k=None, min_p=None,
+                  logit_bias=None, **kwargs) -> ChatCompletion:
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
                            "response_format": response_format, "top_p": top_p, "seed": seed})
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
-                 "repetition_penalty": repetition_penalty, "stop": stop}
+                 "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
+                 "logit_bias": logit_bias}
         self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
         reply = self.reply(messages) if callable(self.reply) else self.reply
         return ChatCompletion([_Choice(_Message(reply))], model=model or "")

@@ -31,6 +31,7 @@ from .logprobs import check_k
 from .penalties import check_penalties
 from .pick import PickStage
 from .sampling import check_seeds, check_top_p
+from .shaping import check_shaping, shaping_kwargs
 from .stop import check_stop
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
@@ -913,7 +914,8 @@ class Qwen2VLEngine(PickStage):
                      seed: int = 0, max_new_tokens: Optional[int] = None,
                      ids_dev: Optional[Sequence[torch.Tensor]] = None,
                      seeds: Optional[Sequence[int]] = None,
-                     penalties: Optional[Sequence[tuple]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
+                     penalties: Optional[Sequence[tuple]] = None,
+                     shaping: Optional[Sequence[tuple]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
         """Prefill the requests into consecutive slots.  The prefills are independent kernel chains: they are issued round-robin
         on a few HIP streams (VIS_PREFILL_STREAMS, default 2: 418 -> 381 ms for 8 images) so that the ragged last round of one image's GEMM /
         attention grids is filled by another image's workgroups.  Returns with the current stream ordered after
@@ -925,6 +927,7 @@ class Qwen2VLEngine(PickStage):
         raises gets no slot and its exception is returned instead of failing the batch.
         ``seeds``: request b's own sampling seed (read by the picks while nucleus sampling / seeds are on).
         ``penalties``: request b's (repetition, frequency, presence) penalties (read by the picks while penalties are on).
+        ``shaping``: request b's (top_k, min_p, bias list) (read by the picks while logit shaping is on).
         Returns (slot of request b or None, exception of request b or None)."""
         B = len(requests)
         lazy = any(callable(r) for r in requests)
@@ -978,6 +981,8 @@ class Qwen2VLEngine(PickStage):
                     self._slot_seed[next_slot] = seeds[b]
                 if penalties is not None:
                     self._slot_pen[next_slot] = penalties[b]
+                if shaping is not None:
+                    self._slot_shape[next_slot] = shaping[b]
                 self.prefill(r[0], r[1], ids_dev=ids_dev[b] if ids_dev else None, temperature=temperature, seed=seed,
                              max_new_tokens=max_new_tokens, slot=next_slot, prefix=prefix_for(r[0]))
                 slots[b] = next_slot
@@ -1024,6 +1029,8 @@ class Qwen2VLEngine(PickStage):
                 self._slot_seed.update({slot_of[b]: seeds[b] for b in grp_all})
             if penalties is not None:
                 self._slot_pen.update({slot_of[b]: penalties[b] for b in grp_all})
+            if shaping is not None:
+                self._slot_shape.update({slot_of[b]: shaping[b] for b in grp_all})
             next_slot += len(grp_all)
             if merged:
                 st = streams[(g0 // vb) % n_streams]         # consecutive groups alternate streams
@@ -1403,7 +1410,7 @@ class Qwen2VLEngine(PickStage):
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
         # temperature, seed and the batch size are kernel arguments baked into the graph; so is what _pick_key() names
         key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch) \
-            + self._pick_key() + self._stop_key()
+            + self._pick_key() + self._stop_key() + self._shape_key()
         if key in self._graphs:
             return self._graphs[key]
         step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
@@ -1522,7 +1529,8 @@ class Qwen2VLEngine(PickStage):
                  temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                  json_mode: bool = False, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
-                 stop=None) -> List[int]:
+                 stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
+                 logit_bias: Optional[dict] = None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
@@ -1541,9 +1549,15 @@ class Qwen2VLEngine(PickStage):
         one in its bytes (vis_stop_scan after every pick; the poll then reads its records, not the token row), also in an
         ``ignore_eos`` run.  Afterwards, always, ``last_finish`` = [(reason, cut)]: "eos", "stop" (cut = the byte offset in
         the returned tokens' bytes where the stop string starts) or "length" (max_new_tokens, the context clamp, or an
-        ``ignore_eos`` run that matched nothing)."""
+        ``ignore_eos`` run that matched nothing).
+        ``top_k`` >= 1, ``min_p`` in [0, 1] (transformers' TopKLogitsWarper / MinPLogitsWarper) and ``logit_bias`` {token id:
+        bias in [-100, 100]}, at most 300 entries (OpenAI's): shaping.py - one launch ahead of the pick adds the biases to
+        the (penalised) logits, then takes out every token below the k-th largest allowed one or less likely than min_p
+        times the most likely one; top_p and the draw see the rest.  None / 0 / {} = off; a greedy request is affected by
+        logit_bias only.  Logprobs keep their meaning (raw logits)."""
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop):
+        shaping = check_shaping(top_k, min_p, logit_bias, 1)
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping):
             self.stop_eos = not ignore_eos
             room = self.max_ctx - len(input_ids) - 1
             if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
@@ -1603,7 +1617,7 @@ class Qwen2VLEngine(PickStage):
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                        json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None) -> list:
+                       stop=None, top_k=None, min_p=None, logit_bias=None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
@@ -1615,7 +1629,8 @@ class Qwen2VLEngine(PickStage):
         ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty``: as in generate, each a number or a sequence
         with one value per request.  ``json_schema``: as in generate, one schema for the whole group.  ``stop``: as in
         generate, one set for the whole group; the shared loop ends when every row has ended.  ``last_finish`` holds one
-        (reason, cut) per request, None for a failed one."""
+        (reason, cut) per request, None for a failed one.  ``top_k``, ``min_p``, ``logit_bias``: as in generate, each one
+        value for the group or a sequence with one value (or None) per request."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -1626,6 +1641,7 @@ class Qwen2VLEngine(PickStage):
         check_top_p(top_p)
         seeds = check_seeds(seeds, n_req)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
+        shaping = check_shaping(top_k, min_p, logit_bias, n_req)
         check_stop(stop)
         if n_req == 1:
             r = requests[0]
@@ -1640,23 +1656,25 @@ class Qwen2VLEngine(PickStage):
                 return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature,
                                       seed if seeds is None else seeds[0], logprobs=logprobs, json_mode=json_mode, json_schema=json_schema,
                                       top_p=top_p, stop=stop, **({} if penalties is None else dict(
-                                          zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))))]
+                                          zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))),
+                                      **shaping_kwargs(shaping))]
             except JsonModeError as e:
                 return [e]
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop):
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
+                                shaping=shaping):
             self.stop_eos = not ignore_eos
             return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, seeds,
-                                        penalties)
+                                        penalties, shaping)
 
     def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                        seeds=None, penalties=None) -> list:
+                        seeds=None, penalties=None, shaping=None) -> list:
         n_req = len(requests)
         # every prompt's own limit (prompt + new tokens <= context) is applied by its prefill; the shared loop below
         # runs to the limit of the longest one
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
         slots, errors = self.prefill_many(requests, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens,
-                                          seeds=seeds, penalties=penalties)
+                                          seeds=seeds, penalties=penalties, shaping=shaping)
         ev[1].record()
         live = [b for b in range(n_req) if slots[b] is not None]
         B = len(live)

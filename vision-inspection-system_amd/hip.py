@@ -70,6 +70,8 @@ _SIGS = {
     "vis_penalty_state_bytes": "ii",
     "vis_penalty_prompt": "pi" + "pi" + "p",
     "vis_penalize_f32": "p" + "ii" + "ppp" + "i" + "pp" + "ii" + "p",
+    "vis_shape_ws_bytes": "ii",
+    "vis_shape_f32": "p" + "ii" + "p" + "i" + "ppppp" + "p" + "i" + "pp" + "i" + "p",
     "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
     "vis_gemm_decode_ksplit": "ii",
     "vis_gemm_decode_bf16": "pppp" + "iiiiiiii" + "p",
@@ -216,6 +218,7 @@ def load() -> ctypes.CDLL:
     lib.vis_logprobs_ws_bytes.restype = ctypes.c_longlong
     lib.vis_sample_ws_bytes.restype = ctypes.c_longlong
     lib.vis_penalty_state_bytes.restype = ctypes.c_longlong
+    lib.vis_shape_ws_bytes.restype = ctypes.c_longlong
     _lib = _Lib(lib)
     return _lib
 
@@ -1418,6 +1421,52 @@ def penalize(logits: torch.Tensor, state: torch.Tensor, params: torch.Tensor, to
                                  _ptr(tokens), tokens.numel() // B, _ptr(step), _ptr(out),
                                  out.stride(0) if out.dim() == 2 else V, B, _stream())
     _check(rc, "vis_penalize_f32")
+
+
+SHAPE_MAX_BIAS = 300    # entries of one row's bias list (shaping.MAX_BIAS; OpenAI's limit for logit_bias)
+
+
+def shape_ws(V: int, batch: int, device) -> torch.Tensor:
+    """Workspace of vis_shape_f32 for up to ``batch`` rows of V logits, [batch, n] uint8 (row b's slice serves one row and
+    receives its record {f32 t, f32 m, int32 |A|, int32 path})."""
+    n = int(load().vis_shape_ws_bytes(V, batch))
+    if n <= 0:
+        raise HipLibraryError(f"shape_ws: unsupported V={V} batch={batch}")
+    return torch.zeros((batch, n // batch), dtype=torch.uint8, device=device)
+
+
+def shape_logits(logits: torch.Tensor, k: torch.Tensor, delta: torch.Tensor, nbias: torch.Tensor, bias_ids: torch.Tensor,
+                 bias_vals: torch.Tensor, out: torch.Tensor, nkept: torch.Tensor, ws: torch.Tensor,
+                 allow: Optional[torch.Tensor] = None) -> None:
+    """Shaped copy of the logits (vis_shape_f32): out = logits + the rows' bias lists, then -inf for every id outside the
+    allow rows, below the rows' k-th largest value, or more than -delta below the row maximum; logits stay intact.  logits,
+    out [V] or [B, V] f32; k, nbias, nkept int32 [B]; delta f32 [B]; bias_ids int32 / bias_vals f32 [B, 300], all in device
+    memory and read at run time; ws from shape_ws (rows >= B); allow: vis_json_mask's int64 rows [B, ceil(V / 64)] or None."""
+    if logits.dtype != torch.float32 or out.dtype != torch.float32 or delta.dtype != torch.float32 \
+            or bias_vals.dtype != torch.float32 or k.dtype != torch.int32 or nbias.dtype != torch.int32 \
+            or bias_ids.dtype != torch.int32 or nkept.dtype != torch.int32 or ws.dtype != torch.uint8:
+        raise HipLibraryError("shape_logits: f32 logits, out, delta, bias_vals / int32 k, nbias, bias_ids, nkept / uint8 "
+                              "workspace required")
+    B = logits.shape[0] if logits.dim() == 2 else 1
+    V = logits.shape[-1]
+    if out.shape != logits.shape or k.numel() != B or delta.numel() != B or nbias.numel() != B or nkept.numel() != B \
+            or bias_ids.numel() != B * SHAPE_MAX_BIAS or bias_vals.numel() != B * SHAPE_MAX_BIAS:
+        raise HipLibraryError("shape_logits: bad parameter shapes")
+    if logits.stride(-1) != 1 or out.stride(-1) != 1 or not (k.is_contiguous() and delta.is_contiguous() and nbias.is_contiguous()
+                                                             and bias_ids.is_contiguous() and bias_vals.is_contiguous()
+                                                             and nkept.is_contiguous() and ws.is_contiguous()) \
+            or ws.numel() < int(load().vis_shape_ws_bytes(V, B)):
+        raise HipLibraryError("shape_logits: bad strides / workspace too small")
+    a2 = None
+    if allow is not None:
+        a2 = allow if allow.dim() == 2 else allow.view(1, -1)
+        if allow.dtype != torch.int64 or a2.shape[0] != B or a2.shape[1] < (V + 63) // 64 or a2.stride(-1) != 1:
+            raise HipLibraryError("shape_logits: allow must be int64 [B, ceil(V / 64)]")
+    rc = load().vis_shape_f32(_ptr(logits), V, logits.stride(0) if logits.dim() == 2 else V, _ptr(a2),
+                              (a2.stride(0) if B > 1 else a2.shape[1]) if a2 is not None else 0, _ptr(k), _ptr(delta),
+                              _ptr(nbias), _ptr(bias_ids), _ptr(bias_vals), _ptr(out),
+                              out.stride(0) if out.dim() == 2 else V, _ptr(nkept), _ptr(ws), B, _stream())
+    _check(rc, "vis_shape_f32")
 
 
 STOP_STATE_INTS = 8     # int32 words of one sequence's vis_stop_scan record (stop.STATE_INTS)

@@ -34,6 +34,7 @@ from . import hip
 from .json_mode import JsonModeError, check_schema
 from .logprobs import check_k
 from .penalties import check_penalties
+from .shaping import check_shaping, shaping_kwargs
 from .pick import PickStage
 from .sampling import check_seeds, check_top_p
 from .stop import check_stop
@@ -667,7 +668,7 @@ class MllamaEngine(PickStage):
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key()
+        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key() + self._shape_key()
         if key in self._graphs:
             return self._graphs[key]
         snap = (self.step.clone(), self.cur_token.clone())
@@ -834,7 +835,7 @@ class MllamaEngine(PickStage):
         self._stop_after_pick(B)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B) + self._pick_key() + self._stop_key()
+        key = (self.temperature, self.seed, B) + self._pick_key() + self._stop_key() + self._shape_key()
         if key in self._graphs_b:
             return self._graphs_b[key]
         snap = (self.step_b.clone(), self.cur_b.clone())
@@ -858,7 +859,7 @@ class MllamaEngine(PickStage):
                        chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
                        top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None) -> list:
+                       stop=None, top_k=None, min_p=None, logit_bias=None) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
@@ -867,7 +868,8 @@ class MllamaEngine(PickStage):
         holds one record per request (None for a failed one).  ``json_mode``: as in generate; a request whose JSON text could
         not be continued gets a JsonModeError.  ``top_p`` / ``seeds`` and the three penalties (a number or one value per request): as in
         Qwen2VLEngine.generate_batch; so are ``json_schema`` and ``stop`` (one schema, one stop set for the whole group) and
-        ``last_finish``.  A reply that ended on EOS keeps its EOS token here, with or without stop strings."""
+        ``last_finish``.  A reply that ended on EOS keeps its EOS token here, with or without stop strings.  ``top_k``,
+        ``min_p``, ``logit_bias`` (one value for the group or one per request): as in Qwen2VLEngine.generate_batch."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -880,6 +882,8 @@ class MllamaEngine(PickStage):
         seed0 = seed if seeds is None else seeds[0]
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
         pen0 = {} if penalties is None else dict(zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))
+        shaping = check_shaping(top_k, min_p, logit_bias, n_req)
+        pen0.update(shaping_kwargs(shaping))
         check_stop(stop)
         lazy = any(callable(r) for r in requests)
         if lazy and n_req == 1:
@@ -902,13 +906,14 @@ class MllamaEngine(PickStage):
                                       json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, **pen0)]
             except JsonModeError as e:
                 return [e]
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop):
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
+                                shaping=shaping):
             self.stop_eos = bool(stop_on_eos)
             return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds,
-                                        penalties)
+                                        penalties, shaping)
 
     def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds=None,
-                        penalties=None) -> list:
+                        penalties=None, shaping=None) -> list:
         n_req = len(requests)
         lazy = any(callable(r) for r in requests)
         slots: List[Optional[int]] = [None] * n_req
@@ -965,6 +970,8 @@ class MllamaEngine(PickStage):
                                 self._slot_seed[B + len(items)] = seeds[b]
                             if penalties is not None:
                                 self._slot_pen[B + len(items)] = penalties[b]
+                            if shaping is not None:
+                                self._slot_shape[B + len(items)] = shaping[b]
                             items.append((B + len(items), ids, cs[0], cs[1]))
                         self._prefill_group(items, temperature, seed)
                     for (b, _, _) in grp:
@@ -981,6 +988,8 @@ class MllamaEngine(PickStage):
                     self._slot_seed[B] = seeds[b]
                 if penalties is not None:
                     self._slot_pen[B] = penalties[b]
+                if shaping is not None:
+                    self._slot_shape[B] = shaping[b]
                 try:
                     if n_streams > 1:
                         st = self._prefill_streams[B % n_streams]
@@ -1059,16 +1068,19 @@ class MllamaEngine(PickStage):
                  chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False,
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
-                 stop=None) -> List[int]:
+                 stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
+                 logit_bias: Optional[dict] = None) -> List[int]:
         """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
         logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
         None = off, no extra launch.  ``json_mode``: every pick restricted to the tokens that continue a JSON object, as in
         Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it).  ``top_p``: nucleus sampling, as in
         Qwen2VLEngine.generate; so are ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty`` (penalties.py)
         and ``json_schema`` (a compiled json_schema.SchemaDFA as the grammar; not together with ``json_mode``).  ``stop`` and
-        ``last_finish``: as in Qwen2VLEngine.generate; a reply that ended on EOS keeps its EOS token here."""
+        ``last_finish``: as in Qwen2VLEngine.generate; a reply that ended on EOS keeps its EOS token here.  ``top_k``,
+        ``min_p`` and ``logit_bias`` (shaping.py): as in Qwen2VLEngine.generate."""
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop):
+        shaping = check_shaping(top_k, min_p, logit_bias, 1)
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping):
             self.stop_eos = bool(stop_on_eos)
             try:
                 return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)

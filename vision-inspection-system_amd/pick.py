@@ -1,6 +1,6 @@
 """The next-token pick and the request switches that steer it (logprobs, JSON mode, a JSON Schema, nucleus sampling /
-seeds, penalties) or watch it (stop strings): which launches turn a row of logits into a token, the state behind each
-switch, and the part of the decode-graph key that depends on them.  Both engines derive from ``PickStage``; nothing else knows this policy."""
+seeds, penalties, top_k / min_p / logit_bias) or watch it (stop strings): which launches turn a row of logits into a
+token, the state behind each switch, and the part of the decode-graph key that depends on them.  Both engines derive from ``PickStage``; nothing else knows this policy."""
 from __future__ import annotations
 
 import contextlib
@@ -13,6 +13,7 @@ from .json_mode import JsonBuffers, SchemaBuffers, check_schema, engine_tokenize
 from .logprobs import LogprobsBuffers, check_k
 from .penalties import NEUTRAL, PenaltyBuffers
 from .sampling import SLOT_SEED_STRIDE, SampleBuffers, check_top_p
+from .shaping import NEUTRAL as SHAPE_NEUTRAL, ShapeBuffers, check_vocab
 from .stop import StopBuffers, check_stop, finish_of, host_finish
 
 
@@ -46,6 +47,11 @@ class PickStage:
         self.pen_on = False
         self._pen: Optional[PenaltyBuffers] = None
         self._slot_pen: Dict[int, tuple] = {}
+        # logit shaping (generate(..., top_k=, min_p=, logit_bias=)): while on, every pick reads the row vis_shape_f32 wrote
+        # (after the penalties and the grammar mask); _slot_shape: slot -> the request's (top_k, min_p, bias list)
+        self.shape_on = False
+        self._shp: Optional[ShapeBuffers] = None
+        self._slot_shape: Dict[int, tuple] = {}
         # stop strings (generate(..., stop=)): while on, vis_stop_scan follows every pick and the engines poll its records
         # instead of the token rows; stop_eos: whether an EOS id ends a row too (off in a run that ignores EOS)
         self.stop_on, self.stop_eos = False, True
@@ -56,11 +62,11 @@ class PickStage:
     # ------------------------------------------------------------------ one request's switches
     @contextlib.contextmanager
     def _pick_request(self, logprobs, json_mode, json_schema, top_p, seeded: bool, penalties: Optional[Sequence[tuple]],
-                      stop=None):
+                      stop=None, *, shaping: Optional[Sequence[tuple]] = None):
         """The switches of one request (or one batch of them) on for the body, and all off again afterwards - also when the
         body, or switching on itself (no tokenizer, a schema the device tables cannot hold), raises.  ``penalties``:
         check_penalties' result; a single request runs in slot 0 and its triple is placed there.  ``stop``: None, a string or
-        1..4 of them (check_stop), one set for the whole group."""
+        1..4 of them (check_stop), one set for the whole group.  ``shaping``: check_shaping's result, placed like the penalties."""
         check_k(logprobs)
         check_schema(json_mode, json_schema)
         if not isinstance(json_mode, bool):
@@ -76,6 +82,9 @@ class PickStage:
             if penalties is not None and len(penalties) == 1:
                 self._slot_pen[0] = penalties[0]
             self._begin_stop(stop)
+            self._begin_shaping(shaping)
+            if shaping is not None and len(shaping) == 1:
+                self._slot_shape[0] = shaping[0]
             yield
         finally:
             self.lp_k = None
@@ -84,6 +93,7 @@ class PickStage:
             self._end_sampling()
             self._end_penalties()
             self.stop_on, self.stop_eos = False, True
+            self._end_shaping()
 
     def _pick_key(self) -> tuple:
         """The switches' part of a decode-graph key.  The logprobs k, the masks and top_p are kernel arguments or launches
@@ -95,6 +105,11 @@ class PickStage:
         """The stop scan's part of a decode-graph key, appended by the engines next to _pick_key(): whether the launch is in
         the step and its one switch that is a kernel argument.  The stop strings themselves are read from device tables."""
         return (self.stop_on, self.stop_eos)
+
+    def _shape_key(self) -> tuple:
+        """The shaping launch's part of a decode-graph key, appended by the engines next to _stop_key(): whether the launch
+        is in the step.  k, delta and the bias lists are read from device memory at replay."""
+        return (self.shape_on,)
 
     # ------------------------------------------------------------------ token log-probabilities
     def _begin_logprobs(self, logprobs: Optional[int]) -> None:
@@ -190,6 +205,27 @@ class PickStage:
         if self.pen_on:
             self._pen.begin(slot, ids_dev, *self._slot_pen.get(slot, NEUTRAL))
 
+    # ------------------------------------------------------------------ logit shaping (top_k, min_p, logit_bias)
+    def _begin_shaping(self, shaping: Optional[Sequence[tuple]]) -> None:
+        """Route every pick of the request about to run through vis_shape_f32 when some request of it asks for top_k, min_p
+        or a logit_bias (shaping: check_shaping's result - one (top_k, min_p, bias list) per request, or None = off)."""
+        if shaping is not None:
+            check_vocab(shaping, self.cfg.vocab)
+        self.shape_on = shaping is not None
+        self._slot_shape = {}
+        if self.shape_on and self._shp is None:
+            self._shp = ShapeBuffers(self.max_batch, self.cfg.vocab, self.device)
+
+    def _end_shaping(self) -> None:
+        self.shape_on = False
+        self._slot_shape = {}
+
+    def _shape_slot(self, slot: int) -> None:
+        """Before a prompt pass's pick: the request's k, its min_p threshold at the temperature it runs at and its bias list
+        in the parameter rows of ``slot``."""
+        if self.shape_on:
+            self._shp.begin(slot, *self._slot_shape.get(slot, SHAPE_NEUTRAL), self.temperature)
+
     # ------------------------------------------------------------------ stop strings / how a reply ended
     def _begin_stop(self, stop: Optional[tuple]) -> None:
         """Switch vis_stop_scan on (with the automaton of ``stop``, check_stop's result, on the device) or off for the request
@@ -250,23 +286,25 @@ class PickStage:
     def _pick(self, logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed, slot: int = 0) -> None:
         """The next-token pick of slots slot .. slot + B - 1: vis_argmax_f32, or in JSON mode vis_json_mask + the masked pick;
         vis_sample_f32 (seeds from the device buffer, the JSON rows as its mask) while nucleus sampling / seeds are on.  While
-        penalties are on, all of them read the penalised copy of the rows (vis_penalize_f32); the raw rows stay intact."""
+        penalties are on, all of them read the penalised copy of the rows (vis_penalize_f32); the raw rows stay intact.  While
+        top_k / min_p / logit_bias are on, vis_shape_f32 runs after the penalties and the mask launch, takes the mask's rows,
+        and the pick reads its copy."""
         if self.pen_on:
             logits = self._pen.apply(logits, tokens, step, slot)
+        allow = self._mask.mask(tokens, step, slot) if self._mask is not None else None
+        if self.shape_on:
+            logits = self._shp.apply(logits, slot, allow)
         if self.smp_on:
-            allow = self._mask.mask(tokens, step, slot) if self._mask is not None else None
             self._smp.pick(logits, tokens, cur_token, step, temperature, self.top_p, slot, allow)
-            return
-        if self._mask is None:
+        elif allow is None:
             hip.argmax(logits, ws_val, ws_idx, tokens, cur_token, step, temperature, seed)
-            return
-        allow = self._mask.mask(tokens, step, slot)
-        hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
+        else:
+            hip.argmax_masked(logits, ws_val, ws_idx, tokens, cur_token, step, allow, temperature, seed)
 
     def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
-        """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode; while nucleus sampling / seeds
-        or penalties are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
-        if self.smp_on or self.pen_on:
+        """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode; while nucleus sampling / seeds,
+        penalties or logit shaping are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
+        if self.smp_on or self.pen_on or self.shape_on:
             hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
             self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
             return
@@ -277,12 +315,13 @@ class PickStage:
         hip.gemv_argmax_masked(x, w, logits, ws_val, ws_idx, tokens, cur_token, step, allow[0], **kw)
 
     def _prompt_pick(self, slot: int, ids_dev: torch.Tensor, logits, tokens, cur_token, step) -> None:
-        """The first token of ``slot``, from the logits of its prompt's last row: a fresh grammar state, row seed and token
-        statistics, then the pick and its logprobs."""
+        """The first token of ``slot``, from the logits of its prompt's last row: a fresh grammar state, row seed, token
+        statistics and shaping parameters, then the pick and its logprobs."""
         if self._mask is not None:
             self._mask.reset(slot)
         self._seed_slot(slot)
         self._penalty_slot(slot, ids_dev)
+        self._shape_slot(slot)
         ws = slice(256 * slot, 256 * (slot + 1))    # per-slot workspace: prefills of different slots may run concurrently
         # on different streams
         self._pick(logits, self.ws_val[ws], self.ws_idx[ws], tokens, cur_token, step, self.temperature,
