@@ -1,0 +1,426 @@
+"""The decode stage of both engines: one token for the single sequence or for B in-flight sequences, the graph that replays
+it, and the ordered chained decode of a device.  Which launches make a step, and in which form every projection is issued,
+is decided here and nowhere else; both engines derive from ``DecodeStage`` and describe their layers to it once."""
+from __future__ import annotations
+
+import logging
+import os
+import threading
+from typing import Dict, List, NamedTuple, Optional, Sequence
+
+import torch
+
+from . import hip
+from .pick import PickStage
+
+_LOG = logging.getLogger("vision_inspection_system_amd.engine")
+
+# the last chained decode call enqueued per device (DecodeStage._decode_ordered orders such calls on the GPU); one lock per
+# device: engines on different GPUs driven from different threads do not serialise their host launch loops
+_CHAIN_LOCKS_GUARD = threading.Lock()
+_CHAIN_ORDER_LOCKS: Dict[Optional[int], threading.Lock] = {}
+_CHAIN_LAST: Dict[Optional[int], "torch.cuda.Event"] = {}
+
+
+def _chain_order_lock(index: Optional[int]) -> threading.Lock:
+    with _CHAIN_LOCKS_GUARD:
+        return _CHAIN_ORDER_LOCKS.setdefault(index, threading.Lock())
+
+
+class DecodeLayer(NamedTuple):
+    """One transformer layer as the decode stage sees it."""
+    w: object                        # qkv_w, o_w, gateup_w, down_w, ln1_w, ln2_w (a cross-attention layer: q_norm too)
+    q8: Optional[dict]               # name -> (e4m3 codes, row scales), "down_w_pad" where K was padded; None: not quantised
+    q4: Optional[dict]               # name -> (MXFP4 codes, block scales); None: not quantised
+    cross: bool                      # cross-attention over the image's static keys instead of self-attention
+    idx: int                         # the layer's index into the self KV cache, or into the cross KV cache
+    bias: Optional[torch.Tensor]     # qkv bias
+
+
+_GEMV = {"bf16": "gemv", "fp8": "gemv_fp8", "mxfp4": "gemv_mxfp4"}      # hip's fused GEMV per weight format; + "_rows": 2..4 rows
+
+
+def _wt(L: DecodeLayer, name: str, fmt: str) -> tuple:
+    """The weight operands of one projection in one format: (w,), (codes, row scales) or (codes, block scales)."""
+    return (getattr(L.w, name),) if fmt == "bf16" else (L.q8 if fmt == "fp8" else L.q4)[name]
+
+
+class DecodeStage(PickStage):
+    """Base class of the engines: works on ``self``, holds no model knowledge.
+
+    Contract - what it reads of the engine, all present before ``_init_decode_stage()`` runs: ``cfg``, ``w.embed``, ``device``,
+    ``max_ctx``; the activation buffers ``d_*`` (single sequence) and ``b_*`` (batched: rows, stream-K partials, and what the
+    fused and fp8 steps add); the caches ``kcache_b`` / ``vcache_b`` [slots, self layers, ...], the rope tables ``cos_t`` /
+    ``sin_t``, the attention workspace ``part_o`` / ``part_ml``, the counters ``step_b`` / ``cur_b`` and the pick stage's rows -
+    each with its slot-0 view (``kcache``, ``step``, ``cur_token``, ``tokens``, ``logits``); ``prompt_len`` and ``_decoded``;
+    ``nsplit`` and the flags ``fused_proj``, ``fold_qkv``, ``fp8_batched``, ``decode_weights``, ``mxfp4_gemm_from`` (read at
+    every step: tests and tools set them after construction); the chain state ``chain_ws``, ``chain_sync``,
+    ``chain_ctx_limit``, ``_chain_launches``; ``has_image`` where a layer is a cross-attention layer.
+    What the models do differently is behind two hooks: ``_decode_rope(B)`` -> (cos, sin, shared_len), the rope tables
+    [B, T, D] of the batched self-attention and the number of leading keys every sequence reads from slot 0, and
+    ``_decode_cross_attn(L, q, att, B)``, the cross-attention launch of layer L for the single sequence (B == 0) or B slots.
+    An engine supplies ``_ensure_graph(chained=)`` with its own graph key (see ``_captured_step``) and checks its own bounds
+    in ``decode()`` before ``_decode_ordered``."""
+
+    def _init_decode_stage(self, layers: Sequence[DecodeLayer], norm_w: torch.Tensor, lm_head: torch.Tensor,
+                           q8_head: Optional[tuple] = None, q4_head: Optional[tuple] = None) -> None:
+        """The model, described once: its layers in order, the final norm, the lm_head in its formats."""
+        self.dec_layers: List[DecodeLayer] = list(layers)
+        self.dec_norm_w = norm_w
+        self.dec_head = {"bf16": (lm_head,), "fp8": q8_head, "mxfp4": q4_head}
+        self.dec_n_self = sum(1 for L in self.dec_layers if not L.cross)     # chained launches per step
+        self._init_pick_stage()      # the request switches of the next-token pick (pick.py)
+
+    # ------------------------------------------------------------------ steps whose projections write their finished rows
+    def _decode_step(self, chained: Optional[bool] = None) -> None:
+        """One token of the single sequence (slot 0): chained layer heads where asked for (default: where the engine has
+        them), the fused GEMVs otherwise."""
+        if chained is None:
+            chained = self.chain_sync is not None
+        self._decode_step_rows(0, chained and self.chain_sync is not None)
+
+    def _decode_step_rows(self, B: int, chained: bool = False) -> None:
+        """The step whose projections are fused GEMVs (norm / bias / residual / SwiGLU in the launch, no partial buffers, no
+        finalisation launches).  B == 0: the single sequence; ``chained``: the head of every self-attention layer (qkv
+        projection -> rope / append / attention -> o projection) as ONE launch (csrc/decode_chain.hip, bit-identical to the
+        four it replaces), the first one reading the new token's embedding row itself, and the pick's first stage in the
+        lm_head epilogue; a cross-attention layer is skipped while the request has no image.
+        B >= 2, a couple of in-flight sequences: the multi-row GEMV (vis_gemv_*_rows) - one pass over the weights for all
+        rows (the stream-K projection pays four finalisations per layer); bf16 or e4m3 weights with bf16 activations, every
+        sequence bit-identical to decoding alone.  Chosen by _decode_step_batched (VIS_ROWS_GEMV).  MXFP4 weights take this
+        step at EVERY batch size: more than 4 sequences issue each projection once per group of 4 rows (the weights are then
+        read ceil(B / 4) times per step: slower than the bf16 stream-K step above ~16 sequences); attention, pick and the
+        request switches stay one batched launch each."""
+        cfg, fmt = self.cfg, self.decode_weights
+        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
+        scale, eps = D ** -0.5, cfg.rms_eps
+        if B:
+            x, x2, qkv, att, act = self.b_x[:B], self.b_x2[:B], self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
+            cur, step, tokens, logits = self.cur_b[:B], self.step_b[:B], self.tokens_b[:B], self.logits_b[:B]
+            cos, sin, shared = self._decode_rope(B)
+        else:
+            x, x2, qkv, att, act = self.d_x[0], self.d_x2[0], self.d_qkv, self.d_attn, self.d_act
+            cur, step, tokens, logits = self.cur_token, self.step, self.tokens, self.logits
+            cos, sin, shared = self.cos_t, self.sin_t, 0
+        gemv, gemv_rows = getattr(hip, _GEMV[fmt]), getattr(hip, _GEMV[fmt] + "_rows")
+
+        def proj(inp, wt, out, residual=None, **kw):
+            if not B:
+                gemv(inp, *wt, out, residual=residual, **kw)
+            elif fmt == "mxfp4":
+                for b0 in range(0, B, 4):
+                    rows = slice(b0, min(b0 + 4, B))
+                    gemv_rows(inp[rows], *wt, out[rows], residual=None if residual is None else residual[rows], **kw)
+            else:
+                gemv_rows(inp, *wt, out, residual=residual, **kw)
+
+        if not (chained and not self.dec_layers[0].cross):     # else the first layer's launch reads the embedding row itself
+            hip.gather_rows(self.w.embed, cur, self.d_x if not B else x)
+        for li, L in enumerate(self.dec_layers):
+            lw = L.w
+            if L.cross:
+                if not B and not self.has_image:
+                    continue
+                q = qkv[..., :Hq * D]
+                proj(x, _wt(L, "qkv_w", fmt), q, norm_w=lw.ln1_w, eps=eps)
+                self._decode_cross_attn(L, q, att, B)
+                proj(att, _wt(L, "o_w", fmt), x2, residual=x)
+            else:
+                kc, vc = (self.kcache_b[:B, L.idx], self.vcache_b[:B, L.idx]) if B else (self.kcache[L.idx], self.vcache[L.idx])
+                if chained:
+                    try:   # layer 0 reads the new token's embedding row itself (x_index): no gather launch
+                        hip.decode_chain(self.w.embed if li == 0 else x, lw.qkv_w, L.bias, lw.ln1_w, lw.o_w, x2, cos, sin, kc, vc,
+                                         step, self.chain_ws, self.chain_sync, Hq, Hkv, D, self.nsplit, scale, eps,
+                                         x_index=cur if li == 0 else None, ctx_bound=self.chain_ctx_limit)
+                    except hip.ChainRefused as e:
+                        # VIS_ERR_UNSUPPORTED and nothing else (a bad argument or a launch error propagates): the grid for
+                        # this context length is larger than the device holds resident -> the four launches, same results;
+                        # said once.  An engine that keeps the chain only with a positive decode_chain_ctx_limit and passes
+                        # that bound (MllamaEngine) never gets here.
+                        if li:
+                            raise
+                        _LOG.warning("%s - decoding on the four launches per layer head (VIS_MAX_CTX=%d)", e, self.max_ctx)
+                        self.chain_sync, self._chain_state, chained = None, None, False
+                        hip.gather_rows(self.w.embed, cur, self.d_x)
+                if not chained:
+                    proj(x, _wt(L, "qkv_w", fmt), qkv, bias=L.bias, norm_w=lw.ln1_w, eps=eps)
+                    hip.decode_attn(qkv, cos, sin, kc, vc, step, self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
+                                    shared_len=shared)
+                    proj(att, _wt(L, "o_w", fmt), x2, residual=x)
+            proj(x2, _wt(L, "gateup_w", fmt), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
+            proj(act, _wt(L, "down_w", fmt), x, residual=x2)
+        if chained:     # the pick's first stage rides in the lm_head epilogue
+            self._gemv_pick(x, *self.dec_head["bf16"], logits, self.ws_val, self.ws_idx, tokens, cur, step,
+                            norm_w=self.dec_norm_w, eps=eps, temperature=self.temperature, seed=self.seed)
+        else:
+            proj(x, self.dec_head[fmt], logits, norm_w=self.dec_norm_w, eps=eps)
+            self._pick(logits, self.ws_val, self.ws_idx, tokens, cur, step, self.temperature, self.seed)
+        self._logprobs_after_pick(B or 1)
+        self._stop_after_pick(B or 1)
+
+    # ---- batched decode: B in-flight sequences (slots 0..B-1) share every weight read of a step
+    def _decode_step_batched(self, B: int) -> None:
+        """Every projection = gemm_decode (weights streamed once for all B sequences, split-K f32 partials) +
+        skinny_finalize (row-wise: sum, bias/residual/SwiGLU, and the RMSNorm of the NEXT projection); self-attention and
+        cross-attention take the sequence index on the grid."""
+        # VIS_ROWS_GEMV=<n> (default 0 = off): batches of 2..n (<= 4) sequences decode on the multi-row GEMV instead.  Measured
+        # at exact 7B shapes (tools/probes/rows_ab.sh): 2 sequences 3.66 -> 3.20 ms per step (bf16), 2.83 -> 2.65 (e4m3
+        # weights); at 3 and 4 the four-row kernel LOSES to the stream-K projection (4.2-4.3 vs 3.7-3.8 ms; fp8 3.8-4.0 vs
+        # 2.9: four LDS reads + four dot products per weight chunk, one workgroup per CU on the down projection).  Off by
+        # default because it trades an invariant for those 6-13 %: a sequence decoded in a batch of 2 would then follow the
+        # single-sequence arithmetic and in a batch of 3+ the stream-K arithmetic - its tokens could depend on the batch size
+        # at near-ties (tests/test_fullsize_gpu.py::test_7b_batch_invariance_and_reproducibility).  A model with
+        # cross-attention layers has no multi-row step.
+        if self.decode_weights == "mxfp4":
+            # the multi-row GEMV at every batch size, unless mxfp4_gemm_from hands the larger ones to the MFMA projection
+            # (the other arithmetic family, see Qwen2VLEngine.__init__)
+            if self.mxfp4_gemm_from is None or B < self.mxfp4_gemm_from:
+                return self._decode_step_rows(B)
+            return self._decode_step_streamk(B)
+        rows_max = int(os.environ.get("VIS_ROWS_GEMV", "0")) if self.dec_n_self == len(self.dec_layers) else 0
+        if 2 <= B <= min(rows_max, 4) and max(self.cfg.intermediate, self.cfg.hidden) * 2 * (2 if B <= 2 else 4) <= 152 * 1024:
+            return self._decode_step_rows(B)
+        if self.fused_proj:
+            self._decode_step_fused(B)
+        else:
+            self._decode_step_streamk(B)
+
+    def _decode_step_streamk(self, B: int) -> None:
+        """The stream-K batched step.  The first half of a projection writes partial slabs: hip.decode_gemm on the bf16
+        weights, hip.decode_gemm_mxfp4 on the FP4 codes (decode_weights="mxfp4" from mxfp4_gemm_from sequences on), or
+        hip.decode_gemm_fp8 on e4m3 weights AND activations (BASELINE configs[4]); the finalisation owns the row.  In the fp8
+        form every finalisation also emits the next projection's input as e4m3 + row scale (so the activation quantiser
+        costs no extra launch), and the o projection stays bf16: its input comes from the attention combine, which does not
+        own whole rows."""
+        cfg, fmt = self.cfg, self.decode_weights
+        if fmt == "fp8" and not self.fp8_batched:
+            fmt = "bf16"
+        fp8 = fmt == "fp8"
+        Hq, Hkv, D, H = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden
+        scale, eps = D ** -0.5, cfg.rms_eps
+        x, x2, qkv, att, act = self.b_x[:B], self.b_x2[:B], self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
+        xn, xn2, part = self.b_xn[:B], self.b_xn2[:B], self.b_part
+        step, nq = self.step_b[:B], qkv.shape[1]
+        cos, sin, shared = self._decode_rope(B)
+        # a_*: the A operand(s) of a projection; to_*: where the finalisation that produces that operand writes it
+        if fp8:
+            xq, x2q, aq = self.b_xq[:B], self.b_x2q[:B], self.b_actq[:B]
+            sxq, sx2q, saq = self.b_sx[0, :B], self.b_sx[1, :B], self.b_sx[2, :B]
+            a_x, a_x2, a_act = (xq, sxq), (x2q, sx2q), (aq, saq)
+            to_x, to_x2, to_act = dict(yn=xn, yq=xq, yq_scale=sxq), dict(yn=xn2, yq=x2q, yq_scale=sx2q), dict(yq=aq, yq_scale=saq)
+            gemm, finalize = hip.decode_gemm_fp8, hip.skinny_finalize_fp8
+        else:
+            a_x, a_x2, a_act = (xn,), (xn2,), (act,)
+            to_x, to_x2, to_act = dict(yn=xn), dict(yn=xn2), {}
+            gemm, finalize = hip.decode_gemm_mxfp4 if fmt == "mxfp4" else hip.decode_gemm, hip.skinny_finalize
+        gemm_o, fmt_o = (gemm, fmt) if not fp8 else (hip.decode_gemm, "bf16")
+
+        def scales(a, wt):     # the fp8 finalisation multiplies the row and column scales back in
+            return dict(sx=a[1], sw=wt[1]) if fp8 else {}
+
+        hip.gather_rows(self.w.embed, self.cur_b[:B], x)
+        if fp8:
+            hip.quant_rows_fp8(x, xq, sxq, norm_w=self.dec_layers[0].w.ln1_w, eps=eps)
+        else:
+            hip.rmsnorm(x, self.dec_layers[0].w.ln1_w, eps, out=xn)
+        for li, L in enumerate(self.dec_layers):
+            lw = L.w
+            wt = _wt(L, "qkv_w", fmt)
+            ks = gemm(*a_x, *wt, part=part)
+            if L.cross:
+                q = qkv[:, :Hq * D]
+                finalize(part, ks, q, Hq * D, eps=eps, **scales(a_x, wt))
+                self._decode_cross_attn(L, q, att, B)
+            elif self.fold_qkv:    # the attention workgroups finalise the qkv columns they read (same bits, one launch less)
+                hip.decode_attn_parts(part, ks, cos, sin, self.kcache_b[:B, L.idx], self.vcache_b[:B, L.idx], step, self.part_o,
+                                      self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, bias=L.bias, shared_len=shared,
+                                      **scales(a_x, wt))
+            else:
+                finalize(part, ks, qkv, nq, bias=L.bias, eps=eps, **scales(a_x, wt))
+                hip.decode_attn(qkv, cos, sin, self.kcache_b[:B, L.idx], self.vcache_b[:B, L.idx], step, self.part_o,
+                                self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, shared_len=shared)
+            ks = gemm_o(att, *_wt(L, "o_w", fmt_o), part=part)
+            finalize(part, ks, x2, H, residual=x, norm_w=lw.ln2_w, eps=eps, **to_x2)
+            wt = _wt(L, "gateup_w", fmt)
+            ks = gemm(*a_x2, *wt, part=part)
+            finalize(part, ks, act, 2 * cfg.intermediate, swiglu=True, eps=eps, **scales(a_x2, wt), **to_act)
+            wt = L.q8.get("down_w_pad", L.q8["down_w"]) if fp8 else _wt(L, "down_w", fmt)
+            ks = gemm(*a_act, *wt, part=part)
+            next_norm = self.dec_layers[li + 1].w.ln1_w if li + 1 < len(self.dec_layers) else self.dec_norm_w
+            finalize(part, ks, x, H, residual=x2, norm_w=next_norm, eps=eps, **scales(a_act, wt), **to_x)
+        gemm(*a_x, *self.dec_head[fmt], out=self.logits_b[:B])
+        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], step, self.temperature,
+                   self.seed)
+        self._logprobs_after_pick(B)
+        self._stop_after_pick(B)
+
+    def _decode_step_fused(self, B: int, projections_only: bool = False) -> int:
+        """One decode step for B in-flight sequences, every projection ONE launch (r05, csrc/decode_stream.hip): the stream-K
+        weight pass, the fixed-order sum of a cut tile's segments by the last workgroup to arrive, and the epilogue - bias (qkv),
+        SwiGLU (gate/up), residual + the NEXT norm's weight + the tile's sum of squares (o, down); the consumer of a normed row
+        applies rs[b] = rsqrt(mean(x^2) + eps) to its finished sums (the RMSNorm, TF modeling_qwen2_vl.py:96-110, split into a
+        per-column and a per-row factor).  5 launches per layer (r04: 9).  fp8 (configs[4]): activations travel as MX blocks
+        written by the producing epilogue.  The tanh gates of Mllama's cross-attention layers are folded into o_w / down_w at
+        load time, so both layer kinds share the sequence.  ``projections_only``: bench.py's replay of the weight-streaming
+        launches alone.  Returns the number of projection launches.  Opt-in (VIS_DECODE_FUSED=1): Qwen2VLEngine.__init__ has
+        the measurements that keep it off by default."""
+        cfg = self.cfg
+        Hq, Hkv, D, H = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden
+        scale, eps = D ** -0.5, cfg.rms_eps
+        x, x2, qkv, att, act = self.b_x[:B], self.b_x2[:B], self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
+        xw, x2w, s1, s2, ws = self.b_xw[:B], self.b_x2w[:B], self.b_ssq1, self.b_ssq2, self.b_proj_ws
+        fp8 = self.decode_weights == "fp8" and self.fp8_batched
+        if fp8:
+            xq, xqs, x2q, x2qs = self.b_xq[:B], self.b_xqs[:B], self.b_x2q[:B], self.b_x2qs[:B]
+            aq, aqs = self.b_actq[:B], self.b_actqs[:B]
+        # Long-K, few-column projections at many sequences (7B down at 33+ sequences: K = 18944, 28 column tiles) keep the
+        # r02-r04 pair - stream-K slabs + the row-owning finalisation, which then also applies the next RMSNorm itself (xw holds
+        # the NORMALISED row, its consumer takes no row factor): a column slab per workgroup would stream 2.4 MB of x each, and
+        # the in-kernel reduction of the stream-K form costs more than the finalisation launch it saves (64 vs 33 + 5 us,
+        # profiles/r05_decode_step_b64_streamk.txt).  VIS_DOWN_PAIR=0 forces the single launch (A/B).
+        down_pair = (not fp8) and hasattr(self, "b_part") and os.environ.get("VIS_DOWN_PAIR", "1") != "0" and \
+            hip.decode_proj_form(B, H, cfg.intermediate, hip.DP_RESID_NORMW, False, False) == "streamk"
+        s1_in = None if down_pair else s1
+        layers = self.dec_layers
+        if not projections_only:
+            cos, sin, shared = self._decode_rope(B)
+            if down_pair:
+                hip.gather_rows(self.w.embed, self.cur_b[:B], x)
+                hip.rmsnorm(x, layers[0].w.ln1_w, eps, out=xw)
+            else:
+                hip.decode_prep_rows(self.w.embed, self.cur_b[:B], layers[0].w.ln1_w, x, None if fp8 else xw, s1,
+                                     xq if fp8 else None, xqs if fp8 else None)
+        for li, L in enumerate(layers):
+            lw = L.w
+            next_norm = layers[li + 1].w.ln1_w if li + 1 < len(layers) else self.dec_norm_w
+            q = qkv[:, :Hq * D] if L.cross else qkv
+            if fp8:
+                hip.decode_proj_fp8(xq, xqs, *L.q8["qkv_w"], ws, hip.DP_PLAIN, out=q, bias=L.bias, ssq_in=s1, norm_dim=H, eps=eps)
+            else:
+                hip.decode_proj(xw, lw.qkv_w, ws, hip.DP_PLAIN, out=q, bias=L.bias, ssq_in=s1_in, norm_dim=H, eps=eps)
+            if projections_only:
+                pass
+            elif L.cross:
+                self._decode_cross_attn(L, q, att, B)
+            else:
+                hip.decode_attn(qkv, cos, sin, self.kcache_b[:B, L.idx], self.vcache_b[:B, L.idx], self.step_b[:B], self.part_o,
+                                self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, shared_len=shared)
+            if fp8:     # the o projection keeps bf16 weights (its input comes from the attention kernel); its epilogue writes MX
+                hip.decode_proj(att, lw.o_w, ws, hip.DP_RESID_NORMW, out=x2, out_q=x2q, out_qs=x2qs, residual=x,
+                                norm_w=lw.ln2_w, ssq_out=s2)
+                hip.decode_proj_fp8(x2q, x2qs, *L.q8["gateup_w"], ws, hip.DP_SWIGLU, out_q=aq, out_qs=aqs, ssq_in=s2,
+                                    norm_dim=H, eps=eps)
+                hip.decode_proj_fp8(aq, aqs, *L.q8.get("down_w_pad", L.q8["down_w"]), ws, hip.DP_RESID_NORMW, out=x, out_q=xq,
+                                    out_qs=xqs, residual=x2, norm_w=next_norm, ssq_out=s1)
+                continue
+            hip.decode_proj(att, lw.o_w, ws, hip.DP_RESID_NORMW, out=x2, out_w=x2w, residual=x, norm_w=lw.ln2_w, ssq_out=s2)
+            hip.decode_proj(x2w, lw.gateup_w, ws, hip.DP_SWIGLU, out=act, ssq_in=s2, norm_dim=H, eps=eps)
+            if down_pair:
+                ks = hip.decode_gemm(act, lw.down_w, part=self.b_part)
+                if not projections_only:
+                    hip.skinny_finalize(self.b_part, ks, x, H, residual=x2, norm_w=next_norm, yn=xw, eps=eps)
+            else:
+                hip.decode_proj(act, lw.down_w, ws, hip.DP_RESID_NORMW, out=x, out_w=xw, residual=x2, norm_w=next_norm,
+                                ssq_out=s1)
+        if fp8:
+            hip.decode_proj_fp8(xq, xqs, *self.dec_head["fp8"], ws, hip.DP_PLAIN, out=self.logits_b[:B], ssq_in=s1, norm_dim=H,
+                                eps=eps)
+        else:
+            hip.decode_proj(xw, *self.dec_head["bf16"], ws, hip.DP_PLAIN, out=self.logits_b[:B], ssq_in=s1_in, norm_dim=H, eps=eps)
+        if not projections_only:
+            self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
+                       self.temperature, self.seed)
+            self._logprobs_after_pick(B)
+            self._stop_after_pick(B)
+        return 4 * len(layers) + 1
+
+    # ------------------------------------------------------------------ graphs
+    def _captured_step(self, cache: dict, capacity: int, key: tuple, B: int, chained: bool) -> torch.cuda.CUDAGraph:
+        """The graph of one step - batched for B sequences, or (B == 0) the single-sequence step - under ``key`` in ``cache``,
+        a FIFO of ``capacity`` graphs; captured on first use.  Whatever a step's launches take as plain arguments
+        (temperature, seed, the batch size, what the pick's keys name) belongs in ``key``."""
+        if key in cache:
+            return cache[key]
+        step_fn = (lambda: self._decode_step_batched(B)) if B else (lambda: self._decode_step(chained))
+        # warm the kernels outside capture, then restore the counters the warm-up advanced
+        saved = (self.step_b.clone(), self.cur_b.clone())
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            step_fn()
+        torch.cuda.current_stream().wait_stream(side)
+        self.step_b.copy_(saved[0])
+        self.cur_b.copy_(saved[1])
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):     # another agent's thread may be allocating
+            step_fn()
+        # capture does not execute; state is unchanged
+        if len(cache) >= capacity:
+            cache.pop(next(iter(cache)))
+        cache[key] = g
+        return g
+
+    def _decode_steps(self, n_steps: int, use_graph: bool, chained: bool = False) -> None:
+        if use_graph:
+            g = self._ensure_graph(chained=chained)
+            if chained and self.chain_sync is None:      # the warm-up met a refusal: the captured step is the unchained one
+                g = self._ensure_graph(chained=False)
+            for _ in range(n_steps):
+                g.replay()
+        else:
+            for _ in range(n_steps):
+                self._decode_step(chained)
+
+    # ------------------------------------------------------------------ the chained decode of a device, in order
+    def _decode_ordered(self, n_steps: int, use_graph: bool) -> None:
+        """n_steps further tokens of the single sequence (the engine's decode() has checked its bounds): on the chained
+        launches while the context stays within ``chain_ctx_limit`` cached keys, on the four launches per layer head from
+        there on (same bits)."""
+        base = self.prompt_len + self._decoded       # step k of this call sees base + k cached keys
+        self._decoded += n_steps
+        n_chain = max(0, min(n_steps, self.chain_ctx_limit - base)) if self.chain_sync is not None else 0
+        if n_chain:
+            # Chained launches wait inside the grid for workgroups of the SAME launch, which only works while that launch can
+            # have its whole grid resident (860 of the device's 1024 slots at 7B shapes).  Two engines decoding on two streams
+            # at once could strand each other (each holding slots the other's producers need; the bounded waits would then
+            # raise).  So the chained decode calls of a device are ordered on the GPU: a call waits for the previous call's
+            # last launch (an event, no host blocking), whatever engine, stream or thread they come from.  Decode is
+            # HBM-bound: nothing is lost.
+            self._chain_epoch_guard(n_chain)
+            with _chain_order_lock(self.device.index):
+                cur = torch.cuda.current_stream(self.device)
+                prev = _CHAIN_LAST.get(self.device.index)
+                if prev is not None:
+                    cur.wait_event(prev)
+                self._decode_steps(n_chain, use_graph, True)
+                ev = torch.cuda.Event()
+                ev.record(cur)
+                _CHAIN_LAST[self.device.index] = ev
+        if n_steps > n_chain:       # no chain, or the context has outgrown the chained grid
+            self._decode_steps(n_steps - n_chain, use_graph, False)
+
+    def _chain_epoch_guard(self, n_steps: int) -> None:
+        """The granule tag of a chained launch is the sync block's 32-bit launch counter + 1.  Long before it can wrap
+        (2^31 launches = ~2.6 days of continuous single-sequence decode) workspace and sync block are zeroed on the stream,
+        between two decode calls - no launch of this engine is in flight then (same stream), and the kernel itself skips
+        tag 0, the mark of a never-written granule (tests/test_kernels_gpu.py::test_decode_chain_epoch_wrap)."""
+        self._chain_launches += n_steps * self.dec_n_self
+        if self._chain_launches >= (1 << 31):
+            self.chain_sync.zero_()
+            self.chain_ws.zero_()
+            self._chain_launches = n_steps * self.dec_n_self
+
+    def generated(self, n: int) -> List[int]:
+        s = self.prompt_len - 1          # the token generated at step i is stored at index (its position - 1)
+        toks = self.tokens[s:s + n].cpu().tolist()
+        self.check_chain()
+        return toks
+
+    def check_chain(self) -> None:
+        """Raise if a bounded wait inside a chained layer-head launch gave up (its results are invalid); the sync block is
+        zeroed so that the engine stays usable.  Called after the token D2H, i.e. when the stream has drained."""
+        if self.chain_sync is not None and int(self.chain_sync[hip.CHAIN_STATUS_WORD].item()) != 0:
+            self.chain_sync.zero_()
+            self.chain_ws.zero_()
+            self._chain_launches = 0
+            raise hip.ChainStalled("vis_decode_chain: a hand-off wait inside the launch timed out (decode results invalid)")

@@ -26,10 +26,10 @@ import numpy as np
 import torch
 
 from . import hip
+from .decode_stage import DecodeLayer, DecodeStage
 from .json_mode import JsonModeError, check_schema
 from .logprobs import check_k
 from .penalties import check_penalties
-from .pick import PickStage
 from .sampling import check_seeds, check_top_p
 from .shaping import check_shaping, shaping_kwargs
 from .stop import check_stop
@@ -137,21 +137,11 @@ def mrope_cos_sin(cfg: Qwen2VLConfig, pos3: np.ndarray) -> Tuple[np.ndarray, np.
     return np.cos(emb).astype(np.float32), np.sin(emb).astype(np.float32)
 
 
-# the last chained decode call enqueued per device (Qwen2VLEngine.decode orders such calls on the GPU); one lock per device:
-# engines on different GPUs driven from different threads do not serialise their host launch loops
-_CHAIN_LOCKS_GUARD = threading.Lock()
-_CHAIN_ORDER_LOCKS: Dict[Optional[int], threading.Lock] = {}
-_CHAIN_LAST: Dict[Optional[int], "torch.cuda.Event"] = {}
 _LOG = logging.getLogger("vision_inspection_system_amd.engine")
 
 
-def _chain_order_lock(index: Optional[int]) -> threading.Lock:
-    with _CHAIN_LOCKS_GUARD:
-        return _CHAIN_ORDER_LOCKS.setdefault(index, threading.Lock())
-
-
 # ----------------------------------------------------------------------------- engine
-class Qwen2VLEngine(PickStage):
+class Qwen2VLEngine(DecodeStage):
     """One model replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
     @staticmethod
@@ -371,7 +361,10 @@ class Qwen2VLEngine(PickStage):
         self.decode_limit = 0
         self.last_first_logits: Optional[torch.Tensor] = None
         self.tokenizer = None
-        self._init_pick_stage()      # the request switches of the next-token pick (pick.py)
+        # what the decode stage needs to know of the model (decode_stage.py); it also sets up the pick stage (pick.py)
+        self._init_decode_stage([DecodeLayer(lw, self.q8[i] if self.q8 else None, self.q4[i] if self.q4 else None, False, i, lw.qkv_b)
+                                 for i, lw in enumerate(weights.llm)], weights.final_norm_w, weights.lm_head,
+                                getattr(self, "q8_lm_head", None), getattr(self, "q4_lm_head", None))
 
     # ------------------------------------------------------------------ vision tower
     def vision_forward(self, frames: Sequence[torch.Tensor], split_rows: bool = True) -> torch.Tensor:
@@ -1121,316 +1114,15 @@ class Qwen2VLEngine(PickStage):
         return P if P >= self.min_shared_prefix else 0
 
     # ------------------------------------------------------------------ decode
-    def _decode_step(self, chained: Optional[bool] = None) -> None:
-        cfg, w = self.cfg, self.w
-        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
-        scale = D ** -0.5
-        if chained is None:
-            chained = self.chain_sync is not None
-        chained = chained and self.chain_sync is not None
-        if not chained:
-            hip.gather_rows(w.embed, self.cur_token, self.d_x)
-        x, x2 = self.d_x, self.d_x2
-        if self.decode_weights in ("fp8", "mxfp4"):    # quantised weights: separate launches, no chained head
-            gemv_q, qw, q_head = (hip.gemv_fp8, self.q8, self.q8_lm_head) if self.decode_weights == "fp8" \
-                else (hip.gemv_mxfp4, self.q4, self.q4_lm_head)
-            for li, lw in enumerate(w.llm):
-                q = qw[li]
-                gemv_q(x[0], *q["qkv_w"], self.d_qkv, bias=lw.qkv_b, norm_w=lw.ln1_w, eps=cfg.rms_eps)
-                hip.decode_attn(self.d_qkv, self.cos_t, self.sin_t, self.kcache[li], self.vcache[li], self.step,
-                                self.part_o, self.part_ml, self.d_attn, Hq, Hkv, D, self.nsplit, scale)
-                gemv_q(self.d_attn, *q["o_w"], x2[0], residual=x[0])
-                gemv_q(x2[0], *q["gateup_w"], self.d_act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=cfg.rms_eps)
-                gemv_q(self.d_act, *q["down_w"], x[0], residual=x2[0])
-            gemv_q(x[0], *q_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
-            self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
-                       self.temperature, self.seed)
-            self._logprobs_after_pick(1)
-            self._stop_after_pick(1)
-            return
-        for li, lw in enumerate(w.llm):
-            if chained:
-                try:   # layer 0 reads the new token's embedding row itself (x_index): no gather launch
-                    hip.decode_chain(w.embed if li == 0 else x[0], lw.qkv_w, lw.qkv_b, lw.ln1_w, lw.o_w, x2[0], self.cos_t,
-                                     self.sin_t, self.kcache[li], self.vcache[li], self.step, self.chain_ws, self.chain_sync,
-                                     Hq, Hkv, D, self.nsplit, scale, cfg.rms_eps, x_index=self.cur_token if li == 0 else None,
-                                     ctx_bound=self.chain_ctx_limit)
-                except hip.ChainRefused as e:
-                    # VIS_ERR_UNSUPPORTED and nothing else (a bad argument or a launch error propagates): the grid for this
-                    # context length is larger than the device holds resident -> the four launches, same results; said once
-                    if li:
-                        raise
-                    _LOG.warning("%s - decoding on the four launches per layer head (VIS_MAX_CTX=%d)", e, self.max_ctx)
-                    self.chain_sync, self._chain_state, chained = None, None, False
-                    hip.gather_rows(w.embed, self.cur_token, self.d_x)
-            if not chained:
-                hip.gemv(x[0], lw.qkv_w, self.d_qkv, bias=lw.qkv_b, norm_w=lw.ln1_w, eps=cfg.rms_eps)
-                hip.decode_attn(self.d_qkv, self.cos_t, self.sin_t, self.kcache[li], self.vcache[li], self.step,
-                                self.part_o, self.part_ml, self.d_attn, Hq, Hkv, D, self.nsplit, scale)
-                hip.gemv(self.d_attn, lw.o_w, x2[0], residual=x[0])
-            hip.gemv(x2[0], lw.gateup_w, self.d_act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=cfg.rms_eps)
-            hip.gemv(self.d_act, lw.down_w, x[0], residual=x2[0])
-        if chained:     # the pick's first stage rides in the lm_head epilogue
-            self._gemv_pick(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
-                            norm_w=w.final_norm_w, eps=cfg.rms_eps, temperature=self.temperature, seed=self.seed)
-            self._logprobs_after_pick(1)
-            self._stop_after_pick(1)
-            return
-        hip.gemv(x[0], w.lm_head, self.logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
-        self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
-                   self.temperature, self.seed)
-        self._logprobs_after_pick(1)
-        self._stop_after_pick(1)
-
-    # ---- batched decode: B in-flight sequences (slots 0..B-1) share every weight read of a step
-    def _decode_step_batched(self, B: int) -> None:
-        """Every projection = gemm_decode (weights streamed once for all B sequences, split-K f32 partials) +
-        skinny_finalize (row-wise: sum, bias/residual/SwiGLU, and the RMSNorm of the NEXT projection)."""
-        # VIS_ROWS_GEMV=<n> (default 0 = off): batches of 2..n (<= 4) sequences decode on the multi-row GEMV instead.  Measured
-        # at exact 7B shapes (tools/probes/rows_ab.sh): 2 sequences 3.66 -> 3.20 ms per step (bf16), 2.83 -> 2.65 (e4m3
-        # weights); at 3 and 4 the four-row kernel LOSES to the stream-K projection (4.2-4.3 vs 3.7-3.8 ms; fp8 3.8-4.0 vs
-        # 2.9: four LDS reads + four dot products per weight chunk, one workgroup per CU on the down projection).  Off by
-        # default because it trades an invariant for those 6-13 %: a sequence decoded in a batch of 2 would then follow the
-        # single-sequence arithmetic and in a batch of 3+ the stream-K arithmetic - its tokens could depend on the batch size
-        # at near-ties (tests/test_fullsize_gpu.py::test_7b_batch_invariance_and_reproducibility).
-        if self.decode_weights == "mxfp4":
-            # the multi-row GEMV at every batch size, unless mxfp4_gemm_from hands the larger ones to the MFMA projection
-            # (the other arithmetic family, see __init__)
-            if self.mxfp4_gemm_from is None or B < self.mxfp4_gemm_from:
-                return self._decode_step_rows(B)
-            q4 = self.q4
-            return self._decode_step_streamk(B, lambda a, li, n, **kw: hip.decode_gemm_mxfp4(a, *q4[li][n], **kw),
-                                             lambda a, **kw: hip.decode_gemm_mxfp4(a, *self.q4_lm_head, **kw))
-        rows_max = int(os.environ.get("VIS_ROWS_GEMV", "0"))
-        if 2 <= B <= min(rows_max, 4) and max(self.cfg.intermediate, self.cfg.hidden) * 2 * (2 if B <= 2 else 4) <= 152 * 1024:
-            return self._decode_step_rows(B)
-        if self.fused_proj:
-            return self._decode_step_fused(B)
-        if self.decode_weights == "fp8" and self.fp8_batched:
-            return self._decode_step_batched_fp8(B)
-        llm = self.w.llm
-        self._decode_step_streamk(B, lambda a, li, n, **kw: hip.decode_gemm(a, getattr(llm[li], n), **kw),
-                                  lambda a, **kw: hip.decode_gemm(a, self.w.lm_head, **kw))
-
-    def _decode_step_streamk(self, B: int, gemm, gemm_head) -> None:
-        """The stream-K batched step: ``gemm(a, layer, name, part=)`` is the first half of a layer projection (hip.decode_gemm on
-        the bf16 weights, or hip.decode_gemm_mxfp4 on the FP4 codes - same partial slabs), ``gemm_head(a, out=)`` the lm_head."""
-        cfg, w = self.cfg, self.w
-        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
-        scale, eps = D ** -0.5, cfg.rms_eps
-        x, x2, qkv, att, act = self.b_x[:B], self.b_x2[:B], self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
-        xn, xn2, part = self.b_xn[:B], self.b_xn2[:B], self.b_part
-        nq = qkv.shape[1]
-        hip.gather_rows(w.embed, self.cur_b[:B], x)
-        hip.rmsnorm(x, w.llm[0].ln1_w, eps, out=xn)
-        n_layers = len(w.llm)
-        for li, lw in enumerate(w.llm):
-            ks = gemm(xn, li, "qkv_w", part=part)
-            if self.fold_qkv:     # the attention workgroups finalise the qkv columns they read (same bits, one launch less)
-                hip.decode_attn_parts(part, ks, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
-                                      self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
-                                      bias=lw.qkv_b, shared_len=self.batch_shared_len)
-            else:
-                hip.skinny_finalize(part, ks, qkv, nq, bias=lw.qkv_b, eps=eps)
-                hip.decode_attn(qkv, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
-                                self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
-                                shared_len=self.batch_shared_len)
-            ks = gemm(att, li, "o_w", part=part)
-            hip.skinny_finalize(part, ks, x2, cfg.hidden, residual=x, norm_w=lw.ln2_w, yn=xn2, eps=eps)
-            ks = gemm(xn2, li, "gateup_w", part=part)
-            hip.skinny_finalize(part, ks, act, 2 * cfg.intermediate, swiglu=True, eps=eps)
-            ks = gemm(act, li, "down_w", part=part)
-            next_norm = w.llm[li + 1].ln1_w if li + 1 < n_layers else w.final_norm_w
-            hip.skinny_finalize(part, ks, x, cfg.hidden, residual=x2, norm_w=next_norm, yn=xn, eps=eps)
-        gemm_head(xn, out=self.logits_b[:B])
-        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
-                   self.temperature, self.seed)
-        self._logprobs_after_pick(B)
-        self._stop_after_pick(B)
-
-    def _decode_step_fused(self, B: int, projections_only: bool = False) -> int:
-        """One decode step for B in-flight sequences, every projection ONE launch (r05, csrc/decode_stream.hip): the stream-K
-        weight pass, the fixed-order sum of a cut tile's segments by the last workgroup to arrive, and the epilogue - bias (qkv),
-        SwiGLU (gate/up), residual + the NEXT norm's weight + the tile's sum of squares (o, down); the consumer of a normed row
-        applies rs[b] = rsqrt(mean(x^2) + eps) to its finished sums (the RMSNorm, TF modeling_qwen2_vl.py:96-110, split into a
-        per-column and a per-row factor).  5 launches per layer (r04: 9).  fp8 (configs[4]): activations travel as MX blocks
-        written by the producing epilogue.  ``projections_only``: bench.py's replay of the weight-streaming launches alone.
-        Returns the number of projection launches."""
-        cfg, w = self.cfg, self.w
-        Hq, Hkv, D, H = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden
-        scale, eps = D ** -0.5, cfg.rms_eps
-        x, x2, qkv, att, act = self.b_x[:B], self.b_x2[:B], self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
-        xw, x2w, s1, s2, ws = self.b_xw[:B], self.b_x2w[:B], self.b_ssq1, self.b_ssq2, self.b_proj_ws
-        fp8 = self.decode_weights == "fp8" and self.fp8_batched
-        if fp8:
-            xq, xqs, x2q, x2qs = self.b_xq[:B], self.b_xqs[:B], self.b_x2q[:B], self.b_x2qs[:B]
-            aq, aqs = self.b_actq[:B], self.b_actqs[:B]
-        # Long-K, few-column projections at many sequences (7B down at 33+ sequences: K = 18944, 28 column tiles) keep the
-        # r02-r04 pair - stream-K slabs + the row-owning finalisation, which then also applies the next RMSNorm itself (xw holds
-        # the NORMALISED row, its consumer takes no row factor): a column slab per workgroup would stream 2.4 MB of x each, and
-        # the in-kernel reduction of the stream-K form costs more than the finalisation launch it saves (64 vs 33 + 5 us,
-        # profiles/r05_decode_step_b64_streamk.txt).  VIS_DOWN_PAIR=0 forces the single launch (A/B).
-        down_pair = (not fp8) and hasattr(self, "b_part") and os.environ.get("VIS_DOWN_PAIR", "1") != "0" and \
-            hip.decode_proj_form(B, H, cfg.intermediate, hip.DP_RESID_NORMW, False, False) == "streamk"
-        s1_in = None if down_pair else s1
-        if not projections_only:
-            if down_pair:
-                hip.gather_rows(w.embed, self.cur_b[:B], x)
-                hip.rmsnorm(x, w.llm[0].ln1_w, eps, out=xw)
-            else:
-                hip.decode_prep_rows(w.embed, self.cur_b[:B], w.llm[0].ln1_w, x, None if fp8 else xw, s1,
-                                     xq if fp8 else None, xqs if fp8 else None)
-        n_layers = len(w.llm)
-        for li, lw in enumerate(w.llm):
-            next_norm = w.llm[li + 1].ln1_w if li + 1 < n_layers else w.final_norm_w
-            if fp8:
-                q8 = self.q8[li]
-                hip.decode_proj_fp8(xq, xqs, *q8["qkv_w"], ws, hip.DP_PLAIN, out=qkv, bias=lw.qkv_b, ssq_in=s1, norm_dim=H, eps=eps)
-            else:
-                hip.decode_proj(xw, lw.qkv_w, ws, hip.DP_PLAIN, out=qkv, bias=lw.qkv_b, ssq_in=s1_in, norm_dim=H, eps=eps)
-            if not projections_only:
-                hip.decode_attn(qkv, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
-                                self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
-                                shared_len=self.batch_shared_len)
-            if fp8:     # the o projection keeps bf16 weights (its input comes from the attention kernel); its epilogue writes MX
-                hip.decode_proj(att, lw.o_w, ws, hip.DP_RESID_NORMW, out=x2, out_q=x2q, out_qs=x2qs, residual=x,
-                                norm_w=lw.ln2_w, ssq_out=s2)
-                hip.decode_proj_fp8(x2q, x2qs, *q8["gateup_w"], ws, hip.DP_SWIGLU, out_q=aq, out_qs=aqs, ssq_in=s2,
-                                    norm_dim=H, eps=eps)
-                hip.decode_proj_fp8(aq, aqs, *q8.get("down_w_pad", q8["down_w"]), ws, hip.DP_RESID_NORMW, out=x, out_q=xq,
-                                    out_qs=xqs, residual=x2, norm_w=next_norm, ssq_out=s1)
-            else:
-                hip.decode_proj(att, lw.o_w, ws, hip.DP_RESID_NORMW, out=x2, out_w=x2w, residual=x, norm_w=lw.ln2_w, ssq_out=s2)
-                hip.decode_proj(x2w, lw.gateup_w, ws, hip.DP_SWIGLU, out=act, ssq_in=s2, norm_dim=H, eps=eps)
-                if down_pair:
-                    ks = hip.decode_gemm(act, lw.down_w, part=self.b_part)
-                    if not projections_only:
-                        hip.skinny_finalize(self.b_part, ks, x, H, residual=x2, norm_w=next_norm, yn=xw, eps=eps)
-                else:
-                    hip.decode_proj(act, lw.down_w, ws, hip.DP_RESID_NORMW, out=x, out_w=xw, residual=x2, norm_w=next_norm,
-                                    ssq_out=s1)
-        if fp8:
-            hip.decode_proj_fp8(xq, xqs, *self.q8_lm_head, ws, hip.DP_PLAIN, out=self.logits_b[:B], ssq_in=s1, norm_dim=H, eps=eps)
-        else:
-            hip.decode_proj(xw, w.lm_head, ws, hip.DP_PLAIN, out=self.logits_b[:B], ssq_in=s1_in, norm_dim=H, eps=eps)
-        if not projections_only:
-            self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
-                       self.temperature, self.seed)
-            self._logprobs_after_pick(B)
-            self._stop_after_pick(B)
-        return 4 * n_layers + 1
-
-    def _decode_step_rows(self, B: int) -> None:
-        """A couple of in-flight sequences: the single-sequence step with the multi-row GEMV (vis_gemv_*_rows) - one pass
-        over the weights for all rows, norm / bias / residual / SwiGLU fused as at B = 1, no partial buffers and no
-        finalisation launches (the stream-K projection pays four of those per layer); bf16 or e4m3 weights with bf16
-        activations, every sequence bit-identical to decoding alone.  Chosen by _decode_step_batched (VIS_ROWS_GEMV).
-        MXFP4 weights take this step at EVERY batch size: more than 4 sequences issue each projection once per group of 4
-        rows (the weights are then read ceil(B / 4) times per step: slower than the bf16 stream-K step above ~16
-        sequences); attention, pick and the request switches stay one batched launch each."""
-        cfg, w = self.cfg, self.w
-        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
-        scale, eps = D ** -0.5, cfg.rms_eps
-        x, x2, qkv, att, act = self.b_x[:B], self.b_x2[:B], self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
-        fp8, fp4 = self.decode_weights == "fp8", self.decode_weights == "mxfp4"
-
-        def proj(inp, wt, out, residual=None, **kw):
-            if fp4:
-                for b0 in range(0, B, 4):
-                    rows = slice(b0, min(b0 + 4, B))
-                    hip.gemv_mxfp4_rows(inp[rows], *wt, out[rows], residual=None if residual is None else residual[rows], **kw)
-            elif fp8:
-                hip.gemv_fp8_rows(inp, *wt, out, residual=residual, **kw)
-            else:
-                hip.gemv_rows(inp, wt, out, residual=residual, **kw)
-
-        hip.gather_rows(w.embed, self.cur_b[:B], x)
-        for li, lw in enumerate(w.llm):
-            q8 = self.q8[li] if fp8 else (self.q4[li] if fp4 else None)
-            pick = (lambda n: q8[n]) if q8 is not None else (lambda n: getattr(lw, n))
-            proj(x, pick("qkv_w"), qkv, bias=lw.qkv_b, norm_w=lw.ln1_w, eps=eps)
-            hip.decode_attn(qkv, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
-                            self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
-                            shared_len=self.batch_shared_len)
-            proj(att, pick("o_w"), x2, residual=x)
-            proj(x2, pick("gateup_w"), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
-            proj(act, pick("down_w"), x, residual=x2)
-        proj(x, self.q8_lm_head if fp8 else (self.q4_lm_head if fp4 else w.lm_head), self.logits_b[:B],
-             norm_w=w.final_norm_w, eps=eps)
-        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
-                   self.temperature, self.seed)
-        self._logprobs_after_pick(B)
-        self._stop_after_pick(B)
-
-    def _decode_step_batched_fp8(self, B: int) -> None:
-        """Batched decode on e4m3 weights AND activations (BASELINE configs[4]): qkv, gate/up, down and the lm_head run
-        on the fp8 stream-K projection; every finalisation also emits the next projection's input as e4m3 + row scale
-        (it owns the row, so the activation quantiser costs no extra launch).  The o projection stays bf16: its input
-        comes from the attention combine, which does not own whole rows."""
-        cfg, w = self.cfg, self.w
-        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
-        scale, eps = D ** -0.5, cfg.rms_eps
-        x, x2, qkv, att, act = self.b_x[:B], self.b_x2[:B], self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
-        xn, xn2, part = self.b_xn[:B], self.b_xn2[:B], self.b_part
-        xq, x2q, aq = self.b_xq[:B], self.b_x2q[:B], self.b_actq[:B]
-        sxq, sx2q, saq = self.b_sx[0, :B], self.b_sx[1, :B], self.b_sx[2, :B]
-        nq = qkv.shape[1]
-        hip.gather_rows(w.embed, self.cur_b[:B], x)
-        hip.quant_rows_fp8(x, xq, sxq, norm_w=w.llm[0].ln1_w, eps=eps)
-        n_layers = len(w.llm)
-        for li, lw in enumerate(w.llm):
-            q8 = self.q8[li]
-            ks = hip.decode_gemm_fp8(xq, sxq, *q8["qkv_w"], part=part)
-            if self.fold_qkv:
-                hip.decode_attn_parts(part, ks, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
-                                      self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
-                                      bias=lw.qkv_b, sx=sxq, sw=q8["qkv_w"][1], shared_len=self.batch_shared_len)
-            else:
-                hip.skinny_finalize_fp8(part, ks, qkv, nq, sx=sxq, sw=q8["qkv_w"][1], bias=lw.qkv_b, eps=eps)
-                hip.decode_attn(qkv, self.cos_b[:B], self.sin_b[:B], self.kcache_b[:B, li], self.vcache_b[:B, li],
-                                self.step_b[:B], self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
-                                shared_len=self.batch_shared_len)
-            ks = hip.decode_gemm(att, lw.o_w, part=part)
-            hip.skinny_finalize_fp8(part, ks, x2, cfg.hidden, residual=x, norm_w=lw.ln2_w, yn=xn2, yq=x2q,
-                                    yq_scale=sx2q, eps=eps)
-            ks = hip.decode_gemm_fp8(x2q, sx2q, *q8["gateup_w"], part=part)
-            hip.skinny_finalize_fp8(part, ks, act, 2 * cfg.intermediate, sx=sx2q, sw=q8["gateup_w"][1], swiglu=True,
-                                    yq=aq, yq_scale=saq, eps=eps)
-            dw = q8.get("down_w_pad", q8["down_w"])
-            ks = hip.decode_gemm_fp8(aq, saq, *dw, part=part)
-            next_norm = w.llm[li + 1].ln1_w if li + 1 < n_layers else w.final_norm_w
-            hip.skinny_finalize_fp8(part, ks, x, cfg.hidden, sx=saq, sw=dw[1], residual=x2, norm_w=next_norm, yn=xn,
-                                    yq=xq, yq_scale=sxq, eps=eps)
-        hip.decode_gemm_fp8(xq, sxq, *self.q8_lm_head, out=self.logits_b[:B])
-        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
-                   self.temperature, self.seed)
-        self._logprobs_after_pick(B)
-        self._stop_after_pick(B)
+    def _decode_rope(self, B: int) -> tuple:
+        """Every slot has its own M-RoPE rows; the batch's shared text prefix is read from slot 0 (DecodeStage hook)."""
+        return self.cos_b[:B], self.sin_b[:B], self.batch_shared_len
 
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
         # temperature, seed and the batch size are kernel arguments baked into the graph; so is what _pick_key() names
         key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch) \
             + self._pick_key() + self._stop_key() + self._shape_key()
-        if key in self._graphs:
-            return self._graphs[key]
-        step_fn = (lambda: self._decode_step_batched(batch)) if batch else (lambda: self._decode_step(chained))
-        # warm the kernels outside capture, then restore the counters the warm-up advanced
-        saved = (self.step_b.clone(), self.cur_b.clone())
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            step_fn()
-        torch.cuda.current_stream().wait_stream(side)
-        self.step_b.copy_(saved[0])
-        self.cur_b.copy_(saved[1])
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):     # another agent's thread may be allocating
-            step_fn()
-        # capture does not execute; state is unchanged
-        if len(self._graphs) >= 8:
-            self._graphs.pop(next(iter(self._graphs)))
-        self._graphs[key] = g
-        return g
+        return self._captured_step(self._graphs, 8, key, batch, chained)
 
     def decode(self, n_steps: int, use_graph: bool = True) -> None:
         """Generate n_steps further tokens (each replays the captured step)."""
@@ -1438,65 +1130,7 @@ class Qwen2VLEngine(PickStage):
             raise ValueError("decode would overflow the KV cache")
         if self.prompt_len + self._decoded + n_steps > self.decode_limit:
             raise ValueError("decode beyond the rope rows prepared by prefill (pass max_new_tokens)")
-        base = self.prompt_len + self._decoded       # step k of this call sees base + k cached keys
-        self._decoded += n_steps
-        n_chain = max(0, min(n_steps, self.chain_ctx_limit - base)) if self.chain_sync is not None else 0
-        if n_chain == 0:
-            return self._decode_steps(n_steps, use_graph, False)
-        # Chained launches wait inside the grid for workgroups of the SAME launch, which only works while that launch can
-        # have its whole grid resident (860 of the device's 1024 slots at 7B shapes).  Two engines decoding on two streams at
-        # once could strand each other (each holding slots the other's producers need; the bounded waits would then raise).
-        # So the chained decode calls of a device are ordered on the GPU: a call waits for the previous call's last launch
-        # (an event, no host blocking), whatever streams or threads they come from.  Decode is HBM-bound: nothing is lost.
-        self._chain_epoch_guard(n_chain)
-        with _chain_order_lock(self.device.index):
-            cur = torch.cuda.current_stream(self.device)
-            prev = _CHAIN_LAST.get(self.device.index)
-            if prev is not None:
-                cur.wait_event(prev)
-            self._decode_steps(n_chain, use_graph, True)
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            _CHAIN_LAST[self.device.index] = ev
-        if n_steps > n_chain:       # the context has outgrown the chained grid: the four launches from here on (same bits)
-            self._decode_steps(n_steps - n_chain, use_graph, False)
-
-    def _chain_epoch_guard(self, n_steps: int) -> None:
-        """The granule tag of a chained launch is the sync block's 32-bit launch counter + 1.  Long before it can wrap
-        (2^31 launches = ~2.6 days of continuous single-sequence decode) workspace and sync block are zeroed on the stream,
-        between two decode calls - no launch of this engine is in flight then (same stream), and the kernel itself skips
-        tag 0, the mark of a never-written granule (tests/test_kernels_gpu.py::test_decode_chain_epoch_wrap)."""
-        self._chain_launches += n_steps * len(self.w.llm)
-        if self._chain_launches >= (1 << 31):
-            self.chain_sync.zero_()
-            self.chain_ws.zero_()
-            self._chain_launches = n_steps * len(self.w.llm)
-
-    def _decode_steps(self, n_steps: int, use_graph: bool, chained: bool = False) -> None:
-        if use_graph:
-            g = self._ensure_graph(0, chained)
-            if chained and self.chain_sync is None:      # the warm-up met a refusal: the captured step is the unchained one
-                g = self._ensure_graph(0, False)
-            for _ in range(n_steps):
-                g.replay()
-        else:
-            for _ in range(n_steps):
-                self._decode_step(chained)
-
-    def generated(self, n: int) -> List[int]:
-        s = self.prompt_len - 1
-        toks = self.tokens[s:s + n].cpu().tolist()
-        self.check_chain()
-        return toks
-
-    def check_chain(self) -> None:
-        """Raise if a bounded wait inside a chained layer-head launch gave up (its results are invalid); the sync block is
-        zeroed so that the engine stays usable.  Called after the token D2H, i.e. when the stream has drained."""
-        if self.chain_sync is not None and int(self.chain_sync[hip.CHAIN_STATUS_WORD].item()) != 0:
-            self.chain_sync.zero_()
-            self.chain_ws.zero_()
-            self._chain_launches = 0
-            raise hip.ChainStalled("vis_decode_chain: a hand-off wait inside the launch timed out (decode results invalid)")
+        self._decode_ordered(n_steps, use_graph)
 
     def disable_chain(self) -> None:
         """Back to the four launches per layer head (same results bit for bit); the captured decode graphs hold chained launches
@@ -1571,7 +1205,7 @@ class Qwen2VLEngine(PickStage):
                 return out
             except hip.ChainStalled as e:
                 # Something else held CU slots this launch's producers needed (another PROCESS sharing the GPU, or other work
-                # of this process on another stream: chained launches of this process are ordered, Qwen2VLEngine.decode,
+                # of this process on another stream: chained launches of this process are ordered, DecodeStage._decode_ordered,
                 # everything else is covered by the bounded wait only).  From the launch after the stall on every chained
                 # launch of the request returned at once (status word read at kernel entry), so what was lost is one wait
                 # bound.  The request is served again on the unchained launches - the same HIP kernels' arithmetic, identical

@@ -31,11 +31,11 @@ import numpy as np
 import torch
 
 from . import hip
+from .decode_stage import DecodeLayer, DecodeStage
 from .json_mode import JsonModeError, check_schema
 from .logprobs import check_k
 from .penalties import check_penalties
 from .shaping import check_shaping, shaping_kwargs
-from .pick import PickStage
 from .sampling import check_seeds, check_top_p
 from .stop import check_stop
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
@@ -98,7 +98,7 @@ def llama3_rope_tables(cfg: MllamaConfig, n: int) -> Tuple[np.ndarray, np.ndarra
     return np.cos(emb).astype(np.float32), np.sin(emb).astype(np.float32)
 
 
-class MllamaEngine(PickStage):
+class MllamaEngine(DecodeStage):
     """One mllama replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
     def __init__(self, cfg: MllamaConfig, weights: MllamaDeviceWeights, device, max_ctx: int = 4096, max_batch: int = 1):
@@ -177,7 +177,7 @@ class MllamaEngine(PickStage):
                                       device=dev)
         # Single-sequence decode: the head of every SELF-attention layer (qkv projection -> rope / append / attention -> o
         # projection) as ONE launch, the lm_head with the pick's first stage in its epilogue - the Inspector's chained step
-        # (csrc/decode_chain.hip, Qwen2VLEngine._decode_step; bit-identical to the launches it replaces); the eight
+        # (csrc/decode_chain.hip, DecodeStage._decode_step; bit-identical to the launches it replaces); the eight
         # cross-attention layers keep their launches.  It runs while the context stays within what the device holds resident
         # for this head shape (11B: 768 projection + 32 merge workgroups + 8 attention items per 64 keys -> 1536 keys) and on
         # the separate launches beyond.  VIS_DECODE_CHAIN=0 = A/B.
@@ -190,8 +190,6 @@ class MllamaEngine(PickStage):
                 self.chain_ws, self.chain_sync = hip.decode_chain_state(dev, Hq, Hkv, self.nsplit)
                 self.chain_ctx_limit = lim
         self.slot_prompt_len = [0] * Bm
-        self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self._graph_key = None
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._graphs_b: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._vis_plans: Dict[tuple, "hip.AttnPlan"] = {}
@@ -201,7 +199,14 @@ class MllamaEngine(PickStage):
         self.has_image = False
         self.decode_limit = 0
         self.tokenizer = None
-        self._init_pick_stage()      # the request switches of the next-token pick (pick.py)
+        # what the decode stage needs to know of the model (decode_stage.py; bf16 weights only); it also sets up the pick stage
+        self.decode_weights, self.fp8_batched, self.mxfp4_gemm_from = "bf16", False, None
+        si = ci = 0
+        layers = []
+        for lw in weights.layers:
+            layers.append(DecodeLayer(lw, None, None, lw.cross, ci if lw.cross else si, None))
+            ci, si = ci + lw.cross, si + (not lw.cross)
+        self._init_decode_stage(layers, weights.norm_w, weights.lm_head)
 
     # ------------------------------------------------------------------ preprocessing (geometry on host, pixels on GPU)
     def prepare_image(self, frame: torch.Tensor):
@@ -618,241 +623,33 @@ class MllamaEngine(PickStage):
                 self.decode_limit = self.max_ctx
 
     # ------------------------------------------------------------------ decode
-    def _decode_step(self, chained: bool = False) -> None:
-        cfg, w = self.cfg, self.w
-        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
-        scale = D ** -0.5
-        chained = chained and self.chain_sync is not None
-        embed_in_chain = chained and not w.layers[0].cross      # the first layer's launch reads the embedding row itself
-        if not embed_in_chain:
-            hip.gather_rows(w.embed, self.cur_token, self.d_x)
-        x, x2 = self.d_x, self.d_x2
-        si = ci = 0
-        for li, lw in enumerate(w.layers):
-            if lw.cross:
-                if not self.has_image:
-                    ci += 1
-                    continue
-                dq = self.d_qkv[:Hq * D]
-                hip.gemv(x[0], lw.qkv_w, dq, norm_w=lw.ln1_w, eps=cfg.rms_eps)
-                hip.decode_cross_attn(dq, lw.q_norm, self.xk[ci], self.xv[ci], self.nkeys_m1, self.part_o,
-                                      self.part_ml, self.d_attn, Hq, Hkv, D, self.xsplit, scale, cfg.rms_eps)
-                ci += 1
-                hip.gemv(self.d_attn, lw.o_w, x2[0], residual=x[0])
-            elif chained:
-                first = li == 0 and embed_in_chain
-                hip.decode_chain(w.embed if first else x[0], lw.qkv_w, None, lw.ln1_w, lw.o_w, x2[0], self.cos_t, self.sin_t,
-                                 self.kcache[si], self.vcache[si], self.step, self.chain_ws, self.chain_sync, Hq, Hkv, D,
-                                 self.nsplit, scale, cfg.rms_eps, x_index=self.cur_token if first else None,
-                                 ctx_bound=self.chain_ctx_limit)
-                si += 1
-            else:
-                hip.gemv(x[0], lw.qkv_w, self.d_qkv, norm_w=lw.ln1_w, eps=cfg.rms_eps)
-                hip.decode_attn(self.d_qkv, self.cos_t, self.sin_t, self.kcache[si], self.vcache[si], self.step,
-                                self.part_o, self.part_ml, self.d_attn, Hq, Hkv, D, self.nsplit, scale)
-                si += 1
-                hip.gemv(self.d_attn, lw.o_w, x2[0], residual=x[0])
-            hip.gemv(x2[0], lw.gateup_w, self.d_act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=cfg.rms_eps)
-            hip.gemv(self.d_act, lw.down_w, x[0], residual=x2[0])
-        if chained:     # the pick's first stage rides in the lm_head epilogue
-            self._gemv_pick(x[0], w.lm_head, self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step,
-                            norm_w=w.norm_w, eps=cfg.rms_eps, temperature=self.temperature, seed=self.seed)
-            self._logprobs_after_pick(1)
-            self._stop_after_pick(1)
-            return
-        hip.gemv(x[0], w.lm_head, self.logits, norm_w=w.norm_w, eps=cfg.rms_eps)
-        self._pick(self.logits, self.ws_val, self.ws_idx, self.tokens, self.cur_token, self.step, self.temperature,
-                   self.seed)
-        self._logprobs_after_pick(1)
-        self._stop_after_pick(1)
+    def _decode_rope(self, B: int) -> tuple:
+        """Plain positions: the one rope table for every sequence (batch stride 0), no shared keys (DecodeStage hook)."""
+        return self.cos_t.unsqueeze(0).expand(B, -1, -1), self.sin_t.unsqueeze(0).expand(B, -1, -1), 0
+
+    def _decode_cross_attn(self, L, q: torch.Tensor, att: torch.Tensor, B: int) -> None:
+        """Attention of the new token(s) over the image's static keys / values of cross layer ``L`` (DecodeStage hook)."""
+        cfg = self.cfg
+        if B:
+            fn, xk, xv, nkeys = hip.decode_cross_attn_batch, self.xk_b[:B, L.idx], self.xv_b[:B, L.idx], self.nkeys_b[:B]
+        else:
+            fn, xk, xv, nkeys = hip.decode_cross_attn, self.xk[L.idx], self.xv[L.idx], self.nkeys_m1
+        fn(q, L.w.q_norm, xk, xv, nkeys, self.part_o, self.part_ml, att, cfg.heads, cfg.kv_heads, cfg.head_dim, self.xsplit,
+           cfg.head_dim ** -0.5, cfg.rms_eps)
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
         key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key() + self._shape_key()
-        if key in self._graphs:
-            return self._graphs[key]
-        snap = (self.step.clone(), self.cur_token.clone())
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._decode_step(chained)               # warm-up outside capture
-        torch.cuda.current_stream().wait_stream(s)
-        self.step.copy_(snap[0]); self.cur_token.copy_(snap[1])
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):     # another agent's thread may be allocating
-            self._decode_step(chained)
-        self.step.copy_(snap[0]); self.cur_token.copy_(snap[1])
-        if len(self._graphs) >= 6:
-            self._graphs.pop(next(iter(self._graphs)))
-        self._graphs[key] = g
-        return g
+        return self._captured_step(self._graphs, 6, key, 0, chained)
 
-    def _decode_steps(self, n_steps: int, use_graph: bool, chained: bool) -> None:
-        if use_graph:
-            g = self._ensure_graph(chained)
-            for _ in range(n_steps):
-                g.replay()
-        else:
-            for _ in range(n_steps):
-                self._decode_step(chained)
+    def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
+        key = (self.temperature, self.seed, B) + self._pick_key() + self._stop_key() + self._shape_key()
+        return self._captured_step(self._graphs_b, 4, key, B, False)
 
     def decode(self, n_steps: int, use_graph: bool = True) -> None:
         if self.prompt_len + self._decoded + n_steps >= self.decode_limit:
             raise ValueError("decode would run past the context window")
-        base = self.prompt_len + self._decoded       # step k of this call sees base + k cached keys
-        n_chain = max(0, min(n_steps, self.chain_ctx_limit - base)) if self.chain_sync is not None else 0
-        if n_chain:
-            # chained launches wait inside the grid for workgroups of the SAME launch: one at a time per device, whatever
-            # engine, thread or stream it comes from (the Inspector's engine shares the GPU): ordered with an event, as in
-            # Qwen2VLEngine.decode
-            from .engine import _CHAIN_LAST, _chain_order_lock
-            n_self = sum(1 for lw in self.w.layers if not lw.cross)
-            self._chain_launches += n_chain * n_self
-            if self._chain_launches >= (1 << 31):     # long before the 32-bit launch counter can wrap (Qwen2VLEngine._chain_epoch_guard)
-                self.chain_sync.zero_()
-                self.chain_ws.zero_()
-                self._chain_launches = n_chain * n_self
-            with _chain_order_lock(self.device.index):
-                cur = torch.cuda.current_stream(self.device)
-                prev = _CHAIN_LAST.get(self.device.index)
-                if prev is not None:
-                    cur.wait_event(prev)
-                self._decode_steps(n_chain, use_graph, True)
-                ev = torch.cuda.Event()
-                ev.record(cur)
-                _CHAIN_LAST[self.device.index] = ev
-        if n_steps > n_chain:
-            self._decode_steps(n_steps - n_chain, use_graph, False)
-        self._decoded += n_steps
-
-    def check_chain(self) -> None:
-        """Raise hip.ChainStalled if a bounded wait inside a chained launch gave up (results invalid); see Qwen2VLEngine.check_chain."""
-        if self.chain_sync is not None and int(self.chain_sync[hip.CHAIN_STATUS_WORD].item()) != 0:
-            self.chain_sync.zero_()
-            self.chain_ws.zero_()
-            self._chain_launches = 0
-            raise hip.ChainStalled("vis_decode_chain: a hand-off wait inside the launch timed out (decode results invalid)")
-
-    # ---- batched decode: B in-flight requests (slots 0..B-1, all with an image) share every weight read of a step
-    def _decode_step_batched(self, B: int) -> None:
-        """Every projection = gemm_decode (weights streamed once for all B sequences, stream-K f32 partials) +
-        skinny_finalize (row-wise: sum, residual / SwiGLU, and the RMSNorm of the NEXT projection); self-attention and
-        cross-attention take the sequence index on the grid."""
-        if self.fused_proj:
-            return self._decode_step_fused(B)
-        cfg, w = self.cfg, self.w
-        Hq, Hkv, D, H = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden
-        scale, eps = D ** -0.5, cfg.rms_eps
-        x, x2, xn, xn2 = self.b_x[:B], self.b_x2[:B], self.b_xn[:B], self.b_xn2[:B]
-        qkv, att, act, part = self.b_qkv[:B], self.b_attn[:B], self.b_act[:B], self.b_part
-        nq = qkv.shape[1]
-        cosb = self.cos_t.unsqueeze(0).expand(B, -1, -1)          # batch stride 0: the rope table is shared
-        sinb = self.sin_t.unsqueeze(0).expand(B, -1, -1)
-        hip.gather_rows(w.embed, self.cur_b[:B], x)
-        hip.rmsnorm(x, w.layers[0].ln1_w, eps, out=xn)
-        n_layers = len(w.layers)
-        si = ci = 0
-        for li, lw in enumerate(w.layers):
-            if lw.cross:
-                q = qkv[:, :Hq * D]
-                ks = hip.decode_gemm(xn, lw.qkv_w, part=part)
-                hip.skinny_finalize(part, ks, q, Hq * D, eps=eps)
-                hip.decode_cross_attn_batch(q, lw.q_norm, self.xk_b[:B, ci], self.xv_b[:B, ci], self.nkeys_b[:B],
-                                            self.part_o, self.part_ml, att, Hq, Hkv, D, self.xsplit, scale, eps)
-                ci += 1
-            else:
-                ks = hip.decode_gemm(xn, lw.qkv_w, part=part)
-                if self.fold_qkv:      # the attention workgroups finalise the qkv columns they read (same bits, one launch less)
-                    hip.decode_attn_parts(part, ks, cosb, sinb, self.kcache_b[:B, si], self.vcache_b[:B, si], self.step_b[:B],
-                                          self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale)
-                else:
-                    hip.skinny_finalize(part, ks, qkv, nq, eps=eps)
-                    hip.decode_attn(qkv, cosb, sinb, self.kcache_b[:B, si], self.vcache_b[:B, si], self.step_b[:B],
-                                    self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale)
-                si += 1
-            ks = hip.decode_gemm(att, lw.o_w, part=part)
-            hip.skinny_finalize(part, ks, x2, H, residual=x, norm_w=lw.ln2_w, yn=xn2, eps=eps)
-            ks = hip.decode_gemm(xn2, lw.gateup_w, part=part)
-            hip.skinny_finalize(part, ks, act, 2 * cfg.intermediate, swiglu=True, eps=eps)
-            ks = hip.decode_gemm(act, lw.down_w, part=part)
-            next_norm = w.layers[li + 1].ln1_w if li + 1 < n_layers else w.norm_w
-            hip.skinny_finalize(part, ks, x, H, residual=x2, norm_w=next_norm, yn=xn, eps=eps)
-        hip.decode_gemm(xn, w.lm_head, out=self.logits_b[:B])
-        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
-                   self.temperature, self.seed)
-        self._logprobs_after_pick(B)
-        self._stop_after_pick(B)
-
-    def _decode_step_fused(self, B: int) -> None:
-        """The batched step with every projection as ONE launch (r05, csrc/decode_stream.hip; see Qwen2VLEngine._decode_step_fused):
-        q / qkv (plain, rs of the input norm), o (+ residual, x ln2_w, sums of squares), gate/up (SwiGLU, rs), down (+ residual,
-        x the next ln1_w, sums of squares); 5 launches per layer instead of 9.  The tanh gates of the cross-attention layers are
-        folded into o_w / down_w at load time, so both layer kinds share the sequence."""
-        cfg, w = self.cfg, self.w
-        Hq, Hkv, D, H = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden
-        scale, eps = D ** -0.5, cfg.rms_eps
-        x, x2, xw, x2w = self.b_x[:B], self.b_x2[:B], self.b_xw[:B], self.b_x2w[:B]
-        qkv, att, act = self.b_qkv[:B], self.b_attn[:B], self.b_act[:B]
-        s1, s2, ws = self.b_ssq1, self.b_ssq2, self.b_proj_ws
-        cosb = self.cos_t.unsqueeze(0).expand(B, -1, -1)          # batch stride 0: the rope table is shared
-        sinb = self.sin_t.unsqueeze(0).expand(B, -1, -1)
-        # the long-K down projection at many sequences keeps the r02-r04 pair of launches (Qwen2VLEngine._decode_step_fused)
-        down_pair = os.environ.get("VIS_DOWN_PAIR", "1") != "0" and \
-            hip.decode_proj_form(B, H, cfg.intermediate, hip.DP_RESID_NORMW, False, False) == "streamk"
-        s1_in = None if down_pair else s1
-        if down_pair:
-            hip.gather_rows(w.embed, self.cur_b[:B], x)
-            hip.rmsnorm(x, w.layers[0].ln1_w, eps, out=xw)
-        else:
-            hip.decode_prep_rows(w.embed, self.cur_b[:B], w.layers[0].ln1_w, x, xw, s1)
-        n_layers = len(w.layers)
-        si = ci = 0
-        for li, lw in enumerate(w.layers):
-            if lw.cross:
-                q = qkv[:, :Hq * D]
-                hip.decode_proj(xw, lw.qkv_w, ws, hip.DP_PLAIN, out=q, ssq_in=s1_in, norm_dim=H, eps=eps)
-                hip.decode_cross_attn_batch(q, lw.q_norm, self.xk_b[:B, ci], self.xv_b[:B, ci], self.nkeys_b[:B],
-                                            self.part_o, self.part_ml, att, Hq, Hkv, D, self.xsplit, scale, eps)
-                ci += 1
-            else:
-                hip.decode_proj(xw, lw.qkv_w, ws, hip.DP_PLAIN, out=qkv, ssq_in=s1_in, norm_dim=H, eps=eps)
-                hip.decode_attn(qkv, cosb, sinb, self.kcache_b[:B, si], self.vcache_b[:B, si], self.step_b[:B],
-                                self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale)
-                si += 1
-            hip.decode_proj(att, lw.o_w, ws, hip.DP_RESID_NORMW, out=x2, out_w=x2w, residual=x, norm_w=lw.ln2_w, ssq_out=s2)
-            hip.decode_proj(x2w, lw.gateup_w, ws, hip.DP_SWIGLU, out=act, ssq_in=s2, norm_dim=H, eps=eps)
-            next_norm = w.layers[li + 1].ln1_w if li + 1 < n_layers else w.norm_w
-            if down_pair:
-                ks = hip.decode_gemm(act, lw.down_w, part=self.b_part)
-                hip.skinny_finalize(self.b_part, ks, x, H, residual=x2, norm_w=next_norm, yn=xw, eps=eps)
-            else:
-                hip.decode_proj(act, lw.down_w, ws, hip.DP_RESID_NORMW, out=x, out_w=xw, residual=x2, norm_w=next_norm,
-                                ssq_out=s1)
-        hip.decode_proj(xw, w.lm_head, ws, hip.DP_PLAIN, out=self.logits_b[:B], ssq_in=s1_in, norm_dim=H, eps=eps)
-        self._pick(self.logits_b[:B], self.ws_val, self.ws_idx, self.tokens_b[:B], self.cur_b[:B], self.step_b[:B],
-                   self.temperature, self.seed)
-        self._logprobs_after_pick(B)
-        self._stop_after_pick(B)
-
-    def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B) + self._pick_key() + self._stop_key() + self._shape_key()
-        if key in self._graphs_b:
-            return self._graphs_b[key]
-        snap = (self.step_b.clone(), self.cur_b.clone())
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._decode_step_batched(B)             # warm-up outside capture
-        torch.cuda.current_stream().wait_stream(s)
-        self.step_b.copy_(snap[0]); self.cur_b.copy_(snap[1])
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):     # another agent's thread may be allocating
-            self._decode_step_batched(B)
-        self.step_b.copy_(snap[0]); self.cur_b.copy_(snap[1])
-        if len(self._graphs_b) >= 4:
-            self._graphs_b.pop(next(iter(self._graphs_b)))
-        self._graphs_b[key] = g
-        return g
+        self._decode_ordered(n_steps, use_graph)
 
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
@@ -1056,12 +853,6 @@ class MllamaEngine(PickStage):
                 outs[b] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
                 self.last_finish[b] = None
         return outs
-
-    def generated(self, n: int) -> List[int]:
-        s = self.prompt_len - 1          # the token generated at step i is stored at index (its position - 1)
-        toks = self.tokens[s:s + n].cpu().tolist()
-        self.check_chain()
-        return toks
 
     def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
