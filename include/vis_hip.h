@@ -172,6 +172,25 @@ int vis_decode_attn_parts(const void* part, int ksplit, int slab_rows, const voi
                           void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD, int cache_tokens, int nsplit,
                           float scale, int batch, long long cache_bs, long long tab_bs, int shared_len, vis_stream_t stream);
 
+/* vis_decode_attn_shared / vis_decode_attn_parts with the shared range named per sequence, in DEVICE memory (int32 [batch]
+ * each, so one captured graph serves every layout): sequence b reads keys / values [0, fork_len[b]) from sequence parent[b]'s
+ * cache and everything from fork_len[b] on - the streaming form's early prefetch, the KV append and the new token included -
+ * from its own.  The n choices of one request are forks of the slot that ran its prompt pass; a batch's common text prefix is
+ * "parent 0, fork_len P".  Contract (the caller's): fork_len[b] % 64 == 0, parent[parent[b]] == parent[b], the parent holds
+ * rows [0, fork_len[b]) itself, the new token's slot >= fork_len[b].  The kernels clamp parent into [0, batch) and round
+ * fork_len down to a multiple of 64 inside [0, cache_tokens): no table content forms an address outside the caches.
+ * Same arithmetic, key order and split plan as the unforked entry points: bit-identical to vis_decode_attn /
+ * vis_decode_attn_parts on caches that hold the parent's rows in every child.  Both forms (split + combine, streaming). */
+int vis_decode_attn_forked(const void* qkv, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                           const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                           int cache_tokens, int nsplit, float scale, int batch, long long qkv_bs, long long cache_bs,
+                           long long tab_bs, const int* parent, const int* fork_len, vis_stream_t stream);
+int vis_decode_attn_parts_forked(const void* part, int ksplit, int slab_rows, const void* bias, const void* sx, const void* sw,
+                                 const void* cos_t, const void* sin_t, void* k_cache, void* v_cache, const void* step_ptr,
+                                 void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD, int cache_tokens, int nsplit,
+                                 float scale, int batch, long long cache_bs, long long tab_bs, const int* parent,
+                                 const int* fork_len, vis_stream_t stream);
+
 /* K10 + K4 + K11 + K10 (single-sequence decode)  the head of a decoder layer as ONE launch:
  *   qkv = W_qkv rmsnorm(x) + b ; attn = attention(rope(q), cache + rope(k), v) ; y = x + W_o attn
  * i.e. vis_gemv_bf16 (norm fused) + vis_decode_attn (split + combine launches) + vis_gemv_bf16 (residual), bit-identical to

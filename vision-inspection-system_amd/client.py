@@ -19,6 +19,7 @@ from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Tuple
 
 from .config import LOCAL_PROVIDER, Qwen2VLConfig
+from .fork import check_n      # noqa: F401  (re-exported: the client's check of ``n``)
 
 logger = logging.getLogger("vision_inspection_system_amd.client")
 
@@ -79,10 +80,10 @@ class _Completions:
                seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
                presence_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
                stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-               logit_bias: Optional[dict] = None, **kwargs) -> ChatCompletion:
+               logit_bias: Optional[dict] = None, n: Optional[int] = None, **kwargs) -> ChatCompletion:
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
                  "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
-                 "logit_bias": logit_bias}
+                 "logit_bias": logit_bias, "n": n}
         kwargs.update({name: v for name, v in given.items() if v is not None})
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
                                      top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
@@ -325,6 +326,21 @@ def schema_of(response_format):
     return dfa
 
 
+def _completion(model_id: str, tok, n_ids: int, toks, rec, fin, timing: dict, nested: bool) -> ChatCompletion:
+    """One request's ChatCompletion from what the engine returned for it: a token list with its logprob record and (reason,
+    cut) - or, ``nested`` (the request asked for n choices), a list of each.  The prompt is counted once."""
+    if not nested:
+        toks, rec, fin = [toks], [rec], [fin]
+    elif rec is None:
+        rec = [None] * len(toks)
+    choices = [_Choice(_Message(_reply_text(model_id, _finished_text(tok, t, f))), index=i, finish_reason=_finish_reason(f),
+                       logprobs=_choice_logprobs(tok, t, r) if r is not None else None)
+               for i, (t, r, f) in enumerate(zip(toks, rec, fin))]
+    done = sum(len(t) for t in toks)
+    return ChatCompletion(choices, model=model_id,
+                          usage={"prompt_tokens": n_ids, "completion_tokens": done, "total_tokens": n_ids + done}, timings=timing)
+
+
 def _choice_logprobs(tok, toks: List[int], rec) -> ChoiceLogprobs:
     """An engine's TokenLogprobs record of one request -> choice.logprobs (one entry per completion token)."""
     def entry(cls, t, lp, **kw):
@@ -432,18 +448,19 @@ class LocalVLMClient:
 
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
                   top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
-                  stop=None, top_k=None, min_p=None, logit_bias=None, **kwargs) -> ChatCompletion:
+                  stop=None, top_k=None, min_p=None, logit_bias=None, n=None, **kwargs) -> ChatCompletion:
         return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
                                   response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
                                   presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop,
-                                  top_k=top_k, min_p=min_p, logit_bias=logit_bias)[0]
+                                  top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n)[0]
 
     def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
                       top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
                       top_p: Optional[float] = None, seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
                       presence_penalty: Optional[float] = None,
                       repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
-                      min_p: Optional[float] = None, logit_bias: Optional[dict] = None) -> List[ChatCompletion]:
+                      min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
+                      n: Optional[int] = None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -478,7 +495,13 @@ class LocalVLMClient:
         (vLLM's / huggingface_hub's, an integer >= 1): only the k most likely allowed tokens stay, ties at the k-th place
         included.  ``min_p`` (vLLM's, in [0, 1]): only tokens at least min_p times as likely as the most likely one stay.
         One launch ahead of the pick (shaping.py), after the penalties and the JSON mask, before top_p and the draw; a
-        greedy request (temperature 0) is affected by logit_bias only.  None / 0 / {} = off.  Logprobs keep their meaning."""
+        greedy request (temperature 0) is affected by logit_bias only.  None / 0 / {} = off.  Logprobs keep their meaning.
+        ``n`` (OpenAI's): an integer in 1..max_batch - that many choices per request, ``choices[i].index`` = i, each with its
+        own text, finish_reason and logprobs, from ONE prompt pass: the further choices read the prompt's keys / values from
+        the first one's cache (fork.py, vis_decode_attn_forked).  Choice i samples with ``seed`` + i; at temperature 0 all
+        choices are equal (and still decoded).  ``usage.prompt_tokens`` counts the prompt once, ``completion_tokens`` is the
+        sum over the choices.  Chunks are filled by choices, max_batch // n requests each.  A request with a choice JSON mode
+        could not continue fails as a whole.  None or 1 = one choice, the calls of before."""
         import torch
         from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
@@ -501,8 +524,10 @@ class LocalVLMClient:
         max_new = int(max_tokens) if max_tokens else 512
         temp = float(temperature) if temperature else 0.0
         out: List[ChatCompletion] = []
+        n = check_n(n, eng.max_batch)
+        n = None if n == 1 else n
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa, stop, shp)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa, stop, shp, n)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -534,15 +559,17 @@ class LocalVLMClient:
             return resolve
 
         with eng.lock:
-            for i in range(0, len(futs), eng.max_batch):
-                idx = range(i, min(len(futs), i + eng.max_batch))
+            per_chunk = eng.max_batch // (n or 1)      # chunks are filled by choices
+            for i in range(0, len(futs), per_chunk):
+                idx = range(i, min(len(futs), i + per_chunk))
                 toks = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp, seed=self.seed,
                                           ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1",
                                           **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}),
                                           **({"json_schema": dfa} if dfa is not None else {}),
                                           **({"top_p": top_p} if top_p is not None else {}),
                                           **({"seeds": [seed] * len(idx)} if seed is not None else {}),
-                                          **({"stop": stop} if stop is not None else {}), **pen, **shp)
+                                          **({"stop": stop} if stop is not None else {}), **pen, **shp,
+                                          **({"n": n} if n is not None else {}))
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
                 fins = getattr(eng, "last_finish", None) or [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", {}))
@@ -557,11 +584,7 @@ class LocalVLMClient:
                             raise t
                         out.append(t)
                         continue
-                    lp = _choice_logprobs(tok, t, rec) if rec is not None else None
-                    out.append(ChatCompletion([_Choice(_Message(_reply_text(model_id, _finished_text(tok, t, fin))),
-                                                       finish_reason=_finish_reason(fin), logprobs=lp)], model=model_id,
-                                              usage={"prompt_tokens": n_ids[j], "completion_tokens": len(t),
-                                                     "total_tokens": n_ids[j] + len(t)}, timings=timing))
+                    out.append(_completion(model_id, tok, n_ids[j], t, rec, fin, timing, n is not None))
         return out
 
 
@@ -588,7 +611,7 @@ class LocalVLMClient:
     def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
                               k: Optional[int] = None, jm: bool = False, top_p: Optional[float] = None,
                               seed: Optional[int] = None, pen: Optional[dict] = None, dfa=None,
-                              stop=None, shp: Optional[dict] = None) -> List[ChatCompletion]:
+                              stop=None, shp: Optional[dict] = None, n: Optional[int] = None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -608,16 +631,14 @@ class LocalVLMClient:
             lpk["stop"] = stop
         lpk.update(pen or {})
         lpk.update(shp or {})
+        nk = {"n": n} if n is not None else {}
+        per_chunk = eng.max_batch // (n or 1)      # chunks are filled by choices
 
-        def seeds_of(n):
-            return {"seeds": [seed] * n} if seed is not None else {}
+        def seeds_of(count):
+            return {"seeds": [seed] * count} if seed is not None else {}
 
         def completion(n_ids, t, rec=None, fin=None):
-            lp = _choice_logprobs(tok, t, rec) if rec is not None else None
-            return ChatCompletion([_Choice(_Message(_reply_text(lm.model_id, _finished_text(tok, t, fin))),
-                                           finish_reason=_finish_reason(fin), logprobs=lp)], model=lm.model_id,
-                                  usage={"prompt_tokens": n_ids, "completion_tokens": len(t), "total_tokens": n_ids + len(t)},
-                                  timings=dict(getattr(eng, "last_timing", {})))
+            return _completion(lm.model_id, tok, n_ids, t, rec, fin, dict(getattr(eng, "last_timing", {})), n is not None)
 
         futs = [ingest.then(m, lambda msgs: self._prepare_mllama(lm, msgs)) for m in batch_of_messages]
         if any(isinstance(m, Future) for m in batch_of_messages):
@@ -634,10 +655,10 @@ class LocalVLMClient:
                 return resolve
 
             with eng.lock:
-                for g0 in range(0, len(futs), eng.max_batch):
-                    idx = range(g0, min(len(futs), g0 + eng.max_batch))
+                for g0 in range(0, len(futs), per_chunk):
+                    idx = range(g0, min(len(futs), g0 + per_chunk))
                     outs = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp,
-                                              seed=self.seed, stop_on_eos=not ignore_eos, **lpk, **seeds_of(len(idx)))
+                                              seed=self.seed, stop_on_eos=not ignore_eos, **lpk, **nk, **seeds_of(len(idx)))
                     recs = eng.last_logprobs if k is not None else [None] * len(idx)
                     fins = eng.last_finish
                     if getattr(eng, "last_timing", None):
@@ -652,22 +673,31 @@ class LocalVLMClient:
         fins: list = [None] * len(prepared)
         with eng.lock:
             with_img = [i for i, (_, f) in enumerate(prepared) if f is not None]
-            for g0 in range(0, len(with_img), eng.max_batch):
-                grp = with_img[g0:g0 + eng.max_batch]
+            for g0 in range(0, len(with_img), per_chunk):
+                grp = with_img[g0:g0 + per_chunk]
                 reqs = [(prepared[i][0], _frame_to_device(prepared[i][1], eng.device)) for i in grp]
                 outs = eng.generate_batch(reqs, max_new_tokens=max_new, temperature=temp, seed=self.seed,
-                                          stop_on_eos=not ignore_eos, **lpk, **seeds_of(len(reqs)))
-                for n, (i, t) in enumerate(zip(grp, outs)):
+                                          stop_on_eos=not ignore_eos, **lpk, **nk, **seeds_of(len(reqs)))
+                for m, (i, t) in enumerate(zip(grp, outs)):
                     toks_out[i] = t
-                    recs[i] = eng.last_logprobs[n] if k is not None else None
-                    fins[i] = eng.last_finish[n]
+                    recs[i] = eng.last_logprobs[m] if k is not None else None
+                    fins[i] = eng.last_finish[m]
             for i, (ids, f) in enumerate(prepared):
-                if f is None:
+                if f is None and n is None:
                     toks_out[i] = eng.generate(ids, None, max_new_tokens=max_new, temperature=temp,
                                                seed=self.seed if seed is None else seed,
                                                stop_on_eos=not ignore_eos, **lpk)
                     recs[i] = eng.last_logprobs[0] if k is not None else None
                     fins[i] = eng.last_finish[0]
+                elif f is None:      # text only (the health check): no batched step without an image - one pass per choice
+                    toks_out[i], recs[i], fins[i] = [], [] if k is not None else None, []
+                    for c in range(n):
+                        toks_out[i].append(eng.generate(ids, None, max_new_tokens=max_new, temperature=temp,
+                                                        seed=(self.seed if seed is None else seed) + c,
+                                                        stop_on_eos=not ignore_eos, **lpk))
+                        if k is not None:
+                            recs[i].append(eng.last_logprobs[0])
+                        fins[i].append(eng.last_finish[0])
         return [completion(len(ids), t, r, f) for (ids, _), t, r, f in zip(prepared, toks_out, recs, fins)]
 
 
@@ -692,15 +722,15 @@ class CannedResponseClient:
 
     def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
                   frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None, top_k=None, min_p=None,
-                  logit_bias=None, **kwargs) -> ChatCompletion:
+                  logit_bias=None, n=None, **kwargs) -> ChatCompletion:
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
                            "response_format": response_format, "top_p": top_p, "seed": seed})
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
                  "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
-                 "logit_bias": logit_bias}
+                 "logit_bias": logit_bias, "n": n}
         self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
         reply = self.reply(messages) if callable(self.reply) else self.reply
-        return ChatCompletion([_Choice(_Message(reply))], model=model or "")
+        return ChatCompletion([_Choice(_Message(reply), index=i) for i in range(check_n(n, 64) or 1)], model=model or "")
 
 
 def make_client(provider: str, api_key: Optional[str] = None, **kwargs):

@@ -463,10 +463,10 @@ extern "C" int vis_gemv_fp8w_rows(const void* x, const void* Wq, const void* sca
 }
 
 // (the split decode attention item - DecAttnArgs, decode_attn_split_body - lives in decode_common.hip.h)
-template <int G>
+template <int G, bool FORK = false>
 __global__ __launch_bounds__(256) void decode_attn_fused_kernel(DecAttnArgs p) {
   __shared__ DecAttnLds<G> L;
-  decode_attn_split_body<G, false>(p, L, blockIdx.x, blockIdx.y, blockIdx.z, ChainCtx{nullptr, nullptr, nullptr, 0u, nullptr});
+  decode_attn_split_body<G, false, FORK>(p, L, blockIdx.x, blockIdx.y, blockIdx.z, ChainCtx{nullptr, nullptr, nullptr, 0u, nullptr});
 }
 
 // ---------------------------------------------------------------------------
@@ -485,7 +485,9 @@ __global__ __launch_bounds__(256) void decode_attn_fused_kernel(DecAttnArgs p) {
 // The eight waves' (m, l, O) are merged once at the end through LDS.  Same arithmetic per (head, key) as the split
 // kernel (bf16-rounded rotated q / k, f32 softmax in the log2 domain, f32 P*V); the summation order over keys differs, so
 // the two forms agree to f32 rounding, not bit for bit.
-template <int G>
+// FORK (vis_decode_attn_forked / _parts_forked): the shared range is per sequence - keys [0, fork_len[seq]) come from sequence
+// fork_parent[seq]'s cache instead of "[0, shared_len) from sequence 0" - still one base-pointer pair, selected wave-uniformly.
+template <int G, bool FORK = false>
 __global__ __launch_bounds__(512) void decode_attn_stream_kernel(DecAttnArgs p, bf16_t* __restrict__ out) {
   constexpr int HD = 128, HALF = 64, NW = 8;
   __shared__ __attribute__((aligned(16))) bf16_t q_s[16][HD];   // heads >= G are zero
@@ -499,8 +501,11 @@ __global__ __launch_bounds__(512) void decode_attn_stream_kernel(DecAttnArgs p, 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, h = lane >> 4;
   const int hkv = blockIdx.x, seq = blockIdx.y;
-  const bf16_t* Kh0 = p.k_cache + (size_t)hkv * p.cache_tokens * 128;     // sequence 0's rows (the batch's shared prefix)
-  const bf16_t* Vh0 = p.v_cache + (size_t)hkv * p.cache_tokens * 128;
+  int sh_seq = 0, sh_len = p.shared_len;
+  if constexpr (FORK) da_fork_row(p, seq, (int)gridDim.y, sh_seq, sh_len);
+  // sequence 0's rows (the batch's shared prefix); FORK: the parent's
+  const bf16_t* Kh0 = p.k_cache + (long long)sh_seq * p.cache_bs + (size_t)hkv * p.cache_tokens * 128;
+  const bf16_t* Vh0 = p.v_cache + (long long)sh_seq * p.cache_bs + (size_t)hkv * p.cache_tokens * 128;
   p.qkv += seq * p.qkv_bs;
   p.k_cache += seq * p.cache_bs;
   p.v_cache += seq * p.cache_bs;
@@ -519,7 +524,7 @@ __global__ __launch_bounds__(512) void decode_attn_stream_kernel(DecAttnArgs p, 
   struct StepRegs { u32x4 k[4]; u32x4 v[4]; };
   auto load_step = [&](StepRegs& r, int j) {          // keys 16 j .. 16 j + 15 (rows clamped: addresses are always valid)
     const int k0 = j * 16;
-    const bool sh = k0 < p.shared_len;             // (wave-uniform; shared_len is a multiple of 16)
+    const bool sh = k0 < sh_len;                   // (wave-uniform; shared_len / fork_len is a multiple of 16)
     const bf16_t* Kb = sh ? Kh0 : Kh;
     const bf16_t* Vb = sh ? Vh0 : Vh;
     const int krow = min(k0 + l15, p.cache_tokens - 1);
@@ -762,6 +767,7 @@ __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float* _
 
 static int decode_attn_launch(const DecAttnArgs& p, void* out, int batch, hipStream_t stream) {
   const int G = p.Hq / p.Hkv;
+  const bool fork = p.fork_parent != nullptr;     // the forked entry points: their own instantiations, same plan
   vis_clear_error();
   // Enough (kv head, sequence) pairs to fill the chip on their own: the streaming form - one workgroup per pair, the
   // whole context in one pass, no partials, no combine.  VIS_DECODE_ATTN_STREAM=0 keeps the split form (A/B).
@@ -770,7 +776,14 @@ static int decode_attn_launch(const DecAttnArgs& p, void* out, int batch, hipStr
   const int stream_env = se ? atoi(se) : 1;
   if (stream_env == 2 || (stream_env && p.Hkv * batch >= 128)) {   // 2: force (tests at small batch)
     const dim3 grid(p.Hkv, batch), block(512);
-    switch (G) {
+    if (fork) switch (G) {
+      case 1: hipLaunchKernelGGL((decode_attn_stream_kernel<1, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
+      case 2: hipLaunchKernelGGL((decode_attn_stream_kernel<2, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
+      case 4: hipLaunchKernelGGL((decode_attn_stream_kernel<4, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
+      case 7: hipLaunchKernelGGL((decode_attn_stream_kernel<7, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
+      default: hipLaunchKernelGGL((decode_attn_stream_kernel<8, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
+    }
+    else switch (G) {
       case 1: hipLaunchKernelGGL(decode_attn_stream_kernel<1>, grid, block, 0, stream, p, (bf16_t*)out); break;
       case 2: hipLaunchKernelGGL(decode_attn_stream_kernel<2>, grid, block, 0, stream, p, (bf16_t*)out); break;
       case 4: hipLaunchKernelGGL(decode_attn_stream_kernel<4>, grid, block, 0, stream, p, (bf16_t*)out); break;
@@ -780,7 +793,14 @@ static int decode_attn_launch(const DecAttnArgs& p, void* out, int batch, hipStr
     return vis_check_launch();
   }
   const dim3 grid(p.Hkv, p.nsplit, batch), block(256);
-  switch (G) {
+  if (fork) switch (G) {
+    case 1: hipLaunchKernelGGL((decode_attn_fused_kernel<1, true>), grid, block, 0, stream, p); break;
+    case 2: hipLaunchKernelGGL((decode_attn_fused_kernel<2, true>), grid, block, 0, stream, p); break;
+    case 4: hipLaunchKernelGGL((decode_attn_fused_kernel<4, true>), grid, block, 0, stream, p); break;
+    case 7: hipLaunchKernelGGL((decode_attn_fused_kernel<7, true>), grid, block, 0, stream, p); break;
+    default: hipLaunchKernelGGL((decode_attn_fused_kernel<8, true>), grid, block, 0, stream, p); break;
+  }
+  else switch (G) {
     case 1: hipLaunchKernelGGL(decode_attn_fused_kernel<1>, grid, block, 0, stream, p); break;
     case 2: hipLaunchKernelGGL(decode_attn_fused_kernel<2>, grid, block, 0, stream, p); break;
     case 4: hipLaunchKernelGGL(decode_attn_fused_kernel<4>, grid, block, 0, stream, p); break;
@@ -815,6 +835,7 @@ extern "C" int vis_decode_attn(const void* qkv, const void* cos_t, const void* s
   p.qkv_bs = qkv_bs; p.cache_bs = cache_bs; p.tab_bs = tab_bs;
   p.q_norm_w = nullptr; p.q_eps = 0.f;
   p.shared_len = 0;
+  p.fork_parent = nullptr; p.fork_len = nullptr;
   da_no_parts(p);
   return decode_attn_launch(p, out, batch, stream);
 }
@@ -825,10 +846,11 @@ extern "C" int vis_decode_attn(const void* qkv, const void* cos_t, const void* s
 // values, same arithmetic: results are bit-identical to vis_decode_attn.  The new token's slot must lie beyond the shared
 // range (it always does: the prefix is part of the prompt).  Streaming form only (Hkv * batch >= 128); smaller batches
 // ignore shared_len.
-extern "C" int vis_decode_attn_shared(const void* qkv, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
-                                      const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
-                                      int cache_tokens, int nsplit, float scale, int batch, long long qkv_bs,
-                                      long long cache_bs, long long tab_bs, int shared_len, hipStream_t stream) {
+static int decode_attn_shared_impl(const void* qkv, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                   const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                                   int cache_tokens, int nsplit, float scale, int batch, long long qkv_bs,
+                                   long long cache_bs, long long tab_bs, int shared_len, const int* fork_parent,
+                                   const int* fork_len, hipStream_t stream) {
   if (shared_len < 0 || shared_len % 64 != 0 || shared_len >= cache_tokens) return VIS_ERR_ARG;
   if (!qkv || !cos_t || !sin_t || !k_cache || !v_cache || !step_ptr || !part_o || !part_ml || !out)
     return VIS_ERR_ARG;
@@ -849,8 +871,35 @@ extern "C" int vis_decode_attn_shared(const void* qkv, const void* cos_t, const 
   p.qkv_bs = qkv_bs; p.cache_bs = cache_bs; p.tab_bs = tab_bs;
   p.q_norm_w = nullptr; p.q_eps = 0.f;
   p.shared_len = shared_len;
+  p.fork_parent = fork_parent; p.fork_len = fork_len;
   da_no_parts(p);
   return decode_attn_launch(p, out, batch, stream);
+}
+
+extern "C" int vis_decode_attn_shared(const void* qkv, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                      const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                                      int cache_tokens, int nsplit, float scale, int batch, long long qkv_bs,
+                                      long long cache_bs, long long tab_bs, int shared_len, hipStream_t stream) {
+  return decode_attn_shared_impl(qkv, cos_t, sin_t, k_cache, v_cache, step_ptr, part_o, part_ml, out, Hq, Hkv, HD, cache_tokens,
+                                 nsplit, scale, batch, qkv_bs, cache_bs, tab_bs, shared_len, nullptr, nullptr, stream);
+}
+
+// vis_decode_attn_shared with the shared range named per sequence, in DEVICE memory (one captured graph serves every fork
+// layout): sequence b reads keys / values [0, fork_len[b]) from sequence parent[b]'s cache and everything from fork_len[b] on -
+// the streaming form's early prefetch, the KV append and the new token included - from its own.  The n choices of one request
+// (generate_batch(.., n=)) are forks of the slot that ran the prompt pass.  Arithmetic, key order and split plan are the
+// unforked kernels': bit-identical to vis_decode_attn on caches that hold the parent's rows in every child.  Both forms (split:
+// a 64-key split lies on one side of a fork length).  The kernels clamp parent into [0, batch) and round fork_len down to a
+// multiple of 64 inside [0, cache_tokens), so no table content forms an address outside the caches; the contract (fork_len %
+// 64 == 0, parents are roots, a parent holds the rows itself, the new token's slot >= fork_len) is the caller's.
+extern "C" int vis_decode_attn_forked(const void* qkv, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                      const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                                      int cache_tokens, int nsplit, float scale, int batch, long long qkv_bs,
+                                      long long cache_bs, long long tab_bs, const int* parent, const int* fork_len,
+                                      hipStream_t stream) {
+  if (!parent || !fork_len || (((uintptr_t)parent | (uintptr_t)fork_len) & 3)) return VIS_ERR_ARG;
+  return decode_attn_shared_impl(qkv, cos_t, sin_t, k_cache, v_cache, step_ptr, part_o, part_ml, out, Hq, Hkv, HD, cache_tokens,
+                                 nsplit, scale, batch, qkv_bs, cache_bs, tab_bs, 0, parent, fork_len, stream);
 }
 
 // vis_decode_attn_shared without the qkv finalisation launch in front of it: the batched qkv projection (vis_gemm_decode_bf16 /
@@ -858,11 +907,12 @@ extern "C" int vis_decode_attn_shared(const void* qkv, const void* cos_t, const 
 // vis_skinny_finalize assumes); every (kv head, sequence) workgroup sums the 1152 columns it needs itself - fixed order, * sx[b] *
 // sw[n] for fp8 partials, + bias, one rounding to bf16: skinny_finalize_kernel's arithmetic (fin_plain_value), so results are
 // bit-identical to vis_skinny_finalize(..) + vis_decode_attn_shared(..), one launch and one ~5 us dependent kernel per layer less.
-extern "C" int vis_decode_attn_parts(const void* part, int ksplit, int slab_rows, const void* bias, const void* sx,
-                                     const void* sw, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
-                                     const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
-                                     int cache_tokens, int nsplit, float scale, int batch, long long cache_bs,
-                                     long long tab_bs, int shared_len, hipStream_t stream) {
+static int decode_attn_parts_impl(const void* part, int ksplit, int slab_rows, const void* bias, const void* sx,
+                                  const void* sw, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                  const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                                  int cache_tokens, int nsplit, float scale, int batch, long long cache_bs,
+                                  long long tab_bs, int shared_len, const int* fork_parent, const int* fork_len,
+                                  hipStream_t stream) {
   if (!part || !cos_t || !sin_t || !k_cache || !v_cache || !step_ptr || !part_o || !part_ml || !out) return VIS_ERR_ARG;
   if (shared_len < 0 || shared_len % 64 != 0 || shared_len >= cache_tokens) return VIS_ERR_ARG;
   if (batch <= 0 || batch > 64 || (batch > 1 && (cache_bs <= 0 || tab_bs < 0)) || (cache_bs % 8)) return VIS_ERR_ARG;
@@ -883,10 +933,35 @@ extern "C" int vis_decode_attn_parts(const void* part, int ksplit, int slab_rows
   p.qkv_bs = 0; p.cache_bs = cache_bs; p.tab_bs = tab_bs;
   p.q_norm_w = nullptr; p.q_eps = 0.f;
   p.shared_len = shared_len;
+  p.fork_parent = fork_parent; p.fork_len = fork_len;
   p.part_n = (Hq + 2 * Hkv) * 128;
   p.qkv_part = (const float*)part; p.part_stride = (long long)slab_rows * p.part_n; p.part_ks = ksplit;
   p.qkv_bias = (const bf16_t*)bias; p.part_sx = (const float*)sx; p.part_sw = (const float*)sw;
   return decode_attn_launch(p, out, batch, stream);
+}
+
+extern "C" int vis_decode_attn_parts(const void* part, int ksplit, int slab_rows, const void* bias, const void* sx,
+                                     const void* sw, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                     const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                                     int cache_tokens, int nsplit, float scale, int batch, long long cache_bs,
+                                     long long tab_bs, int shared_len, hipStream_t stream) {
+  return decode_attn_parts_impl(part, ksplit, slab_rows, bias, sx, sw, cos_t, sin_t, k_cache, v_cache, step_ptr, part_o, part_ml,
+                                out, Hq, Hkv, HD, cache_tokens, nsplit, scale, batch, cache_bs, tab_bs, shared_len, nullptr,
+                                nullptr, stream);
+}
+
+// vis_decode_attn_parts with the fork tables of vis_decode_attn_forked in place of shared_len: bit-identical to
+// vis_decode_attn_parts on caches that hold the parent's rows in every child.
+extern "C" int vis_decode_attn_parts_forked(const void* part, int ksplit, int slab_rows, const void* bias, const void* sx,
+                                            const void* sw, const void* cos_t, const void* sin_t, void* k_cache,
+                                            void* v_cache, const void* step_ptr, void* part_o, void* part_ml, void* out,
+                                            int Hq, int Hkv, int HD, int cache_tokens, int nsplit, float scale, int batch,
+                                            long long cache_bs, long long tab_bs, const int* parent, const int* fork_len,
+                                            hipStream_t stream) {
+  if (!parent || !fork_len || (((uintptr_t)parent | (uintptr_t)fork_len) & 3)) return VIS_ERR_ARG;
+  return decode_attn_parts_impl(part, ksplit, slab_rows, bias, sx, sw, cos_t, sin_t, k_cache, v_cache, step_ptr, part_o, part_ml,
+                                out, Hq, Hkv, HD, cache_tokens, nsplit, scale, batch, cache_bs, tab_bs, 0, parent, fork_len,
+                                stream);
 }
 
 // Cross-attention of one new token over a static key/value set (mllama cross layers, decode): q [Hq*128] straight
@@ -912,6 +987,7 @@ static int decode_cross_attn_impl(const void* q, const void* q_norm_w, const voi
   p.qkv_bs = q_bs; p.cache_bs = kv_bs; p.tab_bs = 0;
   p.q_norm_w = (const bf16_t*)q_norm_w; p.q_eps = eps;
   p.shared_len = 0;
+  p.fork_parent = nullptr; p.fork_len = nullptr;
   da_no_parts(p);
   return decode_attn_launch(p, out, batch, stream);
 }

@@ -305,6 +305,11 @@ struct DecAttnArgs {
   // text prefix a batch inspection shares, copied into every slot by the prompt passes) and are read from sequence 0's
   // copy - same values, so the same result bit for bit, but one HBM read + L2 hits instead of one HBM read per sequence
   int shared_len;
+  // forked kernels only (vis_decode_attn_forked / _parts_forked, FORK instantiations; null otherwise): [batch] device tables -
+  // sequence b reads keys / values [0, fork_len[b]) from sequence fork_parent[b]'s cache and everything from fork_len[b] on
+  // (the append and the new token included) from its own.  fork_len[b] is a multiple of 64 = one split = four streaming steps.
+  const int* fork_parent;
+  const int* fork_len;
   // vis_decode_attn_parts: `qkv` is null and the projection row is finalised HERE from the split-K partials of the batched
   // qkv projection (vis_gemm_decode_*): column n of sequence b = bf16(sum_k part[k * part_stride + b * part_n + n] (* sx[b] *
   // sw[n]) + bias[n]) - skinny_finalize_kernel's arithmetic bit for bit (fin_plain_value), minus its launch
@@ -432,7 +437,15 @@ __device__ __forceinline__ void chain_stage_qkv(const ChainCtx& cc, DecAttnLds<G
   if (publish && tid == 0) gr_st(cc.cue_g + hkv, 1u, cc.tag);
 }
 
-template <int G, bool CHAIN>
+// this sequence's row of the fork tables, made harmless: the parent clamped into [0, batch), the length rounded down to a
+// multiple of 64 and clamped into [0, cache_tokens) - no table content forms an address outside the caches (the host checks
+// the real contract, hip.check_fork_tables).  Uniform loads: one read of each table per workgroup.
+__device__ __forceinline__ void da_fork_row(const DecAttnArgs& p, int seq, int batch, int& parent, int& flen) {
+  parent = min(max(p.fork_parent[seq], 0), batch - 1);
+  flen = min(max(p.fork_len[seq], 0), p.cache_tokens - 1) & ~63;
+}
+
+template <int G, bool CHAIN, bool FORK = false>
 __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<G>& L, int hkv, int split, int seq,
                                                       const ChainCtx& cc) {
   constexpr int HD = 128, HALF = 64;
@@ -441,6 +454,16 @@ __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<
   auto& q_s = L.q_s; auto& knew_s = L.knew_s; auto& vnew_s = L.vnew_s; auto& sc = L.sc; auto& red = L.red; auto& ml = L.ml;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, h = lane >> 4;
+  // FORK: a split (64 keys) below the fork length reads the PARENT's rows; fork lengths are multiples of 64, so a split never
+  // straddles the two caches and the choice is workgroup-uniform.  The append below always goes to the sequence's own cache.
+  long long rd_seq = seq;
+  if constexpr (FORK) {
+    int parent, flen;
+    da_fork_row(p, seq, (int)gridDim.z, parent, flen);
+    if (split * DA_MAXKEYS < flen) rd_seq = parent;
+  }
+  const bf16_t* Kr = p.k_cache + rd_seq * p.cache_bs + (size_t)hkv * p.cache_tokens * 128;
+  const bf16_t* Vr = p.v_cache + rd_seq * p.cache_bs + (size_t)hkv * p.cache_tokens * 128;
   p.qkv += seq * p.qkv_bs;
   p.k_cache += seq * p.cache_bs;
   p.v_cache += seq * p.cache_bs;
@@ -461,13 +484,13 @@ __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<
   for (int gi = 0; gi < KGRP; ++gi) {
     const int row = min(ks + (wave + 4 * gi) * 16 + l15, p.cache_tokens - 1);
 #pragma unroll
-    for (int ds = 0; ds < 4; ++ds) kreg[gi][ds] = *(const u32x4*)(Kh + (size_t)row * HD + ds * 32 + 8 * h);
+    for (int ds = 0; ds < 4; ++ds) kreg[gi][ds] = *(const u32x4*)(Kr + (size_t)row * HD + ds * 32 + 8 * h);
   }
   uint32_t vreg[VROWS];
 #pragma unroll
   for (int i = 0; i < VROWS; ++i) {
     const int row = min(ks + wave + 4 * i, p.cache_tokens - 1);
-    vreg[i] = *(const uint32_t*)(Vh + (size_t)row * HD + 2 * lane);
+    vreg[i] = *(const uint32_t*)(Vr + (size_t)row * HD + 2 * lane);
   }
 
   const int slot = min(*p.step_ptr, p.cache_tokens - 1);

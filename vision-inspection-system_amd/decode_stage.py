@@ -11,6 +11,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence
 import torch
 
 from . import hip
+from .fork import check_fork_tables, fork_layout
 from .pick import PickStage
 
 _LOG = logging.getLogger("vision_inspection_system_amd.engine")
@@ -70,6 +71,94 @@ class DecodeStage(PickStage):
         self.dec_head = {"bf16": (lm_head,), "fp8": q8_head, "mxfp4": q4_head}
         self.dec_n_self = sum(1 for L in self.dec_layers if not L.cross)     # chained launches per step
         self._init_pick_stage()      # the request switches of the next-token pick (pick.py)
+        # several choices per request (generate_batch(.., n=)): while a batch has children, every batched self-attention launch
+        # is the forked one and reads these two device tables (one row per slot; a graph captured once serves every layout)
+        self.fork_on = False
+        self.fork_parent_b: Optional[torch.Tensor] = None
+        self.fork_len_b: Optional[torch.Tensor] = None
+
+    def _attn_share(self, B: int, shared: int) -> dict:
+        """How the batched self-attention of B slots names the keys a slot reads from another slot's cache: the fork tables
+        while the batch has children (the batch's text prefix is in them too), else the one shared length."""
+        if self.fork_on:
+            return dict(fork=(self.fork_parent_b[:B], self.fork_len_b[:B]))
+        return dict(shared_len=shared)
+
+    def _fork_model_state(self, root: int, child: int) -> None:
+        """Hook: copy what the model keeps per slot besides the self KV cache (rope rows, cross-attention keys) from ``root``
+        into ``child``."""
+
+    def _fork_choices(self, roots: Sequence[Optional[int]], n: Sequence[int], prefix_len: int, seeds, penalties,
+                      shaping) -> List[Optional[List[int]]]:
+        """After the prompt passes of a batch (request j in slot roots[j], None = failed): give request j its n[j] - 1 further
+        choices.  A child slot gets the rows of its root's prompt behind the fork length (at most 63, torch copies), the
+        model's per-slot state, the root's last-row logits and then the SAME first pick a prompt pass ends with - a fresh
+        grammar state, stop record and logprob row, the prompt's penalty flags, the request's shaping parameters, its own
+        seed (seeds[j] + i) - so every per-slot row is what a prompt pass of its own would have left.  Returns the slots of
+        every request's choices and switches the forked attention on when there is a child."""
+        live = [j for j in range(len(roots)) if roots[j] is not None]
+        lay = fork_layout([self.slot_prompt_len[roots[j]] for j in live], [n[j] for j in live], prefix_len, self.max_batch)
+        out: List[Optional[List[int]]] = [None] * len(roots)
+        for i, j in enumerate(live):
+            if roots[j] != i:
+                raise RuntimeError("prompt passes did not fill consecutive slots")
+            out[j] = lay.slots[i]
+        for child, root, lo, hi in lay.copies:
+            j = live[root]
+            self.kcache_b[child][:, :, lo:hi].copy_(self.kcache_b[root][:, :, lo:hi])
+            self.vcache_b[child][:, :, lo:hi].copy_(self.vcache_b[root][:, :, lo:hi])
+            self._fork_model_state(root, child)
+            self.logits_b[child].copy_(self.logits_b[root])
+            self.step_b[child:child + 1].fill_(hi - 1)
+            self.slot_prompt_len[child] = hi
+            i = out[j].index(child)
+            if seeds is not None:
+                self._slot_seed[child] = seeds[j] + i
+            if penalties is not None:
+                self._slot_pen[child] = penalties[j]
+            if shaping is not None:
+                self._slot_shape[child] = shaping[j]
+            self._prompt_pick(child, self._slot_ids[root], self.logits_b[child], self.tokens_b[child],
+                              self.cur_b[child:child + 1], self.step_b[child:child + 1])
+        if lay.copies:
+            check_fork_tables(lay.parent, lay.fork_len, self.max_ctx, lay.holds)
+            if self.fork_parent_b is None:
+                self.fork_parent_b = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+                self.fork_len_b = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+            nb = len(lay.parent)
+            self.fork_parent_b[:nb].copy_(torch.tensor(lay.parent, dtype=torch.int32))
+            self.fork_len_b[:nb].copy_(torch.tensor(lay.fork_len, dtype=torch.int32))
+            self.fork_on = True
+        return out
+
+    def _gather_choices(self, choice_slots: Sequence[Optional[List[int]]], errors: Sequence, outs_by_slot: Sequence[list],
+                        starts: Sequence[int], eos, ignore_eos: bool, keep_eos: bool, nested: bool, mask_error) -> list:
+        """After the run: cut every choice's tokens (``_finish``), record its logprobs, and shape the results per request - one
+        token list (``nested`` False: one choice each, as without ``n``) or a list of them; ``last_finish`` and
+        ``last_logprobs`` nest the same way.  A failed request's entry is its exception; a request with a choice the grammar
+        mask could not continue gets ``mask_error()``."""
+        flat = [s for cs in choice_slots if cs is not None for s in cs]
+        cut = dict(zip(flat, self._finish([(s, outs_by_slot[s]) for s in flat], eos, ignore_eos, keep_eos=keep_eos)))
+        fin = dict(zip(flat, self.last_finish))
+        self._record_logprobs([(s, starts[s], len(cut[s])) for s in flat])
+        lps = dict(zip(flat, self.last_logprobs)) if self.last_logprobs is not None else None
+        failed = set(self._mask_failed(flat))
+        outs, fins, lpo = [], [], []
+        for j, cs in enumerate(choice_slots):
+            if cs is None:
+                outs.append(errors[j])
+                fins.append(None)
+                lpo.append(None)
+                continue
+            one = (lambda d: [d[s] for s in cs]) if nested else (lambda d: d[cs[0]])
+            lpo.append(one(lps) if lps is not None else None)
+            bad = bool(failed.intersection(cs))
+            outs.append(mask_error() if bad else one(cut))
+            fins.append(None if bad else one(fin))
+        self.last_finish = fins
+        if lps is not None:
+            self.last_logprobs = lpo
+        return outs
 
     # ------------------------------------------------------------------ steps whose projections write their finished rows
     def _decode_step(self, chained: Optional[bool] = None) -> None:
@@ -145,7 +234,7 @@ class DecodeStage(PickStage):
                 if not chained:
                     proj(x, _wt(L, "qkv_w", fmt), qkv, bias=L.bias, norm_w=lw.ln1_w, eps=eps)
                     hip.decode_attn(qkv, cos, sin, kc, vc, step, self.part_o, self.part_ml, att, Hq, Hkv, D, self.nsplit, scale,
-                                    shared_len=shared)
+                                    **(self._attn_share(B, shared) if B else {}))
                     proj(att, _wt(L, "o_w", fmt), x2, residual=x)
             proj(x2, _wt(L, "gateup_w", fmt), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
             proj(act, _wt(L, "down_w", fmt), x, residual=x2)
@@ -233,12 +322,12 @@ class DecodeStage(PickStage):
                 self._decode_cross_attn(L, q, att, B)
             elif self.fold_qkv:    # the attention workgroups finalise the qkv columns they read (same bits, one launch less)
                 hip.decode_attn_parts(part, ks, cos, sin, self.kcache_b[:B, L.idx], self.vcache_b[:B, L.idx], step, self.part_o,
-                                      self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, bias=L.bias, shared_len=shared,
-                                      **scales(a_x, wt))
+                                      self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, bias=L.bias,
+                                      **self._attn_share(B, shared), **scales(a_x, wt))
             else:
                 finalize(part, ks, qkv, nq, bias=L.bias, eps=eps, **scales(a_x, wt))
                 hip.decode_attn(qkv, cos, sin, self.kcache_b[:B, L.idx], self.vcache_b[:B, L.idx], step, self.part_o,
-                                self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, shared_len=shared)
+                                self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, **self._attn_share(B, shared))
             ks = gemm_o(att, *_wt(L, "o_w", fmt_o), part=part)
             finalize(part, ks, x2, H, residual=x, norm_w=lw.ln2_w, eps=eps, **to_x2)
             wt = _wt(L, "gateup_w", fmt)
@@ -304,7 +393,7 @@ class DecodeStage(PickStage):
                 self._decode_cross_attn(L, q, att, B)
             else:
                 hip.decode_attn(qkv, cos, sin, self.kcache_b[:B, L.idx], self.vcache_b[:B, L.idx], self.step_b[:B], self.part_o,
-                                self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, shared_len=shared)
+                                self.part_ml, att, Hq, Hkv, D, self.nsplit, scale, **self._attn_share(B, shared))
             if fp8:     # the o projection keeps bf16 weights (its input comes from the attention kernel); its epilogue writes MX
                 hip.decode_proj(att, lw.o_w, ws, hip.DP_RESID_NORMW, out=x2, out_q=x2q, out_qs=x2qs, residual=x,
                                 norm_w=lw.ln2_w, ssq_out=s2)

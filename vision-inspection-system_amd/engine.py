@@ -27,6 +27,7 @@ import torch
 
 from . import hip
 from .decode_stage import DecodeLayer, DecodeStage
+from .fork import check_n_list
 from .json_mode import JsonModeError, check_schema
 from .logprobs import check_k
 from .penalties import check_penalties
@@ -1120,8 +1121,9 @@ class Qwen2VLEngine(DecodeStage):
 
     def _ensure_graph(self, batch: int = 0, chained: bool = False) -> torch.cuda.CUDAGraph:
         # temperature, seed and the batch size are kernel arguments baked into the graph; so is what _pick_key() names
-        key = (self.temperature, self.seed, batch, self.batch_shared_len if batch else 0, bool(chained) and not batch) \
-            + self._pick_key() + self._stop_key() + self._shape_key()
+        fork = bool(batch) and self.fork_on     # the fork tables are device memory: one graph for every layout
+        key = (self.temperature, self.seed, batch, self.batch_shared_len if batch and not fork else 0,
+               bool(chained) and not batch, fork) + self._pick_key() + self._stop_key() + self._shape_key()
         return self._captured_step(self._graphs, 8, key, batch, chained)
 
     def decode(self, n_steps: int, use_graph: bool = True) -> None:
@@ -1251,7 +1253,7 @@ class Qwen2VLEngine(DecodeStage):
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                        json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None, top_k=None, min_p=None, logit_bias=None) -> list:
+                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
@@ -1264,7 +1266,14 @@ class Qwen2VLEngine(DecodeStage):
         with one value per request.  ``json_schema``: as in generate, one schema for the whole group.  ``stop``: as in
         generate, one set for the whole group; the shared loop ends when every row has ended.  ``last_finish`` holds one
         (reason, cut) per request, None for a failed one.  ``top_k``, ``min_p``, ``logit_bias``: as in generate, each one
-        value for the group or a sequence with one value (or None) per request."""
+        value for the group or a sequence with one value (or None) per request.
+        ``n``: None, an integer >= 1 or one integer per request - that many sampled choices of each request from ONE prompt
+        pass (fork.py): the further choices take slots behind the requests', read the prompt's keys / values from the slot
+        that ran the prompt pass (vis_decode_attn_forked) and sample with seeds[j] + i (without seeds: the slot-derived seed
+        of the slot they land in).  All choices together must fit max_batch.  With ``n`` given, the entry of a request is a
+        list of n[j] token lists (for a failed request the exception object, as without), and ``last_logprobs`` /
+        ``last_finish`` nest the same way.  At temperature 0 all choices of a request are equal; they are decoded all the
+        same.  A slot is still a full-size cache: ``n`` saves prompt passes and attention traffic, not cache memory."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -1277,7 +1286,18 @@ class Qwen2VLEngine(DecodeStage):
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
         shaping = check_shaping(top_k, min_p, logit_bias, n_req)
         check_stop(stop)
-        if n_req == 1:
+        ns = check_n_list(n, n_req, self.max_batch)
+        if n_req == 1 and ns is not None and ns[0] == 1:      # one choice: today's route, the results nested
+            out = self.generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, logprobs,
+                                      json_mode, top_p, seeds, repetition_penalty, frequency_penalty, presence_penalty,
+                                      json_schema, stop, top_k, min_p, logit_bias)
+            if not isinstance(out[0], Exception):
+                out = [[out[0]]]
+                self.last_finish = [[self.last_finish[0]]]
+                if self.last_logprobs is not None:
+                    self.last_logprobs = [[self.last_logprobs[0]]]
+            return out
+        if n_req == 1 and ns is None:
             r = requests[0]
             if callable(r):
                 try:
@@ -1297,11 +1317,19 @@ class Qwen2VLEngine(DecodeStage):
         with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
                                 shaping=shaping):
             self.stop_eos = not ignore_eos
-            return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, seeds,
-                                        penalties, shaping)
+            try:
+                return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
+                                            seeds, penalties, shaping, ns)
+            finally:
+                self.fork_on = False
+
+    def _fork_model_state(self, root: int, child: int) -> None:
+        """A further choice decodes at its root's M-RoPE positions (DecodeStage hook)."""
+        self.cos_b[child].copy_(self.cos_b[root])
+        self.sin_b[child].copy_(self.sin_b[root])
 
     def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                        seeds=None, penalties=None, shaping=None) -> list:
+                        seeds=None, penalties=None, shaping=None, ns=None) -> list:
         n_req = len(requests)
         # every prompt's own limit (prompt + new tokens <= context) is applied by its prefill; the shared loop below
         # runs to the limit of the longest one
@@ -1311,11 +1339,13 @@ class Qwen2VLEngine(DecodeStage):
                                           seeds=seeds, penalties=penalties, shaping=shaping)
         ev[1].record()
         live = [b for b in range(n_req) if slots[b] is not None]
-        B = len(live)
-        if B == 0:
+        if not live:
             self._record_logprobs([None] * n_req)
             self.last_finish = [None] * n_req
             return list(errors)
+        # the further choices of every request: slots behind the roots', forked from them (no launch and no copy without them)
+        choice_slots = self._fork_choices(slots, ns or [1] * n_req, self.batch_shared_len, seeds, penalties, shaping)
+        B = sum(len(cs) for cs in choice_slots if cs is not None)
         longest = max(self.slot_prompt_len[slots[b]] for b in live)
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
         eos = set(self.cfg.eos_ids)
@@ -1345,14 +1375,5 @@ class Qwen2VLEngine(DecodeStage):
         # host waiting for the lazy requests' decodes is inside prefill_ms here: it is the time until all prompts are in
         self.last_timing = {"prompt_tokens": longest, "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
-        outs = self._finish([(slots[b], outs[slots[b]]) if slots[b] is not None else None for b in range(n_req)], eos, ignore_eos)
-        self._record_logprobs([(slots[b], starts[slots[b]], len(outs[b])) if slots[b] is not None else None
-                               for b in range(n_req)])
-        failed = set(self._mask_failed(range(B)))
-        for b in range(n_req):
-            if slots[b] is None:
-                outs[b] = errors[b]
-            elif slots[b] in failed:
-                outs[b] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
-                self.last_finish[b] = None
-        return outs
+        return self._gather_choices(choice_slots, errors, outs, starts, eos, ignore_eos, False, ns is not None,
+                                    lambda: JsonModeError("json_mode: the vocabulary could not continue the JSON text"))

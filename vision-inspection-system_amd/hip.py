@@ -53,6 +53,8 @@ _SIGS = {
     "vis_decode_attn": "ppppppppp" + "iiiii" + "f" + "i" + "lll" + "p",
     "vis_decode_attn_shared": "ppppppppp" + "iiiii" + "f" + "i" + "lll" + "i" + "p",
     "vis_decode_attn_parts": "p" + "ii" + "p" * 11 + "iiiii" + "f" + "i" + "ll" + "i" + "p",
+    "vis_decode_attn_forked": "ppppppppp" + "iiiii" + "f" + "i" + "lll" + "pp" + "p",
+    "vis_decode_attn_parts_forked": "p" + "ii" + "p" * 11 + "iiiii" + "f" + "i" + "ll" + "pp" + "p",
     "vis_decode_chain_sync_ints": "",
     "vis_decode_chain_ws_bytes": "iii",
     "vis_decode_chain_ctx_limit": "iii",
@@ -995,14 +997,28 @@ def decode_gemm_mxfp4(x: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, part:
     return ks
 
 
+def _fork_tables(who: str, fork, B: int, device, shared_len: int):
+    """(parent, fork_len) of a forked attention call: int32 device tensors with one entry per sequence."""
+    par, fl = fork
+    if shared_len:
+        raise HipLibraryError(f"{who}: give the fork tables or shared_len, not both")
+    for t in (par, fl):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous() \
+                or t.device != device:
+            raise HipLibraryError(f"{who}: fork tables must be contiguous int32 device tensors of {B} entries")
+    return par, fl
+
+
 def decode_attn_parts(part: torch.Tensor, ksplit: int, cos_t: torch.Tensor, sin_t: torch.Tensor, k_cache: torch.Tensor,
                       v_cache: torch.Tensor, step: torch.Tensor, part_o: torch.Tensor, part_ml: torch.Tensor,
                       out: torch.Tensor, n_q: int, n_kv: int, head_dim: int, nsplit: int, scale: float,
                       bias: Optional[torch.Tensor] = None, sx: Optional[torch.Tensor] = None,
-                      sw: Optional[torch.Tensor] = None, shared_len: int = 0) -> torch.Tensor:
+                      sw: Optional[torch.Tensor] = None, shared_len: int = 0,
+                      fork: Optional[tuple] = None) -> torch.Tensor:
     """``skinny_finalize[_fp8](part, ksplit, qkv, ..)`` + ``decode_attn(qkv, ..)`` of a batch as ONE launch: the attention
     workgroups finalise the qkv columns they need from the projection's partial slabs (same bits as the pair).
-    Batch of B: caches [B,Hkv,T,D], tables [B,T,D], step [B], out [B, Hq*D]; ``part`` as decode_gemm[_fp8] left it."""
+    Batch of B: caches [B,Hkv,T,D], tables [B,T,D], step [B], out [B, Hq*D]; ``part`` as decode_gemm[_fp8] left it.
+    ``fork`` = (parent, fork_len), two int32 device tensors [B], in place of ``shared_len``: vis_decode_attn_parts_forked."""
     _bf16(k_cache, "k_cache")
     if step.dtype != torch.int32 or cos_t.dtype != torch.float32 or sin_t.dtype != torch.float32 or part.dtype != torch.float32:
         raise HipLibraryError("decode_attn_parts: step int32 / cos,sin,part f32 required")
@@ -1030,6 +1046,14 @@ def decode_attn_parts(part: torch.Tensor, ksplit: int, cos_t: torch.Tensor, sin_
         raise HipLibraryError("decode_attn_parts: bad scales")
     if v_cache.stride(0) != k_cache.stride(0) or cos_t.stride(0) != sin_t.stride(0):
         raise HipLibraryError("decode_attn_parts: k/v caches (cos/sin tables) must share their batch stride")
+    if fork is not None:
+        par, fl = _fork_tables("decode_attn_parts", fork, B, k_cache.device, shared_len)
+        rc = load().vis_decode_attn_parts_forked(_ptr(part), int(ksplit), rows, _ptr(bias), _ptr(sx), _ptr(sw), _ptr(cos_t),
+                                                 _ptr(sin_t), _ptr(k_cache), _ptr(v_cache), _ptr(step), _ptr(part_o),
+                                                 _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, T, nsplit, scale, B,
+                                                 k_cache.stride(0), cos_t.stride(0), _ptr(par), _ptr(fl), _stream())
+        _check(rc, "vis_decode_attn_parts_forked")
+        return out
     rc = load().vis_decode_attn_parts(_ptr(part), int(ksplit), rows, _ptr(bias), _ptr(sx), _ptr(sw), _ptr(cos_t), _ptr(sin_t),
                                       _ptr(k_cache), _ptr(v_cache), _ptr(step), _ptr(part_o), _ptr(part_ml), _ptr(out),
                                       n_q, n_kv, head_dim, T, nsplit, scale, B, k_cache.stride(0), cos_t.stride(0),
@@ -1041,13 +1065,15 @@ def decode_attn_parts(part: torch.Tensor, ksplit: int, cos_t: torch.Tensor, sin_
 def decode_attn(qkv: torch.Tensor, cos_t: torch.Tensor, sin_t: torch.Tensor, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, step: torch.Tensor, part_o: torch.Tensor, part_ml: torch.Tensor,
                 out: torch.Tensor, n_q: int, n_kv: int, head_dim: int, nsplit: int, scale: float,
-                shared_len: int = 0) -> torch.Tensor:
+                shared_len: int = 0, fork: Optional[tuple] = None) -> torch.Tensor:
     """Fused decode step attention: rope(q,k) + KV append at slot step[b] + attention over step[b]+1 keys.
 
     Single sequence: qkv [nq*D], caches [Hkv,T,D], tables [T,D], step [1].
     Batch of B: qkv [B, nq*D], caches [B,Hkv,T,D], tables [B,T,D], step [B], out [B, Hq*D].
     ``shared_len`` (batch only, a multiple of 64): the first shared_len cached keys are identical in every sequence and are
-    read from sequence 0's copy (vis_decode_attn_shared; same result bit for bit)."""
+    read from sequence 0's copy (vis_decode_attn_shared; same result bit for bit).
+    ``fork`` (batch only) = (parent, fork_len), two int32 device tensors [B]: sequence b reads keys [0, fork_len[b]) from
+    sequence parent[b]'s cache (vis_decode_attn_forked; same result bit for bit)."""
     _bf16(qkv, "qkv"); _bf16(k_cache, "k_cache")
     if step.dtype != torch.int32 or cos_t.dtype != torch.float32 or sin_t.dtype != torch.float32:
         raise HipLibraryError("decode_attn: step int32 / cos,sin f32 required")
@@ -1072,6 +1098,15 @@ def decode_attn(qkv: torch.Tensor, cos_t: torch.Tensor, sin_t: torch.Tensor, k_c
     if batched and (v_cache.stride(0) != cache_bs or cos_t.stride(0) != sin_t.stride(0)):
         raise HipLibraryError("decode_attn: k/v caches (cos/sin tables) must share their batch stride")
     tab_bs = cos_t.stride(0) if batched else 0
+    if fork is not None:
+        if not batched:
+            raise HipLibraryError("decode_attn: fork tables need batched caches [B, Hkv, T, D]")
+        par, fl = _fork_tables("decode_attn", fork, B, k_cache.device, shared_len)
+        rc = load().vis_decode_attn_forked(_ptr(qkv), _ptr(cos_t), _ptr(sin_t), _ptr(k_cache), _ptr(v_cache), _ptr(step),
+                                           _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, T, nsplit, scale,
+                                           B, qkv_bs, cache_bs, tab_bs, _ptr(par), _ptr(fl), _stream())
+        _check(rc, "vis_decode_attn_forked")
+        return out
     if shared_len and batched:
         rc = load().vis_decode_attn_shared(_ptr(qkv), _ptr(cos_t), _ptr(sin_t), _ptr(k_cache), _ptr(v_cache), _ptr(step),
                                            _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, T, nsplit, scale,

@@ -32,6 +32,7 @@ import torch
 
 from . import hip
 from .decode_stage import DecodeLayer, DecodeStage
+from .fork import check_n_list
 from .json_mode import JsonModeError, check_schema
 from .logprobs import check_k
 from .penalties import check_penalties
@@ -643,7 +644,7 @@ class MllamaEngine(DecodeStage):
         return self._captured_step(self._graphs, 6, key, 0, chained)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B) + self._pick_key() + self._stop_key() + self._shape_key()
+        key = (self.temperature, self.seed, B, self.fork_on) + self._pick_key() + self._stop_key() + self._shape_key()
         return self._captured_step(self._graphs_b, 4, key, B, False)
 
     def decode(self, n_steps: int, use_graph: bool = True) -> None:
@@ -656,7 +657,7 @@ class MllamaEngine(DecodeStage):
                        chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
                        top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None, top_k=None, min_p=None, logit_bias=None) -> list:
+                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
@@ -666,7 +667,10 @@ class MllamaEngine(DecodeStage):
         not be continued gets a JsonModeError.  ``top_p`` / ``seeds`` and the three penalties (a number or one value per request): as in
         Qwen2VLEngine.generate_batch; so are ``json_schema`` and ``stop`` (one schema, one stop set for the whole group) and
         ``last_finish``.  A reply that ended on EOS keeps its EOS token here, with or without stop strings.  ``top_k``,
-        ``min_p``, ``logit_bias`` (one value for the group or one per request): as in Qwen2VLEngine.generate_batch."""
+        ``min_p``, ``logit_bias`` (one value for the group or one per request): as in Qwen2VLEngine.generate_batch.  ``n``
+        (several choices per request from one prompt pass): as in Qwen2VLEngine.generate_batch; the image's cross-attention
+        keys / values are copied whole into every further choice's slot, the forked attention serves the self-attention
+        layers."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -682,8 +686,20 @@ class MllamaEngine(DecodeStage):
         shaping = check_shaping(top_k, min_p, logit_bias, n_req)
         pen0.update(shaping_kwargs(shaping))
         check_stop(stop)
+        ns = check_n_list(n, n_req, self.max_batch)
+        if n_req == 1 and ns is not None and ns[0] == 1:      # one choice: today's route, the results nested
+            out = self.generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, logprobs,
+                                      json_mode, top_p, seeds, repetition_penalty, frequency_penalty, presence_penalty,
+                                      json_schema, stop, top_k, min_p, logit_bias)
+            if not isinstance(out[0], Exception):
+                out = [[out[0]]]
+                self.last_finish = [[self.last_finish[0]]]
+                if self.last_logprobs is not None:
+                    self.last_logprobs = [[self.last_logprobs[0]]]
+            return out
+        single = n_req == 1 and ns is None
         lazy = any(callable(r) for r in requests)
-        if lazy and n_req == 1:
+        if lazy and single:
             # one lazy request (always the case with max_batch == 1, where the batched buffers do not even exist): the
             # single-sequence path; its failure stays its own, as in the batched form
             try:
@@ -694,8 +710,8 @@ class MllamaEngine(DecodeStage):
                 self.last_logprobs = [None] if logprobs is not None else None
                 self.last_finish = [None]
                 return [e]
-        if not lazy and (n_req == 1 or any(fr is None for _, fr in requests)):
-            if n_req > 1:
+        if not lazy and (single or any(fr is None for _, fr in requests)):
+            if not single:
                 raise ValueError("generate_batch needs an image in every request (text-only prompts go through generate)")
             ids, fr = requests[0]
             try:
@@ -706,11 +722,20 @@ class MllamaEngine(DecodeStage):
         with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
                                 shaping=shaping):
             self.stop_eos = bool(stop_on_eos)
-            return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds,
-                                        penalties, shaping)
+            try:
+                return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds,
+                                            penalties, shaping, ns)
+            finally:
+                self.fork_on = False
+
+    def _fork_model_state(self, root: int, child: int) -> None:
+        """A further choice attends to its root's image: the cross-attention keys / values, whole (DecodeStage hook)."""
+        self.xk_b[child].copy_(self.xk_b[root])
+        self.xv_b[child].copy_(self.xv_b[root])
+        self.nkeys_b[child:child + 1].copy_(self.nkeys_b[root:root + 1])
 
     def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds=None,
-                        penalties=None, shaping=None) -> list:
+                        penalties=None, shaping=None, ns=None) -> list:
         n_req = len(requests)
         lazy = any(callable(r) for r in requests)
         slots: List[Optional[int]] = [None] * n_req
@@ -813,6 +838,9 @@ class MllamaEngine(DecodeStage):
             self._record_logprobs([None] * n_req)
             self.last_finish = [None] * n_req
             return list(errors)
+        # the further choices of every request: slots behind the roots', forked from them (no launch and no copy without them)
+        choice_slots = self._fork_choices(slots, ns or [1] * n_req, 0, seeds, penalties, shaping)
+        B = sum(len(cs) for cs in choice_slots if cs is not None)
         longest = max(self.slot_prompt_len[s] for s in range(B))
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
         eos = set(self.cfg.eos_ids)
@@ -841,18 +869,8 @@ class MllamaEngine(DecodeStage):
         outs = collect(done)
         self.last_timing = {"prompt_tokens": longest, "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
-        outs = self._finish([(slots[b], outs[slots[b]]) if slots[b] is not None else None for b in range(n_req)], eos,
-                            not stop_on_eos, keep_eos=True)
-        self._record_logprobs([(slots[b], starts[slots[b]], len(outs[b])) if slots[b] is not None else None
-                               for b in range(n_req)])
-        failed = set(self._mask_failed(range(B)))
-        for b in range(n_req):
-            if slots[b] is None:
-                outs[b] = errors[b]
-            elif slots[b] in failed:
-                outs[b] = JsonModeError("json_mode: the vocabulary could not continue the JSON text")
-                self.last_finish[b] = None
-        return outs
+        return self._gather_choices(choice_slots, errors, outs, starts, eos, not stop_on_eos, True, ns is not None,
+                                    lambda: JsonModeError("json_mode: the vocabulary could not continue the JSON text"))
 
     def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,

@@ -58,6 +58,8 @@ class PickStage:
         self._stop: Optional[StopBuffers] = None
         # how each request of the last run ended: (reason, cut) with reason "eos" / "stop" / "length", None for a failed one
         self.last_finish: Optional[list] = None
+        # the device ids of the prompt last picked from in each slot
+        self._slot_ids: Dict[int, torch.Tensor] = {}
 
     # ------------------------------------------------------------------ one request's switches
     @contextlib.contextmanager
@@ -317,6 +319,7 @@ class PickStage:
     def _prompt_pick(self, slot: int, ids_dev: torch.Tensor, logits, tokens, cur_token, step) -> None:
         """The first token of ``slot``, from the logits of its prompt's last row: a fresh grammar state, row seed, token
         statistics and shaping parameters, then the pick and its logprobs."""
+        self._slot_ids[slot] = ids_dev      # a further choice of this request (DecodeStage._fork_choices) starts from them too
         if self._mask is not None:
             self._mask.reset(slot)
         self._seed_slot(slot)
