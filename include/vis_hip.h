@@ -369,6 +369,30 @@ int vis_stop_scan(void* state, const void* tokens, int max_tokens, const void* s
                   const void* byte_class, const void* hits, int cap_states, int cap_classes, int eos_on, int batch,
                   vis_stream_t stream);
 
+/* Token-by-token publication of a reply while the decode loop runs (csrc/stream_publish.hip; stream.py is the reference and
+ * the reader).  One launch AFTER vis_stop_scan: for every row b < batch whose stop-scan record (stop_state, int32 [batch][8])
+ * covers position step[b] - 1 it appends one 16-byte record {token id, safe_bytes, status, cut} at records[b][step[b] - 1]
+ * (int32 [batch][capacity][4], one vector store) and then stores count[b] = step[b] with a system-scope release store;
+ * start[b] = step[b] - 1 goes out with the row's first record.  records, count and start are HOST memory of
+ * vis_host_coherent_alloc (the device addresses).  safe_bytes: bytes of the reply that can no longer be taken back - open
+ * row: bytes so far - depth[state] (depth u8 [n_states]: the depth of every automaton state, i.e. the length of the longest
+ * suffix of the text that is a prefix of a stop string; a state outside the table counts 0); EOS: the bytes in front of the
+ * EOS token; stop: cut, where the match starts.  status: 0 open, 1 EOS, 2 stop.  pub: device int32 [batch], zero = fresh,
+ * mirrors count: a launch repeated at the same step changes nothing.  A row that has ended is published once, at the step
+ * that ended it, and never again (its count is frozen); nothing published is rewritten.  A position at or beyond capacity or
+ * max_tokens is never written.
+ * VIS_ERR_ARG and nothing launched: null pointer, stop_state / records not 16-byte aligned, another pointer not 4-byte
+ * aligned, batch outside 1..64, max_tokens <= 0, capacity < max_tokens, n_states outside 1..257. */
+int vis_stream_publish(const void* stop_state, const void* tokens, int max_tokens, const void* step_ptr, const void* depth,
+                       int n_states, void* pub, void* records, int capacity, void* count, void* start, int batch,
+                       vis_stream_t stream);
+
+/* Host memory a running kernel stores to coherently: hipHostMalloc with the coherent and mapped flags, zero-filled.
+ * *host_ptr: the address the host reads; *dev_ptr: the address kernels are given.  VIS_ERR_ARG: null pointer, bytes outside
+ * 1..2^32; VIS_ERR_LAUNCH: the runtime refused.  vis_host_free takes the host address. */
+int vis_host_coherent_alloc(void** host_ptr, void** dev_ptr, long long bytes);
+int vis_host_free(void* host_ptr);
+
 /* K10 (batched decode), first half.  For up to 64 in-flight sequences the weight matrix is streamed from HBM
  * ONCE per step by <= 256 persistent workgroups (one per CU, 7-stage LDS-DMA ring, stream-K cut of the
  * (128-column tile, K-step) sequence).  part[slot][R][N] (f32), R = 16 / 32 / 64 for B <= 16 / 32 / 64 (one, two or four

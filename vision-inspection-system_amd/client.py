@@ -70,6 +70,143 @@ class ChatCompletion:
     timings: Dict[str, float] = field(default_factory=dict)
 
 
+@dataclass
+class _Delta:
+    role: Optional[str] = None
+    content: Optional[str] = None
+
+
+@dataclass
+class _ChunkChoice:
+    delta: _Delta
+    index: int = 0
+    finish_reason: Optional[str] = None
+    logprobs: Optional[ChoiceLogprobs] = None      # always None: per-chunk logprobs are not offered
+
+
+@dataclass
+class ChatCompletionChunk:
+    """One element of a ``stream=True`` reply (OpenAI's chat.completion.chunk).  Per choice: first a chunk whose delta has
+    role "assistant" and empty content, then content chunks, then one with an empty delta and the finish_reason; with
+    stream_options={"include_usage": True} a last chunk with no choices and the usage."""
+    choices: List[_ChunkChoice]
+    model: str = ""
+    object: str = "chat.completion.chunk"
+    usage: Optional[Dict[str, int]] = None
+    request_index: int = 0      # extension: which request of a complete_many call the chunk belongs to
+
+
+def _role_chunk(model: str, request: int, choice: int) -> ChatCompletionChunk:
+    return ChatCompletionChunk([_ChunkChoice(_Delta(role="assistant", content=""), index=choice)], model, request_index=request)
+
+
+def _content_chunk(model: str, request: int, choice: int, text: str) -> ChatCompletionChunk:
+    return ChatCompletionChunk([_ChunkChoice(_Delta(content=text), index=choice)], model, request_index=request)
+
+
+def _finish_chunk(model: str, request: int, choice: int, reason: str) -> ChatCompletionChunk:
+    return ChatCompletionChunk([_ChunkChoice(_Delta(), index=choice, finish_reason=reason)], model, request_index=request)
+
+
+def _usage_chunk(model: str, request: int, usage: Dict[str, int]) -> ChatCompletionChunk:
+    return ChatCompletionChunk([], model, usage=dict(usage), request_index=request)
+
+
+def _chunks_of(completion: "ChatCompletion", request: int, include_usage: bool):
+    """A finished reply as its chunk sequence: role, one content chunk and the finish chunk per choice."""
+    for c in completion.choices:
+        yield _role_chunk(completion.model, request, c.index)
+        if c.message.content:
+            yield _content_chunk(completion.model, request, c.index, c.message.content)
+        yield _finish_chunk(completion.model, request, c.index, c.finish_reason)
+    if include_usage:
+        u = completion.usage or {"prompt_tokens": 0, "completion_tokens": 0, "total_tokens": 0}
+        yield _usage_chunk(completion.model, request, u)
+
+
+class ChatCompletionStream:
+    """What ``create(..., stream=True)`` returns: an iterator of ChatCompletionChunk.  The engine call runs on a worker
+    thread (under the engine's lock, as every call); ``next()`` polls the request's StreamReader - host memory the GPU
+    publishes every token to while the decode loop runs (stream.py) - and never touches the GPU.  An exception of the worker
+    (a JsonModeError, a request that failed to decode) is raised from ``next()``.  ``close()``, leaving a ``with`` block or
+    dropping the iterator cancels the request: the engine's loop ends at its next ``check_every`` boundary.
+    ``worker_done`` is set when the engine call has returned."""
+
+    def __init__(self, run, reader, model_id: str, include_usage: bool, hold_text: bool):
+        # the worker and the generator hold ``state``, never this object: dropping the iterator runs __del__ at once
+        self._reader = reader
+        self.worker_done = threading.Event()
+        state = {"result": None, "error": None, "done": self.worker_done}
+
+        def work():
+            try:
+                state["result"] = run(reader)
+            except BaseException as e:      # noqa: BLE001 - handed to the consumer
+                state["error"] = e
+            finally:
+                state["done"].set()
+
+        self._gen = self._chunks(state, reader, model_id, include_usage, hold_text)
+        self._thread = threading.Thread(target=work, name="vis-stream", daemon=True)
+        self._thread.start()
+
+    @staticmethod
+    def _chunks(state, reader, model, include_usage, hold_text):
+        started = set()
+        done = state["done"]
+        while True:
+            finished = done.is_set()      # read BEFORE the poll: a poll after it has everything
+            events = reader.poll()
+            if not hold_text:
+                for ev in events:
+                    if (ev.request, ev.choice) not in started:
+                        started.add((ev.request, ev.choice))
+                        yield _role_chunk(model, ev.request, ev.choice)
+                    yield _content_chunk(model, ev.request, ev.choice, ev.text)
+            if finished:
+                break
+            if not events:
+                done.wait(0.001)
+        if state["error"] is not None:
+            raise state["error"]
+        failed = None
+        for j, comp in enumerate(state["result"]):
+            if isinstance(comp, Exception):
+                failed = failed or comp
+                continue
+            for c in comp.choices:
+                if (j, c.index) not in started:
+                    yield _role_chunk(model, j, c.index)
+                    if hold_text and c.message.content:      # VIS_SYNTHETIC_REPLY: the substituted text, once
+                        yield _content_chunk(model, j, c.index, c.message.content)
+                yield _finish_chunk(model, j, c.index, c.finish_reason)
+            if include_usage:
+                yield _usage_chunk(model, j, comp.usage)
+        if failed is not None:
+            raise failed
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> ChatCompletionChunk:
+        return next(self._gen)
+
+    def close(self) -> None:
+        self._reader.cancel()
+        self._gen.close()
+        if self._thread is not threading.current_thread():
+            self._thread.join()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        self._reader.cancel()
+
+
 class _Completions:
     def __init__(self, owner):
         self._owner = owner
@@ -80,7 +217,19 @@ class _Completions:
                seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
                presence_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
                stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-               logit_bias: Optional[dict] = None, n: Optional[int] = None, **kwargs) -> ChatCompletion:
+               logit_bias: Optional[dict] = None, n: Optional[int] = None, stream: Optional[bool] = None,
+               stream_options: Optional[dict] = None, **kwargs):
+        """``stream=True``: an iterator of ChatCompletionChunk instead of a ChatCompletion (``stream_options``: OpenAI's
+        {"include_usage": True}); None or False: the call of before."""
+        from .stream import check_stream, check_stream_options
+        if check_stream(stream):
+            if logprobs:
+                raise ValueError("stream=True together with logprobs=True is not supported: chunks carry no logprobs")
+            kwargs["stream"] = True
+            if check_stream_options(stream_options, True):
+                kwargs["stream_options"] = stream_options
+        else:
+            check_stream_options(stream_options, False)
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
                  "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
                  "logit_bias": logit_bias, "n": n}
@@ -448,11 +597,12 @@ class LocalVLMClient:
 
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
                   top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
-                  stop=None, top_k=None, min_p=None, logit_bias=None, n=None, **kwargs) -> ChatCompletion:
-        return self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
-                                  response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
-                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop,
-                                  top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n)[0]
+                  stop=None, top_k=None, min_p=None, logit_bias=None, n=None, stream=None, stream_options=None, **kwargs):
+        out = self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
+                                 response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
+                                 presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop,
+                                 top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n, stream=stream, stream_options=stream_options)
+        return out if isinstance(out, ChatCompletionStream) else out[0]
 
     def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
                       top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
@@ -460,7 +610,63 @@ class LocalVLMClient:
                       presence_penalty: Optional[float] = None,
                       repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
                       min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
-                      n: Optional[int] = None) -> List[ChatCompletion]:
+                      n: Optional[int] = None, stream: Optional[bool] = None, stream_options: Optional[dict] = None):
+        """As ``_complete_many`` (the keywords are described there), plus ``stream`` (OpenAI's): True returns ONE
+        ChatCompletionStream over the chunks of all requests instead of the list - each chunk carries its request's index
+        as ``request_index`` - while the engine call runs on a worker thread.  Every token is published from the GPU into
+        host memory as it is picked (vis_stream_publish, stream.py), so text arrives while the decode loop runs and the
+        loop keeps its launch-ahead; text that may still turn out to be the start of a stop string is held back.  The
+        streamed text of a choice, its finish_reason and the usage are those of the same call not streamed.  Per choice:
+        a chunk with ``delta.role`` "assistant" and empty content, content chunks, one chunk with an empty delta and the
+        ``finish_reason``; ``stream_options={"include_usage": True}`` adds a chunk with ``choices=[]`` and the ``usage``
+        per request.  Not together with ``logprobs``.  With VIS_SYNTHETIC_REPLY the substituted text comes as one content
+        chunk after the generation.  Closing or dropping the iterator cancels the call at the loop's next poll; an exception
+        of a request is raised from ``next()``.  None or False: the list, as before."""
+        from .stream import StreamReader, check_stream, check_stream_options
+        kw = dict(logprobs=logprobs, top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
+                  frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
+                  repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n)
+        if not check_stream(stream):
+            check_stream_options(stream_options, False)
+            return self._complete_many(model, batch_of_messages, temperature, max_tokens, **kw)
+        include_usage = check_stream_options(stream_options, True)
+        if logprobs:
+            raise ValueError("stream=True together with logprobs=True is not supported: chunks carry no logprobs")
+        model_id = model or self.default_model
+        if not model_id:
+            raise ValueError("no model given")
+        self._check_keywords(**kw)
+        lm = get_model(model_id, self.device)
+        hold = model_id.startswith("synthetic:") and bool(os.environ.get("VIS_SYNTHETIC_REPLY"))
+        return ChatCompletionStream(
+            lambda reader: self._complete_many(model, batch_of_messages, temperature, max_tokens, on_stream=reader, **kw),
+            StreamReader(lm.tokenizer), model_id, include_usage, hold)
+
+    @staticmethod
+    def _check_keywords(logprobs, top_logprobs, response_format, top_p, seed, frequency_penalty, presence_penalty,
+                        repetition_penalty, stop, top_k, min_p, logit_bias, n) -> None:
+        """The argument checks of _complete_many that need no model: a streamed call raises them from create(), not from
+        the first next()."""
+        from .penalties import check_penalties
+        from .sampling import check_seed, check_top_p
+        from .shaping import check_shaping
+        from .stop import check_stop
+        logprobs_k(logprobs, top_logprobs)
+        if schema_of(response_format) is None:
+            json_mode_of(response_format)
+        check_top_p(top_p)
+        check_stop(stop)
+        check_seed(seed)
+        check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
+        check_shaping(top_k, min_p, logit_bias, 1)
+
+    def _complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
+                       top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
+                       top_p: Optional[float] = None, seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
+                       presence_penalty: Optional[float] = None,
+                       repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
+                       min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
+                       n: Optional[int] = None, on_stream=None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -527,7 +733,8 @@ class LocalVLMClient:
         n = check_n(n, eng.max_batch)
         n = None if n == 1 else n
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa, stop, shp, n)
+            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa, stop, shp, n,
+                                              on_stream)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -562,6 +769,8 @@ class LocalVLMClient:
             per_chunk = eng.max_batch // (n or 1)      # chunks are filled by choices
             for i in range(0, len(futs), per_chunk):
                 idx = range(i, min(len(futs), i + per_chunk))
+                if on_stream is not None:
+                    on_stream.requests = list(idx)
                 toks = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp, seed=self.seed,
                                           ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1",
                                           **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}),
@@ -569,7 +778,8 @@ class LocalVLMClient:
                                           **({"top_p": top_p} if top_p is not None else {}),
                                           **({"seeds": [seed] * len(idx)} if seed is not None else {}),
                                           **({"stop": stop} if stop is not None else {}), **pen, **shp,
-                                          **({"n": n} if n is not None else {}))
+                                          **({"n": n} if n is not None else {}),
+                                          **({"on_stream": on_stream} if on_stream is not None else {}))
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
                 fins = getattr(eng, "last_finish", None) or [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", {}))
@@ -611,7 +821,8 @@ class LocalVLMClient:
     def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
                               k: Optional[int] = None, jm: bool = False, top_p: Optional[float] = None,
                               seed: Optional[int] = None, pen: Optional[dict] = None, dfa=None,
-                              stop=None, shp: Optional[dict] = None, n: Optional[int] = None) -> List[ChatCompletion]:
+                              stop=None, shp: Optional[dict] = None, n: Optional[int] = None,
+                              on_stream=None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path."""
@@ -631,6 +842,12 @@ class LocalVLMClient:
             lpk["stop"] = stop
         lpk.update(pen or {})
         lpk.update(shp or {})
+        if on_stream is not None:
+            lpk["on_stream"] = on_stream
+
+        def streams_for(indices):      # which requests of the call the next engine call serves
+            if on_stream is not None:
+                on_stream.requests = list(indices)
         nk = {"n": n} if n is not None else {}
         per_chunk = eng.max_batch // (n or 1)      # chunks are filled by choices
 
@@ -657,6 +874,7 @@ class LocalVLMClient:
             with eng.lock:
                 for g0 in range(0, len(futs), per_chunk):
                     idx = range(g0, min(len(futs), g0 + per_chunk))
+                    streams_for(idx)
                     outs = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp,
                                               seed=self.seed, stop_on_eos=not ignore_eos, **lpk, **nk, **seeds_of(len(idx)))
                     recs = eng.last_logprobs if k is not None else [None] * len(idx)
@@ -676,6 +894,7 @@ class LocalVLMClient:
             for g0 in range(0, len(with_img), per_chunk):
                 grp = with_img[g0:g0 + per_chunk]
                 reqs = [(prepared[i][0], _frame_to_device(prepared[i][1], eng.device)) for i in grp]
+                streams_for(grp)
                 outs = eng.generate_batch(reqs, max_new_tokens=max_new, temperature=temp, seed=self.seed,
                                           stop_on_eos=not ignore_eos, **lpk, **nk, **seeds_of(len(reqs)))
                 for m, (i, t) in enumerate(zip(grp, outs)):
@@ -683,6 +902,8 @@ class LocalVLMClient:
                     recs[i] = eng.last_logprobs[m] if k is not None else None
                     fins[i] = eng.last_finish[m]
             for i, (ids, f) in enumerate(prepared):
+                if f is None:
+                    streams_for([i])
                 if f is None and n is None:
                     toks_out[i] = eng.generate(ids, None, max_new_tokens=max_new, temperature=temp,
                                                seed=self.seed if seed is None else seed,
@@ -722,7 +943,7 @@ class CannedResponseClient:
 
     def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
                   frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None, top_k=None, min_p=None,
-                  logit_bias=None, n=None, **kwargs) -> ChatCompletion:
+                  logit_bias=None, n=None, stream=None, stream_options=None, **kwargs):
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
                            "response_format": response_format, "top_p": top_p, "seed": seed})
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
@@ -730,7 +951,11 @@ class CannedResponseClient:
                  "logit_bias": logit_bias, "n": n}
         self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
         reply = self.reply(messages) if callable(self.reply) else self.reply
-        return ChatCompletion([_Choice(_Message(reply), index=i) for i in range(check_n(n, 64) or 1)], model=model or "")
+        done = ChatCompletion([_Choice(_Message(reply), index=i) for i in range(check_n(n, 64) or 1)], model=model or "")
+        if stream:      # the reply as its chunk sequence: role, one content chunk, the finish chunk (and the usage, if asked for)
+            from .stream import check_stream_options
+            return _chunks_of(done, 0, check_stream_options(stream_options, True))
+        return done
 
 
 def make_client(provider: str, api_key: Optional[str] = None, **kwargs):

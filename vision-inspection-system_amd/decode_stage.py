@@ -246,6 +246,7 @@ class DecodeStage(PickStage):
             self._pick(logits, self.ws_val, self.ws_idx, tokens, cur, step, self.temperature, self.seed)
         self._logprobs_after_pick(B or 1)
         self._stop_after_pick(B or 1)
+        self._stream_after_pick(B or 1)
 
     # ---- batched decode: B in-flight sequences (slots 0..B-1) share every weight read of a step
     def _decode_step_batched(self, B: int) -> None:
@@ -342,6 +343,7 @@ class DecodeStage(PickStage):
                    self.seed)
         self._logprobs_after_pick(B)
         self._stop_after_pick(B)
+        self._stream_after_pick(B)
 
     def _decode_step_fused(self, B: int, projections_only: bool = False) -> int:
         """One decode step for B in-flight sequences, every projection ONE launch (r05, csrc/decode_stream.hip): the stream-K
@@ -421,6 +423,7 @@ class DecodeStage(PickStage):
                        self.temperature, self.seed)
             self._logprobs_after_pick(B)
             self._stop_after_pick(B)
+            self._stream_after_pick(B)
         return 4 * len(layers) + 1
 
     # ------------------------------------------------------------------ graphs
@@ -435,8 +438,12 @@ class DecodeStage(PickStage):
         saved = (self.step_b.clone(), self.cur_b.clone())
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            step_fn()
+        self._graph_warmup = True
+        try:
+            with torch.cuda.stream(side):
+                step_fn()
+        finally:
+            self._graph_warmup = False
         torch.cuda.current_stream().wait_stream(side)
         self.step_b.copy_(saved[0])
         self.cur_b.copy_(saved[1])

@@ -1123,7 +1123,7 @@ class Qwen2VLEngine(DecodeStage):
         # temperature, seed and the batch size are kernel arguments baked into the graph; so is what _pick_key() names
         fork = bool(batch) and self.fork_on     # the fork tables are device memory: one graph for every layout
         key = (self.temperature, self.seed, batch, self.batch_shared_len if batch and not fork else 0,
-               bool(chained) and not batch, fork) + self._pick_key() + self._stop_key() + self._shape_key()
+               bool(chained) and not batch, fork) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key()
         return self._captured_step(self._graphs, 8, key, batch, chained)
 
     def decode(self, n_steps: int, use_graph: bool = True) -> None:
@@ -1166,7 +1166,7 @@ class Qwen2VLEngine(DecodeStage):
                  json_mode: bool = False, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
                  stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 logit_bias: Optional[dict] = None) -> List[int]:
+                 logit_bias: Optional[dict] = None, on_stream=None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
@@ -1190,11 +1190,18 @@ class Qwen2VLEngine(DecodeStage):
         bias in [-100, 100]}, at most 300 entries (OpenAI's): shaping.py - one launch ahead of the pick adds the biases to
         the (penalised) logits, then takes out every token below the k-th largest allowed one or less likely than min_p
         times the most likely one; top_p and the draw see the rest.  None / 0 / {} = off; a greedy request is affected by
-        logit_bias only.  Logprobs keep their meaning (raw logits)."""
+        logit_bias only.  Logprobs keep their meaning (raw logits).
+        ``on_stream`` (a stream.StreamReader the caller polls from another thread): every token is published to it while the
+        loop runs - vis_stream_publish after every pick, behind the stop scan, which is then on with or without ``stop`` -
+        and the loop keeps its launch-ahead.  ``on_stream.cancel()`` ends the loop at its next ``check_every`` boundary (the
+        reply then ended as "length").  Not together with ``logprobs``.  A request served again after a stalled chained
+        launch resets the reader's slot; the reader continues behind what it had handed out (stream.py)."""
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         shaping = check_shaping(top_k, min_p, logit_bias, 1)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping):
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping,
+                                on_stream=on_stream):
             self.stop_eos = not ignore_eos
+            self._stream_bind([[0]])
             room = self.max_ctx - len(input_ids) - 1
             if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
                 self._warned_clamp = True          # said once per engine: the reply may end before the model is done
@@ -1225,7 +1232,7 @@ class Qwen2VLEngine(DecodeStage):
         self.prefill(input_ids, frames, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens, prefix=prefix)
         ev[1].record()
         done, eos = 1, set(self.cfg.eos_ids)
-        while done < max_new_tokens:
+        while done < max_new_tokens and not self._stream_cancelled():
             if self.stop_on:
                 if self._stop_done([0]):
                     break
@@ -1253,7 +1260,7 @@ class Qwen2VLEngine(DecodeStage):
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                        json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None) -> list:
+                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
@@ -1273,7 +1280,8 @@ class Qwen2VLEngine(DecodeStage):
         of the slot they land in).  All choices together must fit max_batch.  With ``n`` given, the entry of a request is a
         list of n[j] token lists (for a failed request the exception object, as without), and ``last_logprobs`` /
         ``last_finish`` nest the same way.  At temperature 0 all choices of a request are equal; they are decoded all the
-        same.  A slot is still a full-size cache: ``n`` saves prompt passes and attention traffic, not cache memory."""
+        same.  A slot is still a full-size cache: ``n`` saves prompt passes and attention traffic, not cache memory.
+        ``on_stream``: as in generate, one reader for the whole group; its events name the request and the choice."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -1290,7 +1298,7 @@ class Qwen2VLEngine(DecodeStage):
         if n_req == 1 and ns is not None and ns[0] == 1:      # one choice: today's route, the results nested
             out = self.generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, logprobs,
                                       json_mode, top_p, seeds, repetition_penalty, frequency_penalty, presence_penalty,
-                                      json_schema, stop, top_k, min_p, logit_bias)
+                                      json_schema, stop, top_k, min_p, logit_bias, on_stream=on_stream)
             if not isinstance(out[0], Exception):
                 out = [[out[0]]]
                 self.last_finish = [[self.last_finish[0]]]
@@ -1309,13 +1317,13 @@ class Qwen2VLEngine(DecodeStage):
             try:
                 return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature,
                                       seed if seeds is None else seeds[0], logprobs=logprobs, json_mode=json_mode, json_schema=json_schema,
-                                      top_p=top_p, stop=stop, **({} if penalties is None else dict(
+                                      top_p=top_p, stop=stop, on_stream=on_stream, **({} if penalties is None else dict(
                                           zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))),
                                       **shaping_kwargs(shaping))]
             except JsonModeError as e:
                 return [e]
         with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
-                                shaping=shaping):
+                                shaping=shaping, on_stream=on_stream):
             self.stop_eos = not ignore_eos
             try:
                 return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
@@ -1345,6 +1353,7 @@ class Qwen2VLEngine(DecodeStage):
             return list(errors)
         # the further choices of every request: slots behind the roots', forked from them (no launch and no copy without them)
         choice_slots = self._fork_choices(slots, ns or [1] * n_req, self.batch_shared_len, seeds, penalties, shaping)
+        self._stream_bind(choice_slots)
         B = sum(len(cs) for cs in choice_slots if cs is not None)
         longest = max(self.slot_prompt_len[slots[b]] for b in live)
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
@@ -1357,7 +1366,7 @@ class Qwen2VLEngine(DecodeStage):
 
         done = 1
         g = self._ensure_graph(B) if use_graph else None
-        while done < max_new_tokens:
+        while done < max_new_tokens and not self._stream_cancelled():
             if self.stop_on:
                 if self._stop_done(range(B)):
                     break

@@ -75,6 +75,9 @@ _SIGS = {
     "vis_shape_ws_bytes": "ii",
     "vis_shape_f32": "p" + "ii" + "p" + "i" + "ppppp" + "p" + "i" + "pp" + "i" + "p",
     "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
+    "vis_stream_publish": "pp" + "i" + "pp" + "i" + "pp" + "i" + "pp" + "i" + "p",
+    "vis_host_coherent_alloc": "ppl",
+    "vis_host_free": "p",
     "vis_gemm_decode_ksplit": "ii",
     "vis_gemm_decode_bf16": "pppp" + "iiiiiiii" + "p",
     "vis_gemm_decode_fp8_ksplit": "ii",
@@ -1539,6 +1542,64 @@ def stop_scan(state: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, tok
                               _ptr(tok_flags), V, _ptr(header), _ptr(trans), _ptr(byte_class), _ptr(hits), trans.shape[0],
                               trans.shape[1], int(bool(eos_on)), B, _stream())
     _check(rc, "vis_stop_scan")
+
+
+STREAM_RECORD_INTS = 4      # int32 words of one vis_stream_publish record: token id, safe_bytes, status, cut
+
+
+class HostCoherent:
+    """``nbytes`` of host memory a running kernel stores to coherently (vis_host_coherent_alloc: hipHostMalloc, coherent +
+    mapped, zero-filled), owned by this object.  ``array`` gives numpy views of it for the host side; ``dev_ptr + offset``
+    is what a kernel is given.  Not a torch tensor on purpose: whether torch's pinned memory is fine-grained is not something
+    to rest on."""
+
+    def __init__(self, nbytes: int):
+        host, dev = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(load().vis_host_coherent_alloc(ctypes.addressof(host), ctypes.addressof(dev), int(nbytes)),
+               "vis_host_coherent_alloc")
+        self.host_ptr, self.dev_ptr, self.nbytes = int(host.value), int(dev.value), int(nbytes)
+
+    def array(self, offset: int, shape, dtype="int32"):
+        import numpy as _np
+        n = int(_np.prod(shape)) * _np.dtype(dtype).itemsize
+        if offset < 0 or offset + n > self.nbytes or self.host_ptr is None:
+            raise HipLibraryError("HostCoherent.array: outside the allocation")
+        buf = (ctypes.c_char * n).from_address(self.host_ptr + offset)
+        return _np.frombuffer(buf, dtype=dtype).reshape(shape)
+
+    def free(self) -> None:
+        if self.host_ptr is not None:
+            _check(load().vis_host_free(self.host_ptr), "vis_host_free")
+            self.host_ptr = self.dev_ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:      # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def stream_publish(stop_state: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, depth: torch.Tensor,
+                   pub: torch.Tensor, records_ptr: int, capacity: int, count_ptr: int, start_ptr: int) -> None:
+    """Append one record per row to the host arrays the reader polls (csrc/stream_publish.hip).  Runs AFTER stop_scan.
+    stop_state [B, 8] int32 (the rows' stop-scan records), tokens [B, T] int32, step [B] int32, depth uint8 [n_states],
+    pub [B] int32 (device mirror of count, zero = fresh); records_ptr / count_ptr / start_ptr: device addresses inside a
+    HostCoherent allocation of the first row's records [capacity][4] int32 (rows ``capacity`` records apart), count and
+    start (int32 [B])."""
+    if stop_state.dim() != 2 or tokens.dim() != 2:
+        raise HipLibraryError("stream_publish: stop_state / tokens must be 2-D")
+    B = stop_state.shape[0]
+    if stop_state.dtype != torch.int32 or stop_state.shape[1] != STOP_STATE_INTS or tokens.dtype != torch.int32 \
+            or step.dtype != torch.int32 or pub.dtype != torch.int32 or depth.dtype != torch.uint8:
+        raise HipLibraryError("stream_publish: int32 stop_state [B, 8] / tokens / step / pub and uint8 depth required")
+    if tokens.shape[0] != B or step.numel() != B or pub.numel() != B:
+        raise HipLibraryError("stream_publish: bad batch shapes")
+    if tokens.stride(1) != 1 or (B > 1 and tokens.stride(0) != tokens.shape[1]) or not (
+            stop_state.is_contiguous() and step.is_contiguous() and pub.is_contiguous() and depth.is_contiguous()):
+        raise HipLibraryError("stream_publish: bad strides")
+    rc = load().vis_stream_publish(_ptr(stop_state), _ptr(tokens), tokens.shape[1], _ptr(step), _ptr(depth), depth.numel(),
+                                   _ptr(pub), records_ptr, int(capacity), count_ptr, start_ptr, B, _stream())
+    _check(rc, "vis_stream_publish")
 
 
 DP_PLAIN, DP_SWIGLU, DP_RESID_NORMW = 0, 1, 2

@@ -640,11 +640,11 @@ class MllamaEngine(DecodeStage):
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key() + self._shape_key()
+        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key()
         return self._captured_step(self._graphs, 6, key, 0, chained)
 
     def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
-        key = (self.temperature, self.seed, B, self.fork_on) + self._pick_key() + self._stop_key() + self._shape_key()
+        key = (self.temperature, self.seed, B, self.fork_on) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key()
         return self._captured_step(self._graphs_b, 4, key, B, False)
 
     def decode(self, n_steps: int, use_graph: bool = True) -> None:
@@ -657,7 +657,7 @@ class MllamaEngine(DecodeStage):
                        chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
                        top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None) -> list:
+                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None) -> list:
         """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
         always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
         A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
@@ -670,7 +670,7 @@ class MllamaEngine(DecodeStage):
         ``min_p``, ``logit_bias`` (one value for the group or one per request): as in Qwen2VLEngine.generate_batch.  ``n``
         (several choices per request from one prompt pass): as in Qwen2VLEngine.generate_batch; the image's cross-attention
         keys / values are copied whole into every further choice's slot, the forked attention serves the self-attention
-        layers."""
+        layers.  ``on_stream``: as in Qwen2VLEngine.generate_batch."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -690,7 +690,7 @@ class MllamaEngine(DecodeStage):
         if n_req == 1 and ns is not None and ns[0] == 1:      # one choice: today's route, the results nested
             out = self.generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, logprobs,
                                       json_mode, top_p, seeds, repetition_penalty, frequency_penalty, presence_penalty,
-                                      json_schema, stop, top_k, min_p, logit_bias)
+                                      json_schema, stop, top_k, min_p, logit_bias, on_stream=on_stream)
             if not isinstance(out[0], Exception):
                 out = [[out[0]]]
                 self.last_finish = [[self.last_finish[0]]]
@@ -705,7 +705,8 @@ class MllamaEngine(DecodeStage):
             try:
                 ids, fr = requests[0]() if callable(requests[0]) else requests[0]
                 return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, **pen0)]
+                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, on_stream=on_stream,
+                                      **pen0)]
             except Exception as e:      # noqa: BLE001
                 self.last_logprobs = [None] if logprobs is not None else None
                 self.last_finish = [None]
@@ -716,11 +717,12 @@ class MllamaEngine(DecodeStage):
             ids, fr = requests[0]
             try:
                 return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, **pen0)]
+                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, on_stream=on_stream,
+                                      **pen0)]
             except JsonModeError as e:
                 return [e]
         with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
-                                shaping=shaping):
+                                shaping=shaping, on_stream=on_stream):
             self.stop_eos = bool(stop_on_eos)
             try:
                 return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds,
@@ -840,6 +842,7 @@ class MllamaEngine(DecodeStage):
             return list(errors)
         # the further choices of every request: slots behind the roots', forked from them (no launch and no copy without them)
         choice_slots = self._fork_choices(slots, ns or [1] * n_req, 0, seeds, penalties, shaping)
+        self._stream_bind(choice_slots)
         B = sum(len(cs) for cs in choice_slots if cs is not None)
         longest = max(self.slot_prompt_len[s] for s in range(B))
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
@@ -852,7 +855,7 @@ class MllamaEngine(DecodeStage):
 
         done = 1
         g = self._ensure_graph_batched(B) if use_graph else None
-        while done < max_new_tokens:
+        while done < max_new_tokens and not self._stream_cancelled():
             if self.stop_on:
                 if self._stop_done(range(B)):
                     break
@@ -878,7 +881,7 @@ class MllamaEngine(DecodeStage):
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
                  stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 logit_bias: Optional[dict] = None) -> List[int]:
+                 logit_bias: Optional[dict] = None, on_stream=None) -> List[int]:
         """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
         logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
         None = off, no extra launch.  ``json_mode``: every pick restricted to the tokens that continue a JSON object, as in
@@ -886,11 +889,14 @@ class MllamaEngine(DecodeStage):
         Qwen2VLEngine.generate; so are ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty`` (penalties.py)
         and ``json_schema`` (a compiled json_schema.SchemaDFA as the grammar; not together with ``json_mode``).  ``stop`` and
         ``last_finish``: as in Qwen2VLEngine.generate; a reply that ended on EOS keeps its EOS token here.  ``top_k``,
-        ``min_p`` and ``logit_bias`` (shaping.py): as in Qwen2VLEngine.generate."""
+        ``min_p`` and ``logit_bias`` (shaping.py): as in Qwen2VLEngine.generate; so is ``on_stream`` (``chunk`` is the
+        boundary at which a cancelled request ends)."""
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         shaping = check_shaping(top_k, min_p, logit_bias, 1)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping):
+        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping,
+                                on_stream=on_stream):
             self.stop_eos = bool(stop_on_eos)
+            self._stream_bind([[0]])
             try:
                 return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
             except hip.ChainStalled as e:
@@ -910,7 +916,7 @@ class MllamaEngine(DecodeStage):
         max_new_tokens = min(max_new_tokens, self.max_ctx - len(input_ids) - 1)
         eos = set(self.cfg.eos_ids)
         done = 1
-        while done < max_new_tokens:
+        while done < max_new_tokens and not self._stream_cancelled():
             if self.stop_on:
                 if self._stop_done([0]):
                     break

@@ -1,5 +1,5 @@
 """The next-token pick and the request switches that steer it (logprobs, JSON mode, a JSON Schema, nucleus sampling /
-seeds, penalties, top_k / min_p / logit_bias) or watch it (stop strings): which launches turn a row of logits into a
+seeds, penalties, top_k / min_p / logit_bias) or watch it (stop strings, streaming): which launches turn a row of logits into a
 token, the state behind each switch, and the part of the decode-graph key that depends on them.  Both engines derive from ``PickStage``; nothing else knows this policy."""
 from __future__ import annotations
 
@@ -14,7 +14,8 @@ from .logprobs import LogprobsBuffers, check_k
 from .penalties import NEUTRAL, PenaltyBuffers
 from .sampling import SLOT_SEED_STRIDE, SampleBuffers, check_top_p
 from .shaping import NEUTRAL as SHAPE_NEUTRAL, ShapeBuffers, check_vocab
-from .stop import StopBuffers, check_stop, finish_of, host_finish
+from .stop import StopBuffers, check_stop, empty_dfa, finish_of, host_finish
+from .stream import StreamBuffers, StreamReader
 
 
 class PickStage:
@@ -56,6 +57,12 @@ class PickStage:
         # instead of the token rows; stop_eos: whether an EOS id ends a row too (off in a run that ignores EOS)
         self.stop_on, self.stop_eos = False, True
         self._stop: Optional[StopBuffers] = None
+        # streaming (generate(..., on_stream=StreamReader)): while on, the stop scan is on too (with the request's stop strings
+        # or with the automaton of no string) and vis_stream_publish follows it after every pick; _reader: the request's reader
+        self.stream_on = False
+        self._stream: Optional[StreamBuffers] = None
+        self._reader: Optional[StreamReader] = None
+        self._graph_warmup = False      # DecodeStage._captured_step: the step now running will be run again at the same counters
         # how each request of the last run ended: (reason, cut) with reason "eos" / "stop" / "length", None for a failed one
         self.last_finish: Optional[list] = None
         # the device ids of the prompt last picked from in each slot
@@ -64,17 +71,22 @@ class PickStage:
     # ------------------------------------------------------------------ one request's switches
     @contextlib.contextmanager
     def _pick_request(self, logprobs, json_mode, json_schema, top_p, seeded: bool, penalties: Optional[Sequence[tuple]],
-                      stop=None, *, shaping: Optional[Sequence[tuple]] = None):
+                      stop=None, *, shaping: Optional[Sequence[tuple]] = None, on_stream: Optional[StreamReader] = None):
         """The switches of one request (or one batch of them) on for the body, and all off again afterwards - also when the
         body, or switching on itself (no tokenizer, a schema the device tables cannot hold), raises.  ``penalties``:
         check_penalties' result; a single request runs in slot 0 and its triple is placed there.  ``stop``: None, a string or
-        1..4 of them (check_stop), one set for the whole group.  ``shaping``: check_shaping's result, placed like the penalties."""
+        1..4 of them (check_stop), one set for the whole group.  ``shaping``: check_shaping's result, placed like the penalties.
+        ``on_stream``: the StreamReader the group's tokens are published to, or None."""
         check_k(logprobs)
         check_schema(json_mode, json_schema)
         if not isinstance(json_mode, bool):
             raise ValueError("json_mode must be True or False")
         check_top_p(top_p)
         stop = check_stop(stop)
+        if on_stream is not None and not isinstance(on_stream, StreamReader):
+            raise ValueError("on_stream must be a stream.StreamReader or None")
+        if on_stream is not None and logprobs is not None:
+            raise ValueError("on_stream together with logprobs is not supported")
         try:
             self._begin_logprobs(logprobs)
             self._begin_schema(json_mode, json_schema)
@@ -83,7 +95,8 @@ class PickStage:
             self._begin_penalties(penalties)
             if penalties is not None and len(penalties) == 1:
                 self._slot_pen[0] = penalties[0]
-            self._begin_stop(stop)
+            self._begin_stop(stop if stop is not None or on_stream is None else empty_dfa())
+            self._begin_stream(on_stream)
             self._begin_shaping(shaping)
             if shaping is not None and len(shaping) == 1:
                 self._slot_shape[0] = shaping[0]
@@ -95,6 +108,9 @@ class PickStage:
             self._end_sampling()
             self._end_penalties()
             self.stop_on, self.stop_eos = False, True
+            if self.stream_on:      # the run is over (its last D2H has drained the stream): the reader hands out the rest
+                self._reader._end_group()
+            self.stream_on, self._reader = False, None
             self._end_shaping()
 
     def _pick_key(self) -> tuple:
@@ -112,6 +128,11 @@ class PickStage:
         """The shaping launch's part of a decode-graph key, appended by the engines next to _stop_key(): whether the launch
         is in the step.  k, delta and the bias lists are read from device memory at replay."""
         return (self.shape_on,)
+
+    def _stream_key(self) -> tuple:
+        """The publishing launch's part of a decode-graph key, appended by the engines next to _shape_key(): whether the
+        launch is in the step.  What it reads and where it writes are device and host addresses fixed for the engine's life."""
+        return (self.stream_on,)
 
     # ------------------------------------------------------------------ token log-probabilities
     def _begin_logprobs(self, logprobs: Optional[int]) -> None:
@@ -248,6 +269,47 @@ class PickStage:
         if self.stop_on:
             self._stop.scan(self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], slot, self.stop_eos)
 
+    # ------------------------------------------------------------------ streaming
+    def _begin_stream(self, reader: Optional[StreamReader]) -> None:
+        """Switch vis_stream_publish on (publishing to ``reader``) or off for the request group about to run.  Runs after
+        _begin_stop, before the group's first prompt pass and outside any captured graph.  The device is drained first: the
+        slots' host words are reset from the host, which needs every launch of an earlier request to have finished, and the
+        depth table is overwritten."""
+        self._reader = reader
+        if reader is None:
+            self.stream_on = False
+            return
+        if self._stream is None:
+            self._stream = StreamBuffers(self.max_batch, self.tokens_b.shape[1], self.device)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self._stream.load(self._stop.dfa)
+        self._stream.count[:] = 0      # what an earlier request left in the slots: a reader bound before its slot's prompt pass
+        #                                must not take it for its own
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        reader._attach(self._stream)
+        self.stream_on = True
+
+    def _stream_after_pick(self, B: int, slot: int = 0) -> None:
+        """vis_stream_publish for slots slot .. slot + B - 1, behind the stop scan of their pick (nothing when off).  The
+        warm-up step of a graph capture publishes nothing: its replay does, and a run that ends before the replay (one new
+        token, a cancelled request) must not have handed out a token it does not return."""
+        if self.stream_on and not self._graph_warmup:
+            self._stream.launch(self._stop.state[slot:slot + B], self.tokens_b[slot:slot + B], self.step_b[slot:slot + B], slot)
+
+    def _stream_bind(self, choice_slots: Sequence[Optional[Sequence[int]]]) -> None:
+        """Tell the reader which slot serves which (request, choice): choice_slots[j] = the slots of request j's choices, None
+        for a failed request (nothing when off).  Records published before this are kept: the arrays are append-only."""
+        if self.stream_on:
+            for j, cs in enumerate(choice_slots):
+                for i, s in enumerate(cs or ()):
+                    self._reader._bind(s, j, i)
+
+    def _stream_cancelled(self) -> bool:
+        """The loops' check at a ``check_every`` boundary: the reader's owner has given up on the request."""
+        return self.stream_on and self._reader.cancelled
+
     def _stop_done(self, slots: Iterable[int]) -> bool:
         """The poll while stop strings are on: True when every one of ``slots`` has ended (EOS or a stop string);
         one small D2H, synchronises."""
@@ -333,3 +395,6 @@ class PickStage:
         if self.stop_on:
             self._stop.reset(slot)
             self._stop_after_pick(1, slot)
+        if self.stream_on:
+            self._reader._reset(slot)
+            self._stream_after_pick(1, slot)

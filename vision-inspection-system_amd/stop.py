@@ -111,6 +111,33 @@ def compile_stop(stops) -> StopDFA:
     return StopDFA(stops, trans, byte_class, np.asarray(hit_len, dtype=np.uint8), np.asarray(hit_id, dtype=np.uint8))
 
 
+def empty_dfa() -> StopDFA:
+    """The automaton of no stop string at all: the start state alone.  vis_stop_scan then counts bytes and finds EOS only
+    (what streaming needs of it when the request names no stop string)."""
+    return StopDFA((), np.zeros((1, 1), dtype=np.uint16), np.zeros(256, dtype=np.uint8), np.zeros(1, dtype=np.uint8),
+                   np.zeros(1, dtype=np.uint8))
+
+
+def depths(dfa: StopDFA) -> np.ndarray:
+    """uint8 [n_states]: the depth of every state in the trie - the length of the longest suffix of the text read so far
+    that is a prefix of a stop string.  Every transition leads at most one level down and the trie edge into a state comes
+    from the level above it, so the depth is the breadth-first distance from the start state."""
+    n = dfa.trans.shape[0]
+    depth = np.full(n, -1, dtype=np.int64)
+    depth[0] = 0
+    frontier = [0]
+    while frontier:
+        nxt = []
+        for st in frontier:
+            for t in np.unique(dfa.trans[st]):
+                if depth[t] < 0:
+                    depth[t] = depth[st] + 1
+                    nxt.append(int(t))
+        frontier = nxt
+    assert depth.min() >= 0 and depth.max() <= MAX_STOP_BYTES
+    return depth.astype(np.uint8)
+
+
 def scan(stops, token_bytes_seq: Sequence[bytes], eos_flags: Optional[Sequence[bool]] = None) -> dict:
     """vis_stop_scan in Python over a whole reply: the bytes of each generated token in turn (``eos_flags[i]``: token i is
     an EOS id).  Returns the record as a dict of reason / n_tokens / cut / which / bytes_so_far / state."""
@@ -189,6 +216,7 @@ class StopBuffers:
         self.byte_class = torch.zeros(256, dtype=torch.uint8, device=device)
         self.hits = torch.zeros((MAX_STATES, 2), dtype=torch.uint8, device=device)                 # (hit_len, hit_id)
         self.stops: Optional[tuple] = None
+        self.dfa: Optional[StopDFA] = None      # the automaton last loaded
 
     def load(self, stops, streams=()) -> StopDFA:
         """Make ``stops`` the stop set of the launches that follow.  Called before a request group's first prompt pass,
@@ -196,6 +224,7 @@ class StopBuffers:
         that launched scans for the previous group) has finished, and those streams then wait for the copies."""
         import torch
         dfa = stops if isinstance(stops, StopDFA) else compile_stop(stops)
+        self.dfa = dfa
         n, c = dfa.trans.shape
         if not (1 <= n <= MAX_STATES and 1 <= c <= MAX_CLASSES):
             raise ValueError(f"stop: {n} states x {c} classes exceed the device tables ({MAX_STATES} x {MAX_CLASSES})")
