@@ -708,7 +708,6 @@ class LocalVLMClient:
         choices are equal (and still decoded).  ``usage.prompt_tokens`` counts the prompt once, ``completion_tokens`` is the
         sum over the choices.  Chunks are filled by choices, max_batch // n requests each.  A request with a choice JSON mode
         could not continue fails as a whole.  None or 1 = one choice, the calls of before."""
-        import torch
         from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
         from .shaping import check_shaping, shaping_kwargs
@@ -720,8 +719,7 @@ class LocalVLMClient:
         stop = check_stop(stop)
         seed = check_seed(seed)
         pen = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        pen = {} if pen is None else dict(zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), pen[0]))
-        shp = {name: v for name, v in shaping_kwargs(check_shaping(top_k, min_p, logit_bias, 1)).items() if v is not None}
+        shp = shaping_kwargs(check_shaping(top_k, min_p, logit_bias, 1))
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
@@ -729,12 +727,38 @@ class LocalVLMClient:
         eng, tok = lm.engine, lm.tokenizer
         max_new = int(max_tokens) if max_tokens else 512
         temp = float(temperature) if temperature else 0.0
-        out: List[ChatCompletion] = []
         n = check_n(n, eng.max_batch)
         n = None if n == 1 else n
+        # What every engine call of this request group gets, built once: the switches that are on (an engine call without a
+        # keyword is the call of before the keyword existed) and the ignore-EOS switch in the engine's spelling.
+        ignore_eos = os.environ.get("VIS_IGNORE_EOS") == "1"
+        gen = dict(max_new_tokens=max_new, temperature=temp,
+                   **({"stop_on_eos": not ignore_eos} if lm.family == "mllama" else {"ignore_eos": ignore_eos}))
+        gen.update({name: v for name, v in dict(logprobs=k, json_mode=jm or None, json_schema=dfa, top_p=top_p, stop=stop,
+                                                **({} if pen is None else dict(zip(
+                                                    ("repetition_penalty", "frequency_penalty", "presence_penalty"), pen[0]))),
+                                                **shp, n=n, on_stream=on_stream).items() if v is not None})
+
+        def serve(indices, request_of):
+            """The requests ``indices`` of this call through generate_batch, in chunks filled by choices (max_batch // n
+            requests each): yields (the chunk's indices, its results, logprob records, finishes and device timing)."""
+            per_chunk = eng.max_batch // (n or 1)
+            for i in range(0, len(indices), per_chunk):
+                idx = indices[i:i + per_chunk]
+                if on_stream is not None:
+                    on_stream.requests = list(idx)      # which requests of the call this engine call serves
+                outs = eng.generate_batch([request_of(j) for j in idx], seed=self.seed, **gen,
+                                          **({"seeds": [seed] * len(idx)} if seed is not None else {}))
+                recs = eng.last_logprobs if k is not None else [None] * len(idx)
+                fins = getattr(eng, "last_finish", None) or [None] * len(idx)
+                timing = dict(getattr(eng, "last_timing", None) or {})
+                if timing:
+                    TIMING_LOG.append({"model": model_id, **timing})
+                    del TIMING_LOG[:-4096]
+                yield idx, outs, recs, fins, timing
+
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, temp, max_new, k, jm, top_p, seed, pen, dfa, stop, shp, n,
-                                              on_stream)
+            return self._complete_mllama_many(lm, batch_of_messages, gen, seed, serve)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -765,27 +789,10 @@ class LocalVLMClient:
                     return ids, [hip.resize_rgb(_frame_to_device(f, eng.device), th, tw) for f, (th, tw) in frames]
             return resolve
 
+        out: List[ChatCompletion] = []
         with eng.lock:
-            per_chunk = eng.max_batch // (n or 1)      # chunks are filled by choices
-            for i in range(0, len(futs), per_chunk):
-                idx = range(i, min(len(futs), i + per_chunk))
-                if on_stream is not None:
-                    on_stream.requests = list(idx)
-                toks = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp, seed=self.seed,
-                                          ignore_eos=os.environ.get("VIS_IGNORE_EOS") == "1",
-                                          **({"logprobs": k} if k is not None else {}), **({"json_mode": True} if jm else {}),
-                                          **({"json_schema": dfa} if dfa is not None else {}),
-                                          **({"top_p": top_p} if top_p is not None else {}),
-                                          **({"seeds": [seed] * len(idx)} if seed is not None else {}),
-                                          **({"stop": stop} if stop is not None else {}), **pen, **shp,
-                                          **({"n": n} if n is not None else {}),
-                                          **({"on_stream": on_stream} if on_stream is not None else {}))
-                recs = eng.last_logprobs if k is not None else [None] * len(idx)
-                fins = getattr(eng, "last_finish", None) or [None] * len(idx)
-                timing = dict(getattr(eng, "last_timing", {}))
+            for idx, toks, recs, fins, timing in serve(range(len(futs)), resolver):
                 if timing:
-                    TIMING_LOG.append({"model": model_id, **timing})
-                    del TIMING_LOG[:-4096]
                     logger.debug("%s: %d request(s): prompt pass %.1f ms, %d decode steps in %.1f ms (device time)", model_id,
                                  len(idx), timing["prefill_ms"], timing["decode_steps"], timing["decode_ms"])
                 for j, t, rec, fin in zip(idx, toks, recs, fins):
@@ -796,7 +803,6 @@ class LocalVLMClient:
                         continue
                     out.append(_completion(model_id, tok, n_ids[j], t, rec, fin, timing, n is not None))
         return out
-
 
     def _prepare_mllama(self, lm, messages):
         """messages -> (token ids, decoded uint8 RGB frame or None).  The JPEG is decoded on the host, the tile canvas is
@@ -818,41 +824,16 @@ class LocalVLMClient:
             raise ValueError("the mllama backend takes one image per request (what the reference sends)")
         return build_llama_chat_ids(lm.tokenizer, messages, len(frames)), (frames[0] if frames else None)
 
-    def _complete_mllama_many(self, lm, batch_of_messages, temp: float, max_new: int,
-                              k: Optional[int] = None, jm: bool = False, top_p: Optional[float] = None,
-                              seed: Optional[int] = None, pen: Optional[dict] = None, dfa=None,
-                              stop=None, shp: Optional[dict] = None, n: Optional[int] = None,
-                              on_stream=None) -> List[ChatCompletion]:
+    def _complete_mllama_many(self, lm, batch_of_messages, gen: dict, seed: Optional[int], serve) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
-        (the agents' health check) take the single-sequence path."""
-        import torch
+        (the agents' health check) take the single-sequence path.  ``gen`` / ``seed`` / ``serve``: the engine keywords, the
+        call's seed and the chunked generate_batch of _complete_many."""
         from concurrent.futures import Future
         eng, tok = lm.engine, lm.tokenizer
         from . import ingest
-        ignore_eos = os.environ.get("VIS_IGNORE_EOS") == "1"
-        lpk = {"logprobs": k} if k is not None else {}
-        if jm:
-            lpk["json_mode"] = True
-        if dfa is not None:
-            lpk["json_schema"] = dfa
-        if top_p is not None:
-            lpk["top_p"] = top_p
-        if stop is not None:
-            lpk["stop"] = stop
-        lpk.update(pen or {})
-        lpk.update(shp or {})
-        if on_stream is not None:
-            lpk["on_stream"] = on_stream
-
-        def streams_for(indices):      # which requests of the call the next engine call serves
-            if on_stream is not None:
-                on_stream.requests = list(indices)
-        nk = {"n": n} if n is not None else {}
-        per_chunk = eng.max_batch // (n or 1)      # chunks are filled by choices
-
-        def seeds_of(count):
-            return {"seeds": [seed] * count} if seed is not None else {}
+        k, n, on_stream = gen.get("logprobs"), gen.get("n"), gen.get("on_stream")
+        one = {name: v for name, v in gen.items() if name != "n"}      # generate's keywords: one choice per call
 
         def completion(n_ids, t, rec=None, fin=None):
             return _completion(lm.model_id, tok, n_ids, t, rec, fin, dict(getattr(eng, "last_timing", {})), n is not None)
@@ -872,16 +853,7 @@ class LocalVLMClient:
                 return resolve
 
             with eng.lock:
-                for g0 in range(0, len(futs), per_chunk):
-                    idx = range(g0, min(len(futs), g0 + per_chunk))
-                    streams_for(idx)
-                    outs = eng.generate_batch([resolver(j) for j in idx], max_new_tokens=max_new, temperature=temp,
-                                              seed=self.seed, stop_on_eos=not ignore_eos, **lpk, **nk, **seeds_of(len(idx)))
-                    recs = eng.last_logprobs if k is not None else [None] * len(idx)
-                    fins = eng.last_finish
-                    if getattr(eng, "last_timing", None):
-                        TIMING_LOG.append({"model": lm.model_id, **eng.last_timing})
-                        del TIMING_LOG[:-4096]
+                for idx, outs, recs, fins, _ in serve(range(len(futs)), resolver):
                     out.extend(t if isinstance(t, Exception) else completion(n_ids[j], t, r, f)
                                for j, t, r, f in zip(idx, outs, recs, fins))
             return out
@@ -891,34 +863,22 @@ class LocalVLMClient:
         fins: list = [None] * len(prepared)
         with eng.lock:
             with_img = [i for i, (_, f) in enumerate(prepared) if f is not None]
-            for g0 in range(0, len(with_img), per_chunk):
-                grp = with_img[g0:g0 + per_chunk]
-                reqs = [(prepared[i][0], _frame_to_device(prepared[i][1], eng.device)) for i in grp]
-                streams_for(grp)
-                outs = eng.generate_batch(reqs, max_new_tokens=max_new, temperature=temp, seed=self.seed,
-                                          stop_on_eos=not ignore_eos, **lpk, **nk, **seeds_of(len(reqs)))
-                for m, (i, t) in enumerate(zip(grp, outs)):
-                    toks_out[i] = t
-                    recs[i] = eng.last_logprobs[m] if k is not None else None
-                    fins[i] = eng.last_finish[m]
+            for grp, outs, lps, ends, _ in serve(with_img, lambda i: (prepared[i][0], _frame_to_device(prepared[i][1], eng.device))):
+                for i, t, r, f in zip(grp, outs, lps, ends):
+                    toks_out[i], recs[i], fins[i] = t, r, f
             for i, (ids, f) in enumerate(prepared):
-                if f is None:
-                    streams_for([i])
-                if f is None and n is None:
-                    toks_out[i] = eng.generate(ids, None, max_new_tokens=max_new, temperature=temp,
-                                               seed=self.seed if seed is None else seed,
-                                               stop_on_eos=not ignore_eos, **lpk)
-                    recs[i] = eng.last_logprobs[0] if k is not None else None
-                    fins[i] = eng.last_finish[0]
-                elif f is None:      # text only (the health check): no batched step without an image - one pass per choice
-                    toks_out[i], recs[i], fins[i] = [], [] if k is not None else None, []
-                    for c in range(n):
-                        toks_out[i].append(eng.generate(ids, None, max_new_tokens=max_new, temperature=temp,
-                                                        seed=(self.seed if seed is None else seed) + c,
-                                                        stop_on_eos=not ignore_eos, **lpk))
-                        if k is not None:
-                            recs[i].append(eng.last_logprobs[0])
-                        fins[i].append(eng.last_finish[0])
+                if f is not None:
+                    continue
+                if on_stream is not None:
+                    on_stream.requests = [i]
+                # text only (the health check): no batched step without an image - one pass per choice
+                choices = [(eng.generate(ids, None, seed=(self.seed if seed is None else seed) + c, **one),
+                            eng.last_logprobs[0] if k is not None else None, eng.last_finish[0]) for c in range(n or 1)]
+                if n is None:
+                    toks_out[i], recs[i], fins[i] = choices[0]
+                else:
+                    toks_out[i], fins[i] = [c[0] for c in choices], [c[2] for c in choices]
+                    recs[i] = [c[1] for c in choices] if k is not None else None
         return [completion(len(ids), t, r, f) for (ids, _), t, r, f in zip(prepared, toks_out, recs, fins)]
 
 

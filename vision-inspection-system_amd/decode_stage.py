@@ -1,6 +1,7 @@
 """The decode stage of both engines: one token for the single sequence or for B in-flight sequences, the graph that replays
 it, and the ordered chained decode of a device.  Which launches make a step, and in which form every projection is issued,
-is decided here and nowhere else; both engines derive from ``DecodeStage`` and describe their layers to it once."""
+is decided here and nowhere else; both engines derive from ``DecodeStage`` (through ``generation.Generation``, which drives
+a request through these steps) and describe their layers to it once."""
 from __future__ import annotations
 
 import logging

@@ -26,14 +26,8 @@ import numpy as np
 import torch
 
 from . import hip
-from .decode_stage import DecodeLayer, DecodeStage
-from .fork import check_n_list
-from .json_mode import JsonModeError, check_schema
-from .logprobs import check_k
-from .penalties import check_penalties
-from .sampling import check_seeds, check_top_p
-from .shaping import check_shaping, shaping_kwargs
-from .stop import check_stop
+from .decode_stage import DecodeLayer
+from .generation import Generation
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
 
@@ -142,7 +136,7 @@ _LOG = logging.getLogger("vision_inspection_system_amd.engine")
 
 
 # ----------------------------------------------------------------------------- engine
-class Qwen2VLEngine(DecodeStage):
+class Qwen2VLEngine(Generation):
     """One model replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
     @staticmethod
@@ -1160,6 +1154,31 @@ class Qwen2VLEngine(DecodeStage):
             _LOG.warning("vis_decode_chain: %d requests served on the four launches since the stall - chained layer head back on",
                          self._chain_clean_requests)
 
+    # ------------------------------------------------------------------ generation (the loops: generation.Generation)
+    def _fork_prefix_len(self) -> int:
+        """The text prefix the batch's roots read from slot 0 (Generation hook)."""
+        return self.batch_shared_len
+
+    def _batch_graph(self, B: int) -> torch.cuda.CUDAGraph:
+        return self._ensure_graph(B)
+
+    def _clamp_request(self, input_ids: Sequence[int], max_new_tokens: int) -> int:
+        """The reply clamped to the context in front of the prompt pass, which prepares that many rope rows (Generation
+        hook); said once per engine: the reply may end before the model is done."""
+        room = self.max_ctx - len(input_ids) - 1
+        if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
+            self._warned_clamp = True
+            _LOG.warning("max_tokens=%d does not fit the context (prompt %d + reply <= VIS_MAX_CTX=%d): generating at most %d",
+                         max_new_tokens, len(input_ids), self.max_ctx, max(1, room))
+        return max(1, min(max_new_tokens, room))
+
+    def _prompt_pass(self, input_ids, frames, max_new_tokens, temperature, seed) -> None:
+        """The single sequence's prompt pass (Generation hook)."""
+        # the text in front of the image (the agents' fixed inspection prompt): its K / V come from the prefix cache
+        P = self.text_prefix_len(input_ids) if os.environ.get("VIS_SHARE_PREFIX", "1") != "0" else 0
+        prefix = self.cached_prefix(input_ids, P, temperature, seed) if P else None
+        self.prefill(input_ids, frames, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens, prefix=prefix)
+
     def generate(self, input_ids: Sequence[int], frames: Sequence[torch.Tensor] = (), max_new_tokens: int = 128,
                  ignore_eos: bool = False, use_graph: bool = True, check_every: int = 16,
                  temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
@@ -1167,222 +1186,30 @@ class Qwen2VLEngine(DecodeStage):
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
                  stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                  logit_bias: Optional[dict] = None, on_stream=None) -> List[int]:
-        """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
-        ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
-        first EOS (exclusive).  ``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record
-        (log-softmax of the raw logits - independent of temperature and seed - for every returned token, plus its k most
-        likely alternatives); None = off, no extra launch.  ``json_mode``: every pick is restricted to the tokens that
-        continue a JSON object (json_grammar; needs ``self.tokenizer``): the reply is a prefix of one, complete when it
-        ended on EOS; JsonModeError when the vocabulary could not continue it.  Logprobs keep their meaning (raw logits),
-        so top_logprobs may list tokens the mask forbade.  ``top_p`` in [0, 1]: nucleus sampling (sampling.py) - each pick
-        draws from the shortest most-likely prefix holding top_p of the temperature-scaled mass; None or 1 = off.
-        ``repetition_penalty`` > 0 (transformers' meaning: over prompt and generated ids), ``frequency_penalty`` /
-        ``presence_penalty`` in [-2, 2] (OpenAI's: over generated ids): penalties.py - applied to the raw logits ahead of
-        everything above; None or 1 / 0 / 0 = off.  Logprobs keep their meaning (raw logits).
-        ``json_schema`` (a json_schema.SchemaDFA): as ``json_mode``, with the schema's compiled DFA as the grammar
-        (vis_schema_mask): a reply that ended on EOS is a document of the schema.  Not together with ``json_mode``.
-        ``stop``: a string or 1..4 of them (stop.py): the reply ends with the token that completes the first occurrence of
-        one in its bytes (vis_stop_scan after every pick; the poll then reads its records, not the token row), also in an
-        ``ignore_eos`` run.  Afterwards, always, ``last_finish`` = [(reason, cut)]: "eos", "stop" (cut = the byte offset in
-        the returned tokens' bytes where the stop string starts) or "length" (max_new_tokens, the context clamp, or an
-        ``ignore_eos`` run that matched nothing).
-        ``top_k`` >= 1, ``min_p`` in [0, 1] (transformers' TopKLogitsWarper / MinPLogitsWarper) and ``logit_bias`` {token id:
-        bias in [-100, 100]}, at most 300 entries (OpenAI's): shaping.py - one launch ahead of the pick adds the biases to
-        the (penalised) logits, then takes out every token below the k-th largest allowed one or less likely than min_p
-        times the most likely one; top_p and the draw see the rest.  None / 0 / {} = off; a greedy request is affected by
-        logit_bias only.  Logprobs keep their meaning (raw logits).
-        ``on_stream`` (a stream.StreamReader the caller polls from another thread): every token is published to it while the
-        loop runs - vis_stream_publish after every pick, behind the stop scan, which is then on with or without ``stop`` -
-        and the loop keeps its launch-ahead.  ``on_stream.cancel()`` ends the loop at its next ``check_every`` boundary (the
-        reply then ended as "length").  Not together with ``logprobs``.  A request served again after a stalled chained
-        launch resets the reader's slot; the reader continues behind what it had handed out (stream.py)."""
-        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        shaping = check_shaping(top_k, min_p, logit_bias, 1)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping,
-                                on_stream=on_stream):
-            self.stop_eos = not ignore_eos
-            self._stream_bind([[0]])
-            room = self.max_ctx - len(input_ids) - 1
-            if max_new_tokens > room and not getattr(self, "_warned_clamp", False):
-                self._warned_clamp = True          # said once per engine: the reply may end before the model is done
-                _LOG.warning("max_tokens=%d does not fit the context (prompt %d + reply <= VIS_MAX_CTX=%d): generating at most %d",
-                             max_new_tokens, len(input_ids), self.max_ctx, max(1, room))
-            max_new_tokens = max(1, min(max_new_tokens, room))
-            try:
-                out = self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
-                self._maybe_reenable_chain()
-                return out
-            except hip.ChainStalled as e:
-                # Something else held CU slots this launch's producers needed (another PROCESS sharing the GPU, or other work
-                # of this process on another stream: chained launches of this process are ordered, DecodeStage._decode_ordered,
-                # everything else is covered by the bounded wait only).  From the launch after the stall on every chained
-                # launch of the request returned at once (status word read at kernel entry), so what was lost is one wait
-                # bound.  The request is served again on the unchained launches - the same HIP kernels' arithmetic, identical
-                # tokens - and the engine stays on them for the next VIS_CHAIN_RETRY_AFTER requests.
-                _LOG.warning("%s - continuing on the unchained decode step", e)
-                self.disable_chain()
-                return self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
+        """One request through the single-sequence loop: Generation._generate describes every parameter.  Here a reply that
+        ended on EOS is cut in front of it, and a ``max_new_tokens`` the context cannot hold is clamped with a warning, once
+        per engine (_clamp_request)."""
+        return self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
+                              logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
+                              frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
+                              stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream)
 
-    def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed) -> List[int]:
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time (SURVEY section 5: tracing)
-        ev[0].record()
-        # the text in front of the image (the agents' fixed inspection prompt): its K / V come from the prefix cache
-        P = self.text_prefix_len(input_ids) if os.environ.get("VIS_SHARE_PREFIX", "1") != "0" else 0
-        prefix = self.cached_prefix(input_ids, P, temperature, seed) if P else None
-        self.prefill(input_ids, frames, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens, prefix=prefix)
-        ev[1].record()
-        done, eos = 1, set(self.cfg.eos_ids)
-        while done < max_new_tokens and not self._stream_cancelled():
-            if self.stop_on:
-                if self._stop_done([0]):
-                    break
-            elif not ignore_eos:
-                toks = self.generated(done)
-                if any(t in eos for t in toks):
-                    break
-            n = min(check_every if not ignore_eos or self.stop_on else max_new_tokens, max_new_tokens - done)
-            self.decode(n, use_graph=use_graph)
-            done += n
-        ev[2].record()
-        toks = self.generated(done)                                         # D2H: synchronises, the events have completed
-        self.last_timing = {"prompt_tokens": len(input_ids), "prefill_ms": ev[0].elapsed_time(ev[1]),
-                            "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": 1}
-        toks = self._finish([(0, toks)], eos, ignore_eos)[0]
-        self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
-        if self._mask_failed([0]):
-            self.last_finish = [None]
-            raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
-        return toks
-
-    # ------------------------------------------------------------------ batched generation
     def generate_batch(self, requests: Sequence,
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                        json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
                        stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None) -> list:
-        """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
-        (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
-        (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
-        Returns one token list per request; for a lazy request whose callable raised, the exception object instead.
-        ``logprobs``: as in generate; ``last_logprobs`` then holds one record per request (None for a failed one).
-        ``json_mode``: as in generate; a request whose JSON text could not be continued gets a JsonModeError.
-        ``top_p``: as in generate.  ``seeds``: one integer per request, its own sampling seed in place of the slot-derived
-        one, so a request's sampled reply does not depend on its slot or on what shares the batch.
-        ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty``: as in generate, each a number or a sequence
-        with one value per request.  ``json_schema``: as in generate, one schema for the whole group.  ``stop``: as in
-        generate, one set for the whole group; the shared loop ends when every row has ended.  ``last_finish`` holds one
-        (reason, cut) per request, None for a failed one.  ``top_k``, ``min_p``, ``logit_bias``: as in generate, each one
-        value for the group or a sequence with one value (or None) per request.
-        ``n``: None, an integer >= 1 or one integer per request - that many sampled choices of each request from ONE prompt
-        pass (fork.py): the further choices take slots behind the requests', read the prompt's keys / values from the slot
-        that ran the prompt pass (vis_decode_attn_forked) and sample with seeds[j] + i (without seeds: the slot-derived seed
-        of the slot they land in).  All choices together must fit max_batch.  With ``n`` given, the entry of a request is a
-        list of n[j] token lists (for a failed request the exception object, as without), and ``last_logprobs`` /
-        ``last_finish`` nest the same way.  At temperature 0 all choices of a request are equal; they are decoded all the
-        same.  A slot is still a full-size cache: ``n`` saves prompt passes and attention traffic, not cache memory.
-        ``on_stream``: as in generate, one reader for the whole group; its events name the request and the choice."""
-        n_req = len(requests)
-        if not 1 <= n_req <= self.max_batch:
-            raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
-        check_k(logprobs)
-        if not isinstance(json_mode, bool):
-            raise ValueError("json_mode must be True or False")
-        check_schema(json_mode, json_schema)
-        check_top_p(top_p)
-        seeds = check_seeds(seeds, n_req)
-        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
-        shaping = check_shaping(top_k, min_p, logit_bias, n_req)
-        check_stop(stop)
-        ns = check_n_list(n, n_req, self.max_batch)
-        if n_req == 1 and ns is not None and ns[0] == 1:      # one choice: today's route, the results nested
-            out = self.generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, logprobs,
-                                      json_mode, top_p, seeds, repetition_penalty, frequency_penalty, presence_penalty,
-                                      json_schema, stop, top_k, min_p, logit_bias, on_stream=on_stream)
-            if not isinstance(out[0], Exception):
-                out = [[out[0]]]
-                self.last_finish = [[self.last_finish[0]]]
-                if self.last_logprobs is not None:
-                    self.last_logprobs = [[self.last_logprobs[0]]]
-            return out
-        if n_req == 1 and ns is None:
-            r = requests[0]
-            if callable(r):
-                try:
-                    r = r()
-                except Exception as e:      # noqa: BLE001
-                    self.last_logprobs = [None] if logprobs is not None else None
-                    self.last_finish = [None]
-                    return [e]
-            try:
-                return [self.generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph, check_every, temperature,
-                                      seed if seeds is None else seeds[0], logprobs=logprobs, json_mode=json_mode, json_schema=json_schema,
-                                      top_p=top_p, stop=stop, on_stream=on_stream, **({} if penalties is None else dict(
-                                          zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))),
-                                      **shaping_kwargs(shaping))]
-            except JsonModeError as e:
-                return [e]
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
-                                shaping=shaping, on_stream=on_stream):
-            self.stop_eos = not ignore_eos
-            try:
-                return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                                            seeds, penalties, shaping, ns)
-            finally:
-                self.fork_on = False
+        """Up to max_batch requests through one shared decode loop: Generation._generate_batch describes every parameter.
+        The requests are [(input_ids, frames)], text-only ones included; prompts that start with the same text share its
+        keys / values (prefill_many)."""
+        return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
+                                    logprobs=logprobs, json_mode=json_mode, top_p=top_p, seeds=seeds,
+                                    repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
+                                    presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
+                                    min_p=min_p, logit_bias=logit_bias, n=n, on_stream=on_stream)
 
     def _fork_model_state(self, root: int, child: int) -> None:
         """A further choice decodes at its root's M-RoPE positions (DecodeStage hook)."""
         self.cos_b[child].copy_(self.cos_b[root])
         self.sin_b[child].copy_(self.sin_b[root])
-
-    def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                        seeds=None, penalties=None, shaping=None, ns=None) -> list:
-        n_req = len(requests)
-        # every prompt's own limit (prompt + new tokens <= context) is applied by its prefill; the shared loop below
-        # runs to the limit of the longest one
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        slots, errors = self.prefill_many(requests, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens,
-                                          seeds=seeds, penalties=penalties, shaping=shaping)
-        ev[1].record()
-        live = [b for b in range(n_req) if slots[b] is not None]
-        if not live:
-            self._record_logprobs([None] * n_req)
-            self.last_finish = [None] * n_req
-            return list(errors)
-        # the further choices of every request: slots behind the roots', forked from them (no launch and no copy without them)
-        choice_slots = self._fork_choices(slots, ns or [1] * n_req, self.batch_shared_len, seeds, penalties, shaping)
-        self._stream_bind(choice_slots)
-        B = sum(len(cs) for cs in choice_slots if cs is not None)
-        longest = max(self.slot_prompt_len[slots[b]] for b in live)
-        max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
-        eos = set(self.cfg.eos_ids)
-        starts = [self.slot_prompt_len[s] - 1 for s in range(B)]
-
-        def collect(n):
-            t = self.tokens_b[:B].cpu()
-            return [t[b, starts[b]:starts[b] + n].tolist() for b in range(B)]
-
-        done = 1
-        g = self._ensure_graph(B) if use_graph else None
-        while done < max_new_tokens and not self._stream_cancelled():
-            if self.stop_on:
-                if self._stop_done(range(B)):
-                    break
-            elif not ignore_eos and all(any(t in eos for t in seq) for seq in collect(done)):
-                break
-            n = min(check_every if not ignore_eos or self.stop_on else max_new_tokens, max_new_tokens - done)
-            for _ in range(n):
-                if g is not None:
-                    g.replay()
-                else:
-                    self._decode_step_batched(B)
-            done += n
-        ev[2].record()
-        outs = collect(done)
-        # host waiting for the lazy requests' decodes is inside prefill_ms here: it is the time until all prompts are in
-        self.last_timing = {"prompt_tokens": longest, "prefill_ms": ev[0].elapsed_time(ev[1]),
-                            "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
-        return self._gather_choices(choice_slots, errors, outs, starts, eos, ignore_eos, False, ns is not None,
-                                    lambda: JsonModeError("json_mode: the vocabulary could not continue the JSON text"))

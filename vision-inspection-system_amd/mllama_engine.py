@@ -31,14 +31,8 @@ import numpy as np
 import torch
 
 from . import hip
-from .decode_stage import DecodeLayer, DecodeStage
-from .fork import check_n_list
-from .json_mode import JsonModeError, check_schema
-from .logprobs import check_k
-from .penalties import check_penalties
-from .shaping import check_shaping, shaping_kwargs
-from .sampling import check_seeds, check_top_p
-from .stop import check_stop
+from .decode_stage import DecodeLayer
+from .generation import Generation
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
 
 
@@ -99,7 +93,7 @@ def llama3_rope_tables(cfg: MllamaConfig, n: int) -> Tuple[np.ndarray, np.ndarra
     return np.cos(emb).astype(np.float32), np.sin(emb).astype(np.float32)
 
 
-class MllamaEngine(DecodeStage):
+class MllamaEngine(Generation):
     """One mllama replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
     def __init__(self, cfg: MllamaConfig, weights: MllamaDeviceWeights, device, max_ctx: int = 4096, max_batch: int = 1):
@@ -643,7 +637,8 @@ class MllamaEngine(DecodeStage):
         key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key()
         return self._captured_step(self._graphs, 6, key, 0, chained)
 
-    def _ensure_graph_batched(self, B: int) -> torch.cuda.CUDAGraph:
+    def _batch_graph(self, B: int) -> torch.cuda.CUDAGraph:
+        """The captured batched step (Generation hook)."""
         key = (self.temperature, self.seed, B, self.fork_on) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key()
         return self._captured_step(self._graphs_b, 4, key, B, False)
 
@@ -652,83 +647,54 @@ class MllamaEngine(DecodeStage):
             raise ValueError("decode would run past the context window")
         self._decode_ordered(n_steps, use_graph)
 
+    # ------------------------------------------------------------------ generation (the loops: generation.Generation)
+    keep_eos = True                      # a reply that ended on EOS keeps its EOS token here, with or without stop strings
+    lazy_single_owns_failure = True      # one lazy request: whatever fails in it, its prompt pass too, stays its own
+    single_route_check_every = 32        # generate_batch with one request runs generate at ITS default chunk
+
+    def _prompt_pass(self, input_ids, frame, max_new_tokens, temperature, seed) -> None:
+        """The single sequence's prompt pass; it prepares no rope rows, so the reply's length is not its concern
+        (Generation hook)."""
+        self.prefill(input_ids, frame, temperature=temperature, seed=seed)
+
+    def _check_batch(self, requests: Sequence) -> None:
+        """The batched step always runs the cross-attention layers (Generation hook)."""
+        if not any(callable(r) for r in requests) and any(fr is None for _, fr in requests):
+            raise ValueError("generate_batch needs an image in every request (text-only prompts go through generate)")
+
+    def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
+                 temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
+                 chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False,
+                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
+                 stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
+                 logit_bias: Optional[dict] = None, on_stream=None) -> List[int]:
+        """One request through the single-sequence loop: Generation._generate describes every parameter, with
+        ``stop_on_eos`` = not ignore_eos, ``chunk`` = check_every (the boundary at which a cancelled request ends) and
+        ``frame`` the request's one image or None.  A reply that ended on EOS keeps its EOS token here; a ``max_new_tokens``
+        the context cannot hold is clamped silently; after a stalled chained launch this engine stays on the separate
+        launches for good."""
+        return self._generate(input_ids, frame, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
+                              logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
+                              frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
+                              stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream)
+
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
                        chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
                        top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
                        stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None) -> list:
-        """requests: [(input_ids, frame)] for up to max_batch images (every request carries an image: the batched step
-        always runs the cross-attention layers).  Prompt passes run per request; the decode steps are shared.
-        A request may be a zero-argument callable returning the pair (the batch seam: it waits for the image's host
-        decode, so the prompt pass of image 0 runs while images 1.. are still being decoded); one that raises gets no
-        slot and its exception takes its place in the returned list.  ``logprobs``: as in generate; ``last_logprobs`` then
-        holds one record per request (None for a failed one).  ``json_mode``: as in generate; a request whose JSON text could
-        not be continued gets a JsonModeError.  ``top_p`` / ``seeds`` and the three penalties (a number or one value per request): as in
-        Qwen2VLEngine.generate_batch; so are ``json_schema`` and ``stop`` (one schema, one stop set for the whole group) and
-        ``last_finish``.  A reply that ended on EOS keeps its EOS token here, with or without stop strings.  ``top_k``,
-        ``min_p``, ``logit_bias`` (one value for the group or one per request): as in Qwen2VLEngine.generate_batch.  ``n``
-        (several choices per request from one prompt pass): as in Qwen2VLEngine.generate_batch; the image's cross-attention
-        keys / values are copied whole into every further choice's slot, the forked attention serves the self-attention
-        layers.  ``on_stream``: as in Qwen2VLEngine.generate_batch."""
-        n_req = len(requests)
-        if not 1 <= n_req <= self.max_batch:
-            raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
-        check_k(logprobs)
-        if not isinstance(json_mode, bool):
-            raise ValueError("json_mode must be True or False")
-        check_schema(json_mode, json_schema)
-        check_top_p(top_p)
-        seeds = check_seeds(seeds, n_req)
-        seed0 = seed if seeds is None else seeds[0]
-        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
-        pen0 = {} if penalties is None else dict(zip(("repetition_penalty", "frequency_penalty", "presence_penalty"), penalties[0]))
-        shaping = check_shaping(top_k, min_p, logit_bias, n_req)
-        pen0.update(shaping_kwargs(shaping))
-        check_stop(stop)
-        ns = check_n_list(n, n_req, self.max_batch)
-        if n_req == 1 and ns is not None and ns[0] == 1:      # one choice: today's route, the results nested
-            out = self.generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, logprobs,
-                                      json_mode, top_p, seeds, repetition_penalty, frequency_penalty, presence_penalty,
-                                      json_schema, stop, top_k, min_p, logit_bias, on_stream=on_stream)
-            if not isinstance(out[0], Exception):
-                out = [[out[0]]]
-                self.last_finish = [[self.last_finish[0]]]
-                if self.last_logprobs is not None:
-                    self.last_logprobs = [[self.last_logprobs[0]]]
-            return out
-        single = n_req == 1 and ns is None
-        lazy = any(callable(r) for r in requests)
-        if lazy and single:
-            # one lazy request (always the case with max_batch == 1, where the batched buffers do not even exist): the
-            # single-sequence path; its failure stays its own, as in the batched form
-            try:
-                ids, fr = requests[0]() if callable(requests[0]) else requests[0]
-                return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, on_stream=on_stream,
-                                      **pen0)]
-            except Exception as e:      # noqa: BLE001
-                self.last_logprobs = [None] if logprobs is not None else None
-                self.last_finish = [None]
-                return [e]
-        if not lazy and (single or any(fr is None for _, fr in requests)):
-            if not single:
-                raise ValueError("generate_batch needs an image in every request (text-only prompts go through generate)")
-            ids, fr = requests[0]
-            try:
-                return [self.generate(ids, fr, max_new_tokens, temperature, seed0, stop_on_eos, use_graph, logprobs=logprobs,
-                                      json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop, on_stream=on_stream,
-                                      **pen0)]
-            except JsonModeError as e:
-                return [e]
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
-                                shaping=shaping, on_stream=on_stream):
-            self.stop_eos = bool(stop_on_eos)
-            try:
-                return self._generate_batch(requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds,
-                                            penalties, shaping, ns)
-            finally:
-                self.fork_on = False
+        """Up to max_batch requests through one shared decode loop: Generation._generate_batch describes every parameter
+        (``stop_on_eos`` / ``chunk`` as in generate).  requests: [(input_ids, frame)]; every request of a batch carries an
+        image - one text-only request alone takes the single-sequence path.  A reply that ended on EOS keeps its EOS token.
+        With ``n``, the image's cross-attention keys / values are copied whole into every further choice's slot and the
+        forked attention serves the self-attention layers."""
+        return self._generate_batch(requests, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
+                                    logprobs=logprobs, json_mode=json_mode, top_p=top_p, seeds=seeds,
+                                    repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
+                                    presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
+                                    min_p=min_p, logit_bias=logit_bias, n=n, on_stream=on_stream)
 
     def _fork_model_state(self, root: int, child: int) -> None:
         """A further choice attends to its root's image: the cross-attention keys / values, whole (DecodeStage hook)."""
@@ -736,15 +702,21 @@ class MllamaEngine(DecodeStage):
         self.xv_b[child].copy_(self.xv_b[root])
         self.nkeys_b[child:child + 1].copy_(self.nkeys_b[root:root + 1])
 
-    def _generate_batch(self, requests, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk, seeds=None,
-                        penalties=None, shaping=None, ns=None) -> list:
+    def prefill_many(self, requests: Sequence, temperature: float = 0.0, seed: int = 0, max_new_tokens: Optional[int] = None,
+                     seeds: Optional[Sequence[int]] = None, penalties: Optional[Sequence[tuple]] = None,
+                     shaping: Optional[Sequence[tuple]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
+        """The prompt passes of a batch into consecutive slots (Generation hook, the contract of
+        Qwen2VLEngine.prefill_many): requests [(input_ids, frame)] or zero-argument callables returning that pair (the batch
+        seam: a callable waits for the image's host decode, so the prompt pass of image 0 runs while images 1.. are still
+        being decoded).  With a callable among them a request that fails gets no slot and keeps its exception; without,
+        the failure is raised.  ``seeds`` / ``penalties`` / ``shaping``: request b's rows, read by the picks while the
+        switch is on; ``max_new_tokens`` is not needed (no rope rows are prepared per request).  Returns with the current
+        stream ordered after all passes: (slot of request b or None, exception of request b or None)."""
         n_req = len(requests)
         lazy = any(callable(r) for r in requests)
         slots: List[Optional[int]] = [None] * n_req
         errors: List[Optional[Exception]] = [None] * n_req
         B = 0
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
         # The prompt passes are independent kernel chains (own buffers, own cache slot): issued round-robin on two HIP
         # streams (VIS_PREFILL_STREAMS, as in Qwen2VLEngine.prefill_many) the ragged last round of one image's GEMM /
         # attention grids - the 6432-row tower is 1-1.5 rounds of the chip per projection - is filled by the other's.
@@ -835,105 +807,4 @@ class MllamaEngine(DecodeStage):
         if n_streams > 1:
             for st in self._prefill_streams[:n_streams]:
                 cur.wait_stream(st)
-        ev[1].record()
-        if B == 0:
-            self._record_logprobs([None] * n_req)
-            self.last_finish = [None] * n_req
-            return list(errors)
-        # the further choices of every request: slots behind the roots', forked from them (no launch and no copy without them)
-        choice_slots = self._fork_choices(slots, ns or [1] * n_req, 0, seeds, penalties, shaping)
-        self._stream_bind(choice_slots)
-        B = sum(len(cs) for cs in choice_slots if cs is not None)
-        longest = max(self.slot_prompt_len[s] for s in range(B))
-        max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - longest - 1))
-        eos = set(self.cfg.eos_ids)
-        starts = [self.slot_prompt_len[b] - 1 for b in range(B)]
-
-        def collect(n):
-            t = self.tokens_b[:B].cpu()
-            return [t[b, starts[b]:starts[b] + n].tolist() for b in range(B)]
-
-        done = 1
-        g = self._ensure_graph_batched(B) if use_graph else None
-        while done < max_new_tokens and not self._stream_cancelled():
-            if self.stop_on:
-                if self._stop_done(range(B)):
-                    break
-            elif stop_on_eos and all(any(t in eos for t in seq) for seq in collect(done)):
-                break
-            n = min(chunk if stop_on_eos or self.stop_on else max_new_tokens, max_new_tokens - done)
-            for _ in range(n):
-                if g is not None:
-                    g.replay()
-                else:
-                    self._decode_step_batched(B)
-            done += n
-        ev[2].record()
-        outs = collect(done)
-        self.last_timing = {"prompt_tokens": longest, "prefill_ms": ev[0].elapsed_time(ev[1]),
-                            "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
-        return self._gather_choices(choice_slots, errors, outs, starts, eos, not stop_on_eos, True, ns is not None,
-                                    lambda: JsonModeError("json_mode: the vocabulary could not continue the JSON text"))
-
-    def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
-                 temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                 chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False,
-                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
-                 stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 logit_bias: Optional[dict] = None, on_stream=None) -> List[int]:
-        """``logprobs`` = k in 0..20: afterwards ``last_logprobs`` holds one TokenLogprobs record (log-softmax of the raw
-        logits - independent of temperature and seed - for every returned token, plus its k most likely alternatives);
-        None = off, no extra launch.  ``json_mode``: every pick restricted to the tokens that continue a JSON object, as in
-        Qwen2VLEngine.generate (JsonModeError when the vocabulary could not continue it).  ``top_p``: nucleus sampling, as in
-        Qwen2VLEngine.generate; so are ``repetition_penalty``, ``frequency_penalty`` and ``presence_penalty`` (penalties.py)
-        and ``json_schema`` (a compiled json_schema.SchemaDFA as the grammar; not together with ``json_mode``).  ``stop`` and
-        ``last_finish``: as in Qwen2VLEngine.generate; a reply that ended on EOS keeps its EOS token here.  ``top_k``,
-        ``min_p`` and ``logit_bias`` (shaping.py): as in Qwen2VLEngine.generate; so is ``on_stream`` (``chunk`` is the
-        boundary at which a cancelled request ends)."""
-        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        shaping = check_shaping(top_k, min_p, logit_bias, 1)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping,
-                                on_stream=on_stream):
-            self.stop_eos = bool(stop_on_eos)
-            self._stream_bind([[0]])
-            try:
-                return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
-            except hip.ChainStalled as e:
-                # a chained launch could not get its waiting workgroups resident (another process on the GPU): the request is
-                # served again on the separate launches - identical tokens - and this engine stays on them
-                import logging
-                logging.getLogger("vision_inspection_system_amd.engine").warning("%s - continuing on the unchained decode step", e)
-                self.chain_sync = None
-                self._graphs.clear()
-                return self._generate(input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk)
-
-    def _generate(self, input_ids, frame, max_new_tokens, temperature, seed, stop_on_eos, use_graph, chunk) -> List[int]:
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]      # per-stage device time, as in Qwen2VLEngine
-        ev[0].record()
-        self.prefill(input_ids, frame, temperature=temperature, seed=seed)
-        ev[1].record()
-        max_new_tokens = min(max_new_tokens, self.max_ctx - len(input_ids) - 1)
-        eos = set(self.cfg.eos_ids)
-        done = 1
-        while done < max_new_tokens and not self._stream_cancelled():
-            if self.stop_on:
-                if self._stop_done([0]):
-                    break
-            else:
-                toks = self.generated(done)
-                if stop_on_eos and any(t in eos for t in toks):
-                    break
-            n = min(chunk, max_new_tokens - done)
-            self.decode(n, use_graph)
-            done += n
-        ev[2].record()
-        toks = self.generated(done)                      # D2H: synchronises, the events have completed
-        self.last_timing = {"prompt_tokens": len(input_ids), "prefill_ms": ev[0].elapsed_time(ev[1]),
-                            "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": 1}
-        toks = self._finish([(0, toks)], eos, not stop_on_eos, keep_eos=True)[0]
-        self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
-        if self._mask_failed([0]):
-            self.last_finish = [None]
-            raise JsonModeError("json_mode: the vocabulary could not continue the JSON text")
-        return toks
+        return slots, errors
