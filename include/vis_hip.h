@@ -349,6 +349,30 @@ int vis_shape_f32(const void* logits, int V, int ld_logits, const void* allow, i
                   const void* nbias, const void* bias_ids, const void* bias_vals, void* out, int ld_out, void* nkept,
                   void* ws, int batch, vis_stream_t stream);
 
+/* Token bans ahead of the pick (csrc/ban.hip; ban.py is the reference): no_repeat_ngram_size (transformers'
+ * NoRepeatNGramLogitsProcessor), bad_words (transformers' NoBadWordsLogitsProcessor, vLLM's) and min_tokens (vLLM's).  One
+ * launch per pick, after the penalties and ahead of the grammar mask and the shaping.  History of row b < batch: h =
+ * prompt_ids[b][0 .. prompt_len[b]) followed by tokens[b][gen_start[b] .. step[b]), L ids, G = step[b] - gen_start[b] of
+ * them generated (gen_start = 0: the row holds generated ids only and step counts them, the prompt pass's pick included).
+ * Banned:
+ *   n = ngram[b] >= 1: h[i+n-1] for every i with i + n - 1 < L and h[i .. i+n-2] == h[L-n+1 .. L-1] (n = 1: every id of h);
+ *   word w of m = word_len[w] ids: w[m-1] when m == 1, or when L >= m-1 and h[L-m+1 .. L-1] == w[0 .. m-2] (a match may
+ *   straddle the prompt / generated boundary);
+ *   every eos_ids[e], e < n_eos, while G < min_tokens[b].
+ * out[b][v] = -inf for banned v in [0, V), logits[b][v] bit for bit otherwise; logits are left intact (out != logits); ids of
+ * h outside [0, V) are compared like any other and never written.  A row with all three off is copied.  ngram, min_tokens,
+ * prompt_len, gen_start int32 [batch], prompt_ids int32 [batch][ld_prompt], words int32 [16][8] (row w = word w), eos_ids
+ * int32 [8]: device memory, read at run time - a captured launch serves any values.  word_len: HOST memory, n_words ints;
+ * with n_words and n_eos it is a launch argument.  prompt_len is clamped to 0..ld_prompt, step to 0..max_tokens, gen_start
+ * to 0..step.  A row's result depends on that row alone; a repeated launch changes nothing.
+ * VIS_ERR_ARG and nothing launched: null pointer (word_len may be null at n_words = 0), V outside 1..262144, ld_logits /
+ * ld_out < V, batch outside 1..64, max_tokens or ld_prompt <= 0, n_words outside 0..16, a word length outside 1..8, n_eos
+ * outside 0..8, a device pointer not 4-byte aligned, out == logits. */
+int vis_ban_f32(const void* logits, int V, int ld_logits, const void* prompt_ids, int ld_prompt, const void* prompt_len,
+                const void* tokens, int max_tokens, const void* gen_start, const void* step_ptr, const void* ngram,
+                const void* min_tokens, const void* words, const int* word_len, int n_words, const void* eos_ids, int n_eos,
+                void* out, int ld_out, int batch, vis_stream_t stream);
+
 /* Stop sequences and how a reply ended (csrc/stop_scan.hip; stop.py compiles the tables and is the reference).  One launch
  * AFTER each pick: for every row b < batch folds the tokens picked since the row's last launch (positions [pos, step[b]) of
  * tokens[b][max_tokens]; on the first launch after a reset the one at step[b] - 1) byte by byte - token table as

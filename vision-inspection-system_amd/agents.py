@@ -93,6 +93,43 @@ def shaping_kwargs() -> dict:
     return out
 
 
+def ban_kwargs() -> dict:
+    """VIS_NO_REPEAT_NGRAM=<integer in 1..64>, VIS_BAD_WORDS=<JSON list of up to 16 strings>, VIS_MIN_TOKENS=<integer >= 0>
+    (default unset): the analysis and verify requests pass no_repeat_ngram_size= / bad_words= / min_tokens= with them - a
+    report that cannot loop on an entry without a penalty on the punctuation it must repeat, that cannot open with a phrase
+    of several tokens, and that cannot end at once on EOS.  Not together with VIS_JSON_MODE / VIS_JSON_SCHEMA (the client
+    refuses the request).  Unset: the calls are as before."""
+    from .ban import check_bad_words, check_min_tokens, check_ngram
+    out = {}
+    v = os.environ.get("VIS_NO_REPEAT_NGRAM", "").strip()
+    if v:
+        try:
+            out["no_repeat_ngram_size"] = check_ngram(int(v))
+        except ValueError:
+            raise ValueError("VIS_NO_REPEAT_NGRAM must be an integer in 0..64") from None
+    v = os.environ.get("VIS_BAD_WORDS", "").strip()
+    if v:
+        import json
+        try:
+            words = json.loads(v)
+        except ValueError:
+            raise ValueError("VIS_BAD_WORDS must be a JSON list of strings") from None
+        if not isinstance(words, list):
+            raise ValueError("VIS_BAD_WORDS must be a JSON list of strings")
+        try:
+            check_bad_words(words)
+        except ValueError as e:
+            raise ValueError(f"VIS_BAD_WORDS: {e}") from None
+        out["bad_words"] = words
+    v = os.environ.get("VIS_MIN_TOKENS", "").strip()
+    if v:
+        try:
+            out["min_tokens"] = check_min_tokens(int(v))
+        except ValueError:
+            raise ValueError("VIS_MIN_TOKENS must be an integer >= 0") from None
+    return out
+
+
 def stop_kwargs() -> dict:
     """VIS_STOP=<JSON string or list of up to 4 strings> (default unset): the analysis and verify requests pass it as stop=,
     so a report ends in front of the first of them (VIS_STOP='["```"]': at the fence that closes its JSON block) instead of
@@ -139,7 +176,7 @@ class _BaseAgent:
                 completion = self.client.chat.completions.create(
                     model=self.model_id, messages=messages, temperature=self.temperature, max_tokens=self.max_tokens,
                     **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs(),
-                    **shaping_kwargs())
+                    **shaping_kwargs(), **ban_kwargs())
                 return completion.choices[0].message.content
             except Exception as e:
                 text = str(e)
@@ -379,7 +416,7 @@ def _many(agent, image_paths, contexts, prepared=None) -> list:
             if hasattr(agent.client, "complete_many"):
                 replies = agent.client.complete_many(agent.model_id, msgs, agent.temperature, agent.max_tokens,
                                                      **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs(),
-                                                     **shaping_kwargs())
+                                                     **shaping_kwargs(), **ban_kwargs())
                 texts = [r if isinstance(r, Exception) else r.choices[0].message.content for r in replies]
             else:
                 texts = [agent.client.chat.completions.create(model=agent.model_id, messages=m,
@@ -387,7 +424,7 @@ def _many(agent, image_paths, contexts, prepared=None) -> list:
                                                               max_tokens=agent.max_tokens,
                                                               **json_mode_kwargs(), **seed_kwargs(),
                                                               **penalty_kwargs(), **stop_kwargs(),
-                                                              **shaping_kwargs()).choices[0].message.content
+                                                              **shaping_kwargs(), **ban_kwargs()).choices[0].message.content
                          for m in msgs]
         except Exception as e:
             agent.logger.error(f"{agent.nickname}: batched call failed: {e}", exc_info=True)

@@ -218,7 +218,8 @@ class _Completions:
                presence_penalty: Optional[float] = None, repetition_penalty: Optional[float] = None,
                stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                logit_bias: Optional[dict] = None, n: Optional[int] = None, stream: Optional[bool] = None,
-               stream_options: Optional[dict] = None, **kwargs):
+               stream_options: Optional[dict] = None, no_repeat_ngram_size: Optional[int] = None,
+               bad_words: Optional[list] = None, min_tokens: Optional[int] = None, **kwargs):
         """``stream=True``: an iterator of ChatCompletionChunk instead of a ChatCompletion (``stream_options``: OpenAI's
         {"include_usage": True}); None or False: the call of before."""
         from .stream import check_stream, check_stream_options
@@ -232,7 +233,8 @@ class _Completions:
             check_stream_options(stream_options, False)
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
                  "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
-                 "logit_bias": logit_bias, "n": n}
+                 "logit_bias": logit_bias, "n": n, "no_repeat_ngram_size": no_repeat_ngram_size, "bad_words": bad_words,
+                 "min_tokens": min_tokens}
         kwargs.update({name: v for name, v in given.items() if v is not None})
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
                                      top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
@@ -425,6 +427,17 @@ def logprobs_k(logprobs, top_logprobs) -> Optional[int]:
     return int(top_logprobs or 0)
 
 
+def check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format) -> dict:
+    """``no_repeat_ngram_size`` / ``bad_words`` / ``min_tokens`` of one request, checked without a model (ban.check_ban; how
+    many ids a word has is the tokenizer's to say, when the request is switched on): the engine keywords that are on ({} when
+    none is).  ``min_tokens`` is held against ``max_tokens`` (the client's default of 512 when that is not given); together
+    with a response_format that turns a grammar on they are a ValueError."""
+    from .ban import ban_kwargs, check_ban
+    grammar = isinstance(response_format, dict) and response_format.get("type") in ("json_object", "json_schema")
+    ban = check_ban(no_repeat_ngram_size, bad_words, min_tokens, 1, int(max_tokens) if max_tokens else 512, json_mode=grammar)
+    return {name: v for name, v in ban_kwargs(ban).items() if v}
+
+
 def json_mode_of(response_format) -> bool:
     """OpenAI's response_format -> JSON mode on / off: None or {"type": "text"} = off, {"type": "json_object"} = on
     (json_grammar: the reply is a JSON object).  Anything else raises ValueError; checked before any model is loaded, and
@@ -597,11 +610,13 @@ class LocalVLMClient:
 
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
                   top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
-                  stop=None, top_k=None, min_p=None, logit_bias=None, n=None, stream=None, stream_options=None, **kwargs):
+                  stop=None, top_k=None, min_p=None, logit_bias=None, n=None, stream=None, stream_options=None,
+                  no_repeat_ngram_size=None, bad_words=None, min_tokens=None, **kwargs):
         out = self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
                                  response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop,
-                                 top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n, stream=stream, stream_options=stream_options)
+                                 top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n, stream=stream, stream_options=stream_options,
+                                 no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
         return out if isinstance(out, ChatCompletionStream) else out[0]
 
     def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
@@ -610,7 +625,9 @@ class LocalVLMClient:
                       presence_penalty: Optional[float] = None,
                       repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
                       min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
-                      n: Optional[int] = None, stream: Optional[bool] = None, stream_options: Optional[dict] = None):
+                      n: Optional[int] = None, stream: Optional[bool] = None, stream_options: Optional[dict] = None,
+                      no_repeat_ngram_size: Optional[int] = None, bad_words: Optional[list] = None,
+                      min_tokens: Optional[int] = None):
         """As ``_complete_many`` (the keywords are described there), plus ``stream`` (OpenAI's): True returns ONE
         ChatCompletionStream over the chunks of all requests instead of the list - each chunk carries its request's index
         as ``request_index`` - while the engine call runs on a worker thread.  Every token is published from the GPU into
@@ -625,7 +642,8 @@ class LocalVLMClient:
         from .stream import StreamReader, check_stream, check_stream_options
         kw = dict(logprobs=logprobs, top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
                   frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
-                  repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n)
+                  repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n,
+                  no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
         if not check_stream(stream):
             check_stream_options(stream_options, False)
             return self._complete_many(model, batch_of_messages, temperature, max_tokens, **kw)
@@ -635,7 +653,7 @@ class LocalVLMClient:
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
-        self._check_keywords(**kw)
+        self._check_keywords(max_tokens=max_tokens, **kw)
         lm = get_model(model_id, self.device)
         hold = model_id.startswith("synthetic:") and bool(os.environ.get("VIS_SYNTHETIC_REPLY"))
         return ChatCompletionStream(
@@ -644,7 +662,8 @@ class LocalVLMClient:
 
     @staticmethod
     def _check_keywords(logprobs, top_logprobs, response_format, top_p, seed, frequency_penalty, presence_penalty,
-                        repetition_penalty, stop, top_k, min_p, logit_bias, n) -> None:
+                        repetition_penalty, stop, top_k, min_p, logit_bias, n, no_repeat_ngram_size=None, bad_words=None,
+                        min_tokens=None, max_tokens=None) -> None:
         """The argument checks of _complete_many that need no model: a streamed call raises them from create(), not from
         the first next()."""
         from .penalties import check_penalties
@@ -659,6 +678,7 @@ class LocalVLMClient:
         check_seed(seed)
         check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         check_shaping(top_k, min_p, logit_bias, 1)
+        check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
 
     def _complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
                        top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
@@ -666,7 +686,8 @@ class LocalVLMClient:
                        presence_penalty: Optional[float] = None,
                        repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
                        min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
-                       n: Optional[int] = None, on_stream=None) -> List[ChatCompletion]:
+                       n: Optional[int] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
+                       bad_words: Optional[list] = None, min_tokens: Optional[int] = None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -707,7 +728,14 @@ class LocalVLMClient:
         the first one's cache (fork.py, vis_decode_attn_forked).  Choice i samples with ``seed`` + i; at temperature 0 all
         choices are equal (and still decoded).  ``usage.prompt_tokens`` counts the prompt once, ``completion_tokens`` is the
         sum over the choices.  Chunks are filled by choices, max_batch // n requests each.  A request with a choice JSON mode
-        could not continue fails as a whole.  None or 1 = one choice, the calls of before."""
+        could not continue fails as a whole.  None or 1 = one choice, the calls of before.
+        ``no_repeat_ngram_size`` (transformers' / vLLM's, an integer in 1..64): no n-gram of prompt + reply occurs twice.
+        ``bad_words`` (vLLM's): up to 16 strings of 1..8 tokens each that the reply never contains as token sequences; a word
+        the tokenizer spells differently behind a space is banned in both spellings (both count against the 16).
+        ``min_tokens`` (vLLM's, <= max_tokens): no EOS before that many completion tokens; it holds back EOS only, a ``stop``
+        string may still end the reply earlier.  One launch ahead of the pick (ban.py), after the penalties.  None / 0 / []
+        = off.  Not together with a ``response_format`` of json_object or json_schema: ValueError.  Checked before any GPU
+        work.  Logprobs keep their meaning."""
         from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
         from .shaping import check_shaping, shaping_kwargs
@@ -720,6 +748,7 @@ class LocalVLMClient:
         seed = check_seed(seed)
         pen = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         shp = shaping_kwargs(check_shaping(top_k, min_p, logit_bias, 1))
+        bans = check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
@@ -737,7 +766,7 @@ class LocalVLMClient:
         gen.update({name: v for name, v in dict(logprobs=k, json_mode=jm or None, json_schema=dfa, top_p=top_p, stop=stop,
                                                 **({} if pen is None else dict(zip(
                                                     ("repetition_penalty", "frequency_penalty", "presence_penalty"), pen[0]))),
-                                                **shp, n=n, on_stream=on_stream).items() if v is not None})
+                                                **shp, **bans, n=n, on_stream=on_stream).items() if v is not None})
 
         def serve(indices, request_of):
             """The requests ``indices`` of this call through generate_batch, in chunks filled by choices (max_batch // n
@@ -903,12 +932,15 @@ class CannedResponseClient:
 
     def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
                   frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None, top_k=None, min_p=None,
-                  logit_bias=None, n=None, stream=None, stream_options=None, **kwargs):
+                  logit_bias=None, n=None, stream=None, stream_options=None, no_repeat_ngram_size=None, bad_words=None,
+                  min_tokens=None, **kwargs):
+        check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
                            "response_format": response_format, "top_p": top_p, "seed": seed})
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
                  "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
-                 "logit_bias": logit_bias, "n": n}
+                 "logit_bias": logit_bias, "n": n, "no_repeat_ngram_size": no_repeat_ngram_size, "bad_words": bad_words,
+                 "min_tokens": min_tokens}
         self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
         reply = self.reply(messages) if callable(self.reply) else self.reply
         done = ChatCompletion([_Choice(_Message(reply), index=i) for i in range(check_n(n, 64) or 1)], model=model or "")

@@ -94,7 +94,7 @@ class DecodeStage(PickStage):
         """After the prompt passes of a batch (request j in slot roots[j], None = failed): give request j its n[j] - 1 further
         choices.  A child slot gets the rows of its root's prompt behind the fork length (at most 63, torch copies), the
         model's per-slot state, the root's last-row logits and then the SAME first pick a prompt pass ends with - a fresh
-        grammar state, stop record and logprob row, the prompt's penalty flags, the request's shaping parameters, its own
+        grammar state, stop record and logprob row, the prompt's penalty flags, the request's shaping and ban parameters, its own
         seed (seeds[j] + i) - so every per-slot row is what a prompt pass of its own would have left.  Returns the slots of
         every request's choices and switches the forked attention on when there is a child."""
         live = [j for j in range(len(roots)) if roots[j] is not None]
@@ -119,6 +119,8 @@ class DecodeStage(PickStage):
                 self._slot_pen[child] = penalties[j]
             if shaping is not None:
                 self._slot_shape[child] = shaping[j]
+            if root in self._slot_ban:      # a further choice inherits its request's bans
+                self._slot_ban[child] = self._slot_ban[root]
             self._prompt_pick(child, self._slot_ids[root], self.logits_b[child], self.tokens_b[child],
                               self.cur_b[child:child + 1], self.step_b[child:child + 1])
         if lay.copies:

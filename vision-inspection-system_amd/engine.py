@@ -903,7 +903,8 @@ class Qwen2VLEngine(Generation):
                      ids_dev: Optional[Sequence[torch.Tensor]] = None,
                      seeds: Optional[Sequence[int]] = None,
                      penalties: Optional[Sequence[tuple]] = None,
-                     shaping: Optional[Sequence[tuple]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
+                     shaping: Optional[Sequence[tuple]] = None,
+                     ban: Optional[Sequence[tuple]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
         """Prefill the requests into consecutive slots.  The prefills are independent kernel chains: they are issued round-robin
         on a few HIP streams (VIS_PREFILL_STREAMS, default 2: 418 -> 381 ms for 8 images) so that the ragged last round of one image's GEMM /
         attention grids is filled by another image's workgroups.  Returns with the current stream ordered after
@@ -916,6 +917,7 @@ class Qwen2VLEngine(Generation):
         ``seeds``: request b's own sampling seed (read by the picks while nucleus sampling / seeds are on).
         ``penalties``: request b's (repetition, frequency, presence) penalties (read by the picks while penalties are on).
         ``shaping``: request b's (top_k, min_p, bias list) (read by the picks while logit shaping is on).
+        ``ban``: request b's (no_repeat_ngram_size, min_tokens) (read by the picks while token bans are on).
         Returns (slot of request b or None, exception of request b or None)."""
         B = len(requests)
         lazy = any(callable(r) for r in requests)
@@ -971,6 +973,8 @@ class Qwen2VLEngine(Generation):
                     self._slot_pen[next_slot] = penalties[b]
                 if shaping is not None:
                     self._slot_shape[next_slot] = shaping[b]
+                if ban is not None:
+                    self._slot_ban[next_slot] = ban[b]
                 self.prefill(r[0], r[1], ids_dev=ids_dev[b] if ids_dev else None, temperature=temperature, seed=seed,
                              max_new_tokens=max_new_tokens, slot=next_slot, prefix=prefix_for(r[0]))
                 slots[b] = next_slot
@@ -1019,6 +1023,8 @@ class Qwen2VLEngine(Generation):
                 self._slot_pen.update({slot_of[b]: penalties[b] for b in grp_all})
             if shaping is not None:
                 self._slot_shape.update({slot_of[b]: shaping[b] for b in grp_all})
+            if ban is not None:
+                self._slot_ban.update({slot_of[b]: ban[b] for b in grp_all})
             next_slot += len(grp_all)
             if merged:
                 st = streams[(g0 // vb) % n_streams]         # consecutive groups alternate streams
@@ -1117,7 +1123,7 @@ class Qwen2VLEngine(Generation):
         # temperature, seed and the batch size are kernel arguments baked into the graph; so is what _pick_key() names
         fork = bool(batch) and self.fork_on     # the fork tables are device memory: one graph for every layout
         key = (self.temperature, self.seed, batch, self.batch_shared_len if batch and not fork else 0,
-               bool(chained) and not batch, fork) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key()
+               bool(chained) and not batch, fork) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key() + self._ban_key()
         return self._captured_step(self._graphs, 8, key, batch, chained)
 
     def decode(self, n_steps: int, use_graph: bool = True) -> None:
@@ -1185,21 +1191,24 @@ class Qwen2VLEngine(Generation):
                  json_mode: bool = False, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
                  stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 logit_bias: Optional[dict] = None, on_stream=None) -> List[int]:
+                 logit_bias: Optional[dict] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
+                 bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None) -> List[int]:
         """One request through the single-sequence loop: Generation._generate describes every parameter.  Here a reply that
         ended on EOS is cut in front of it, and a ``max_new_tokens`` the context cannot hold is clamped with a warning, once
         per engine (_clamp_request)."""
         return self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
                               logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
                               frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
-                              stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream)
+                              stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
+                              no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
 
     def generate_batch(self, requests: Sequence,
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
                        check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
                        json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None) -> list:
+                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None,
+                       no_repeat_ngram_size=None, bad_words=None, min_tokens=None) -> list:
         """Up to max_batch requests through one shared decode loop: Generation._generate_batch describes every parameter.
         The requests are [(input_ids, frames)], text-only ones included; prompts that start with the same text share its
         keys / values (prefill_many)."""
@@ -1207,7 +1216,8 @@ class Qwen2VLEngine(Generation):
                                     logprobs=logprobs, json_mode=json_mode, top_p=top_p, seeds=seeds,
                                     repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
                                     presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
-                                    min_p=min_p, logit_bias=logit_bias, n=n, on_stream=on_stream)
+                                    min_p=min_p, logit_bias=logit_bias, n=n, on_stream=on_stream,
+                                    no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
 
     def _fork_model_state(self, root: int, child: int) -> None:
         """A further choice decodes at its root's M-RoPE positions (DecodeStage hook)."""

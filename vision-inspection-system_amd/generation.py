@@ -10,6 +10,7 @@ from typing import List, Sequence
 import torch
 
 from . import hip
+from .ban import ban_kwargs, check_ban
 from .decode_stage import DecodeStage
 from .fork import check_n_list
 from .json_mode import JsonModeError, check_schema
@@ -31,8 +32,9 @@ class Generation(DecodeStage):
     which know one spelling: ``ignore_eos``, ``check_every``, ``frames`` (whatever the engine's prompt pass takes as images).
     What an engine supplies:
       ``_prompt_pass(input_ids, frames, max_new_tokens, temperature, seed)``: the single sequence's prompt pass into slot 0;
-      ``prefill_many(requests, temperature=, seed=, max_new_tokens=, seeds=, penalties=, shaping=) -> (slots, errors)``: the
-        prompt passes of a batch into consecutive slots; a lazy request that failed has no slot and its exception;
+      ``prefill_many(requests, temperature=, seed=, max_new_tokens=, seeds=, penalties=, shaping=[, ban=]) -> (slots,
+        errors)``: the prompt passes of a batch into consecutive slots; a lazy request that failed has no slot and its
+        exception (``ban`` is passed only while token bans are on);
       ``_batch_graph(B)``: the captured batched step under the engine's own graph key;
       ``decode(n_steps, use_graph=)``: n further tokens of the single sequence, its own bounds checked;
     and may override: ``keep_eos``, ``lazy_single_owns_failure``, ``single_route_check_every``, ``_fork_prefix_len()``,
@@ -76,7 +78,7 @@ class Generation(DecodeStage):
     def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, *,
                   logprobs=None, json_mode=False, top_p=None, repetition_penalty=None, frequency_penalty=None,
                   presence_penalty=None, json_schema=None, stop=None, top_k=None, min_p=None, logit_bias=None,
-                  on_stream=None) -> List[int]:
+                  on_stream=None, no_repeat_ngram_size=None, bad_words=None, min_tokens=None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive; inclusive for an engine with ``keep_eos``).  ``logprobs`` = k in 0..20: afterwards
@@ -106,11 +108,20 @@ class Generation(DecodeStage):
         loop runs - vis_stream_publish after every pick, behind the stop scan, which is then on with or without ``stop`` -
         and the loop keeps its launch-ahead.  ``on_stream.cancel()`` ends the loop at its next ``check_every`` boundary (the
         reply then ended as "length").  Not together with ``logprobs``.  A request served again after a stalled chained
-        launch resets the reader's slot; the reader continues behind what it had handed out (stream.py)."""
+        launch resets the reader's slot; the reader continues behind what it had handed out (stream.py).
+        ``no_repeat_ngram_size`` in 1..64 (transformers' NoRepeatNGramLogitsProcessor: no n-gram of prompt + reply occurs
+        twice), ``bad_words``, up to 16 strings of 1..8 token ids each (transformers' NoBadWordsLogitsProcessor / vLLM's: the
+        token that would complete one is never picked; a word the tokenizer spells differently behind a space is banned in
+        both spellings) and ``min_tokens`` <= max_new_tokens (vLLM's: no EOS id before that many tokens): ban.py - one launch
+        after the penalties takes the banned ids out of the pick.  None / 0 / [] = off.  Not together with ``json_mode`` /
+        ``json_schema`` (ValueError: a ban could leave the grammar no token).  ``min_tokens`` holds back EOS ids only: a
+        ``stop`` string may still end the reply earlier.  Logprobs keep their meaning (raw logits)."""
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         shaping = check_shaping(top_k, min_p, logit_bias, 1)
+        ban = check_ban(no_repeat_ngram_size, bad_words, min_tokens, 1, max_new_tokens, json_mode=json_mode,
+                        json_schema=json_schema)
         with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping,
-                                on_stream=on_stream):
+                                on_stream=on_stream, **({} if ban is None else {"ban": ban})):
             self.stop_eos = not ignore_eos
             self._stream_bind([[0]])
             max_new_tokens = self._clamp_request(input_ids, max_new_tokens)
@@ -165,7 +176,8 @@ class Generation(DecodeStage):
     def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, *,
                         logprobs=None, json_mode=False, top_p=None, seeds=None, repetition_penalty=None,
                         frequency_penalty=None, presence_penalty=None, json_schema=None, stop=None, top_k=None, min_p=None,
-                        logit_bias=None, n=None, on_stream=None) -> list:
+                        logit_bias=None, n=None, on_stream=None, no_repeat_ngram_size=None, bad_words=None,
+                        min_tokens=None) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
@@ -186,7 +198,10 @@ class Generation(DecodeStage):
         list of n[j] token lists (for a failed request the exception object, as without), and ``last_logprobs`` /
         ``last_finish`` nest the same way.  At temperature 0 all choices of a request are equal; they are decoded all the
         same.  A slot is still a full-size cache: ``n`` saves prompt passes and attention traffic, not cache memory.
-        ``on_stream``: as in generate, one reader for the whole group; its events name the request and the choice."""
+        ``on_stream``: as in generate, one reader for the whole group; its events name the request and the choice.
+        ``no_repeat_ngram_size``, ``min_tokens``: as in generate, each one value for the group or a sequence with one value
+        per request; ``bad_words``: as in generate, one list for the whole group.  The choices of a request (``n``) inherit
+        its values."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
@@ -198,10 +213,12 @@ class Generation(DecodeStage):
         seeds = check_seeds(seeds, n_req)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
         shaping = check_shaping(top_k, min_p, logit_bias, n_req)
+        ban = check_ban(no_repeat_ngram_size, bad_words, min_tokens, n_req, max_new_tokens, json_mode=json_mode,
+                        json_schema=json_schema)
         check_stop(stop)
         ns = check_n_list(n, n_req, self.max_batch)
         switches = dict(logprobs=logprobs, json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop,
-                        on_stream=on_stream)
+                        on_stream=on_stream, **ban_kwargs(ban))
         if n_req == 1 and ns is not None and ns[0] == 1:      # one choice: the route without n, the results nested
             out = self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
                                        seeds=seeds, repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
@@ -242,23 +259,24 @@ class Generation(DecodeStage):
                 raise
         self._check_batch(requests)
         with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
-                                shaping=shaping, on_stream=on_stream):
+                                shaping=shaping, on_stream=on_stream, **({} if ban is None else {"ban": ban})):
             self.stop_eos = not ignore_eos
             try:
                 return self._run_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                                       seeds, penalties, shaping, ns)
+                                       seeds, penalties, shaping, ns, ban)
             finally:
                 self.fork_on = False
 
     def _run_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, seeds, penalties,
-                   shaping, ns) -> list:
+                   shaping, ns, ban=None) -> list:
         n_req = len(requests)
         # every prompt's own limit (prompt + new tokens <= context) is applied by its prefill; the shared loop below
         # runs to the limit of the longest one
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
         slots, errors = self.prefill_many(requests, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens,
-                                          seeds=seeds, penalties=penalties, shaping=shaping)
+                                          seeds=seeds, penalties=penalties, shaping=shaping,
+                                          **({} if ban is None else {"ban": ban.rows}))
         ev[1].record()
         live = [b for b in range(n_req) if slots[b] is not None]
         if not live:

@@ -74,6 +74,7 @@ _SIGS = {
     "vis_penalize_f32": "p" + "ii" + "ppp" + "i" + "pp" + "ii" + "p",
     "vis_shape_ws_bytes": "ii",
     "vis_shape_f32": "p" + "ii" + "p" + "i" + "ppppp" + "p" + "i" + "pp" + "i" + "p",
+    "vis_ban_f32": "p" + "ii" + "p" + "i" + "pp" + "i" + "pppppp" + "i" + "p" + "i" + "p" + "ii" + "p",
     "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
     "vis_stream_publish": "pp" + "i" + "pp" + "i" + "pp" + "i" + "pp" + "i" + "p",
     "vis_host_coherent_alloc": "ppl",
@@ -1505,6 +1506,37 @@ def shape_logits(logits: torch.Tensor, k: torch.Tensor, delta: torch.Tensor, nbi
                               _ptr(nbias), _ptr(bias_ids), _ptr(bias_vals), _ptr(out),
                               out.stride(0) if out.dim() == 2 else V, _ptr(nkept), _ptr(ws), B, _stream())
     _check(rc, "vis_shape_f32")
+
+
+BAN_MAX_WORDS, BAN_MAX_WORD_LEN, BAN_MAX_EOS = 16, 8, 8     # the tables of vis_ban_f32 (ban.py)
+
+
+def ban(logits: torch.Tensor, prompt_ids: torch.Tensor, prompt_len: torch.Tensor, tokens: torch.Tensor, gen_start: torch.Tensor,
+        step: torch.Tensor, ngram: torch.Tensor, min_tokens: torch.Tensor, words: torch.Tensor, word_len: Sequence[int],
+        eos_ids: torch.Tensor, n_eos: int, out: torch.Tensor) -> None:
+    """Copy of the logits with the banned ids at -inf (vis_ban_f32): no_repeat_ngram_size, bad_words and min_tokens over the
+    rows' history = prompt_ids[b][:prompt_len[b]] followed by tokens[b][gen_start[b]:step[b]]; logits stay intact.  logits,
+    out [V] or [B, V] f32; prompt_ids int32 [B, P]; tokens int32 [T] / [B, T]; prompt_len, gen_start, step, ngram, min_tokens
+    int32 [B]; words int32 [16, 8] (row w = word w, its length word_len[w], a host sequence); eos_ids int32 [8], the first
+    n_eos in use - all tensors in device memory, read at run time."""
+    ints = (prompt_ids, prompt_len, tokens, gen_start, step, ngram, min_tokens, words, eos_ids)
+    if logits.dtype != torch.float32 or out.dtype != torch.float32 or any(t.dtype != torch.int32 for t in ints):
+        raise HipLibraryError("ban: f32 logits, out / int32 ids, tokens and per-row parameters required")
+    B = logits.shape[0] if logits.dim() == 2 else 1
+    V = logits.shape[-1]
+    if out.shape != logits.shape or any(t.numel() != B for t in (prompt_len, gen_start, step, ngram, min_tokens)) \
+            or tokens.numel() % B or prompt_ids.numel() % B or prompt_ids.numel() == 0 \
+            or words.numel() != BAN_MAX_WORDS * BAN_MAX_WORD_LEN or eos_ids.numel() != BAN_MAX_EOS:
+        raise HipLibraryError("ban: bad parameter shapes")
+    if logits.stride(-1) != 1 or out.stride(-1) != 1 or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("ban: bad strides")
+    lens = [int(m) for m in word_len]
+    arr = (ctypes.c_int * max(1, len(lens)))(*lens)
+    rc = load().vis_ban_f32(_ptr(logits), V, logits.stride(0) if logits.dim() == 2 else V, _ptr(prompt_ids),
+                            prompt_ids.numel() // B, _ptr(prompt_len), _ptr(tokens), tokens.numel() // B, _ptr(gen_start),
+                            _ptr(step), _ptr(ngram), _ptr(min_tokens), _ptr(words), arr, len(lens), _ptr(eos_ids), int(n_eos),
+                            _ptr(out), out.stride(0) if out.dim() == 2 else V, B, _stream())
+    _check(rc, "vis_ban_f32")
 
 
 STOP_STATE_INTS = 8     # int32 words of one sequence's vis_stop_scan record (stop.STATE_INTS)

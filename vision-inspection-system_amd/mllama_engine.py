@@ -634,12 +634,12 @@ class MllamaEngine(Generation):
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
-        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key()
+        key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key() + self._ban_key()
         return self._captured_step(self._graphs, 6, key, 0, chained)
 
     def _batch_graph(self, B: int) -> torch.cuda.CUDAGraph:
         """The captured batched step (Generation hook)."""
-        key = (self.temperature, self.seed, B, self.fork_on) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key()
+        key = (self.temperature, self.seed, B, self.fork_on) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key() + self._ban_key()
         return self._captured_step(self._graphs_b, 4, key, B, False)
 
     def decode(self, n_steps: int, use_graph: bool = True) -> None:
@@ -668,7 +668,8 @@ class MllamaEngine(Generation):
                  top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
                  stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 logit_bias: Optional[dict] = None, on_stream=None) -> List[int]:
+                 logit_bias: Optional[dict] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
+                 bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None) -> List[int]:
         """One request through the single-sequence loop: Generation._generate describes every parameter, with
         ``stop_on_eos`` = not ignore_eos, ``chunk`` = check_every (the boundary at which a cancelled request ends) and
         ``frame`` the request's one image or None.  A reply that ended on EOS keeps its EOS token here; a ``max_new_tokens``
@@ -677,14 +678,16 @@ class MllamaEngine(Generation):
         return self._generate(input_ids, frame, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
                               logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
                               frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
-                              stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream)
+                              stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
+                              no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
 
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
                        chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
                        top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None) -> list:
+                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None,
+                       no_repeat_ngram_size=None, bad_words=None, min_tokens=None) -> list:
         """Up to max_batch requests through one shared decode loop: Generation._generate_batch describes every parameter
         (``stop_on_eos`` / ``chunk`` as in generate).  requests: [(input_ids, frame)]; every request of a batch carries an
         image - one text-only request alone takes the single-sequence path.  A reply that ended on EOS keeps its EOS token.
@@ -694,7 +697,8 @@ class MllamaEngine(Generation):
                                     logprobs=logprobs, json_mode=json_mode, top_p=top_p, seeds=seeds,
                                     repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
                                     presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
-                                    min_p=min_p, logit_bias=logit_bias, n=n, on_stream=on_stream)
+                                    min_p=min_p, logit_bias=logit_bias, n=n, on_stream=on_stream,
+                                    no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
 
     def _fork_model_state(self, root: int, child: int) -> None:
         """A further choice attends to its root's image: the cross-attention keys / values, whole (DecodeStage hook)."""
@@ -704,12 +708,13 @@ class MllamaEngine(Generation):
 
     def prefill_many(self, requests: Sequence, temperature: float = 0.0, seed: int = 0, max_new_tokens: Optional[int] = None,
                      seeds: Optional[Sequence[int]] = None, penalties: Optional[Sequence[tuple]] = None,
-                     shaping: Optional[Sequence[tuple]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
+                     shaping: Optional[Sequence[tuple]] = None,
+                     ban: Optional[Sequence[tuple]] = None) -> Tuple[List[Optional[int]], List[Optional[Exception]]]:
         """The prompt passes of a batch into consecutive slots (Generation hook, the contract of
         Qwen2VLEngine.prefill_many): requests [(input_ids, frame)] or zero-argument callables returning that pair (the batch
         seam: a callable waits for the image's host decode, so the prompt pass of image 0 runs while images 1.. are still
         being decoded).  With a callable among them a request that fails gets no slot and keeps its exception; without,
-        the failure is raised.  ``seeds`` / ``penalties`` / ``shaping``: request b's rows, read by the picks while the
+        the failure is raised.  ``seeds`` / ``penalties`` / ``shaping`` / ``ban``: request b's rows, read by the picks while the
         switch is on; ``max_new_tokens`` is not needed (no rope rows are prepared per request).  Returns with the current
         stream ordered after all passes: (slot of request b or None, exception of request b or None)."""
         n_req = len(requests)
@@ -768,6 +773,8 @@ class MllamaEngine(Generation):
                                 self._slot_pen[B + len(items)] = penalties[b]
                             if shaping is not None:
                                 self._slot_shape[B + len(items)] = shaping[b]
+                            if ban is not None:
+                                self._slot_ban[B + len(items)] = ban[b]
                             items.append((B + len(items), ids, cs[0], cs[1]))
                         self._prefill_group(items, temperature, seed)
                     for (b, _, _) in grp:
@@ -786,6 +793,8 @@ class MllamaEngine(Generation):
                     self._slot_pen[B] = penalties[b]
                 if shaping is not None:
                     self._slot_shape[B] = shaping[b]
+                if ban is not None:
+                    self._slot_ban[B] = ban[b]
                 try:
                     if n_streams > 1:
                         st = self._prefill_streams[B % n_streams]

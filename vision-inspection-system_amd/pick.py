@@ -1,5 +1,5 @@
 """The next-token pick and the request switches that steer it (logprobs, JSON mode, a JSON Schema, nucleus sampling /
-seeds, penalties, top_k / min_p / logit_bias) or watch it (stop strings, streaming): which launches turn a row of logits into a
+seeds, penalties, top_k / min_p / logit_bias, no_repeat_ngram_size / bad_words / min_tokens) or watch it (stop strings, streaming): which launches turn a row of logits into a
 token, the state behind each switch, and the part of the decode-graph key that depends on them.  Both engines derive from ``PickStage``; nothing else knows this policy."""
 from __future__ import annotations
 
@@ -9,6 +9,7 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import torch
 
 from . import hip
+from .ban import NEUTRAL as BAN_NEUTRAL, BanBuffers, BanRequest, bad_word_ids
 from .json_mode import JsonBuffers, SchemaBuffers, check_schema, engine_tokenizer
 from .logprobs import LogprobsBuffers, check_k
 from .penalties import NEUTRAL, PenaltyBuffers
@@ -53,6 +54,12 @@ class PickStage:
         self.shape_on = False
         self._shp: Optional[ShapeBuffers] = None
         self._slot_shape: Dict[int, tuple] = {}
+        # token bans (generate(..., no_repeat_ngram_size=, bad_words=, min_tokens=)): while on, every pick reads the row
+        # vis_ban_f32 wrote (after the penalties, ahead of the grammar mask and the shaping); _slot_ban: slot -> the request's
+        # (no_repeat_ngram_size, min_tokens)
+        self.ban_on = False
+        self._ban: Optional[BanBuffers] = None
+        self._slot_ban: Dict[int, tuple] = {}
         # stop strings (generate(..., stop=)): while on, vis_stop_scan follows every pick and the engines poll its records
         # instead of the token rows; stop_eos: whether an EOS id ends a row too (off in a run that ignores EOS)
         self.stop_on, self.stop_eos = False, True
@@ -71,12 +78,14 @@ class PickStage:
     # ------------------------------------------------------------------ one request's switches
     @contextlib.contextmanager
     def _pick_request(self, logprobs, json_mode, json_schema, top_p, seeded: bool, penalties: Optional[Sequence[tuple]],
-                      stop=None, *, shaping: Optional[Sequence[tuple]] = None, on_stream: Optional[StreamReader] = None):
+                      stop=None, *, shaping: Optional[Sequence[tuple]] = None, on_stream: Optional[StreamReader] = None,
+                      ban: Optional[BanRequest] = None):
         """The switches of one request (or one batch of them) on for the body, and all off again afterwards - also when the
         body, or switching on itself (no tokenizer, a schema the device tables cannot hold), raises.  ``penalties``:
         check_penalties' result; a single request runs in slot 0 and its triple is placed there.  ``stop``: None, a string or
         1..4 of them (check_stop), one set for the whole group.  ``shaping``: check_shaping's result, placed like the penalties.
-        ``on_stream``: the StreamReader the group's tokens are published to, or None."""
+        ``on_stream``: the StreamReader the group's tokens are published to, or None.  ``ban``: check_ban's result, its rows
+        placed like the penalties; not together with JSON mode or a schema."""
         check_k(logprobs)
         check_schema(json_mode, json_schema)
         if not isinstance(json_mode, bool):
@@ -87,6 +96,9 @@ class PickStage:
             raise ValueError("on_stream must be a stream.StreamReader or None")
         if on_stream is not None and logprobs is not None:
             raise ValueError("on_stream together with logprobs is not supported")
+        if ban is not None and (json_mode or json_schema is not None):
+            raise ValueError("no_repeat_ngram_size / bad_words / min_tokens together with JSON mode or a JSON schema is not "
+                             "supported: a ban could leave the grammar no token")
         try:
             self._begin_logprobs(logprobs)
             self._begin_schema(json_mode, json_schema)
@@ -100,6 +112,9 @@ class PickStage:
             self._begin_shaping(shaping)
             if shaping is not None and len(shaping) == 1:
                 self._slot_shape[0] = shaping[0]
+            self._begin_ban(ban)
+            if ban is not None and len(ban.rows) == 1:
+                self._slot_ban[0] = ban.rows[0]
             yield
         finally:
             self.lp_k = None
@@ -112,6 +127,7 @@ class PickStage:
                 self._reader._end_group()
             self.stream_on, self._reader = False, None
             self._end_shaping()
+            self._end_ban()
 
     def _pick_key(self) -> tuple:
         """The switches' part of a decode-graph key.  The logprobs k, the masks and top_p are kernel arguments or launches
@@ -128,6 +144,12 @@ class PickStage:
         """The shaping launch's part of a decode-graph key, appended by the engines next to _stop_key(): whether the launch
         is in the step.  k, delta and the bias lists are read from device memory at replay."""
         return (self.shape_on,)
+
+    def _ban_key(self) -> tuple:
+        """The ban launch's part of a decode-graph key, appended by the engines next to _stream_key(): whether the launch is
+        in the step, and the lengths of the group's words, which are launch arguments.  n, min_tokens, the prompts and the
+        words' ids are read from device memory at replay."""
+        return (self.ban_on, self._ban.word_len) if self.ban_on else (False,)
 
     def _stream_key(self) -> tuple:
         """The publishing launch's part of a decode-graph key, appended by the engines next to _shape_key(): whether the
@@ -249,6 +271,35 @@ class PickStage:
         if self.shape_on:
             self._shp.begin(slot, *self._slot_shape.get(slot, SHAPE_NEUTRAL), self.temperature)
 
+    # ------------------------------------------------------------------ token bans (no_repeat_ngram_size, bad_words, min_tokens)
+    def _begin_ban(self, ban: Optional[BanRequest]) -> None:
+        """Route every pick of the request group about to run through vis_ban_f32 when some request of it asks for
+        no_repeat_ngram_size, bad_words or min_tokens (ban: check_ban's result, or None = off).  The words are tokenised here
+        with the engine's tokenizer and uploaded before the group's first prompt pass, outside any captured graph."""
+        self._slot_ban = {}
+        if ban is None:
+            self.ban_on = False
+            return
+        word_ids = bad_word_ids(ban.words, engine_tokenizer(self)) if ban.words else []
+        for w in word_ids:
+            for t in w:
+                if not 0 <= t < self.cfg.vocab:
+                    raise ValueError(f"bad_words: token id {t} is outside the vocabulary [0, {self.cfg.vocab})")
+        if self._ban is None:
+            self._ban = BanBuffers(self.max_batch, self.tokens_b.shape[1], self.cfg.vocab, self.cfg.eos_ids, self.device)
+        self._ban.load(word_ids, getattr(self, "_prefill_streams", ()))
+        self.ban_on = True
+
+    def _end_ban(self) -> None:
+        self.ban_on = False
+        self._slot_ban = {}
+
+    def _ban_slot(self, slot: int, ids_dev: torch.Tensor, step: torch.Tensor) -> None:
+        """Before a prompt pass's pick: the request's n and min_tokens, its prompt ids and the position its reply starts at
+        (``step`` as it stands in front of the pick) in the rows of ``slot``."""
+        if self.ban_on:
+            self._ban.begin(slot, ids_dev, step, *self._slot_ban.get(slot, BAN_NEUTRAL))
+
     # ------------------------------------------------------------------ stop strings / how a reply ended
     def _begin_stop(self, stop: Optional[tuple]) -> None:
         """Switch vis_stop_scan on (with the automaton of ``stop``, check_stop's result, on the device) or off for the request
@@ -352,9 +403,12 @@ class PickStage:
         vis_sample_f32 (seeds from the device buffer, the JSON rows as its mask) while nucleus sampling / seeds are on.  While
         penalties are on, all of them read the penalised copy of the rows (vis_penalize_f32); the raw rows stay intact.  While
         top_k / min_p / logit_bias are on, vis_shape_f32 runs after the penalties and the mask launch, takes the mask's rows,
-        and the pick reads its copy."""
+        and the pick reads its copy.  While no_repeat_ngram_size / bad_words / min_tokens are on, vis_ban_f32 runs after
+        the penalties and ahead of the mask launch: mask, shaping and pick read its copy."""
         if self.pen_on:
             logits = self._pen.apply(logits, tokens, step, slot)
+        if self.ban_on:
+            logits = self._ban.apply(logits, tokens, step, slot)
         allow = self._mask.mask(tokens, step, slot) if self._mask is not None else None
         if self.shape_on:
             logits = self._shp.apply(logits, slot, allow)
@@ -367,8 +421,8 @@ class PickStage:
 
     def _gemv_pick(self, x, w, logits, ws_val, ws_idx, tokens, cur_token, step, **kw) -> None:
         """The fused lm_head + pick of the single-sequence step (slot 0), masked in JSON mode; while nucleus sampling / seeds,
-        penalties or logit shaping are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
-        if self.smp_on or self.pen_on or self.shape_on:
+        penalties, logit shaping or token bans are on, the plain lm_head GEMV writes the f32 logits and _pick follows."""
+        if self.smp_on or self.pen_on or self.shape_on or self.ban_on:
             hip.gemv(x, w, logits, norm_w=kw.get("norm_w"), eps=kw.get("eps", 1e-6))
             self._pick(logits, ws_val, ws_idx, tokens, cur_token, step, kw.get("temperature", 0.0), kw.get("seed", 0))
             return
@@ -387,6 +441,7 @@ class PickStage:
         self._seed_slot(slot)
         self._penalty_slot(slot, ids_dev)
         self._shape_slot(slot)
+        self._ban_slot(slot, ids_dev, step)
         ws = slice(256 * slot, 256 * (slot + 1))    # per-slot workspace: prefills of different slots may run concurrently
         # on different streams
         self._pick(logits, self.ws_val[ws], self.ws_idx[ws], tokens, cur_token, step, self.temperature,
