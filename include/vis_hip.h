@@ -224,7 +224,7 @@ int vis_decode_chain(const void* x, const void* x_idx, int x_rows, const void* W
 
 /* K10 + K12  lm_head of the single-sequence step with the pick's first stage in its epilogue, then the merging launch:
  * logits[N] f32 = W rmsnorm(x); tokens[*step] = cur_token = pick; *step += 1 - the pick vis_gemv_bf16 + vis_argmax_f32 make
- * (same comparison, same Gumbel noise), one launch fewer.  ws_val / ws_idx: 2048 floats / ints. */
+ * (same comparison, same Gumbel noise, id 0 when every logit is NaN), one launch fewer.  ws_val / ws_idx: 2048 floats / ints. */
 int vis_gemv_bf16_argmax(const void* x, const void* W, const void* norm_w, void* logits, int N, int K, int ldw, float eps,
                          void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token, void* step_ptr,
                          float inv_temp, unsigned seed, vis_stream_t stream);
@@ -232,7 +232,9 @@ int vis_gemv_bf16_argmax(const void* x, const void* W, const void* norm_w, void*
 /* K12  next-token pick: tokens[*step] = cur_token = argmax(logits) (first index on ties, like
  * torch.argmax), then *step += 1.  inv_temp > 0 samples at temperature 1/inv_temp by Gumbel-max with a
  * counter hash of (seed, *step, index); inv_temp == 0 is greedy (the reference request passes
- * temperature=, src/agents/vlm_inspector.py:108).  ws_val/ws_idx: 256 floats / 256 ints of workspace. */
+ * temperature=, src/agents/vlm_inspector.py:108).  NaN logits take no part; a row with no comparable logit (all NaN)
+ * picks id 0, never an id outside the vocabulary; step >= max_tokens stores no token but still writes cur_token and
+ * advances the step.  ws_val/ws_idx: 256 floats / 256 ints of workspace. */
 int vis_argmax_f32(const void* logits, int V, void* ws_val, void* ws_idx, void* tokens, int max_tokens,
                    void* cur_token, void* step_ptr, float inv_temp, unsigned seed, int batch, int ld_logits,
                    vis_stream_t stream);

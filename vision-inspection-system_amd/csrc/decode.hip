@@ -1071,8 +1071,9 @@ __global__ __launch_bounds__(256) void argmax_stage1_masked_kernel(const float* 
   argmax_stage1_body<true>(logits, V, bval, bidx, inv_temp, seed, step_ptr, ld_logits, allow, ld_allow);
 }
 
-// MASK: a row with no allowed id at all (a caller's empty mask; vis_json_mask never leaves one) stores id 0 rather than
-// the sentinel, so the next step's embedding gather stays inside the table.
+// A row with nothing to pick from - no allowed id at all (a caller's empty mask; vis_json_mask never leaves one) or no
+// comparable logit (every candidate NaN) - stores id 0 rather than the sentinel, masked or not (as vis_sample_f32 does):
+// the next step's embedding gather stays inside the table and the host never decodes an id outside the vocabulary.
 template <bool MASK>
 __device__ __forceinline__ void argmax_stage2_body(const float* __restrict__ bval, const int* __restrict__ bidx, int nb,
                                                    int* __restrict__ tokens, int max_tokens, int* __restrict__ cur_token,
@@ -1097,7 +1098,7 @@ __device__ __forceinline__ void argmax_stage2_body(const float* __restrict__ bva
     if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
   }
   if (lane == 0) {
-    if (MASK && bi == 0x7fffffff) bi = 0;
+    if (bi == 0x7fffffff) bi = 0;
     const int st = *step_ptr;
     if (st < max_tokens) tokens[st] = bi;
     *cur_token = bi;
@@ -1184,7 +1185,7 @@ __device__ __forceinline__ void argmax_merge_body(const float* __restrict__ bval
   if (tid == 0) {
     for (int w = 1; w < 4; ++w)
       if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-    if (MASK && bi == 0x7fffffff) bi = 0;
+    if (bi == 0x7fffffff) bi = 0;
     const int st = *step_ptr;
     if (st < max_tokens) tokens[st] = bi;
     *cur_token = bi;
