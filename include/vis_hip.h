@@ -607,9 +607,11 @@ int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, const void* sw,
  * honouring the VIS_GEMM_* A/B variables exactly as the launchers do (both launch FROM this plan).  aligned16: C and R
  * (if any) are 16-byte aligned; split: a split-K call of vis_gemm_fp8 (work != NULL).  Writes plan[0] = launches,
  * plan[1] = LDS-staged "wide" epilogue (else direct), plan[2] = non-temporal C stores, then per launch five ints
- * {kernel id, first W row, W rows, tiles_m, tiles_n}.  Kernel ids: 1 = 128x128, 2 = 3-stage 256x128, 4 = 2-phase
- * 256x256, 5 / 6 = 2-phase 256x128 / 256x192, 7 = 256x256 ping-pong, 8 = 128x256 ping-pong half-tiles.  Returns the
- * number of launches (<= 4), or 0 for arguments the launcher rejects by shape or when plan_ints < 3 + 5 * launches.
+ * {kernel id, first W row, W rows, tiles_m, tiles_n}.  Kernel ids, the same in both queries: 1 = 128x128, 7 = 256x256 ping-pong,
+ * 8 = 128x256 ping-pong half-tiles (bf16 only); they are also the values VIS_GEMM_TILE (1, 7, 8) and VIS_GEMM8_TILE
+ * (1, 7) accept.  Returns the number of launches (<= 4), or 0 for arguments the launcher rejects by shape, when
+ * plan_ints < 3 + 5 * launches, or when that variable holds any other non-zero value (the launchers then return
+ * VIS_ERR_ARG).
  * The queries see no pointers: what the launchers reject by pointer (null, misaligned operands) or by the presence of a
  * bias (vis_gemm_fp8 takes none with SwiGLU) still gets a plan. */
 int vis_gemm_bf16_plan(int M, int N, int K, int ldc, int ldr, int act, int has_residual, int aligned16, int* plan,

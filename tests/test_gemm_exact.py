@@ -17,7 +17,7 @@ def hip():
     if not os.path.exists(os.path.join(ROOT, "vision-inspection-system_amd", "csrc", "libvis_hip.so")):
         import __graft_entry__ as g
         g.build()
-    for v in ("VIS_GEMM_TILE", "VIS_GEMM_PP", "VIS_GEMM_MIX1", "VIS_GEMM_HALF", "VIS_GEMM_WIDE", "VIS_GEMM_NT", "VIS_GEMM8_TILE"):
+    for v in ("VIS_GEMM_TILE", "VIS_GEMM_MIX1", "VIS_GEMM_HALF", "VIS_GEMM_WIDE", "VIS_GEMM_NT", "VIS_GEMM8_TILE"):
         assert v not in os.environ, f"{v} is set: the table is stated for the default dispatch"
     from vision_inspection_system_amd import hip as h
     h.load()
@@ -137,6 +137,101 @@ def test_fp8_production_plans(hip):
         got = [(l["kernel"], l["n0"], l["tiles_m"], l["tiles_n"]) for l in hip.gemm_fp8_plan(M, N, K)["launches"]]
         assert got == w, (M, N, K)
         assert hip.gemm_fp8_plan(M, N, K, split=True)["kernels"] == (big,)     # split-K: always the big tile
+
+
+@pytest.fixture(scope="module")
+def plan_table():
+    """tests/golden/gemm_plans.json: the default dispatch over a sweep, recorded by tests/golden/gen_gemm_plans.py."""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import gen_gemm_plans as gen
+    with open(gen.OUT) as f:
+        table = json.load(f)
+    assert table["axes"] == gen.AXES, "the recorded table was made for another sweep: re-record it (gen_gemm_plans.py)"
+    return gen, table
+
+
+def test_plans_match_the_recorded_table(hip, plan_table):
+    """The default dispatch did not move: every plan of the sweep (launch list, wide, nt) equals the recorded one."""
+    gen, table = plan_table
+    for entry in ("bf16", "fp8"):
+        points, got = list(gen.points(entry)), gen.plan_rows(hip, entry)
+        assert len(points) == len(got) == len(table[entry])
+        moved = [(p, g, w) for p, g, w in zip(points, got, table[entry]) if g != w]
+        assert not moved, (f"{entry}: {len(moved)} plans differ from the table; first (M, N, K, act, residual, split) = "
+                           f"{moved[0][0]}: now {moved[0][1]}, recorded {moved[0][2]}")
+
+
+def test_kernel_names_cover_exactly_what_the_plans_can_return(hip, plan_table):
+    _, table = plan_table
+    seen = {e: {k for row in table[e] for k in row[2::5]} for e in ("bf16", "fp8")}
+    assert seen == {"bf16": {1, 7, 8}, "fp8": {1, 7}}
+    assert set(hip.GEMM_KERNEL_NAMES) == seen["bf16"] and set(hip.GEMM_FP8_KERNEL_NAMES) == seen["fp8"]
+    assert all(hip.GEMM_FP8_KERNEL_NAMES[k] == hip.GEMM_KERNEL_NAMES[k] for k in seen["fp8"])   # an id means one tile
+
+
+_OVERRIDE_CHILD = """
+import ctypes, json, sys
+sys.path.insert(0, sys.argv[1])
+from vision_inspection_system_amd import hip
+lib = hip.load()
+buf = (ctypes.c_int * 23)()
+ptr = ctypes.cast(buf, ctypes.c_void_p)
+out = {}
+n = lib.vis_gemm_bf16_plan(2249, 4608, 3584, 4608, 0, 0, 0, 1, ptr, 23)
+out["bf16"] = list(buf[:3 + 5 * n]) if n else 0
+n = lib.vis_gemm_fp8_plan(2249, 4608, 3584, 4608, 0, 0, 0, 1, 0, ptr, 23)
+out["fp8"] = list(buf[:3 + 5 * n]) if n else 0
+import torch
+out["gpu_initialised"] = torch.cuda.is_initialized()
+print(json.dumps(out))
+"""
+
+
+def test_tile_override_values(hip):
+    """VIS_GEMM_TILE takes 1, 7, 8 and VIS_GEMM8_TILE 1, 7 - the ids of kernels that exist; any other non-zero value makes
+    the plan query return 0 (and the launchers VIS_ERR_ARG) instead of quietly running the default; VIS_GEMM_PP is no longer
+    read.  The variables are read once per process, hence the children (all started at once; they only ask for plans)."""
+    import json
+    import subprocess
+    import sys
+    # (VIS_GEMM_TILE, VIS_GEMM8_TILE) -> (kernel id every bf16 launch must have or 0, the same for fp8); None: unset
+    settings = {("1", "1"): (1, 1), ("7", "7"): (7, 7), ("8", "4"): (8, 0), ("2", "2"): (0, 0), ("4", None): (0, None),
+                ("5", None): (0, None), ("6", None): (0, None), ("3", None): (0, None)}
+    base = {k: v for k, v in os.environ.items() if not k.startswith("VIS_GEMM")}
+
+    def start(env):
+        return subprocess.Popen([sys.executable, "-c", _OVERRIDE_CHILD, ROOT], env={**base, **env}, stdout=subprocess.PIPE,
+                                stderr=subprocess.PIPE, text=True)
+    procs = {key: start({k: v for k, v in zip(("VIS_GEMM_TILE", "VIS_GEMM8_TILE"), key) if v is not None}) for key in settings}
+    procs["pp"] = start({"VIS_GEMM_PP": "0"})
+    results = {}
+    for key, p in procs.items():
+        so, se = p.communicate(timeout=300)
+        assert p.returncode == 0, f"{key}: {se[-2000:]}"
+        results[key] = json.loads(so.strip().splitlines()[-1])
+        assert not results[key]["gpu_initialised"]
+    lib = hip.load()
+    import ctypes
+    buf = (ctypes.c_int * 23)()
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    n = lib.vis_gemm_bf16_plan(2249, 4608, 3584, 4608, 0, 0, 0, 1, ptr, 23)
+    default = {"bf16": list(buf[:3 + 5 * n])}
+    n = lib.vis_gemm_fp8_plan(2249, 4608, 3584, 4608, 0, 0, 0, 1, 0, ptr, 23)
+    default["fp8"] = list(buf[:3 + 5 * n])
+    assert default["bf16"][3::5] == [7] and default["fp8"][3::5] == [7]
+    for key, want in settings.items():
+        for entry, kernel in zip(("bf16", "fp8"), want):
+            got = results[key][entry]
+            if kernel is None:                       # this entry's variable is unset: its default plan
+                assert got == default[entry], (key, entry)
+            elif kernel == 0:
+                assert got == 0, (key, entry, got)
+            else:
+                assert got != 0 and got[0] >= 1 and set(got[3::5]) == {kernel}, (key, entry, got)
+                assert got[1:3] == default[entry][1:3]                       # epilogue form and store policy: not the tile's business
+    assert {e: results["pp"][e] for e in ("bf16", "fp8")} == default
 
 
 def test_plan_query_argument_checks(hip):

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/fp8_pmc
 rm -rf $O && mkdir -p $O
-export VIS_GEMM8_TILE=4
+export VIS_GEMM8_TILE=7
 : > $O/summary.txt
 for SH in "fc1 19600 5120 1280 1" "qkv 19600 3840 1280 0" "gateup 5156 37888 3584 3"; do
   set -- $SH

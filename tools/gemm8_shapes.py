@@ -1,6 +1,6 @@
 """fp8 GEMM time per production shape under the current VIS_GEMM8_TILE setting (unset = the library's cost model, 1 = 128 x 128,
-4 = 256 x 256 ping-pong): run once per setting and compare the columns - the check of vis_gemm_fp8's tile choice.
-  for t in "" 1 4; do VIS_GEMM8_TILE=$t python tools/gemm8_shapes.py; done"""
+7 = 256 x 256 ping-pong): run once per setting and compare the columns - the check of vis_gemm_fp8's tile choice.
+  for t in "" 1 7; do VIS_GEMM8_TILE=$t python tools/gemm8_shapes.py; done"""
 import math, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

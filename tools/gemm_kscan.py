@@ -1,7 +1,7 @@
 """Fixed cost per tile vs cost per K-step of the GEMM tile kernels: one round of the chip (4096 x 4096 = 256 tiles of
 256 x 256) at K = 256 .. 8192, for each forced tile kernel; prints t(K) and the least-squares a + b * (K / 64).
-python tools/gemm_kscan.py  (set VIS_GEMM_TILE in the environment to pick the kernel: 7 = ping-pong 256x256;
-KS_FP8=1: the fp8 kernels instead, VIS_GEMM8_TILE=4 / 1 forces the 256x256 / 128x128 tile; K-steps are then 128 wide)"""
+python tools/gemm_kscan.py  (set VIS_GEMM_TILE in the environment to pick the kernel: 7 = ping-pong 256x256, 8 = 128x256
+half-tiles, 1 = 128x128; KS_FP8=1: the fp8 kernels instead, VIS_GEMM8_TILE=7 / 1 forces the 256x256 / 128x128 tile; K-steps are then 128 wide)"""
 import math, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,6 @@
 #!/bin/bash
 # PMC passes over tools/gemm_bench.py for one shape (run ON the GPU box): bash tools/gemm_pmc.sh TILE M N K
+# TILE = a VIS_GEMM_TILE value: 0 (the library's choice), 1 = 128x128, 7 = 256x256 ping-pong, 8 = 128x256 half-tiles
 set -e
 T=$1; M=$2; N=$3; K=$4
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"

@@ -1,6 +1,7 @@
 """Which tile kernel for the ragged production shapes, in the cache state they run in (operands and output not resident:
-a 1 GiB fill between calls).  VIS_GEMM_TILE picks the kernel for the whole process (0/unset = the product's rule):
-  for t in 0 7 6 5 4 1; do VIS_GEMM_TILE=$t python tools/gemm_tiles_ab.py; done"""
+a 1 GiB fill between calls).  VIS_GEMM_TILE picks the kernel for the whole process (0/unset = the product's rule,
+7 = 256x256 ping-pong, 8 = 128x256 ping-pong half-tiles, 1 = 128x128; any other value is rejected):
+  for t in 0 7 8 1; do VIS_GEMM_TILE=$t python tools/gemm_tiles_ab.py; done"""
 import math, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

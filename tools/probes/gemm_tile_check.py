@@ -1,5 +1,5 @@
 """Bitwise A/B of a forced GEMM tile kernel against the product's choice: python tools/probes/gemm_tile_check.py dump OUT.pt
-(under VIS_GEMM_TILE=<n> or unset), then ... cmp A.pt B.pt.  Shapes: the ragged production ones with their epilogues plus
+(under VIS_GEMM_TILE=1|7|8 or unset), then ... cmp A.pt B.pt.  Shapes: the ragged production ones with their epilogues plus
 edge cases (rows / columns that do not fill a tile, K not a multiple of the unroll)."""
 import math, os, sys
 import torch

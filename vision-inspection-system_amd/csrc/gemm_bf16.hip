@@ -220,340 +220,15 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_128x128_kernel(GemmArgs p) {
 }
 
 // ---------------------------------------------------------------------------
-// 256x128x64 tile, 512 threads = 8 waves (4 x 2, each 64x64), ONE workgroup per CU, 3-stage LDS ring
-// (3 x 48 KiB).  The global_load_lds of K-step t+2 are issued while step t is computed; the only waits in the
-// loop are a COUNTED s_waitcnt vmcnt(6) (this thread's 6 loads of step t+1 may stay in flight) and one raw
-// s_barrier per K-step - never a __syncthreads(), whose fence would drain the in-flight LDS-DMA.
-//   iteration t:  wait(stage t landed) ; barrier ; issue stage t+2 into the buffer everyone just finished
-//                 reading (stage t-1) ; ds_read + 32 MFMA on stage t
-// The barrier both publishes stage t (every wave waited for its own part) and retires the reads of stage t-1.
-#define GEMM2_BM 256
-#define GEMM2_STAGE_BYTES ((GEMM2_BM + GEMM_BN) * GEMM_BK * 2)  // 49152
-#define GEMM2_LDS_BYTES (3 * GEMM2_STAGE_BYTES)                  // 147456
-
-__global__ __launch_bounds__(512, 2) void gemm_bf16_256x128_kernel(GemmArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char lds2[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l15 = lane & 15, h = lane >> 4;
-
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int tn = id / p.tiles_m, tm = id - tn * p.tiles_m;
-  const int m0 = tm * GEMM2_BM, n0 = tn * GEMM_BN;
-
-  uint32_t a_off[4], w_off[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = i * 512 + tid;
-    const int row = c >> 3;
-    const int ch = (c & 7) ^ (row & 7);
-    a_off[i] = (uint32_t)(min(m0 + row, p.M - 1) - m0) * (uint32_t)(p.lda * 2) + ch * 16;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = i * 512 + tid;
-    const int row = c >> 3;
-    const int ch = (c & 7) ^ (row & 7);
-    w_off[i] = (uint32_t)(min(n0 + row, p.N - 1) - n0) * (uint32_t)(p.ldw * 2) + ch * 16;
-  }
-  const char* a_base = (const char*)(p.A + (size_t)m0 * p.lda);
-  const char* w_base = (const char*)(p.W + (size_t)n0 * p.ldw);
-  const int wave_base = __builtin_amdgcn_readfirstlane(tid >> 6) * 1024;
-  constexpr int A_BYTES = GEMM2_BM * GEMM_BK * 2;  // 32 KiB
-
-  auto stage = [&](int buf) {
-    char* base = lds2 + buf * GEMM2_STAGE_BYTES + wave_base;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_base + a_off[i]),
-                                       (__attribute__((address_space(3))) void*)(base + i * 8192), 16, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_base + w_off[i]),
-                                       (__attribute__((address_space(3))) void*)(base + A_BYTES + i * 8192), 16, 0,
-                                       0);
-    a_base += GEMM_BK * 2;
-    w_base += GEMM_BK * 2;
-  };
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int sw = lane & 7;
-  const int rd0 = l15 * 128 + (((0 + h) ^ sw) << 4);
-  const int rd1 = l15 * 128 + (((4 + h) ^ sw) << 4);
-  const int a_rd = wm * 64 * 128;
-  const int w_rd = A_BYTES + wn * 64 * 128;
-
-  // Software pipeline (fragments double-buffered in registers, one barrier per K-step placed BETWEEN the two
-  // MFMA clusters so every LDS fragment read overlaps a cluster instead of stalling behind the barrier):
-  //   F0 = frags(t, k-half 0) already in registers
-  //   A:  ds_read F1 = frags(t, 1)          || 16 MFMA on F0
-  //       s_waitcnt vmcnt(0) [stage t+1, issued a whole K-step ago] ; s_barrier ; issue stage t+2 -> buf (t+2)%3
-  //   B:  ds_read F0 = frags(t+1, 0)        || 16 MFMA on F1
-  // Buffer (t+2)%3 == (t-1)%3 was last read in iteration t-1 (its MFMAs have retired before this barrier).
-  const int nk = p.K / GEMM_BK;
-  stage(0);
-  if (nk > 1) stage(1);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(6) : "memory");
-  if (nk == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  bf16x8 af0[4], wf0[4], af1[4], wf1[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) af0[i] = *(const bf16x8*)(lds2 + a_rd + i * 2048 + rd0);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) wf0[j] = *(const bf16x8*)(lds2 + w_rd + j * 2048 + rd0);
-  auto mfma16 = [&](bf16x8 (&wf)[4], bf16x8 (&af)[4]) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  int buf = 0;
-  // main loop: every K-step except the last; the body is branch-free apart from the (uniform) stage issue, so
-  // the compiler's s_waitcnt lgkmcnt counts stay exact (fragment reads always overlap an MFMA cluster)
-  for (int kt = 0; kt + 1 < nk; ++kt) {
-    const char* base = lds2 + buf * GEMM2_STAGE_BYTES;
-    const int nbuf = (buf == 2) ? 0 : buf + 1;
-    // phase A.  F0 crossed the loop back-edge, so hipcc waits lgkmcnt(0) before its first use: issue the F1
-    // reads only AFTER the first MFMA (order pinned), then they overlap the other 15 MFMAs of the cluster.
-    __builtin_amdgcn_s_setprio(1);
-    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf0[0], af0[0], acc[0][0], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af1[i] = *(const bf16x8*)(base + a_rd + i * 2048 + rd1);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wf1[j] = *(const bf16x8*)(base + w_rd + j * 2048 + rd1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (i | j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf0[j], af0[i], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // stage kt+1 (issued a whole K-step ago) has landed
-    __builtin_amdgcn_s_barrier();
-    if (kt + 2 < nk) stage((nbuf == 2) ? 0 : nbuf + 1);
-    const char* nbase = lds2 + nbuf * GEMM2_STAGE_BYTES;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af0[i] = *(const bf16x8*)(nbase + a_rd + i * 2048 + rd0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wf0[j] = *(const bf16x8*)(nbase + w_rd + j * 2048 + rd0);
-    mfma16(wf1, af1);                                   // phase B (overlaps the F0 reads just issued)
-    buf = nbuf;
-  }
-  {  // last K-step
-    const char* base = lds2 + buf * GEMM2_STAGE_BYTES;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af1[i] = *(const bf16x8*)(base + a_rd + i * 2048 + rd1);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wf1[j] = *(const bf16x8*)(base + w_rd + j * 2048 + rd1);
-    mfma16(wf0, af0);
-    mfma16(wf1, af1);
-  }
-  gemm_epilogue(p, acc, m0 + wm * 64, n0 + wn * 64, l15, h);
-}
-
-// ---------------------------------------------------------------------------
-// 256x256x64 tile, 512 threads = 8 waves (2 x 4), each wave a 128x64 output block (8 x 4 MFMA tiles, 128
-// accumulator VGPRs), ONE workgroup per CU, two 64 KiB LDS buffers.  Compared with 64x64 per wave this reads
-// 25 % fewer fragment bytes from LDS per MFMA and stages half the LDS-DMA bytes per FLOP.
-// Per K-step t (fragments double-buffered in registers, one barrier per K-step placed between the two halves):
-//   A:   ds_read F1 = frags(t, k-half 1)   || 32 MFMA on F0 = frags(t, k-half 0)
-//   mid: s_waitcnt lgkmcnt(0)  - every read of buffer t%2 has landed in registers
-//        s_waitcnt vmcnt(0)    - stage t+1 (issued one K-step ago) has landed
-//        s_barrier             - ... for every wave; buffer t%2 is now dead
-//        issue stage t+2 -> buffer t%2   (has phase B(t) + phase A(t+1) to land)
-//        ds_read F0 = frags(t+1, k-half 0) from buffer (t+1)%2
-//   B:   32 MFMA on F1
+// Edge of the big tile (256 x 256 outputs): the plan's tile arithmetic and the split-K launcher's grid use it.
 #define GEMM4_B 256
-#define GEMM4_STAGE_BYTES (2 * GEMM4_B * GEMM_BK * 2)  // 65536
-#define GEMM4_LDS_BYTES (2 * GEMM4_STAGE_BYTES)        // 131072
 
-// NT = 16-column MFMA tiles per wave: 4 -> 256 x 256 tile, 3 -> 256 x 192 (LLM qkv: 9 x 24 = 216 tiles = one round of
-// the chip instead of 1.27 rounds of 128 x 128 tiles), 2 -> 256 x 128.  Same pipeline; the W panel is NT x 64 rows.
-template <int NT>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_256xN_kernel(GemmArgs p) {
-  constexpr int BN4 = 64 * NT;                    // tile columns
-  constexpr int WI = BN4 / 64;                    // W LDS-DMA instructions per thread per stage (= NT)
-  constexpr int NF = 8 + NT;                      // fragment reads per k-half
-  extern __shared__ __attribute__((aligned(16))) char lds4[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 2, wn = wave & 3;
-  const int l15 = lane & 15, h = lane >> 4;
-
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int tn = id / p.tiles_m, tm = id - tn * p.tiles_m;
-  const int m0 = tm * GEMM4_B, n0 = tn * BN4;
-
-  uint32_t a_off[4], w_off[WI];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = i * 512 + tid;
-    const int row = c >> 3;
-    const int ch = (c & 7) ^ (row & 7);
-    a_off[i] = (uint32_t)(min(m0 + row, p.M - 1) - m0) * (uint32_t)(p.lda * 2) + ch * 16;
-    if (i < WI) w_off[i] = (uint32_t)(min(n0 + row, p.N - 1) - n0) * (uint32_t)(p.ldw * 2) + ch * 16;
-  }
-  // split-K (p.part != null): grid.y slices of the K range, f32 partial tiles to part[slice][M][N]
-  const int nk_all = p.K / GEMM_BK;
-  const int kt0 = p.part ? (int)((long long)nk_all * blockIdx.y / p.ksplit) : 0;
-  const int kt1 = p.part ? (int)((long long)nk_all * (blockIdx.y + 1) / p.ksplit) : nk_all;
-  const char* a_base = (const char*)(p.A + (size_t)m0 * p.lda) + (size_t)kt0 * GEMM_BK * 2;
-  const char* w_base = (const char*)(p.W + (size_t)n0 * p.ldw) + (size_t)kt0 * GEMM_BK * 2;
-  const int wave_base = __builtin_amdgcn_readfirstlane(tid >> 6) * 1024;
-  constexpr int A_BYTES = GEMM4_B * GEMM_BK * 2;  // 32 KiB
-
-  // K tile kt -> LDS buffer buf.  kt is clamped by the caller, so the call is unconditional (no branch to
-  // split the scheduling region); a redundant trailing stage lands in a dead buffer.
-  auto stage = [&](int buf, int kt) {
-    char* base = lds4 + buf * GEMM4_STAGE_BYTES + wave_base;
-    const char* a_k = a_base + kt * (GEMM_BK * 2);
-    const char* w_k = w_base + kt * (GEMM_BK * 2);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_k + a_off[i]),
-                                       (__attribute__((address_space(3))) void*)(base + i * 8192), 16, 0, 0);
-#pragma unroll
-    for (int i = 0; i < WI; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_k + w_off[i]),
-                                       (__attribute__((address_space(3))) void*)(base + A_BYTES + i * 8192), 16, 0,
-                                       0);
-  };
-
-  f32x4 acc[8][NT];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int sw = lane & 7;
-  const int rd0 = l15 * 128 + (((0 + h) ^ sw) << 4);
-  const int rd1 = l15 * 128 + (((4 + h) ^ sw) << 4);
-  const int a_rd = wm * 128 * 128;            // + i * 2048
-  const int w_rd = A_BYTES + wn * (16 * NT) * 128;   // + j * 2048
-
-  bf16x8 af0[8], wf0[NT], af1[8], wf1[NT];
-  auto read_frags = [&](bf16x8 (&af)[8], bf16x8 (&wf)[NT], const char* base, int rd) {
-#pragma unroll
-    for (int j = 0; j < NT; ++j) wf[j] = *(const bf16x8*)(base + w_rd + j * 2048 + rd);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) af[i] = *(const bf16x8*)(base + a_rd + i * 2048 + rd);
-  };
-  auto mfma32 = [&](bf16x8 (&wf)[NT], bf16x8 (&af)[8], int skip_first) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        if ((i | j) >= skip_first)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-  };
-
-  const int nk = kt1 - kt0;
-  stage(0, 0);
-  stage(1, min(1, nk - 1));
-  if (NT == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if (NT == 3) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  read_frags(af0, wf0, lds4, rd0);
-  int buf = 0;
-  for (int kt = 0; kt + 1 < nk; ++kt) {
-    const char* base = lds4 + buf * GEMM4_STAGE_BYTES;
-    // phase A: first MFMA (the conservative lgkmcnt(0) before the first use of the back-edge-carried F0 must
-    // not wait for F1), then F1 reads interleaved one per MFMA
-    __builtin_amdgcn_s_setprio(1);
-    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf0[0], af0[0], acc[0][0], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    read_frags(af1, wf1, base, rd1);
-    mfma32(wf0, af0, 1);
-#pragma unroll
-    for (int g = 0; g < NF; ++g) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one DS read
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 8 * NT - 1 - NF, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    // mid
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    stage(buf, min(kt + 2, nk - 1));
-    read_frags(af0, wf0, lds4 + (buf ^ 1) * GEMM4_STAGE_BYTES, rd0);
-    // phase B: MFMAs on F1 start at once; the stage issue and the F0 reads ride between them
-    mfma32(wf1, af1, 0);
-#pragma unroll
-    for (int g = 0; g < 4 + WI; ++g) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);  // one VMEM (LDS-DMA)
-    }
-#pragma unroll
-    for (int g = 0; g < NF; ++g) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 8 * NT - (4 + WI) - NF, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    buf ^= 1;
-  }
-  {  // last K-step
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // also drains the redundant trailing stages
-    const char* base = lds4 + buf * GEMM4_STAGE_BYTES;
-    read_frags(af1, wf1, base, rd1);
-    mfma32(wf0, af0, 0);
-    mfma32(wf1, af1, 0);
-  }
-
-  if (p.part) {  // split-K: raw f32 partial sums, 16-byte stores (lane holds 4 consecutive columns)
-    float* dst = p.part + (size_t)blockIdx.y * p.M * p.N;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = m0 + wm * 128 + i * 16 + l15;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int n = n0 + wn * (16 * NT) + j * 16 + 4 * h;
-        if (n < p.N) *(f32x4*)(dst + (size_t)m * p.N + n) = acc[i][j];
-      }
-    }
-    return;
-  }
-  if (p.wide && !(p.act == ACT_SWIGLU && (NT & 1))) {
-    // every wave's fragment reads have been consumed by its MFMAs and its LDS-DMA drained (vmcnt(0) above); one
-    // barrier makes that true for the whole workgroup before the buffers become staging space
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    gemm_epilogue_wide_dispatch<8, NT>(p, acc, m0 + wm * 128, n0 + wn * (16 * NT), lane, lds4 + wave * 16384);
-    return;
-  }
-  // epilogue: two 64-row halves through the shared 4x4 epilogue
-#pragma unroll
-  for (int hm = 0; hm < 2; ++hm) {
-    f32x4 sub[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sub[i][j] = (j < NT) ? acc[hm * 4 + i][j < NT ? j : 0] : (f32x4){0.f, 0.f, 0.f, 0.f};
-    gemm_epilogue_n(p, sub, m0 + wm * 128 + hm * 64, n0 + wn * (16 * NT), l15, h, NT);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// 256 x 256 x 64 "ping-pong" tile: the two waves that share a SIMD (wave w and w + 4: row groups wr = 0 / 1) run
+// 256 x 256 x 64 "ping-pong" tile, 512 threads = 8 waves (2 x 4: wr = wave >> 2, wc = wave & 3), ONE workgroup per CU.
+// A wave owns a 128 x 64 output block = 8 x 4 MFMA 16x16x32 tiles (acc[i][j], i = 16-row block, j = 16-column block:
+// 128 accumulator VGPRs) in the layout of every bf16 tile kernel here (W is the MFMA's A operand): a lane holds
+// D[n = n0 + 64 wc + 16 j + 4 h + r][m = m0 + 128 wr + 16 i + l15], r = 0..3, four consecutive output columns.  Compared
+// with 64 x 64 per wave this reads 25 % fewer fragment bytes from LDS per MFMA and stages half the LDS-DMA bytes per FLOP.
+// The two waves that share a SIMD (wave w and w + 4: row groups wr = 0 / 1) run
 // half a phase apart, so one of them is always inside an MFMA cluster while the other issues its LDS reads and
 // LDS-DMA stages.  A K-tile is four phases; a phase = {fragment reads + one half-tile stage | s_barrier |
 // 16 MFMAs (one 64 x 32 quadrant of the wave's 128 x 64 output over the whole K-tile) | s_barrier}, and group
@@ -574,7 +249,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_256xN_kernel(GemmArgs p) {
 // their wait).  WAR: a half-tile is restaged >= 2 phases after the phase that read it, except B-h0, restaged one
 // phase after - its 4 reads are issued first and retired by lgkmcnt(8) BEFORE the reading phase's first barrier.
 // sched_barrier(0) at every s_barrier keeps hipcc from moving reads / MFMAs across them (the placement above IS
-// the synchronisation).  Same accumulator layout and epilogue as gemm_bf16_256xN_kernel<4>.
+// the synchronisation).
+// Epilogue hand-over: after the loop every wave has drained its own LDS-DMA (vmcnt(0)) and executed the same number of
+// barriers.  A split-K slice (p.part) stores its raw f32 accumulators, 16 bytes per lane.  The wide form takes one more
+// barrier - the operand buffers become staging space, 16 KiB per wave - and hands the whole 8 x 4 block to
+// gemm_epilogue_wide_dispatch<8, 4>; the direct form passes the block's two 64-row halves through the 4 x 4 epilogue
+// it shares with the other tile shapes (gemm_epilogue_n).
 #define GEMM5_HALF_BYTES 16384
 #define GEMM5_BUF_BYTES 65536
 #define GEMM5_LDS_BYTES 131072
@@ -1406,51 +1086,53 @@ __global__ __launch_bounds__(256) void gemm_splitk_finalize_kernel(GemmArgs p) {
   }
 }
 
-// Tile choice, measured on MI355X (tools/gemm_bench.py, tools/kbench.py).  VIS_GEMM_TILE=1|2|4 forces a shape.
-//  * 256x256 (1 WG/CU): best per-tile rate; used when its last round of 256 CUs is at least half full, and for
-//    wide problems (>= 3 rounds) with the ragged remainder columns handed to a second launch (LLM gate/up:
-//    9 x 148 tiles = 5.2 rounds -> 142 columns here + 6 columns below, instead of 6 rounds);
-//  * 256x192 / 256x128 forms of the same pipelined kernel (NT = 3 / 2): problems whose grid is then one (nearly) full
-//    round - LLM qkv 9 x 24 = 216 tiles (0.095 -> 0.071 ms against 1.27 rounds of 128x128 tiles), LLM o 9 x 28 = 252,
-//    ViT fc2 20 x 10 = 200; the older 3-stage 256x128 kernel (VIS_GEMM_TILE=2) is 3-5 % slower and kept for A/B;
-//  * 128x256 ping-pong half-tiles (1 WG/CU): what would otherwise go to 128x128 tiles, when the half-tile grid needs
+// Tile choice among the three tile kernels, measured on MI355X (tools/gemm_bench.py, tools/gemm_tiles_ab.py):
+//  * 7 = 256x256 ping-pong (1 WG/CU): best per-tile rate; whole problems where the cost model below puts its rounds of
+//    256 tiles under the 128x128 grid's rounds of 512, and the whole rounds of a grid whose last round would be thin, with
+//    the ragged remainder columns handed to a second launch (LLM gate/up: 9 x 148 tiles = 5.2 rounds -> 142 columns here
+//    + 6 columns on half-tiles, instead of 6 rounds);
+//  * 8 = 128x256 ping-pong half-tiles (1 WG/CU): what would otherwise go to 128x128 tiles, when the half-tile grid needs
 //    no more rounds (LLM o, ViT proj, the gate/up remainder columns, the merger);
-//  * 128x128 (2 WG/CU): everything else.
+//  * 1 = 128x128 (2 WG/CU): everything else.
 // The choice is host arithmetic on (M, N, K) alone and lives in gemm_plan(); gemm_dispatch() launches FROM that plan and
-// vis_gemm_bf16_plan() exports it, so what a test asks about and what runs cannot drift apart.
-// Kernel ids (the VIS_GEMM_TILE values where one exists): 1 = 128x128, 2 = 3-stage 256x128, 4 = 2-phase 256x256,
-// 5 / 6 = 2-phase 256x128 / 256x192, 7 = 256x256 ping-pong, 8 = 128x256 ping-pong half-tiles.
-#define GEMM_PLAN_MAX 4
-struct GemmLaunch { int kernel, n0, ncols, tiles_m, tiles_n; };   // covers W rows [n0, n0 + ncols)
-struct GemmPlan { int n; GemmLaunch l[GEMM_PLAN_MAX]; };
+// vis_gemm_bf16_plan() exports it (GemmPlan, gemm_epilogue.hip.h).
+
+// VIS_GEMM_TILE: 0 or unset = by the rules above, 1 | 7 | 8 = that kernel for every call (A/B).  Any other value is -1:
+// the launchers return VIS_ERR_ARG and the plan query 0 - a mistyped A/B run must not quietly measure the default.
+static int gemm_forced_tile() {
+  static const int forced = [] {
+    const char* e = getenv("VIS_GEMM_TILE");
+    const int v = e ? atoi(e) : 0;
+    return (v == 0 || v == 1 || v == 7 || v == 8) ? v : -1;
+  }();
+  return forced;
+}
 
 static void gemm_plan(int M, int Ntot, int K, GemmPlan* plan) {
-  static const int forced = [] { const char* e = getenv("VIS_GEMM_TILE"); return e ? atoi(e) : 0; }();
-  static const int pp_env = [] { const char* e = getenv("VIS_GEMM_PP"); return e ? atoi(e) : 1; }();   // 0: the 2-phase kernel (A/B)
+  const int forced = gemm_forced_tile();
   static const int mix1 = [] { const char* e = getenv("VIS_GEMM_MIX1"); return e ? atoi(e) : 64; }();
   static const bool half_ok = [] { const char* e = getenv("VIS_GEMM_HALF"); return !(e && atoi(e) == 0); }();
   plan->n = 0;
+  if (forced < 0) return;
   int n0 = 0;
   for (;;) {
     const int N = Ntot - n0;
     const int tn1 = (N + GEMM_BN - 1) / GEMM_BN;
     const int tm4 = (M + GEMM4_B - 1) / GEMM4_B, tn4 = (N + GEMM4_B - 1) / GEMM4_B;
     const int t4 = tm4 * tn4, last = t4 % 256;
-    const bool big = forced == 2;   // the 3-stage 256x128 kernel: A/B only
-    const bool use_pp = (pp_env != 0 && forced != 4) || forced == 7;
     // Kernel choice by a two-line cost model fitted to cold-cache timings of the production shapes (tools/gemm_tiles_ab.py,
     // r02): a 256x256 ping-pong tile costs ~1.41 us per 64-wide K-step + 4.3 us (prologue + epilogue), one per CU; a
     // 128x128 tile ~1.2 us per K-step + 3 us with two per CU.  Rounds are what ragged grids pay for:
     //   ViT qkv  4900x3840x1280: 300 tiles of 256^2 = 2 rounds (66 us) beat 1170 of 128^2 = 3 rounds (78 us);
-    //   LLM qkv  2249x4608x3584: 162 tiles of 256^2 on 63 % of the CUs (83 us) still beat 216 tiles of 256x192 (90 us);
-    //   LLM o    2249x3584x3584: 504 tiles of 128^2 = one full round of two per CU (75 us) beat 252 of 256x128 (85 us).
+    //   LLM qkv  2249x4608x3584: 162 tiles of 256^2 on 63 % of the CUs (83 us) against 648 of 128^2 = 2 rounds (140 by the model);
+    //   LLM o    2249x3584x3584: 504 tiles of 128^2 = one full round of two per CU (75 us) against 126 of 256^2 (83 by the model).
     // Every kernel accumulates K in the same order, so the choice (which depends on M) never changes a result bit
     // (tests/test_gemm_exact_gpu.py::test_row_count_invariance_*).
     const int nk64 = K / GEMM_BK;
     const int t1 = ((M + GEMM_BM - 1) / GEMM_BM) * tn1;
     const float cost1 = (float)((t1 + 511) / 512) * (1.2f * nk64 + 3.0f);
     const float cost4 = (float)((t4 + 255) / 256) * (1.41f * nk64 + 4.3f);
-    bool huge = forced ? (forced == 4 || forced == 7) : (K >= 256 && M > 128 && N > 128 && cost4 < cost1);
+    bool huge = forced ? forced == 7 : (K >= 256 && M > 128 && N > 128 && cost4 < cost1);
     int cols4 = tn4;  // 256-wide tile columns given to the 256x256 kernel
     // ... and (r05) ONE whole round + a remainder of fewer than 64 tiles: the second round of a 294-tile grid (LLM o at four images)
     // or a 264-tile one (the Auditor's qkv) costs almost a full round for 15 % / 3 % of the tiles - 155 -> 141 us and 162 -> 141 us
@@ -1466,13 +1148,6 @@ static void gemm_plan(int M, int Ntot, int K, GemmPlan* plan) {
     GemmLaunch& L = plan->l[plan->n++];
     L.n0 = n0;
     L.ncols = N;
-    // 256 x 192 / 256 x 128 forms of the 2-phase pipelined kernel: A/B only (r02: never the fastest on a production shape)
-    if (forced == 6 || forced == 5) {
-      L.kernel = forced;
-      L.tiles_m = tm4;
-      L.tiles_n = forced == 6 ? (N + 191) / 192 : tn1;
-      return;
-    }
     // 128 x 256 ping-pong half-tiles wherever the 128 x 128 kernel would run and the half-tile grid needs no more rounds
     // than its grid does (LLM o: 252 half-tiles = one round, 74.9 -> 68.0 us; ViT proj 195: 36.4 -> 33.6; the gate/up
     // remainder 108: 62.0 -> 56.6 - tools/gemm_tiles_ab.py, cold caches).  Its K-tile costs 1.14 us against the 128 x 128
@@ -1488,7 +1163,7 @@ static void gemm_plan(int M, int Ntot, int K, GemmPlan* plan) {
       return;
     }
     if (huge) {
-      L.kernel = use_pp ? 7 : 4;
+      L.kernel = 7;
       if (cols4 < tn4) L.ncols = cols4 * GEMM4_B;
       L.tiles_m = tm4;
       L.tiles_n = cols4;
@@ -1496,8 +1171,8 @@ static void gemm_plan(int M, int Ntot, int K, GemmPlan* plan) {
       n0 += cols4 * GEMM4_B;   // remainder columns [n0, Ntot): same problem, shifted operands
       continue;
     }
-    L.kernel = big ? 2 : 1;
-    L.tiles_m = big ? (M + GEMM2_BM - 1) / GEMM2_BM : (M + GEMM_BM - 1) / GEMM_BM;
+    L.kernel = 1;
+    L.tiles_m = (M + GEMM_BM - 1) / GEMM_BM;
     L.tiles_n = tn1;
     return;
   }
@@ -1506,6 +1181,7 @@ static void gemm_plan(int M, int Ntot, int K, GemmPlan* plan) {
 static int gemm_dispatch(GemmArgs p, hipStream_t stream) {
   GemmPlan plan;
   gemm_plan(p.M, p.N, p.K, &plan);
+  if (plan.n == 0) return VIS_ERR_ARG;   // VIS_GEMM_TILE names no kernel
   for (int i = 0; i < plan.n; ++i) {
     const GemmLaunch& L = plan.l[i];
     GemmArgs q = p;
@@ -1519,19 +1195,6 @@ static int gemm_dispatch(GemmArgs p, hipStream_t stream) {
     q.tiles_n = L.tiles_n;
     const dim3 grid(q.tiles_m * q.tiles_n);
     switch (L.kernel) {
-      case 5:
-      case 6: {
-        static const bool attr_ok = [] {
-          return hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     GEMM4_LDS_BYTES) == hipSuccess &&
-                 hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     GEMM4_LDS_BYTES) == hipSuccess;
-        }();
-        if (!attr_ok) return VIS_ERR_LAUNCH;
-        if (L.kernel == 6) hipLaunchKernelGGL(gemm_bf16_256xN_kernel<3>, grid, dim3(512), GEMM4_LDS_BYTES, stream, q);
-        else hipLaunchKernelGGL(gemm_bf16_256xN_kernel<2>, grid, dim3(512), GEMM4_LDS_BYTES, stream, q);
-        break;
-      }
       case 8: {
         static const bool attr6_ok = [] {
           return hipFuncSetAttribute((const void*)gemm_bf16_128x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1541,32 +1204,13 @@ static int gemm_dispatch(GemmArgs p, hipStream_t stream) {
         hipLaunchKernelGGL(gemm_bf16_128x256_pp_kernel, grid, dim3(512), GEMM6_LDS_BYTES, stream, q);
         break;
       }
-      case 4:
       case 7: {
-        static const bool attr4_ok = [] {
-          return hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     GEMM4_LDS_BYTES) == hipSuccess;
+        static const bool attr5_ok = [] {
+          return hipFuncSetAttribute((const void*)gemm_bf16_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     GEMM5_LDS_BYTES) == hipSuccess;
         }();
-        if (!attr4_ok) return VIS_ERR_LAUNCH;
-        if (L.kernel == 7) {
-          static const bool attr5_ok = [] {
-            return hipFuncSetAttribute((const void*)gemm_bf16_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       GEMM5_LDS_BYTES) == hipSuccess;
-          }();
-          if (!attr5_ok) return VIS_ERR_LAUNCH;
-          hipLaunchKernelGGL(gemm_bf16_256x256_pp_kernel, grid, dim3(512), GEMM5_LDS_BYTES, stream, q);
-        } else {
-          hipLaunchKernelGGL(gemm_bf16_256xN_kernel<4>, grid, dim3(512), GEMM4_LDS_BYTES, stream, q);
-        }
-        break;
-      }
-      case 2: {
-        static const bool attr_ok = [] {
-          return hipFuncSetAttribute((const void*)gemm_bf16_256x128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     GEMM2_LDS_BYTES) == hipSuccess;
-        }();
-        if (!attr_ok) return VIS_ERR_LAUNCH;
-        hipLaunchKernelGGL(gemm_bf16_256x128_kernel, grid, dim3(512), GEMM2_LDS_BYTES, stream, q);
+        if (!attr5_ok) return VIS_ERR_LAUNCH;
+        hipLaunchKernelGGL(gemm_bf16_256x256_pp_kernel, grid, dim3(512), GEMM5_LDS_BYTES, stream, q);
         break;
       }
       default:
@@ -1576,8 +1220,7 @@ static int gemm_dispatch(GemmArgs p, hipStream_t stream) {
   return VIS_OK;
 }
 
-// Host-only: what vis_gemm_bf16 would launch (no HIP call).  plan[0] = launches, plan[1] = wide epilogue, plan[2] =
-// non-temporal stores, then per launch {kernel id, first W row, W rows, tiles_m, tiles_n}.
+// Host-only: what vis_gemm_bf16 would launch (no HIP call), in the layout of gemm_plan_export.
 extern "C" int vis_gemm_bf16_plan(int M, int N, int K, int ldc, int ldr, int act, int has_residual, int aligned16,
                                   int* plan, int plan_ints) {
   if (!plan || M <= 0 || N <= 0 || K <= 0 || K % GEMM_BK != 0 || N % 4 != 0) return 0;
@@ -1585,15 +1228,7 @@ extern "C" int vis_gemm_bf16_plan(int M, int N, int K, int ldc, int ldr, int act
   if (act == ACT_SWIGLU && (N % 32 != 0 || has_residual)) return 0;
   GemmPlan g;
   gemm_plan(M, N, K, &g);
-  if (plan_ints < 3 + 5 * g.n) return 0;
-  plan[0] = g.n;
-  plan[1] = gemm_wide_ok(N, ldc, has_residual, ldr, aligned16, act);
-  plan[2] = gemm_nt_on(M, N, act);
-  for (int i = 0; i < g.n; ++i) {
-    int* o = plan + 3 + 5 * i;
-    o[0] = g.l[i].kernel; o[1] = g.l[i].n0; o[2] = g.l[i].ncols; o[3] = g.l[i].tiles_m; o[4] = g.l[i].tiles_n;
-  }
-  return g.n;
+  return gemm_plan_export(g, gemm_wide_ok(N, ldc, has_residual, ldr, aligned16, act), gemm_nt_on(M, N, act), plan, plan_ints);
 }
 
 // C-ABI launcher (declared in include/vis_hip.h)
@@ -1638,11 +1273,12 @@ static int gemm_splitk_launch(const void* A, const void* W, const void* bias, co
   if (act < ACT_NONE || act >= ACT_SWIGLU) return VIS_ERR_ARG;
   if (ksplit < 2 || ksplit > 8 || K / GEMM_BK < 2 * ksplit) return VIS_ERR_ARG;
   if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)R | (uintptr_t)work) & 15) return VIS_ERR_ARG;
-  static const bool attr4_ok = [] {
-    return hipFuncSetAttribute((const void*)gemm_bf16_256xN_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               GEMM4_LDS_BYTES) == hipSuccess;
+  if (gemm_forced_tile() < 0) return VIS_ERR_ARG;
+  static const bool attr5_ok = [] {
+    return hipFuncSetAttribute((const void*)gemm_bf16_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               GEMM5_LDS_BYTES) == hipSuccess;
   }();
-  if (!attr4_ok) return VIS_ERR_LAUNCH;
+  if (!attr5_ok) return VIS_ERR_LAUNCH;
   GemmArgs p;
   p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.bias = (const bf16_t*)bias; p.R = (const bf16_t*)R; p.C = (bf16_t*)C;
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.act = act;
@@ -1650,17 +1286,7 @@ static int gemm_splitk_launch(const void* A, const void* W, const void* bias, co
   p.tiles_m = (M + GEMM4_B - 1) / GEMM4_B;
   p.tiles_n = (N + GEMM4_B - 1) / GEMM4_B;
   vis_clear_error();
-  static const int pp_env = [] { const char* e = getenv("VIS_GEMM_PP"); return e ? atoi(e) : 1; }();
-  if (pp_env) {
-    static const bool attr5_ok = [] {
-      return hipFuncSetAttribute((const void*)gemm_bf16_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 GEMM5_LDS_BYTES) == hipSuccess;
-    }();
-    if (!attr5_ok) return VIS_ERR_LAUNCH;
-    hipLaunchKernelGGL(gemm_bf16_256x256_pp_kernel, dim3(p.tiles_m * p.tiles_n, ksplit), dim3(512), GEMM5_LDS_BYTES, stream, p);
-  } else {
-    hipLaunchKernelGGL(gemm_bf16_256xN_kernel<4>, dim3(p.tiles_m * p.tiles_n, ksplit), dim3(512), GEMM4_LDS_BYTES, stream, p);
-  }
+  hipLaunchKernelGGL(gemm_bf16_256x256_pp_kernel, dim3(p.tiles_m * p.tiles_n, ksplit), dim3(512), GEMM5_LDS_BYTES, stream, p);
   if (finalize) {
     const long long total = (long long)M * (N / 8);
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);

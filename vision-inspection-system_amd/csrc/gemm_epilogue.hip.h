@@ -39,6 +39,27 @@ static inline int gemm_nt_on(int M, int N, int act) {
   return nt_env == 2 || (nt_env == 1 && (size_t)M * (act == ACT_SWIGLU ? N / 2 : N) * 2 >= ((size_t)64 << 20));
 }
 
+// What one call launches (host arithmetic on the shape alone): the launchers launch FROM this record and the plan queries
+// export it, so what a test asks about and what runs cannot drift apart.  n == 0: nothing may be launched (the file's
+// VIS_GEMM_TILE / VIS_GEMM8_TILE names no kernel).  A kernel id means the same tile in both files: 1 = 128x128,
+// 7 = 256x256 ping-pong, 8 = 128x256 ping-pong half-tiles (bf16 only); the fp8 plan uses two of the slots.
+#define GEMM_PLAN_MAX 4
+struct GemmLaunch { int kernel, n0, ncols, tiles_m, tiles_n; };   // covers W rows [n0, n0 + ncols)
+struct GemmPlan { int n; GemmLaunch l[GEMM_PLAN_MAX]; };
+// plan[0] = launches, plan[1] = wide epilogue, plan[2] = non-temporal stores, then per launch {kernel id, first W row,
+// W rows, tiles_m, tiles_n}; returns the number of launches, 0 when there are none or `plan_ints` is too small
+static inline int gemm_plan_export(const GemmPlan& g, int wide, int nt, int* plan, int plan_ints) {
+  if (g.n <= 0 || plan_ints < 3 + 5 * g.n) return 0;
+  plan[0] = g.n;
+  plan[1] = wide;
+  plan[2] = nt;
+  for (int i = 0; i < g.n; ++i) {
+    int* o = plan + 3 + 5 * i;
+    o[0] = g.l[i].kernel; o[1] = g.l[i].n0; o[2] = g.l[i].ncols; o[3] = g.l[i].tiles_m; o[4] = g.l[i].tiles_n;
+  }
+  return g.n;
+}
+
 // ---------------------------------------------------------------------------
 // Wide epilogue: the wave's accumulator tile goes through a wave-private 16 KiB LDS region and leaves as whole
 // 16-byte chunks of C rows (8 lanes cover one 128-byte row segment), instead of 8-byte stores at a row stride

@@ -5,15 +5,15 @@
 //   A_q [M][lda] e4m3 bytes with a per-ROW (per-token) f32 scale sa, W_q [N][ldw] e4m3 bytes with a per-output-row
 //   f32 scale sw (hip.quantize_fp8_rows), f32 accumulation, bf16 output; same epilogues as vis_gemm_bf16.
 //
-// Structure = the 256x256 bf16 kernel (gemm_bf16.hip) with the K-step doubled to 128 elements - which is again 128
-// BYTES per tile row, so the LDS-DMA staging, the source-side XOR swizzle and the two 64 KiB buffers are identical:
-//  * 512 threads = 8 waves (2 x 4), 128 x 64 outputs per wave (8 x 4 MFMA tiles, 128 accumulator VGPRs);
+// Structure = the bf16 tile kernels (gemm_bf16.hip) with the K-step doubled to 128 elements - which is again 128
+// BYTES per tile row, so the LDS-DMA staging, the source-side XOR swizzle and the LDS buffers are laid out the same way:
+//  * two tile kernels: 256 x 256 ping-pong (512 threads = 8 waves (2 x 4), 128 x 64 outputs per wave = 8 x 4 MFMA tiles,
+//    128 accumulator VGPRs, two 64 KiB buffers, one workgroup per CU) and 128 x 128 (4 waves x 64 x 64, two per CU);
 //  * operand lane map (checked with exact integer data, tools/probes/mfma_f8_probe.hip): lane l holds
 //    X[row l & 15][k = 32 (l >> 4) + j], j = 0..31 - i.e. 16-byte chunks 2h and 2h+1 of its row (two ds_read_b128
-//    at the swizzled positions), 8 VGPRs per tile; C/D as for bf16;
-//  * a K-step is 32 MFMAs of K = 128 per wave.  Its operands are fat (96 VGPRs per K-step), so fragments are NOT
-//    double-buffered across K-steps; instead the step is split by m: [B, A0] -> 16 MFMAs while A1 is read ->
-//    one barrier (all reads of this buffer done, next stage landed) -> refill of this buffer -> 16 MFMAs.
+//    at the swizzled positions), 8 VGPRs per tile; C/D as for bf16: W is the MFMA's A operand, so a lane holds
+//    D[n = nbase + 16 j + 4 h + r][m = mbase + 16 i + l15], r = 0..3 - four consecutive output columns;
+//  * a K-step of the big tile is 32 MFMAs of K = 128 per wave, in four phases of 8 (one 64 x 32 quadrant each).
 #include "common.hip.h"
 
 #define F8_B 256
@@ -230,153 +230,13 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_128x128_kernel(GemmF8Args p) 
   f8_epilogue(p, acc, m0 + wm * 64, n0 + wn * 64, l15, h);
 }
 
-__global__ __launch_bounds__(512, 2) void gemm_fp8_256x256_kernel(GemmF8Args p) {
-  extern __shared__ __attribute__((aligned(16))) char lds8[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 2, wn = wave & 3;
-  const int l15 = lane & 15, h = lane >> 4;
-
-  const int nwg = p.tiles_m * p.tiles_n;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int tn = id / p.tiles_m, tm = id - tn * p.tiles_m;
-  const int m0 = tm * F8_B, n0 = tn * F8_B;
-
-  uint32_t a_off[4], w_off[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = i * 512 + tid;
-    const int row = c >> 3;
-    const int ch = (c & 7) ^ F8_SWZ(row);
-    a_off[i] = (uint32_t)(min(m0 + row, p.M - 1) - m0) * (uint32_t)p.lda + ch * 16;
-    w_off[i] = (uint32_t)(min(n0 + row, p.N - 1) - n0) * (uint32_t)p.ldw + ch * 16;
-  }
-  const int nk_all = p.K / F8_BK;
-  const int kt0 = p.part ? (int)((long long)nk_all * blockIdx.y / p.ksplit) : 0;
-  const int kt1 = p.part ? (int)((long long)nk_all * (blockIdx.y + 1) / p.ksplit) : nk_all;
-  const char* a_base = (const char*)(p.A + (size_t)m0 * p.lda) + (size_t)kt0 * F8_BK;
-  const char* w_base = (const char*)(p.W + (size_t)n0 * p.ldw) + (size_t)kt0 * F8_BK;
-  const int wave_base = __builtin_amdgcn_readfirstlane(tid >> 6) * 1024;
-  constexpr int A_BYTES = F8_B * F8_BK;  // 32 KiB
-
-  auto stage = [&](int buf, int kt) {
-    char* base = lds8 + buf * F8_STAGE_BYTES + wave_base;
-    const char* a_k = a_base + kt * F8_BK;
-    const char* w_k = w_base + kt * F8_BK;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_k + a_off[i]),
-                                       (__attribute__((address_space(3))) void*)(base + i * 8192), 16, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(w_k + w_off[i]),
-                                       (__attribute__((address_space(3))) void*)(base + A_BYTES + i * 8192), 16, 0,
-                                       0);
-  };
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int sw = F8_SWZ(l15);
-  const int rdlo = l15 * 128 + (((2 * h) ^ sw) << 4);
-  const int rdhi = l15 * 128 + (((2 * h + 1) ^ sw) << 4);
-  const int a_rd = wm * 128 * 128;           // + i * 2048
-  const int w_rd = A_BYTES + wn * 64 * 128;  // + j * 2048
-
-  auto frag = [&](const char* p0) -> i32x8 {
-    const u32x4 lo = *(const u32x4*)(p0 + rdlo), hi = *(const u32x4*)(p0 + rdhi);
-    return (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-  };
-
-  const int nk = kt1 - kt0;
-  stage(0, 0);
-  stage(1, min(1, nk - 1));
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  int buf = 0;
-  i32x8 af[4];   // A rows 0..63 of the wave's tile for the CURRENT K-step (read one half-step ahead)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) af[i] = frag(lds8 + a_rd + i * 2048);
-  for (int kt = 0; kt < nk; ++kt) {
-    const char* base = lds8 + buf * F8_STAGE_BYTES;
-    i32x8 wf[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wf[j] = frag(base + w_rd + j * 2048);
-    __builtin_amdgcn_s_setprio(1);
-    // phase A: column-major over the W fragments, so the first MFMAs start as soon as wf[0] has landed
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[j], af[i], acc[i][j], 0, 0, 0, 0x7f7f7f7f, 0,
-                                                                     0x7f7f7f7f);
-    i32x8 ag[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ag[i] = frag(base + a_rd + (4 + i) * 2048);
-    __builtin_amdgcn_s_setprio(0);
-    // mid: every read of this buffer has landed in registers; the next stage has landed; buffer is dead
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (kt + 2 < nk) stage(buf, kt + 2);
-    __builtin_amdgcn_s_setprio(1);
-    // phase B: rows 64..127; the next K-step's rows 0..63 are read underneath (af is free since phase A)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        acc[4 + i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[j], ag[i], acc[4 + i][j], 0, 0, 0,
-                                                                         0x7f7f7f7f, 0, 0x7f7f7f7f);
-    if (kt + 1 < nk) {
-      const char* nb = lds8 + (buf ^ 1) * F8_STAGE_BYTES;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = frag(nb + a_rd + i * 2048);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    buf ^= 1;
-  }
-
-  if (p.part) {  // split-K: raw (unscaled) f32 partial sums; the finalize kernel applies scales and the epilogue
-    float* dst = p.part + (size_t)blockIdx.y * p.M * p.N;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = m0 + wm * 128 + i * 16 + l15;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn * 64 + j * 16 + 4 * h;
-        if (n < p.N) *(f32x4*)(dst + (size_t)m * p.N + n) = acc[i][j];
-      }
-    }
-    return;
-  }
-  if (p.wide) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();   // slower waves may still be reading fragments of the last K-step
-    gemm_epilogue_wide_dispatch<8, 4>(p, acc, m0 + wm * 128, n0 + wn * 64, lane, lds8 + wave * 16384,
-                                      F8Scale<8>(p, m0 + wm * 128, n0 + wn * 64, l15, h));
-    return;
-  }
-  // epilogue: two 64-row halves through the shared 4x4 epilogue
-#pragma unroll
-  for (int hm = 0; hm < 2; ++hm) {
-    f32x4 sub[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sub[i][j] = acc[hm * 4 + i][j];
-    f8_epilogue(p, sub, m0 + wm * 128 + hm * 64, n0 + wn * 64, l15, h);
-  }
-}
-
 // The ping-pong schedule of gemm_bf16_256x256_pp_kernel (gemm_bf16.hip: half-tile layout, stage / read / wait table and
 // the hazard argument are written out there) on the fp8 MFMA: the tile row is again 128 bytes per K-step (128 e4m3
 // elements), a fragment is two 16-byte chunks (2h, 2h+1) per lane, a phase is 8 MFMAs of K = 128 - the same LDS
-// traffic, the same LDS-DMA count and the same MFMA time per phase as the bf16 kernel.
+// traffic, the same LDS-DMA count and the same MFMA time per phase as the bf16 kernel.  Wave (wr, wc) = (wave >> 2,
+// wave & 3) owns outputs [m0 + 128 wr, + 128) x [n0 + 64 wc, + 64) as acc[8][4]; after the loop a split-K slice stores
+// the raw sums, the wide epilogue takes the whole block with the tile's scales from LDS, and the direct form passes the
+// block's two 64-row halves through f8_epilogue.
 #define F8P_HALF_BYTES 16384
 #define F8P_BUF_BYTES 65536
 #define F8P_B0 0
@@ -609,21 +469,24 @@ __global__ __launch_bounds__(256) void gemm_fp8_splitk_finalize_kernel(GemmF8Arg
   }
 }
 
-// Tile choice by a cost model in us, fitted to tools/gemm_kscan.py KS_FP8=1 on the r05 kernels (VIS_GEMM8_TILE=1|4 forces):
+// Tile choice between the two tile kernels by a cost model in us, fitted to tools/gemm_kscan.py KS_FP8=1 on the r05 kernels:
 //   256 x 256 ping-pong, one workgroup per CU : a round of 256 tiles costs 8.2 + 1.27 per 128-wide K-step
 //   128 x 128, two workgroups per CU          : a round of 512 tiles costs 4.5 + 1.06 per K-step
 // candidates: everything on one kernel, or whole rounds of the big tile + the remaining columns on the small one (a
 // second launch: + 2 us).  r04's rule ("256 only when the last round is at least half full") sent the LLM's qkv / o
 // projections at 4 images (378 / 294 big tiles) to the small kernel: 121 / 118 us where two big rounds take ~88.
-// Host arithmetic only: vis_gemm_fp8 launches from this plan and vis_gemm_fp8_plan exports it.
-// Kernel ids: 1 = 128x128, 4 = 2-phase 256x256, 7 = 256x256 ping-pong.
-struct GemmF8Launch { int kernel, n0, ncols, tiles_m, tiles_n; };   // covers W rows [n0, n0 + ncols)
-struct GemmF8Plan { int n; GemmF8Launch l[2]; };
-
-static void gemm_fp8_plan(int M, int N, int K, bool split, GemmF8Plan* plan) {
-  static const int pp_env = [] { const char* e = getenv("VIS_GEMM_PP"); return e ? atoi(e) : 1; }();   // 0: 2-phase kernel (A/B)
-  static const int forced = [] { const char* e = getenv("VIS_GEMM8_TILE"); return e ? atoi(e) : 0; }();
-  const int k256 = pp_env ? 7 : 4;
+// Host arithmetic only: vis_gemm_fp8 launches from this plan and vis_gemm_fp8_plan exports it (GemmPlan, gemm_epilogue.hip.h;
+// kernel ids 1 = 128x128, 7 = 256x256 ping-pong - a split-K call always runs the latter).
+// VIS_GEMM8_TILE: 0 or unset = by the model, 1 | 7 = that kernel for every call (A/B).  Any other value leaves the plan
+// empty: vis_gemm_fp8 returns VIS_ERR_ARG and the plan query 0 - a mistyped A/B run must not quietly measure the default.
+static void gemm_fp8_plan(int M, int N, int K, bool split, GemmPlan* plan) {
+  static const int forced = [] {
+    const char* e = getenv("VIS_GEMM8_TILE");
+    const int v = e ? atoi(e) : 0;
+    return (v == 0 || v == 1 || v == 7) ? v : -1;
+  }();
+  plan->n = 0;
+  if (forced < 0) return;
   const int tiles_m = (M + F8_B - 1) / F8_B, tiles_n = (N + F8_B - 1) / F8_B;
   const int t4 = tiles_m * tiles_n;
   const int nk = K / F8_BK;
@@ -636,16 +499,16 @@ static void gemm_fp8_plan(int M, int N, int K, bool split, GemmF8Plan* plan) {
   const float cost_mixed = (cols4 > 0 && n_off < N)
                                ? rounds((long long)cols4 * tiles_m, 256) * c256 + rounds(tiles128(N - n_off), 512) * c128 + 2.f
                                : 1e30f;
-  int choice;   // 4: big, 1: small, 5: mixed
-  if (split || forced == 4) choice = 4;
+  int choice;   // 7: big, 1: small, 5: mixed
+  if (split || forced == 7) choice = 7;
   else if (forced == 1 || M < 1024) choice = 1;
-  else choice = (cost_big <= cost_small && cost_big <= cost_mixed) ? 4 : (cost_mixed < cost_small ? 5 : 1);
-  if (choice == 4) {
+  else choice = (cost_big <= cost_small && cost_big <= cost_mixed) ? 7 : (cost_mixed < cost_small ? 5 : 1);
+  if (choice == 7) {
     plan->n = 1;
-    plan->l[0] = {k256, 0, N, tiles_m, tiles_n};
+    plan->l[0] = {7, 0, N, tiles_m, tiles_n};
   } else if (choice == 5) {
     plan->n = 2;
-    plan->l[0] = {k256, 0, n_off, tiles_m, cols4};
+    plan->l[0] = {7, 0, n_off, tiles_m, cols4};
     plan->l[1] = {1, n_off, N - n_off, (M + 127) / 128, (N - n_off + 127) / 128};
   } else {
     plan->n = 1;
@@ -653,25 +516,17 @@ static void gemm_fp8_plan(int M, int N, int K, bool split, GemmF8Plan* plan) {
   }
 }
 
-// Host-only: what vis_gemm_fp8 would launch (no HIP call); `split` = a split-K call (work != NULL).  plan[] as for
-// vis_gemm_bf16_plan.
+// Host-only: what vis_gemm_fp8 would launch (no HIP call); `split` = a split-K call (work != NULL).  plan[] in the layout
+// of gemm_plan_export, as for vis_gemm_bf16_plan.
 extern "C" int vis_gemm_fp8_plan(int M, int N, int K, int ldc, int ldr, int act, int has_residual, int aligned16,
                                  int split, int* plan, int plan_ints) {
   if (!plan || M <= 0 || N <= 0 || K <= 0 || K % F8_BK != 0 || N % 4 != 0) return 0;
   if (ldc % 4 != 0 || (has_residual && ldr % 4 != 0) || act < F8_ACT_NONE || act > F8_ACT_SWIGLU) return 0;
   if (act == F8_ACT_SWIGLU && (N % 32 != 0 || has_residual)) return 0;
   if (split && (N % 8 != 0 || ldc % 8 != 0 || (has_residual && ldr % 8 != 0) || act == F8_ACT_SWIGLU || !aligned16)) return 0;
-  GemmF8Plan g;
+  GemmPlan g;
   gemm_fp8_plan(M, N, K, split != 0, &g);
-  if (plan_ints < 3 + 5 * g.n) return 0;
-  plan[0] = g.n;
-  plan[1] = gemm_wide_ok(N, ldc, has_residual, ldr, aligned16, act);
-  plan[2] = gemm_nt_on(M, N, act);
-  for (int i = 0; i < g.n; ++i) {
-    int* o = plan + 3 + 5 * i;
-    o[0] = g.l[i].kernel; o[1] = g.l[i].n0; o[2] = g.l[i].ncols; o[3] = g.l[i].tiles_m; o[4] = g.l[i].tiles_n;
-  }
-  return g.n;
+  return gemm_plan_export(g, gemm_wide_ok(N, ldc, has_residual, ldr, aligned16, act), gemm_nt_on(M, N, act), plan, plan_ints);
 }
 
 // work != NULL with ksplit in 2..8: split-K (f32 partials in `work`, ksplit*M*N floats; needs N % 8 == 0, no SwiGLU)
@@ -685,10 +540,11 @@ extern "C" int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, cons
   if (act == F8_ACT_SWIGLU && (N % 32 != 0 || bias || R)) return VIS_ERR_ARG;
   if (((uintptr_t)Aq | (uintptr_t)Wq | (uintptr_t)sw) & 15) return VIS_ERR_ARG;
   if (((uintptr_t)C | (uintptr_t)bias | (uintptr_t)R) & 7 || ((uintptr_t)sa & 3)) return VIS_ERR_ARG;
+  GemmPlan plan;
+  gemm_fp8_plan(M, N, K, work != nullptr, &plan);
+  if (plan.n == 0) return VIS_ERR_ARG;   // VIS_GEMM8_TILE names no kernel
   static const bool attr_ok = [] {
-    return hipFuncSetAttribute((const void*)gemm_fp8_256x256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               F8_LDS_BYTES) == hipSuccess &&
-           hipFuncSetAttribute((const void*)gemm_fp8_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    return hipFuncSetAttribute((const void*)gemm_fp8_256x256_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                F8_LDS_BYTES) == hipSuccess;
   }();
   if (!attr_ok) return VIS_ERR_LAUNCH;
@@ -708,10 +564,8 @@ extern "C" int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, cons
     p.part = (float*)work; p.ksplit = ksplit;
   }
   vis_clear_error();
-  GemmF8Plan plan;
-  gemm_fp8_plan(M, N, K, work != nullptr, &plan);
   for (int i = 0; i < plan.n; ++i) {
-    const GemmF8Launch& L = plan.l[i];
+    const GemmLaunch& L = plan.l[i];
     GemmF8Args q = p;
     const int c_off = (act == F8_ACT_SWIGLU) ? L.n0 / 2 : L.n0;
     q.W += (size_t)L.n0 * ldw;
@@ -724,7 +578,6 @@ extern "C" int vis_gemm_fp8(const void* Aq, const void* sa, const void* Wq, cons
     q.tiles_n = L.tiles_n;
     const dim3 grid(q.tiles_m * q.tiles_n, L.kernel == 1 ? 1 : p.ksplit);
     if (L.kernel == 7) hipLaunchKernelGGL(gemm_fp8_256x256_pp_kernel, grid, dim3(512), F8_LDS_BYTES, stream, q);
-    else if (L.kernel == 4) hipLaunchKernelGGL(gemm_fp8_256x256_kernel, grid, dim3(512), F8_LDS_BYTES, stream, q);
     else hipLaunchKernelGGL(gemm_fp8_128x128_kernel, grid, dim3(256), 0, stream, q);
   }
   if (work) {

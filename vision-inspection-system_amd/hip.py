@@ -376,17 +376,18 @@ def gemm_fp8(aq: torch.Tensor, sa: torch.Tensor, wq: torch.Tensor, sw: torch.Ten
     return out
 
 
-GEMM_KERNEL_NAMES = {1: "128x128", 2: "256x128_3stage", 4: "256x256_2phase", 5: "256x128_2phase", 6: "256x192_2phase",
-                     7: "256x256_pp", 8: "128x256_pp"}
+# kernel ids of the plan queries (csrc/gemm_bf16.hip, csrc/gemm_fp8.hip); an id names the same tile shape in both
+GEMM_KERNEL_NAMES = {1: "128x128", 7: "256x256_pp", 8: "128x256_pp"}
+GEMM_FP8_KERNEL_NAMES = {1: "128x128", 7: "256x256_pp"}
 
 
-def _gemm_plan(fn, args) -> dict:
+def _gemm_plan(fn, args, names) -> dict:
     import ctypes
     buf = (ctypes.c_int * 23)()
     n = fn(*args, ctypes.cast(buf, ctypes.c_void_p), 23)
     if n <= 0:
         raise HipLibraryError(f"gemm plan: arguments rejected {args}")
-    launches = [dict(kernel=GEMM_KERNEL_NAMES[buf[3 + 5 * i]], n0=buf[4 + 5 * i], ncols=buf[5 + 5 * i],
+    launches = [dict(kernel=names[buf[3 + 5 * i]], n0=buf[4 + 5 * i], ncols=buf[5 + 5 * i],
                      tiles_m=buf[6 + 5 * i], tiles_n=buf[7 + 5 * i]) for i in range(n)]
     return dict(wide=bool(buf[1]), nt=bool(buf[2]), launches=launches, kernels=tuple(l["kernel"] for l in launches))
 
@@ -398,7 +399,8 @@ def gemm_plan(M: int, N: int, K: int, act: int = ACT_NONE, ldc: Optional[int] = 
     n_out = N // 2 if act == ACT_SWIGLU else N
     ldc = n_out if ldc is None else ldc
     ldr = (ldc if ldr is None else ldr) if residual else 0
-    return _gemm_plan(load().vis_gemm_bf16_plan, (M, N, K, ldc, ldr, act, int(residual), int(aligned16)))
+    return _gemm_plan(load().vis_gemm_bf16_plan, (M, N, K, ldc, ldr, act, int(residual), int(aligned16)),
+                      GEMM_KERNEL_NAMES)
 
 
 def gemm_fp8_plan(M: int, N: int, K: int, act: int = ACT_NONE, ldc: Optional[int] = None, ldr: Optional[int] = None,
@@ -407,7 +409,8 @@ def gemm_fp8_plan(M: int, N: int, K: int, act: int = ACT_NONE, ldc: Optional[int
     n_out = N // 2 if act == ACT_SWIGLU else N
     ldc = n_out if ldc is None else ldc
     ldr = (ldc if ldr is None else ldr) if residual else 0
-    return _gemm_plan(load().vis_gemm_fp8_plan, (M, N, K, ldc, ldr, act, int(residual), int(aligned16), int(split)))
+    return _gemm_plan(load().vis_gemm_fp8_plan, (M, N, K, ldc, ldr, act, int(residual), int(aligned16), int(split)),
+                      GEMM_FP8_KERNEL_NAMES)
 
 
 # --------------------------------------------------------------------------- K3 / K5
