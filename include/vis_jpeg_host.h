@@ -5,7 +5,9 @@
  *
  * Supported: baseline / 8-bit extended-sequential Huffman JPEG with one interleaved scan; 1 component (grey) or 3
  * (YCbCr: luma 1x1, 2x1 or 2x2, chroma 1x1); restart markers.  Everything else returns VIS_JPEG_UNSUPPORTED (-1) and the
- * caller decodes with PIL; damaged data returns VIS_JPEG_CORRUPT (-2). */
+ * caller decodes with PIL; damaged data returns VIS_JPEG_CORRUPT (-2).  A stream with a block whose weighted coefficient
+ * sum exceeds the bound derived in jpeg_host.c (16-bit intermediates of libjpeg-turbo's SIMD inverse DCT could wrap or
+ * saturate, so decoders disagree about it) returns VIS_JPEG_RANGE (-3) from vis_jpeg_decode_coeffs: PIL decodes it. */
 #ifndef VIS_JPEG_HOST_H
 #define VIS_JPEG_HOST_H
 #include <stddef.h>
@@ -32,7 +34,8 @@ typedef struct {
 
 int vis_jpeg_info_size(void);                                               /* sizeof(VisJpegInfo), for bindings */
 int vis_jpeg_probe(const uint8_t* data, size_t n, VisJpegInfo* info);      /* 0, or -1 unsupported, -2 corrupt */
-/* coeffs: component planes back to back, blocks row-major, 64 int16 per block in natural order, NOT dequantised */
+/* coeffs: component planes back to back, blocks row-major, 64 int16 per block in natural order, NOT dequantised;
+ * 0, or -2 corrupt, -3 out of the range the GPU half reproduces bit for bit */
 int vis_jpeg_decode_coeffs(const uint8_t* data, size_t n, const VisJpegInfo* info, int16_t* coeffs);
 
 #ifdef __cplusplus

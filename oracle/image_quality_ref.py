@@ -16,6 +16,11 @@ def gray_u8(rgb: np.ndarray) -> np.ndarray:
 
 
 def laplacian_reflect101(gray: np.ndarray) -> np.ndarray:
-    """ksize-1 Laplacian (4-neighbour) with BORDER_REFLECT_101."""
-    p = np.pad(gray, 1, mode="reflect")
+    """ksize-1 Laplacian (4-neighbour) with BORDER_REFLECT_101.  Along an axis of size 1 reflect-101 has nothing to
+    reflect about: OpenCV's borderInterpolate maps every index to 0 there, i.e. the neighbour is the pixel itself."""
+    p = gray
+    for axis in (0, 1):
+        pad = [(0, 0), (0, 0)]
+        pad[axis] = (1, 1)
+        p = np.pad(p, pad, mode="reflect" if gray.shape[axis] > 1 else "edge")
     return p[:-2, 1:-1] + p[2:, 1:-1] + p[1:-1, :-2] + p[1:-1, 2:] - 4 * gray

@@ -52,7 +52,10 @@ def idct_blocks(coeffs, qt):
     c = coeffs.astype(np.int64).reshape(-1, 8, 8) * np.asarray(qt, dtype=np.int64).reshape(8, 8)
     ws = _idct_1d(c.transpose(0, 2, 1), CONST_BITS - PASS1_BITS).transpose(0, 2, 1)      # pass 1: columns
     out = _idct_1d(ws, CONST_BITS + PASS1_BITS + 3)                                      # pass 2: rows
-    out = ((out + 512) & 1023) - 512                                                     # range_limit[x & RANGE_MASK]
+    # Range limit: saturation, as libjpeg-turbo's SIMD islow does it (packssdw / packsswb, then +128).  jidctint.c itself
+    # looks up range_limit[x & RANGE_MASK] and wraps outside [-512, 511]; PIL does not follow that.  The SIMD code also
+    # keeps some intermediates in 16-bit lanes; this statement is exact only where none of them overflows, which is what
+    # csrc/jpeg_host.c guarantees for every stream it accepts (RANGE_LIMIT; tests/test_jpeg_craft.py).
     return np.clip(out + 128, 0, 255).astype(np.uint8)
 
 

@@ -18,6 +18,10 @@ def test_numpy_statement_basics():
     lap = laplacian_reflect101(g)
     assert lap[1, 1] == g[0, 1] + g[2, 1] + g[1, 0] + g[1, 2] - 4 * g[1, 1]
     assert lap[0, 0] == 2 * g[1, 0] + 2 * g[0, 1] - 4 * g[0, 0]   # reflect-101: index -1 -> 1
+    row = np.array([[3, 10, 4]], dtype=np.int64)                  # one row: the vertical neighbours are the pixel itself
+    assert laplacian_reflect101(row).tolist() == [[2 * 10 - 2 * 3, 3 + 4 - 2 * 10, 2 * 10 - 2 * 4]]
+    assert laplacian_reflect101(row.T).tolist() == laplacian_reflect101(row).T.tolist()
+    assert laplacian_reflect101(np.array([[9]], dtype=np.int64)).tolist() == [[0]]
 
 
 def test_scores_follow_the_reference_formulas():
@@ -33,18 +37,17 @@ def test_scores_follow_the_reference_formulas():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("h,w", [(1, 1), (2, 3), (37, 53), (480, 640), (1024, 1024)])
+@pytest.mark.parametrize("h,w", [(1, 1), (2, 3), (37, 53), (480, 640), (1024, 1024), (1, 7), (7, 1), (1, 300), (300, 1)])
 def test_gpu_stats_equal_numpy_statement(h, w):
     import torch
     from vision_inspection_system_amd import hip
     rng = np.random.default_rng(h * 1000 + w)
     rgb = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
     g = gray_u8(rgb)
-    lap = laplacian_reflect101(g) if min(h, w) > 1 else None
+    lap = laplacian_reflect101(g)
     sg, sl, sq = hip.image_stats(torch.from_numpy(rgb).to("cuda:0"))
     assert sg == int(g.sum())
-    if lap is not None:
-        assert sl == int(lap.sum()) and sq == int((lap * lap).sum())       # exact integers
+    assert sl == int(lap.sum()) and sq == int((lap * lap).sum())           # exact integers, one-row frames included
 
 
 @pytest.mark.gpu

@@ -782,6 +782,12 @@ def test_patchify_matches_reference_layout(hip, device):
     got = out.float().cpu().numpy()
     assert np.abs(got[:, :1176] - p).max() < 2e-2
     assert np.abs(got[:, 1176:]).max() == 0.0
+    # and exactly: bf16 round-to-nearest-even of the float64 value of every (level, channel) pair (tests/frontend_exact.py)
+    import frontend_exact as F
+    bits = out.view(torch.int16).cpu().numpy().view(np.uint16)
+    F.check_levels(bits[:, :1176], F.qwen_layout(img.astype(np.int64)), F.qwen_layout(F.channel_image(H, W)),
+                   F.level_table(mean, std), "patchify 56x84")
+    assert (bits[:, 1176:] == 0).all()
 
 
 # ----------------------------------------------------------------------------- K10 batched decode projection

@@ -1,7 +1,7 @@
 // GPU half of the service-side JPEG decode.  The host (csrc/jpeg_host.c) has parsed the
 // markers and Huffman-decoded the scan into quantised DCT coefficients; here:
 //   jpeg_idct_kernel   : one thread per 8x8 block - dequantise, libjpeg's integer "islow" inverse DCT
-//                        (jidctint.c jpeg_idct_islow: 13-bit constants, 2 extra bits between the passes), +128, clamp;
+//                        (jidctint.c jpeg_idct_islow: 13-bit constants, 2 extra bits between the passes), +128, saturate;
 //                        writes the component planes (uint8, whole MCUs).
 //   jpeg_rgb_kernel    : one thread per output pixel quad - "fancy" triangle chroma upsampling (jdsample.c
 //                        h2v1_fancy_upsample / h2v2_fancy_upsample; replication when the chroma plane is <= 2 samples
@@ -99,7 +99,10 @@ __global__ __launch_bounds__(128) void jpeg_idct_kernel(JpegArgs p) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) ws[r][c] = out[r];
   }
-  // pass 2: rows, range limit (libjpeg's table index is masked to 10 bits), +128
+  // pass 2: rows, +128, clamp to [0, 255].  Plain C libjpeg masks the sample to 10 bits before its range-limit table, so
+  // a sample outside [-512, 511] wraps there; libjpeg-turbo's SIMD code (what PIL runs) saturates, like this.  The host
+  // parser declines every stream in which a 16-bit intermediate of that SIMD code could wrap (jpeg_host.c, RANGE_LIMIT),
+  // so inside what reaches this kernel the clamp is the whole rule.
   uint8_t* dst = plane + ((size_t)by * 8) * (bw * 8) + bx * 8;
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
@@ -108,8 +111,7 @@ __global__ __launch_bounds__(128) void jpeg_idct_kernel(JpegArgs p) {
     uint32_t lo = 0, hi = 0;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      int v = ((out[c] + 512) & 1023) - 512 + 128;
-      v = min(max(v, 0), 255);
+      const int v = min(max(out[c] + 128, 0), 255);
       if (c < 4) lo |= (uint32_t)v << (8 * c);
       else hi |= (uint32_t)v << (8 * (c - 4));
     }

@@ -10,7 +10,9 @@
 // This file: marker parsing + Huffman decoding of baseline (SOF0 / 8-bit SOF1) JPEGs with one interleaved scan,
 // 1 component (grey) or 3 components (YCbCr; luma 1x1, 2x1 or 2x2, chroma 1x1), restart markers included.
 // Anything else (progressive, arithmetic coding, CMYK, Adobe RGB, multi-scan, 12-bit, exotic sampling) returns
-// VIS_JPEG_UNSUPPORTED and the caller decodes that image with PIL instead.
+// VIS_JPEG_UNSUPPORTED and the caller decodes that image with PIL instead.  So does a stream whose coefficients are so
+// large that libjpeg-turbo's 16-bit SIMD inverse DCT could wrap or saturate an intermediate (VIS_JPEG_RANGE, see
+// RANGE_LIMIT below): valid files, but no photograph - what they decode to depends on the libjpeg build.
 //
 // C ABI (include/vis_jpeg_host.h); built by `make` / __graft_entry__.build() with gcc into libvis_jpeg_host.so.
 #include <stdint.h>
@@ -20,6 +22,7 @@
 #define VIS_JPEG_OK 0
 #define VIS_JPEG_UNSUPPORTED (-1)
 #define VIS_JPEG_CORRUPT (-2)
+#define VIS_JPEG_RANGE (-3)
 
 typedef struct {
   int width, height, ncomp;
@@ -285,6 +288,27 @@ static inline int receive_extend(Bits* b, int s) {
   return (v < (1 << (s - 1))) ? v - (1 << s) + 1 : v;
 }
 
+// ---- the bound behind VIS_JPEG_RANGE
+// csrc/jpeg.hip runs the islow inverse DCT in 32-bit integers and clamps the sample to [0, 255].  libjpeg-turbo's SIMD
+// islow (what PIL runs) keeps the dequantised coefficients, the sums in0 +- in4, in7 + in3, in5 + in1 of either pass and
+// the column pass's outputs in 16-bit lanes (wrapping adds, saturating packs) and saturates the final sample; plain C
+// libjpeg instead masks the sample to 10 bits before its table lookup.  All of them agree with the kernel exactly when
+// none of the 16-bit quantities leaves int16 (samples outside [-512, 511] then clamp, which is also what the SIMD code
+// does).  A sufficient condition, from the parsed coefficients alone: with x[u][v] = coef * q the dequantised block
+// (u = vertical frequency) and g[u] = max over the eight outputs of the 1-D basis weight of frequency u
+// (g[0] = g[4] = 1, g[2] = g[6] = sqrt2 cos(pi/8) = 1.30656, g[odd] = sqrt2 cos(pi/16) = 1.38704),
+//     T = sum over the block of g[u] |x[u][v]|
+// bounds   |x| and every sum of two x                   by T          (g >= 1),
+//          every column-pass output ws (scaled by 4)     by 4 T_v + 1  (T_v = column v's share of T),
+//          every sum of two ws of different columns      by 4 T + 2,
+// so T <= 8000 keeps all of them inside +-32002 < 2^15 (and every 32-bit product sum below 2^30).  GAIN holds g in
+// 1/1024ths rounded UP (1421/1024 = 1.38770, 1339/1024 = 1.30762), which also covers the 13-bit rounding of the
+// transform's own constants (their combinations are within 5e-5 of the true weights).  The agents' photographs sit far
+// below: a block of 8-bit samples has an orthonormal spectrum of l1 norm <= 8192 in the worst case and q85 noise
+// measures T ~ 4200 (tests/test_jpeg_craft.py holds every PIL-written test image under the limit).
+static const uint32_t GAIN[8] = {1024, 1421, 1339, 1421, 1024, 1421, 1339, 1421};
+#define RANGE_LIMIT (8000ull * 1024ull)
+
 // coeffs: [component 0 blocks (row-major over bh x bw)] [component 1 ...] [component 2 ...], 64 int16 each, natural
 // order, NOT dequantised (the GPU multiplies by info->qt).  Blocks are zero-filled first.
 int vis_jpeg_decode_coeffs(const uint8_t* d, size_t n, const VisJpegInfo* info, int16_t* coeffs) {
@@ -299,6 +323,9 @@ int vis_jpeg_decode_coeffs(const uint8_t* d, size_t n, const VisJpegInfo* info, 
     off += (size_t)info->bw[c] * info->bh[c];
   }
   memset(coeffs, 0, off * 64 * sizeof(int16_t));
+  uint32_t wq[3][64];  // GAIN[u] * q per natural index: a block's T is sum |coef| * wq
+  for (int c = 0; c < info->ncomp; ++c)
+    for (int k = 0; k < 64; ++k) wq[c][k] = GAIN[k >> 3] * info->qt[c][k];
   Bits b;
   b.d = d; b.pos = (size_t)info->sos_offset; b.n = n; b.acc = 0; b.cnt = 0; b.marker = 0; b.fake = 0;
   int pred[3] = {0, 0, 0};
@@ -328,6 +355,7 @@ int vis_jpeg_decode_coeffs(const uint8_t* d, size_t n, const VisJpegInfo* info, 
             pred[c] += receive_extend(&b, t);
             if (pred[c] < -32768 || pred[c] > 32767) return VIS_JPEG_CORRUPT;  // no valid stream leaves the int16 range
             blk[0] = (int16_t)pred[c];
+            uint64_t t_sum = (uint64_t)(pred[c] < 0 ? -pred[c] : pred[c]) * wq[c][0];
             int k = 1;
             while (k < 64) {
               const int rs = decode_sym(&b, &ac[c]);
@@ -340,9 +368,12 @@ int vis_jpeg_decode_coeffs(const uint8_t* d, size_t n, const VisJpegInfo* info, 
               }
               k += r;
               if (k > 63) return VIS_JPEG_CORRUPT;
-              blk[ZIGZAG[k]] = (int16_t)receive_extend(&b, s);
+              const int val = receive_extend(&b, s);
+              blk[ZIGZAG[k]] = (int16_t)val;
+              t_sum += (uint64_t)(val < 0 ? -val : val) * wq[c][ZIGZAG[k]];
               ++k;
             }
+            if (t_sum > RANGE_LIMIT) return VIS_JPEG_RANGE;
           }
         }
       }

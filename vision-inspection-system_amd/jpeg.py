@@ -5,7 +5,8 @@ libvis_jpeg_host.so) - quantised DCT coefficients, no pixels.  ``to_rgb_device``
 upload of the coefficients (the size of the RGB frame it replaces) and two HIP kernels - dequantise + integer inverse
 DCT per 8x8 block, then triangle chroma upsampling + fixed-point YCbCr -> RGB - bit-exact with libjpeg-turbo's default
 decoder, i.e. with what ``PIL.Image.open(...).convert("RGB")`` returns (tests/test_jpeg.py, tests/test_jpeg_gpu.py).
-JPEG flavours the C parser declines (progressive, CMYK, ...) return None from ``parse``: the caller uses PIL for them.
+JPEG flavours the C parser declines (progressive, CMYK, ..., or coefficients beyond the range in which every libjpeg build
+decodes alike) return None from ``parse``: the caller uses PIL for them.
 ``VIS_GPU_JPEG=0`` switches the whole path off (A/B)."""
 from __future__ import annotations
 
@@ -79,13 +80,25 @@ class JpegCoeffs:
         return {k: getattr(self, k) for k in ("width", "height", "ncomp", "hs", "vs", "bw", "bh", "dw", "dh", "qt")}
 
 
+DECLINE_REASONS = {-1: "unsupported", -2: "corrupt", -3: "range"}
+
+
 def parse(data: bytes) -> Optional[JpegCoeffs]:
-    """Huffman-decode a JPEG byte string; None when the flavour is not handled here or the data is damaged (the caller
-    then lets PIL decide what to do with it, like before)."""
+    """Huffman-decode a JPEG byte string; None when the flavour is not handled here, the data is damaged or the
+    coefficients are beyond what the GPU half reproduces bit for bit (the caller then lets PIL decide what to do with it,
+    like before)."""
+    return parse_status(data)[0]
+
+
+def parse_status(data: bytes):
+    """``parse`` with the reason: (JpegCoeffs, "ok") or (None, "unsupported" | "corrupt" | "range").  "range": a valid
+    stream with a block whose coefficients are so large that a 16-bit intermediate of libjpeg-turbo's SIMD inverse DCT
+    could overflow (the bound is derived in csrc/jpeg_host.c) - decoders disagree about such blocks, so PIL decodes it."""
     lib = host_lib()
     info = _Info()
-    if lib.vis_jpeg_probe(data, len(data), ctypes.byref(info)) != 0:
-        return None
+    rc = lib.vis_jpeg_probe(data, len(data), ctypes.byref(info))
+    if rc != 0:
+        return None, DECLINE_REASONS.get(rc, "corrupt")
     # On a GPU process the Huffman decoder writes straight into page-locked memory (this pool thread allocates it; PyTorch's
     # caching host allocator recycles the blocks): the engine thread then only queues an async copy instead of first copying
     # 3 MB into a staging buffer - 64-image seam: 6.9 ms of launch-thread time per image for upload + IDCT / resize launches
@@ -98,13 +111,14 @@ def parse(data: bytes) -> Optional[JpegCoeffs]:
         except RuntimeError:
             pinned = None
     coeffs = pinned.numpy() if pinned is not None else np.empty((info.total_blocks, 64), dtype=np.int16)
-    if lib.vis_jpeg_decode_coeffs(data, len(data), ctypes.byref(info), coeffs.ctypes.data) != 0:   # releases the GIL
-        return None
+    rc = lib.vis_jpeg_decode_coeffs(data, len(data), ctypes.byref(info), coeffs.ctypes.data)        # releases the GIL
+    if rc != 0:
+        return None, DECLINE_REASONS.get(rc, "corrupt")
     n = info.ncomp
     t = lambda a: tuple(int(a[i]) for i in range(n))
     qt = np.array([[info.qt[c][k] for k in range(64)] for c in range(3)], dtype=np.uint16)
     return JpegCoeffs(info.width, info.height, n, t(info.hs), t(info.vs), t(info.bw), t(info.bh), t(info.dw), t(info.dh),
-                      qt, coeffs, pinned)
+                      qt, coeffs, pinned), "ok"
 
 
 def _pin_coeffs() -> bool:
