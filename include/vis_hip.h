@@ -638,6 +638,39 @@ int vis_skinny_finalize_fp8(const void* part, int ksplit, const void* sx, const 
                             const void* R, const void* norm_w, void* y, void* yn, void* yq, void* yq_scale, int B,
                             int N, int ldr, int ldy, int ldyn, int ldyq, int swiglu, float eps, vis_stream_t stream);
 
+/* ---- Lossless n-gram speculative decoding of one greedy sequence (csrc/spec.hip, spec.py) ----
+ * A step runs R = 1 + k rows (1 <= R <= 4: the current token and up to k drafted ones) through vis_gemv_*_rows, then:
+ *
+ * vis_decode_attn_draft: vis_decode_attn for the `rows` rows of ONE sequence.  Row r of qkv [rows][qkv_ld] (packed
+ * projection rows, qkv_ld >= (Hq + 2 Hkv) * 128, a multiple of 8) sits at position *step_ptr + r: rope row, cache row and
+ * keys [0, *step_ptr + r] follow from it; the rows are causal among themselves.  Caches [Hkv][cache_tokens][128], tables
+ * [cache_tokens][128], workspaces part_o [rows][Hq][nsplit][128] / part_ml [rows][Hq][nsplit][2] f32, out [rows][Hq*128].
+ * Three launches (append every row, attend, combine) with vis_decode_attn's split plan and key order: output row r and
+ * the cache are bit-identical to `rows` successive vis_decode_attn launches at advancing steps.  A row at a position
+ * >= cache_tokens reads and writes nothing (its output row keeps what it held).  *step_ptr is not changed. */
+int vis_decode_attn_draft(const void* qkv, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                          const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                          int cache_tokens, int nsplit, float scale, int rows, long long qkv_ld, vis_stream_t stream);
+
+/* vis_spec_accept: p_r = the greedy pick of logits row r ([rows][ld_logits] f32; vis_argmax_f32's comparison: ties to the
+ * lowest id, a row without a comparable logit picks 0); d = *n_draft clamped to 0..rows-1; a = the number of leading
+ * r < d with draft[r] == p_r, clamped so that *step_ptr + a <= *limit (the last index of `tokens` the request may
+ * write; also clamped to max_tokens - 1).  Writes tokens[*step_ptr + r] = p_r for r = 0..a, *cur_token = p_a,
+ * *step_ptr += a + 1 and adds (1, d, a) to counters[0..2] (steps, proposed, accepted).  With *step_ptr > *limit on
+ * entry nothing is written at all.  ws_val / ws_idx: 256 entries per row.  Two launches. */
+int vis_spec_accept(const void* logits, int V, int ld_logits, int rows, const void* draft, const void* n_draft,
+                    const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
+                    void* step_ptr, void* counters, vis_stream_t stream);
+
+/* vis_spec_draft: prompt lookup over the history h = prompt_ids[0 .. *prompt_len) followed by tokens[*gen_start ..
+ * *step_ptr) (vis_ban_f32's reading), length L.  For m = lookup_max down to lookup_min (1 <= min <= max <= 8) with
+ * L > m: the LATEST j < L - m with h[j .. j+m) == h[L-m .. L); the first m with a match writes draft[0 .. d) =
+ * h[j+m .. j+m+d), d = min(k, L - j - m) (1 <= k <= 3; ids clamped into [0, vocab)), and *n_draft = d.  No match:
+ * *n_draft = 0, draft untouched.  One workgroup, no host round trip.  spec.propose() is the definition. */
+int vis_spec_draft(const void* prompt_ids, int ld_prompt, const void* prompt_len, const void* tokens, int max_tokens,
+                   const void* gen_start, const void* step_ptr, int k, int lookup_max, int lookup_min, int vocab,
+                   void* draft, void* n_draft, vis_stream_t stream);
+
 /* ---- Row f2: Llama-3.2-11B-Vision ("mllama") Auditor, reference src/agents/vlm_auditor.py:81-83,:152-158 ---- */
 
 /* Resized RGB frame -> patch rows of the tile canvas (zero padding applied to RAW pixels, then rescale/normalise;

@@ -149,6 +149,21 @@ def stop_kwargs() -> dict:
     return {"stop": stop}
 
 
+def speculative_kwargs(client, model_id, temperature, others: dict) -> dict:
+    """VIS_SPECULATIVE=k (1..3; default unset / 0 = off): a single analysis or verify request passes speculative={"method":
+    "ngram", "num_speculative_tokens": k} - lossless n-gram speculative decoding (spec.py): the report's JSON template
+    stands in the prompt, and what the reply copies of it costs fewer weight passes; the reply itself is unchanged.  Only
+    on requests that carry none of the switches it excludes (``others``: the keywords of the VIS_* switches above; a
+    temperature), only to this package's own clients, and not to an mllama model.  Unset: the calls are as before."""
+    from .client import CannedResponseClient, LocalVLMClient, is_mllama_model
+    from .spec import from_env
+    sp = from_env()
+    if sp is None or others or temperature or not isinstance(client, (LocalVLMClient, CannedResponseClient)) \
+            or is_mllama_model(model_id):
+        return {}
+    return {"speculative": {"method": "ngram", "num_speculative_tokens": sp.k}}
+
+
 def _logger(name: str) -> logging.Logger:
     try:  # pragma: no cover - only inside the reference application
         from utils.logger import setup_logger  # type: ignore
@@ -173,10 +188,11 @@ class _BaseAgent:
         delay = 1
         for attempt in range(max_retries):
             try:
+                kw = dict(**json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs(), **shaping_kwargs(),
+                          **ban_kwargs())
                 completion = self.client.chat.completions.create(
                     model=self.model_id, messages=messages, temperature=self.temperature, max_tokens=self.max_tokens,
-                    **json_mode_kwargs(), **seed_kwargs(), **penalty_kwargs(), **stop_kwargs(),
-                    **shaping_kwargs(), **ban_kwargs())
+                    **kw, **speculative_kwargs(self.client, self.model_id, self.temperature, kw))
                 return completion.choices[0].message.content
             except Exception as e:
                 text = str(e)

@@ -219,9 +219,14 @@ class _Completions:
                stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                logit_bias: Optional[dict] = None, n: Optional[int] = None, stream: Optional[bool] = None,
                stream_options: Optional[dict] = None, no_repeat_ngram_size: Optional[int] = None,
-               bad_words: Optional[list] = None, min_tokens: Optional[int] = None, **kwargs):
+               bad_words: Optional[list] = None, min_tokens: Optional[int] = None, speculative=None, **kwargs):
         """``stream=True``: an iterator of ChatCompletionChunk instead of a ChatCompletion (``stream_options``: OpenAI's
-        {"include_usage": True}); None or False: the call of before."""
+        {"include_usage": True}); None or False: the call of before.
+        ``speculative`` (extension; vLLM's names): {"method": "ngram", "num_speculative_tokens": k in 1..3[,
+        "prompt_lookup_max": 4, "prompt_lookup_min": 2]} - lossless n-gram speculative decoding (spec.py): the same text
+        and usage in fewer weight passes where the reply repeats earlier text.  A greedy single request of a Qwen2-VL model
+        only: ValueError with a temperature, a seed, ``n`` > 1 or any other sampling / constraint / stop / stream / logprobs
+        keyword.  None: the call of before."""
         from .stream import check_stream, check_stream_options
         if check_stream(stream):
             if logprobs:
@@ -236,6 +241,8 @@ class _Completions:
                  "logit_bias": logit_bias, "n": n, "no_repeat_ngram_size": no_repeat_ngram_size, "bad_words": bad_words,
                  "min_tokens": min_tokens}
         kwargs.update({name: v for name, v in given.items() if v is not None})
+        if speculative is not None:
+            kwargs["speculative"] = speculative
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
                                      top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
                                      **kwargs)
@@ -427,6 +434,29 @@ def logprobs_k(logprobs, top_logprobs) -> Optional[int]:
     return int(top_logprobs or 0)
 
 
+def check_speculative_request(speculative, temperature=None, seed=None, **switches):
+    """``speculative`` of one ``create`` call, checked without a model: spec.check_speculative's record, or ValueError when
+    the dict is malformed or the request carries something a speculative step cannot (spec.check_exclusive names it)."""
+    from . import spec
+    sp = spec.check_speculative(speculative)
+    spec.check_exclusive(sp, float(temperature) if temperature else 0.0, seed, **switches)
+    return sp
+
+
+def is_mllama_model(model_id: Optional[str]) -> bool:
+    """Whether ``model_id`` names a model of the mllama family, found out without loading it."""
+    import json
+    if not model_id:
+        return False
+    if model_id.startswith("synthetic:"):
+        return model_id.startswith("synthetic:mllama")
+    path = resolve_model_dir(model_id)
+    if path is None or not os.path.exists(os.path.join(path, "config.json")):
+        return False
+    with open(os.path.join(path, "config.json")) as f:
+        return json.load(f).get("model_type") == "mllama"
+
+
 def check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format) -> dict:
     """``no_repeat_ngram_size`` / ``bad_words`` / ``min_tokens`` of one request, checked without a model (ban.check_ban; how
     many ids a word has is the tokenizer's to say, when the request is switched on): the engine keywords that are on ({} when
@@ -611,7 +641,17 @@ class LocalVLMClient:
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
                   top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
                   stop=None, top_k=None, min_p=None, logit_bias=None, n=None, stream=None, stream_options=None,
-                  no_repeat_ngram_size=None, bad_words=None, min_tokens=None, **kwargs):
+                  no_repeat_ngram_size=None, bad_words=None, min_tokens=None, speculative=None, **kwargs):
+        if speculative is not None:
+            sp = check_speculative_request(
+                speculative, temperature, seed, logprobs=logprobs, top_logprobs=top_logprobs, response_format=response_format,
+                top_p=top_p, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
+                repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n,
+                stream=stream, no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
+            if is_mllama_model(model or self.default_model):
+                raise ValueError("speculative decoding is offered for Qwen2-VL / Qwen2.5-VL models only: the Mllama engine's "
+                                 "cross-attention rows have no multi-row form")
+            return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp)[0]
         out = self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
                                  response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop,
@@ -687,7 +727,8 @@ class LocalVLMClient:
                        repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
                        min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
                        n: Optional[int] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
-                       bad_words: Optional[list] = None, min_tokens: Optional[int] = None) -> List[ChatCompletion]:
+                       bad_words: Optional[list] = None, min_tokens: Optional[int] = None,
+                       speculative=None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -735,7 +776,9 @@ class LocalVLMClient:
         ``min_tokens`` (vLLM's, <= max_tokens): no EOS before that many completion tokens; it holds back EOS only, a ``stop``
         string may still end the reply earlier.  One launch ahead of the pick (ban.py), after the penalties.  None / 0 / []
         = off.  Not together with a ``response_format`` of json_object or json_schema: ValueError.  Checked before any GPU
-        work.  Logprobs keep their meaning."""
+        work.  Logprobs keep their meaning.
+        ``speculative`` (a spec.SpecConfig, from ``create`` only - ``complete_many`` does not offer it): the ONE request of the
+        call goes through the engine's ``generate(.., speculative=)``; every other keyword is off then (create checks)."""
         from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
         from .shaping import check_shaping, shaping_kwargs
@@ -758,6 +801,8 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         n = check_n(n, eng.max_batch)
         n = None if n == 1 else n
+        if speculative is not None and (len(batch_of_messages) != 1 or lm.family == "mllama"):
+            raise ValueError("speculative decoding serves one request of a Qwen2-VL / Qwen2.5-VL model per call")
         # What every engine call of this request group gets, built once: the switches that are on (an engine call without a
         # keyword is the call of before the keyword existed) and the ignore-EOS switch in the engine's spelling.
         ignore_eos = os.environ.get("VIS_IGNORE_EOS") == "1"
@@ -776,8 +821,12 @@ class LocalVLMClient:
                 idx = indices[i:i + per_chunk]
                 if on_stream is not None:
                     on_stream.requests = list(idx)      # which requests of the call this engine call serves
-                outs = eng.generate_batch([request_of(j) for j in idx], seed=self.seed, **gen,
-                                          **({"seeds": [seed] * len(idx)} if seed is not None else {}))
+                if speculative is not None:      # one greedy request, no other switch: the single-sequence loop, speculating
+                    ids, frames = request_of(idx[0])()
+                    outs = [eng.generate(ids, frames, speculative=speculative, **gen)]
+                else:
+                    outs = eng.generate_batch([request_of(j) for j in idx], seed=self.seed, **gen,
+                                              **({"seeds": [seed] * len(idx)} if seed is not None else {}))
                 recs = eng.last_logprobs if k is not None else [None] * len(idx)
                 fins = getattr(eng, "last_finish", None) or [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", None) or {})
@@ -933,14 +982,20 @@ class CannedResponseClient:
     def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
                   frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None, top_k=None, min_p=None,
                   logit_bias=None, n=None, stream=None, stream_options=None, no_repeat_ngram_size=None, bad_words=None,
-                  min_tokens=None, **kwargs):
+                  min_tokens=None, speculative=None, **kwargs):
         check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
+        if speculative is not None:
+            check_speculative_request(
+                speculative, temperature, seed, response_format=response_format, top_p=top_p,
+                frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, repetition_penalty=repetition_penalty,
+                stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n, stream=stream,
+                no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens, **kwargs)
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
                            "response_format": response_format, "top_p": top_p, "seed": seed})
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
                  "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
                  "logit_bias": logit_bias, "n": n, "no_repeat_ngram_size": no_repeat_ngram_size, "bad_words": bad_words,
-                 "min_tokens": min_tokens}
+                 "min_tokens": min_tokens, "speculative": speculative}
         self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
         reply = self.reply(messages) if callable(self.reply) else self.reply
         done = ChatCompletion([_Choice(_Message(reply), index=i) for i in range(check_n(n, 64) or 1)], model=model or "")

@@ -708,61 +708,13 @@ __global__ __launch_bounds__(512) void decode_attn_stream_kernel(DecAttnArgs p, 
   }
 }
 
-// merge the per-split partials of one query head (only the splits that ran): 256 threads = 128 dims x 2
-// split-halves; the first partial loads are issued before the position is known
-#define CB_PRE 32   // partial rows preloaded per thread: covers 64 splits = 4096 cached keys
+// merge the per-split partials of one query head (decode_attn_combine_body, decode_common.hip.h)
 __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float* __restrict__ part_o,
                                                                   const float* __restrict__ part_ml,
                                                                   bf16_t* __restrict__ out, int nsplit,
                                                                   const int* __restrict__ step_ptr,
                                                                   int cache_tokens) {
-  constexpr int HD = 128;
-  __shared__ float wgt[256];
-  __shared__ float osum[2][HD];
-  __shared__ float wm[4];
-  const int hq = blockIdx.x, seq = blockIdx.y, tid = threadIdx.x, d = tid & 127, half = tid >> 7;
-  part_o += (size_t)seq * gridDim.x * nsplit * HD;
-  part_ml += (size_t)seq * gridDim.x * nsplit * 2;
-  out += (size_t)seq * gridDim.x * HD;
-  step_ptr += seq;
-  const float* po = part_o + (size_t)hq * nsplit * HD + d;
-  const float* ml = part_ml + (size_t)hq * nsplit * 2;
-  // ONE level of loads: the partials of the first 2 x CB_PRE split slots, the statistics of every slot and the position
-  // are all requested at once; slots that did not run this step hold stale data and are masked (selected away, never
-  // multiplied) once the position has arrived.  Before, position -> statistics -> late partials were three dependent
-  // round trips in a kernel that does nothing else.
-  float v[CB_PRE];
-#pragma unroll
-  for (int j = 0; j < CB_PRE; ++j) v[j] = po[(size_t)min(half + 2 * j, nsplit - 1) * HD];
-  const int sl = min(tid, nsplit - 1);
-  const float m_raw = ml[sl * 2], l_raw = ml[sl * 2 + 1];
-  const int ctx = min(*step_ptr, cache_tokens - 1) + 1;
-  const int active = min((ctx + DA_MAXKEYS - 1) / DA_MAXKEYS, nsplit);  // splits that ran
-  const float m = (tid < active) ? m_raw : -1.0e30f;
-  const float l = (tid < active) ? l_raw : 0.f;
-  float M = wave_max(m);
-  if ((tid & 63) == 0) wm[tid >> 6] = M;
-  __syncthreads();
-  M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-  const float w = (tid < active) ? exp2f(m - M) : 0.f;
-  wgt[tid] = w;
-  const float lw = wave_sum(w * l);
-  __syncthreads();
-  if ((tid & 63) == 0) wm[tid >> 6] = lw;
-  float o = 0.f;
-#pragma unroll
-  for (int j = 0; j < CB_PRE; ++j) {
-    const int s = half + 2 * j;
-    if (s < active) o += wgt[s] * v[j];
-  }
-  for (int s = half + 2 * CB_PRE; s < active; s += 2) o += wgt[s] * po[(size_t)s * HD];   // contexts past 64 splits
-  osum[half][d] = o;
-  __syncthreads();
-  if (tid < HD) {
-    const float lt = wm[0] + wm[1] + wm[2] + wm[3];
-    const float ot = osum[0][tid] + osum[1][tid];
-    out[(size_t)hq * HD + tid] = f2bf(lt > 0.f ? ot / lt : 0.f);
-  }
+  decode_attn_combine_body(part_o, part_ml, out, nsplit, step_ptr, cache_tokens, false);
 }
 
 static int decode_attn_launch(const DecAttnArgs& p, void* out, int batch, hipStream_t stream) {

@@ -387,6 +387,12 @@ struct DecAttnLds {
 // the packed projection row is produced by OTHER workgroups of the same launch, so the item first collects its kv group's
 // rows from their granules (`cc`) and leaves its partials as granules for the merging workgroups.
 // Returns the number of keys of the split (0: the split lies past the context and nothing was written).
+// DRAFT (vis_decode_attn_draft, csrc/spec.hip): `seq` is row r of ONE sequence's speculative step - its projection row is
+// qkv + r * qkv_bs, its position *step_ptr + r, and cache, tables and step_ptr are the sequence's own (no per-row offset).  A
+// row whose position is >= cache_tokens returns before it has read anything.  DRAFT == 1 is the append pass (rope of the new
+// key, K / V stored at the position by the split that owns it, nothing else); DRAFT == 2 the attention pass over keys
+// [0, position], which appends nothing: row r reads what the append pass stored for rows 0 .. r - 1, so the two are two
+// launches.  The arithmetic per (head, key) is untouched: row r equals the plain launch at step *step_ptr + r bit for bit.
 struct ChainCtx {
   const gran_t* qkv_g;  // [Nqkv / 2] granule i = projection rows 2 i, 2 i + 1 (two bf16)
   gran_t* part_g;       // [Hq][nsplit][130] granules: 128 unnormalised outputs (f32 bits), running max, sum
@@ -445,7 +451,7 @@ __device__ __forceinline__ void da_fork_row(const DecAttnArgs& p, int seq, int b
   flen = min(max(p.fork_len[seq], 0), p.cache_tokens - 1) & ~63;
 }
 
-template <int G, bool CHAIN, bool FORK = false>
+template <int G, bool CHAIN, bool FORK = false, int DRAFT = 0>
 __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<G>& L, int hkv, int split, int seq,
                                                       const ChainCtx& cc) {
   constexpr int HD = 128, HALF = 64;
@@ -469,7 +475,13 @@ __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<
   p.v_cache += seq * p.cache_bs;
   p.cos_t += seq * p.tab_bs;
   p.sin_t += seq * p.tab_bs;
-  p.step_ptr += seq;
+  int dpos = 0;
+  if constexpr (DRAFT) {
+    dpos = max(*p.step_ptr, 0) + seq;
+    if (dpos >= p.cache_tokens) return 0;
+  } else {
+    p.step_ptr += seq;
+  }
   p.part_o += (size_t)seq * p.Hq * p.nsplit * 128;
   p.part_ml += (size_t)seq * p.Hq * p.nsplit * 2;
   // Split s always owns keys [128 s, 128 s + 128): the row addresses do not depend on the position, so the
@@ -493,7 +505,7 @@ __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<
     vreg[i] = *(const uint32_t*)(Vr + (size_t)row * HD + 2 * lane);
   }
 
-  const int slot = min(*p.step_ptr, p.cache_tokens - 1);
+  const int slot = DRAFT ? dpos : min(*p.step_ptr, p.cache_tokens - 1);
   const int ctx = slot + 1;
   if (ks >= ctx) return 0;  // whole block: nothing to attend to (its partials are never read by the combine)
   const int ke = min(ks + DA_MAXKEYS, ctx);
@@ -538,10 +550,11 @@ __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<
     if (tid < HD) vnew_s[tid] = CHAIN ? L.raw[G + 1][tid] : da_qkv(p, seq, (p.Hq + p.Hkv + hkv) * HD + tid);
     __syncthreads();
     owner = (slot >= ks) && (slot < ke);
-    if (owner && tid < HD) {  // KV-cache append (no other block reads this row in this launch)
+    if (DRAFT != 2 && owner && tid < HD) {  // KV-cache append (no other block reads this row in this launch)
       Kh[(size_t)slot * HD + tid] = knew_s[tid];
       Vh[(size_t)slot * HD + tid] = vnew_s[tid];
     }
+    if constexpr (DRAFT == 1) return nk;
   } else {
     // ---- cross-attention: q_norm (RMSNorm over the 128 dims of each head, HF rounding: normalised value to
     //      bf16, then times the weight), one wave per head
@@ -663,3 +676,61 @@ __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<
   return nk;
 }
 
+// merge the per-split partials of one query head (only the splits that ran): 256 threads = 128 dims x 2
+// split-halves; the first partial loads are issued before the position is known
+#define CB_PRE 32   // partial rows preloaded per thread: covers 64 splits = 4096 cached keys
+// (the body of decode_attn_combine_kernel; vis_decode_attn_draft's combine calls it with `row_pos` = 1: the grid's y index
+// is then row r of ONE sequence, at position *step_ptr + r, instead of sequence r at step_ptr[r])
+__device__ __forceinline__ void decode_attn_combine_body(const float* __restrict__ part_o,
+                                                         const float* __restrict__ part_ml,
+                                                         bf16_t* __restrict__ out, int nsplit,
+                                                         const int* __restrict__ step_ptr,
+                                                         int cache_tokens, const bool row_pos) {
+  constexpr int HD = 128;
+  __shared__ float wgt[256];
+  __shared__ float osum[2][HD];
+  __shared__ float wm[4];
+  const int hq = blockIdx.x, seq = blockIdx.y, tid = threadIdx.x, d = tid & 127, half = tid >> 7;
+  part_o += (size_t)seq * gridDim.x * nsplit * HD;
+  part_ml += (size_t)seq * gridDim.x * nsplit * 2;
+  out += (size_t)seq * gridDim.x * HD;
+  if (!row_pos) step_ptr += seq;
+  const float* po = part_o + (size_t)hq * nsplit * HD + d;
+  const float* ml = part_ml + (size_t)hq * nsplit * 2;
+  // ONE level of loads: the partials of the first 2 x CB_PRE split slots, the statistics of every slot and the position
+  // are all requested at once; slots that did not run this step hold stale data and are masked (selected away, never
+  // multiplied) once the position has arrived.  Before, position -> statistics -> late partials were three dependent
+  // round trips in a kernel that does nothing else.
+  float v[CB_PRE];
+#pragma unroll
+  for (int j = 0; j < CB_PRE; ++j) v[j] = po[(size_t)min(half + 2 * j, nsplit - 1) * HD];
+  const int sl = min(tid, nsplit - 1);
+  const float m_raw = ml[sl * 2], l_raw = ml[sl * 2 + 1];
+  const int ctx = min(row_pos ? max(*step_ptr, 0) + seq : *step_ptr, cache_tokens - 1) + 1;
+  const int active = min((ctx + DA_MAXKEYS - 1) / DA_MAXKEYS, nsplit);  // splits that ran
+  const float m = (tid < active) ? m_raw : -1.0e30f;
+  const float l = (tid < active) ? l_raw : 0.f;
+  float M = wave_max(m);
+  if ((tid & 63) == 0) wm[tid >> 6] = M;
+  __syncthreads();
+  M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+  const float w = (tid < active) ? exp2f(m - M) : 0.f;
+  wgt[tid] = w;
+  const float lw = wave_sum(w * l);
+  __syncthreads();
+  if ((tid & 63) == 0) wm[tid >> 6] = lw;
+  float o = 0.f;
+#pragma unroll
+  for (int j = 0; j < CB_PRE; ++j) {
+    const int s = half + 2 * j;
+    if (s < active) o += wgt[s] * v[j];
+  }
+  for (int s = half + 2 * CB_PRE; s < active; s += 2) o += wgt[s] * po[(size_t)s * HD];   // contexts past 64 splits
+  osum[half][d] = o;
+  __syncthreads();
+  if (tid < HD) {
+    const float lt = wm[0] + wm[1] + wm[2] + wm[3];
+    const float ot = osum[0][tid] + osum[1][tid];
+    out[(size_t)hq * HD + tid] = f2bf(lt > 0.f ? ot / lt : 0.f);
+  }
+}

@@ -1,0 +1,246 @@
+// Lossless n-gram speculative decoding of ONE greedy sequence (spec.py, DecodeStage._decode_step_spec): a step runs R = 1 + k
+// rows - the current token and up to k drafted ones - through every projection in one pass over the weights
+// (vis_gemv_*_rows, each row bit-identical to the single-row kernel), and keeps the longest prefix of the drafts the model
+// itself would have picked.  The three pieces that did not exist:
+//
+//  * vis_decode_attn_draft: vis_decode_attn for the R rows of one sequence.  Row r sits at position *step_ptr + r: it takes
+//    that rope row, its K / V go to that cache row, it attends over keys [0, *step_ptr + r].  Three launches behind the one
+//    entry point: APPEND (every row's rotated key and its value into the cache), ATTEND (the split items of every row,
+//    appending nothing), COMBINE.  Row r reads the cache rows of rows 0 .. r - 1, which is why append and attend cannot share a
+//    launch - the hazard that makes vis_decode_attn(batch = R, cache_bs = 0) wrong.  All three run decode_attn_split_body /
+//    decode_attn_combine_body (decode_common.hip.h) with the split plan and key order of vis_decode_attn, so output row r and
+//    the cache are, bit for bit, what R successive vis_decode_attn launches at advancing steps leave.  A row at a position
+//    >= cache_tokens returns before it reads or writes anything.
+//  * vis_spec_accept: the greedy pick of every row (vis_argmax_f32's comparison: larger value, ties to the lower id, a row
+//    without a comparable logit picks id 0), the count `a` of leading drafts that equal the pick of the row in front of them,
+//    and the bookkeeping of a step that produced a + 1 tokens.
+//  * vis_spec_draft: prompt lookup - the latest earlier occurrence of the last m ids of the history (m from lookup_max down
+//    to lookup_min) and the ids that followed it.  spec.propose() is its definition.
+//
+// Every index that comes from device memory (*step_ptr, the draft count, the limit, lengths, token ids) is clamped before it
+// forms an address.
+#include "decode_common.hip.h"
+#include <math.h>
+
+#define SP_MAXROWS 4
+#define SP_MAXLOOKUP 8
+
+// ------------------------------------------------------------------------------------------------ vis_decode_attn_draft
+template <int G>
+__global__ __launch_bounds__(256) void spec_attn_append_kernel(DecAttnArgs p) {
+  __shared__ DecAttnLds<G> L;
+  // the split that owns the row's position (the body checks the range again, before it reads anything else)
+  const int pos = max(*p.step_ptr, 0) + (int)blockIdx.y;
+  if (pos >= p.cache_tokens) return;
+  decode_attn_split_body<G, false, false, 1>(p, L, blockIdx.x, pos / DA_MAXKEYS, blockIdx.y,
+                                             ChainCtx{nullptr, nullptr, nullptr, 0u, nullptr});
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void spec_attn_attend_kernel(DecAttnArgs p) {
+  __shared__ DecAttnLds<G> L;
+  decode_attn_split_body<G, false, false, 2>(p, L, blockIdx.x, blockIdx.y, blockIdx.z, ChainCtx{nullptr, nullptr, nullptr, 0u, nullptr});
+}
+
+__global__ __launch_bounds__(256) void spec_attn_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                                bf16_t* __restrict__ out, int nsplit,
+                                                                const int* __restrict__ step_ptr, int cache_tokens) {
+  if (max(*step_ptr, 0) + (int)blockIdx.y >= cache_tokens) return;     // workgroup-uniform: a row past the cache has no partials
+  decode_attn_combine_body(part_o, part_ml, out, nsplit, step_ptr, cache_tokens, true);
+}
+
+template <int G>
+static void spec_attn_launch(const DecAttnArgs& p, bf16_t* out, int rows, hipStream_t stream) {
+  hipLaunchKernelGGL(spec_attn_append_kernel<G>, dim3(p.Hkv, rows), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(spec_attn_attend_kernel<G>, dim3(p.Hkv, p.nsplit, rows), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(spec_attn_combine_kernel, dim3(p.Hq, rows), dim3(256), 0, stream, (const float*)p.part_o,
+                     (const float*)p.part_ml, out, p.nsplit, p.step_ptr, p.cache_tokens);
+}
+
+extern "C" int vis_decode_attn_draft(const void* qkv, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                     const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                                     int cache_tokens, int nsplit, float scale, int rows, long long qkv_ld,
+                                     hipStream_t stream) {
+  if (!qkv || !cos_t || !sin_t || !k_cache || !v_cache || !step_ptr || !part_o || !part_ml || !out) return VIS_ERR_ARG;
+  if (rows < 1 || rows > SP_MAXROWS) return VIS_ERR_ARG;
+  if (HD != 128 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) return VIS_ERR_ARG;
+  if (qkv_ld < (long long)(Hq + 2 * Hkv) * 128 || (qkv_ld % 8)) return VIS_ERR_ARG;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 7 && G != 8) return VIS_ERR_ARG;  // instantiated GQA group sizes
+  if (nsplit <= 0 || nsplit > 256 || cache_tokens <= 0) return VIS_ERR_ARG;
+  if ((long long)nsplit * DA_MAXKEYS < cache_tokens) return VIS_ERR_ARG;  // every key must be covered
+  if (((uintptr_t)k_cache | (uintptr_t)v_cache) & 15) return VIS_ERR_ARG;
+  if (((uintptr_t)step_ptr | (uintptr_t)part_o | (uintptr_t)part_ml | (uintptr_t)cos_t | (uintptr_t)sin_t) & 3) return VIS_ERR_ARG;
+  if (((uintptr_t)qkv | (uintptr_t)out) & 1) return VIS_ERR_ARG;
+  DecAttnArgs p;
+  p.qkv = (const bf16_t*)qkv; p.cos_t = (const float*)cos_t; p.sin_t = (const float*)sin_t;
+  p.k_cache = (bf16_t*)k_cache; p.v_cache = (bf16_t*)v_cache; p.step_ptr = (const int*)step_ptr;
+  p.part_o = (float*)part_o; p.part_ml = (float*)part_ml;
+  p.Hq = Hq; p.Hkv = Hkv; p.cache_tokens = cache_tokens; p.nsplit = nsplit;
+  p.scale_log2 = scale * 1.4426950408889634f;
+  p.qkv_bs = qkv_ld; p.cache_bs = 0; p.tab_bs = 0;      // the rows share one cache and one pair of rope tables
+  p.q_norm_w = nullptr; p.q_eps = 0.f;
+  p.shared_len = 0;
+  p.fork_parent = nullptr; p.fork_len = nullptr;
+  da_no_parts(p);
+  vis_clear_error();
+  switch (G) {
+    case 1: spec_attn_launch<1>(p, (bf16_t*)out, rows, stream); break;
+    case 2: spec_attn_launch<2>(p, (bf16_t*)out, rows, stream); break;
+    case 4: spec_attn_launch<4>(p, (bf16_t*)out, rows, stream); break;
+    case 7: spec_attn_launch<7>(p, (bf16_t*)out, rows, stream); break;
+    default: spec_attn_launch<8>(p, (bf16_t*)out, rows, stream); break;
+  }
+  return vis_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------------ vis_spec_accept
+// vis_argmax_f32's comparison: the candidate replaces the best when it is larger, or equal with the lower id.  NaN compares
+// false both ways and is never picked; the sentinel id (no comparable logit) becomes id 0 where the pick is used.
+__device__ __forceinline__ void sp_better(float& best, int& bi, float v, int i) {
+  if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+}
+
+__device__ __forceinline__ void sp_wave_best(float& best, int& bi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    sp_better(best, bi, ov, oi);
+  }
+}
+
+// stage 1: grid (nb, rows), 256 threads: workgroup x of row r leaves (max, lowest id) over its ids in ws[r][x]
+__global__ __launch_bounds__(256) void spec_pick_kernel(const float* __restrict__ logits, int V, int ld,
+                                                        float* __restrict__ bval, int* __restrict__ bidx) {
+  const int tid = threadIdx.x, row = blockIdx.y;
+  const float* __restrict__ x = logits + (size_t)row * ld;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = blockIdx.x * 256 + tid; i < V; i += gridDim.x * 256) sp_better(best, bi, x[i], i);
+  sp_wave_best(best, bi);
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) sp_better(best, bi, sv[w], si[w]);
+    bval[row * 256 + blockIdx.x] = best;
+    bidx[row * 256 + blockIdx.x] = bi;
+  }
+}
+
+// stage 2: one workgroup of 256 threads, wave r merges row r; then lane 0 of wave 0 does the step's bookkeeping
+__global__ __launch_bounds__(256) void spec_accept_kernel(const float* __restrict__ bval, const int* __restrict__ bidx, int nb,
+                                                          int rows, const int* __restrict__ draft,
+                                                          const int* __restrict__ n_draft, const int* __restrict__ limit,
+                                                          int* __restrict__ tokens, int max_tokens, int* __restrict__ cur_token,
+                                                          int* __restrict__ step_ptr, int* __restrict__ counters) {
+  __shared__ int pick[SP_MAXROWS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave < rows) {
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < nb; i += 64) sp_better(best, bi, bval[wave * 256 + i], bidx[wave * 256 + i]);
+    sp_wave_best(best, bi);
+    if (lane == 0) pick[wave] = (bi == 0x7fffffff) ? 0 : bi;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int st = *step_ptr;
+  const int lim = min(*limit, max_tokens - 1);
+  if (st < 0 || st > lim) return;     // the request has all its tokens: a step issued ahead of the poll changes nothing
+  const int d = min(max(*n_draft, 0), rows - 1);
+  int a = 0;
+  while (a < d && draft[a] == pick[a]) ++a;
+  a = min(a, lim - st);               // tokens[st .. st + a] are written: st + a <= limit
+  for (int r = 0; r <= a; ++r) tokens[st + r] = pick[r];
+  *cur_token = pick[a];
+  *step_ptr = st + a + 1;
+  counters[0] += 1;
+  counters[1] += d;
+  counters[2] += a;
+}
+
+extern "C" int vis_spec_accept(const void* logits, int V, int ld_logits, int rows, const void* draft, const void* n_draft,
+                               const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
+                               void* step_ptr, void* counters, hipStream_t stream) {
+  if (!logits || !draft || !n_draft || !limit || !ws_val || !ws_idx || !tokens || !cur_token || !step_ptr || !counters)
+    return VIS_ERR_ARG;
+  if (V <= 0 || rows < 1 || rows > SP_MAXROWS || ld_logits < V || max_tokens <= 0) return VIS_ERR_ARG;
+  if (((uintptr_t)logits | (uintptr_t)draft | (uintptr_t)n_draft | (uintptr_t)limit | (uintptr_t)ws_val | (uintptr_t)ws_idx |
+       (uintptr_t)tokens | (uintptr_t)cur_token | (uintptr_t)step_ptr | (uintptr_t)counters) & 3)
+    return VIS_ERR_ARG;
+  const int nb = min(256, (V + 255) / 256);
+  vis_clear_error();
+  hipLaunchKernelGGL(spec_pick_kernel, dim3(nb, rows), dim3(256), 0, stream, (const float*)logits, V, ld_logits,
+                     (float*)ws_val, (int*)ws_idx);
+  hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx, nb, rows,
+                     (const int*)draft, (const int*)n_draft, (const int*)limit, (int*)tokens, max_tokens, (int*)cur_token,
+                     (int*)step_ptr, (int*)counters);
+  return vis_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------------- vis_spec_draft
+// History h = prompt[0 .. plen) followed by tokens[gen0 .. step), length L (vis_ban_f32's reading of the same rows).  For m =
+// lookup_max down to lookup_min with L > m: the largest j < L - m with h[j .. j + m) == h[L - m .. L); the first m that has
+// one wins: draft = h[j + m .. min(j + m + k, L)), *n_draft its length.  No match: *n_draft = 0 and draft is left alone.
+// One workgroup: 256 lanes take the candidate starts j in strides, the largest matching j is reduced through LDS.
+__global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__ prompt, int ld_prompt, const int* __restrict__ plen,
+                                                         const int* __restrict__ tokens, int max_tokens,
+                                                         const int* __restrict__ gen0, const int* __restrict__ step_ptr, int k,
+                                                         int lookup_max, int lookup_min, int vocab, int* __restrict__ draft,
+                                                         int* __restrict__ n_draft) {
+  __shared__ int wbest[4];
+  const int tid = threadIdx.x;
+  const int P = min(max(*plen, 0), ld_prompt);
+  const int end = min(max(*step_ptr, 0), max_tokens);
+  const int s0 = min(max(*gen0, 0), end);
+  const int L = P + (end - s0);
+  const int* __restrict__ gn = tokens + s0;
+#define SP_H(i) ((i) < P ? prompt[(i)] : gn[(i) - P])
+  for (int m = lookup_max; m >= lookup_min; --m) {
+    if (L <= m) continue;     // (uniform) no room for the pattern and one id after an earlier copy of it
+    int tail[SP_MAXLOOKUP];
+#pragma unroll
+    for (int i = 0; i < SP_MAXLOOKUP; ++i) tail[i] = (i < m) ? SP_H(L - m + i) : 0;
+    int best = -1;
+    for (int j = tid; j < L - m; j += 256) {
+      bool match = true;
+#pragma unroll
+      for (int i = 0; i < SP_MAXLOOKUP; ++i)
+        if (i < m && match) match = SP_H(j + i) == tail[i];
+      if (match) best = j;      // ascending j per lane: the last one stays
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+    __syncthreads();            // the previous round's readers are through
+    if ((tid & 63) == 0) wbest[tid >> 6] = best;
+    __syncthreads();
+    best = max(max(wbest[0], wbest[1]), max(wbest[2], wbest[3]));
+    if (best >= 0) {            // uniform
+      const int from = best + m, d = min(k, L - from);
+      if (tid < d) draft[tid] = min(max(SP_H(from + tid), 0), vocab - 1);
+      if (tid == 0) *n_draft = d;
+      return;
+    }
+  }
+#undef SP_H
+  if (tid == 0) *n_draft = 0;
+}
+
+extern "C" int vis_spec_draft(const void* prompt_ids, int ld_prompt, const void* prompt_len, const void* tokens, int max_tokens,
+                              const void* gen_start, const void* step_ptr, int k, int lookup_max, int lookup_min, int vocab,
+                              void* draft, void* n_draft, hipStream_t stream) {
+  if (!prompt_ids || !prompt_len || !tokens || !gen_start || !step_ptr || !draft || !n_draft) return VIS_ERR_ARG;
+  if (ld_prompt <= 0 || max_tokens <= 0 || vocab <= 0 || k < 1 || k > SP_MAXROWS - 1) return VIS_ERR_ARG;
+  if (lookup_max < 1 || lookup_max > SP_MAXLOOKUP || lookup_min < 1 || lookup_min > lookup_max) return VIS_ERR_ARG;
+  if (((uintptr_t)prompt_ids | (uintptr_t)prompt_len | (uintptr_t)tokens | (uintptr_t)gen_start | (uintptr_t)step_ptr |
+       (uintptr_t)draft | (uintptr_t)n_draft) & 3)
+    return VIS_ERR_ARG;
+  vis_clear_error();
+  hipLaunchKernelGGL(spec_draft_kernel, dim3(1), dim3(256), 0, stream, (const int*)prompt_ids, ld_prompt, (const int*)prompt_len,
+                     (const int*)tokens, max_tokens, (const int*)gen_start, (const int*)step_ptr, k, lookup_max, lookup_min,
+                     vocab, (int*)draft, (int*)n_draft);
+  return vis_check_launch();
+}

@@ -11,7 +11,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
-from . import hip
+from . import hip, spec
 from .fork import check_fork_tables, fork_layout
 from .pick import PickStage
 
@@ -77,6 +77,10 @@ class DecodeStage(PickStage):
         self.fork_on = False
         self.fork_parent_b: Optional[torch.Tensor] = None
         self.fork_len_b: Optional[torch.Tensor] = None
+        # speculative decoding of the single sequence (generate(.., speculative=)): buffers and graphs on first use
+        self._spec: Optional[spec.SpecBuffers] = None
+        self._spec_cfg: Optional[spec.SpecConfig] = None
+        self._spec_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
 
     def _attn_share(self, B: int, shared: int) -> dict:
         """How the batched self-attention of B slots names the keys a slot reads from another slot's cache: the fork tables
@@ -250,6 +254,87 @@ class DecodeStage(PickStage):
         self._logprobs_after_pick(B or 1)
         self._stop_after_pick(B or 1)
         self._stream_after_pick(B or 1)
+
+    # ---- speculative decode of the single sequence (spec.py): 1..R tokens per weight pass
+    def _spec_begin(self, cfg: "spec.SpecConfig", max_new_tokens: int) -> "spec.SpecBuffers":
+        """Behind the prompt pass of a speculative request (its rope rows prepared for max_new_tokens + R - 1 further
+        positions): the step's buffers take over the first token and the prompt's ids; ``limit`` is the index of the token
+        row the reply's last token goes to, so the reply has exactly max_new_tokens tokens however a step's run ends."""
+        if self.dec_n_self != len(self.dec_layers):
+            raise ValueError("speculative decoding is not supported on a model with cross-attention layers")
+        spec.check_rows_fit(self.cfg, cfg.rows)
+        if self._spec is None:
+            self._spec = spec.SpecBuffers(self.cfg, self.nsplit, self.max_ctx, self.device)
+        self._spec_cfg = cfg
+        start = self.prompt_len - 1
+        self._spec.begin(self.cur_token, self._slot_ids[0], start, min(start + max_new_tokens - 1, self.max_ctx - 2))
+        return self._spec
+
+    def _decode_step_spec(self, R: int, propose: bool = True) -> None:
+        """One speculative step of the single sequence: rows [cur, draft 0 .. draft R-2] at positions step .. step + R - 1
+        through the multi-row GEMVs (one pass over the weights, every row the single-row kernel's bits), the draft
+        attention (row r = the plain launch at step + r, bit for bit), the lm_head into [R, V] f32, then vis_spec_accept -
+        which keeps the drafts the picks confirm and advances ``step`` by 1..R - and vis_spec_draft for the next step.
+        Never the chained launch: the chain is bit-identical to the four launches, so the tokens are the chained step's.
+        ``propose`` False leaves the draft row and its count alone (a test plants them)."""
+        cfg, fmt, sp = self.cfg, self.decode_weights, self._spec
+        Hq, Hkv, D = cfg.heads, cfg.kv_heads, cfg.head_dim
+        scale, eps = D ** -0.5, cfg.rms_eps
+        x, x2, qkv, att, act, logits = sp.x[:R], sp.x2[:R], sp.qkv[:R], sp.attn[:R], sp.act[:R], sp.logits[:R]
+        gemv_rows = getattr(hip, _GEMV[fmt] + "_rows")
+        hip.gather_rows(self.w.embed, sp.ids[:R], x)
+        for L in self.dec_layers:
+            lw = L.w
+            gemv_rows(x, *_wt(L, "qkv_w", fmt), qkv, bias=L.bias, norm_w=lw.ln1_w, eps=eps)
+            hip.decode_attn_draft(qkv, self.cos_t, self.sin_t, self.kcache[L.idx], self.vcache[L.idx], self.step, sp.part_o,
+                                  sp.part_ml, att, Hq, Hkv, D, self.nsplit, scale)
+            gemv_rows(att, *_wt(L, "o_w", fmt), x2, residual=x)
+            gemv_rows(x2, *_wt(L, "gateup_w", fmt), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
+            gemv_rows(act, *_wt(L, "down_w", fmt), x, residual=x2)
+        gemv_rows(x, *self.dec_head[fmt], logits, norm_w=self.dec_norm_w, eps=eps)
+        hip.spec_accept(logits, sp.draft, sp.n_draft, sp.limit, sp.ws_val, sp.ws_idx, self.tokens, sp.cur, self.step,
+                        sp.counters)
+        if propose and R > 1:
+            c = self._spec_cfg
+            hip.spec_draft(sp.prompt, sp.prompt_len, self.tokens, sp.gen_start, self.step, R - 1, c.lookup_max, c.lookup_min,
+                           cfg.vocab, sp.draft, sp.n_draft)
+
+    def _spec_graph(self, R: int) -> torch.cuda.CUDAGraph:
+        """The captured speculative step, keyed by (R, weight format, the lookup window): its launches read everything else
+        from device memory.  The warm-up step advances the request's counters; they are put back before the capture."""
+        c = self._spec_cfg
+        key = ("spec", R, self.decode_weights, c.lookup_max, c.lookup_min)
+        if key in self._spec_graphs:
+            return self._spec_graphs[key]
+        sp = self._spec
+        saved = (self.step_b.clone(), sp.ids.clone(), sp._ints.clone())
+        start = max(0, min(int(self.step.item()), self.tokens.numel() - R))      # the token row entries the warm-up may write
+        row = self.tokens[start:start + R].clone()
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._decode_step_spec(R)
+        torch.cuda.current_stream().wait_stream(side)
+        self.step_b.copy_(saved[0])
+        sp.ids.copy_(saved[1])
+        sp._ints.copy_(saved[2])
+        self.tokens[start:start + R].copy_(row)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._decode_step_spec(R)
+        if len(self._spec_graphs) >= 4:
+            self._spec_graphs.pop(next(iter(self._spec_graphs)))
+        self._spec_graphs[key] = g
+        return g
+
+    def _decode_steps_spec(self, n_steps: int, R: int, use_graph: bool) -> None:
+        if use_graph:
+            g = self._spec_graph(R)
+            for _ in range(n_steps):
+                g.replay()
+        else:
+            for _ in range(n_steps):
+                self._decode_step_spec(R)
 
     # ---- batched decode: B in-flight sequences (slots 0..B-1) share every weight read of a step
     def _decode_step_batched(self, B: int) -> None:

@@ -139,6 +139,8 @@ _LOG = logging.getLogger("vision_inspection_system_amd.engine")
 class Qwen2VLEngine(Generation):
     """One model replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
+    speculative_supported = True      # generate(.., speculative=): spec.py
+
     @staticmethod
     def check_decode_weights(cfg: Qwen2VLConfig, decode_weights: str) -> None:
         """Refuse an unknown decode precision, or one the model's shapes do not fit (needs no GPU)."""
@@ -1192,7 +1194,8 @@ class Qwen2VLEngine(Generation):
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
                  stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                  logit_bias: Optional[dict] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
-                 bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None) -> List[int]:
+                 bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None,
+                 speculative=None) -> List[int]:
         """One request through the single-sequence loop: Generation._generate describes every parameter.  Here a reply that
         ended on EOS is cut in front of it, and a ``max_new_tokens`` the context cannot hold is clamped with a warning, once
         per engine (_clamp_request)."""
@@ -1200,7 +1203,8 @@ class Qwen2VLEngine(Generation):
                               logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
                               frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
                               stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
-                              no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
+                              no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens,
+                              speculative=speculative)
 
     def generate_batch(self, requests: Sequence,
                        max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,

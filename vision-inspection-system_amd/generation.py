@@ -9,7 +9,7 @@ from typing import List, Sequence
 
 import torch
 
-from . import hip
+from . import hip, spec
 from .ban import ban_kwargs, check_ban
 from .decode_stage import DecodeStage
 from .fork import check_n_list
@@ -49,6 +49,9 @@ class Generation(DecodeStage):
     # generate_batch with ONE request takes the single-sequence loop: polled at the call's own interval (None, Qwen2-VL) or
     # at this one whatever the call said (Mllama: 32, the default ``chunk`` of its ``generate``).
     single_route_check_every = None
+    # generate(.., speculative=): the Qwen2-VL / Qwen2.5-VL engine only.  Mllama's cross-attention rows would need a
+    # draft form of their own (the static keys are shared, but the q_norm rows and the has_image skip are per step).
+    speculative_supported = False
 
     # ------------------------------------------------------------------ hooks with a default
     def _fork_prefix_len(self) -> int:
@@ -78,7 +81,7 @@ class Generation(DecodeStage):
     def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, *,
                   logprobs=None, json_mode=False, top_p=None, repetition_penalty=None, frequency_penalty=None,
                   presence_penalty=None, json_schema=None, stop=None, top_k=None, min_p=None, logit_bias=None,
-                  on_stream=None, no_repeat_ngram_size=None, bad_words=None, min_tokens=None) -> List[int]:
+                  on_stream=None, no_repeat_ngram_size=None, bad_words=None, min_tokens=None, speculative=None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive; inclusive for an engine with ``keep_eos``).  ``logprobs`` = k in 0..20: afterwards
@@ -115,7 +118,24 @@ class Generation(DecodeStage):
         both spellings) and ``min_tokens`` <= max_new_tokens (vLLM's: no EOS id before that many tokens): ban.py - one launch
         after the penalties takes the banned ids out of the pick.  None / 0 / [] = off.  Not together with ``json_mode`` /
         ``json_schema`` (ValueError: a ban could leave the grammar no token).  ``min_tokens`` holds back EOS ids only: a
-        ``stop`` string may still end the reply earlier.  Logprobs keep their meaning (raw logits)."""
+        ``stop`` string may still end the reply earlier.  Logprobs keep their meaning (raw logits).
+        ``speculative``: None (off: exactly the launches of before), the integer k in 1..3 or {"method": "ngram",
+        "num_speculative_tokens": k, "prompt_lookup_max": 4, "prompt_lookup_min": 2} (spec.py): a decode step carries the
+        current token and up to k ids drafted by prompt lookup over prompt + reply through ONE pass over the weights and
+        keeps the drafts the model's own greedy picks confirm - the reply is the plain reply token for token, in fewer
+        weight passes where the reply repeats earlier text.  Greedy single requests of the Qwen2-VL engines only: ValueError
+        with a temperature, a seed or any switch above (they advance one token at a time).  Afterwards ``last_timing`` holds
+        ``spec_steps`` / ``spec_proposed`` / ``spec_accepted``."""
+        sp = spec.check_speculative(speculative)
+        if sp is not None:
+            if not self.speculative_supported:
+                raise ValueError("speculative decoding is offered by the Qwen2-VL / Qwen2.5-VL engine only: this engine's "
+                                 "cross-attention rows have no multi-row form")
+            spec.check_exclusive(sp, temperature, seed, logprobs=logprobs, json_mode=json_mode, top_p=top_p,
+                                 repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
+                                 presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
+                                 min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
+                                 no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
         penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
         shaping = check_shaping(top_k, min_p, logit_bias, 1)
         ban = check_ban(no_repeat_ngram_size, bad_words, min_tokens, 1, max_new_tokens, json_mode=json_mode,
@@ -125,6 +145,8 @@ class Generation(DecodeStage):
             self.stop_eos = not ignore_eos
             self._stream_bind([[0]])
             max_new_tokens = self._clamp_request(input_ids, max_new_tokens)
+            if sp is not None:      # no chained launch in a speculative step: nothing of the stall handling below applies
+                return self._run_single_spec(sp, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every)
             try:
                 out = self._run_single(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
                 self._maybe_reenable_chain()
@@ -166,6 +188,41 @@ class Generation(DecodeStage):
         if self._mask_failed([0]):
             self.last_finish = [None]
             raise self._mask_error()
+        return toks
+
+    def _run_single_spec(self, sp: "spec.SpecConfig", input_ids, frames, max_new_tokens, ignore_eos, use_graph,
+                         check_every) -> List[int]:
+        """_run_single with speculative steps: ``check_every`` steps are issued ahead as there, then the poll reads the device
+        step counter together with the token row - a step has produced 1..R tokens.  Ends at EOS or when the reply has
+        max_new_tokens tokens (the device ``limit`` cuts the last step's run there; steps issued past it change nothing)."""
+        R = sp.rows
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        self._prompt_pass(input_ids, frames, max_new_tokens + R - 1, 0.0, 0)      # rope rows for the rows past the last token
+        ev[1].record()
+        max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - len(input_ids) - 1))
+        buf = self._spec_begin(sp, max_new_tokens)
+        start, eos = self.prompt_len - 1, set(self.cfg.eos_ids)
+
+        def poll():      # one D2H each: the step counter, then the tokens it covers
+            n = min(int(self.step.item()) - start, max_new_tokens)
+            return self.tokens[start:start + n].cpu().tolist()
+
+        toks, steps = poll(), 0
+        while len(toks) < max_new_tokens and (ignore_eos or not any(t in eos for t in toks)):
+            n = min(check_every, max_new_tokens - len(toks))
+            self._decode_steps_spec(n, R, use_graph)
+            steps += n
+            toks = poll()
+        ev[2].record()
+        torch.cuda.current_stream().synchronize()
+        self._decoded = len(toks) - 1
+        c = buf.read_counters()
+        self.last_timing = {"prompt_tokens": len(input_ids), "prefill_ms": ev[0].elapsed_time(ev[1]),
+                            "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": steps, "sequences": 1,
+                            "spec_steps": c[0], "spec_proposed": c[1], "spec_accepted": c[2]}
+        toks = self._finish([(0, toks)], eos, ignore_eos, keep_eos=self.keep_eos)[0]
+        self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
         return toks
 
     @staticmethod

@@ -75,6 +75,9 @@ _SIGS = {
     "vis_shape_ws_bytes": "ii",
     "vis_shape_f32": "p" + "ii" + "p" + "i" + "ppppp" + "p" + "i" + "pp" + "i" + "p",
     "vis_ban_f32": "p" + "ii" + "p" + "i" + "pp" + "i" + "pppppp" + "i" + "p" + "i" + "p" + "ii" + "p",
+    "vis_decode_attn_draft": "ppppppppp" + "iiiii" + "f" + "i" + "l" + "p",
+    "vis_spec_accept": "p" + "iii" + "pppppp" + "i" + "ppp" + "p",
+    "vis_spec_draft": "pi" + "pp" + "i" + "pp" + "iiii" + "pp" + "p",
     "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
     "vis_stream_publish": "pp" + "i" + "pp" + "i" + "pp" + "i" + "pp" + "i" + "p",
     "vis_host_coherent_alloc": "ppl",
@@ -1540,6 +1543,77 @@ def ban(logits: torch.Tensor, prompt_ids: torch.Tensor, prompt_len: torch.Tensor
                             _ptr(step), _ptr(ngram), _ptr(min_tokens), _ptr(words), arr, len(lens), _ptr(eos_ids), int(n_eos),
                             _ptr(out), out.stride(0) if out.dim() == 2 else V, B, _stream())
     _check(rc, "vis_ban_f32")
+
+
+SPEC_MAX_ROWS, SPEC_MAX_LOOKUP = 4, 8     # SP_MAXROWS / SP_MAXLOOKUP of csrc/spec.hip (spec.py)
+
+
+def decode_attn_draft(qkv: torch.Tensor, cos_t: torch.Tensor, sin_t: torch.Tensor, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor, step: torch.Tensor, part_o: torch.Tensor, part_ml: torch.Tensor,
+                      out: torch.Tensor, n_q: int, n_kv: int, head_dim: int, nsplit: int, scale: float) -> torch.Tensor:
+    """decode_attn for the R = 1..4 rows of ONE sequence's speculative step (vis_decode_attn_draft): row r of qkv [R, nq*D]
+    sits at position step[0] + r - its rope row, its cache row, keys [0, step[0] + r].  Caches [Hkv, T, D], tables [T, D],
+    step int32 [1] (left as it is), workspaces for R rows, out [R, Hq*D].  Row r and the cache are bit-identical to R
+    successive decode_attn calls at advancing steps; a row at a position >= T reads and writes nothing."""
+    _bf16(qkv, "qkv"); _bf16(k_cache, "k_cache"); _bf16(v_cache, "v_cache"); _bf16(out, "out")
+    if step.dtype != torch.int32 or step.numel() != 1 or cos_t.dtype != torch.float32 or sin_t.dtype != torch.float32:
+        raise HipLibraryError("decode_attn_draft: step int32 [1] / cos,sin f32 required")
+    if k_cache.dim() != 3 or k_cache.shape[0] != n_kv or k_cache.shape[2] != head_dim or v_cache.shape != k_cache.shape \
+            or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise HipLibraryError("decode_attn_draft: caches must be contiguous [Hkv, cache_tokens, head_dim]")
+    T = k_cache.shape[1]
+    if cos_t.shape != (T, head_dim) or sin_t.shape != cos_t.shape or not cos_t.is_contiguous() or not sin_t.is_contiguous():
+        raise HipLibraryError("decode_attn_draft: cos/sin tables must be [cache_tokens, head_dim]")
+    nq = (n_q + 2 * n_kv) * head_dim
+    if qkv.dim() != 2 or not 1 <= qkv.shape[0] <= SPEC_MAX_ROWS or qkv.shape[1] != nq or qkv.stride(1) != 1:
+        raise HipLibraryError("decode_attn_draft: qkv must be [1..4, (Hq + 2 Hkv) * D]")
+    R = qkv.shape[0]
+    if part_o.dtype != torch.float32 or part_ml.dtype != torch.float32 or part_o.numel() < R * n_q * nsplit * head_dim \
+            or part_ml.numel() < R * n_q * nsplit * 2 or out.shape != (R, n_q * head_dim) or not out.is_contiguous():
+        raise HipLibraryError("decode_attn_draft: workspace/output too small")
+    rc = load().vis_decode_attn_draft(_ptr(qkv), _ptr(cos_t), _ptr(sin_t), _ptr(k_cache), _ptr(v_cache), _ptr(step),
+                                      _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, T, nsplit, scale, R,
+                                      qkv.stride(0), _stream())
+    _check(rc, "vis_decode_attn_draft")
+    return out
+
+
+def spec_accept(logits: torch.Tensor, draft: torch.Tensor, n_draft: torch.Tensor, limit: torch.Tensor, ws_val: torch.Tensor,
+                ws_idx: torch.Tensor, tokens: torch.Tensor, cur_token: torch.Tensor, step: torch.Tensor,
+                counters: torch.Tensor) -> None:
+    """The accept step of a speculative step (vis_spec_accept): logits f32 [R, V] (R = 1..4), draft int32 [>= R - 1], n_draft
+    / limit / cur_token / step int32 [1], tokens int32 [T], counters int32 [3] (steps, proposed, accepted), ws_val f32 /
+    ws_idx int32 of >= 256 * R entries - all device memory.  spec.accept_ref() is the numpy restatement."""
+    ints = (draft, n_draft, limit, ws_idx, tokens, cur_token, step, counters)
+    if logits.dtype != torch.float32 or ws_val.dtype != torch.float32 or any(t.dtype != torch.int32 for t in ints):
+        raise HipLibraryError("spec_accept: f32 logits, ws_val / int32 everything else required")
+    if logits.dim() != 2 or not 1 <= logits.shape[0] <= SPEC_MAX_ROWS or logits.stride(1) != 1:
+        raise HipLibraryError("spec_accept: logits must be [1..4, V] with unit column stride")
+    R, V = logits.shape
+    if draft.numel() < max(1, R - 1) or any(t.numel() != 1 for t in (n_draft, limit, cur_token, step)) or counters.numel() != 3 \
+            or ws_val.numel() < 256 * R or ws_idx.numel() < 256 * R or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("spec_accept: bad parameter shapes")
+    rc = load().vis_spec_accept(_ptr(logits), V, logits.stride(0), R, _ptr(draft), _ptr(n_draft), _ptr(limit), _ptr(ws_val),
+                                _ptr(ws_idx), _ptr(tokens), tokens.numel(), _ptr(cur_token), _ptr(step), _ptr(counters),
+                                _stream())
+    _check(rc, "vis_spec_accept")
+
+
+def spec_draft(prompt_ids: torch.Tensor, prompt_len: torch.Tensor, tokens: torch.Tensor, gen_start: torch.Tensor,
+               step: torch.Tensor, k: int, lookup_max: int, lookup_min: int, vocab: int, draft: torch.Tensor,
+               n_draft: torch.Tensor) -> None:
+    """The prompt-lookup drafter (vis_spec_draft) over the history prompt_ids[:prompt_len[0]] followed by
+    tokens[gen_start[0]:step[0]]: up to k ids into draft int32 [>= k], their count into n_draft int32 [1] - all device
+    memory, read at run time.  Equals spec.propose() exactly."""
+    ints = (prompt_ids, prompt_len, tokens, gen_start, step, draft, n_draft)
+    if any(t.dtype != torch.int32 for t in ints) or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("spec_draft: contiguous int32 tensors required")
+    if any(t.numel() != 1 for t in (prompt_len, gen_start, step, n_draft)) or prompt_ids.numel() == 0 or draft.numel() < k:
+        raise HipLibraryError("spec_draft: bad parameter shapes")
+    rc = load().vis_spec_draft(_ptr(prompt_ids), prompt_ids.numel(), _ptr(prompt_len), _ptr(tokens), tokens.numel(),
+                               _ptr(gen_start), _ptr(step), int(k), int(lookup_max), int(lookup_min), int(vocab), _ptr(draft),
+                               _ptr(n_draft), _stream())
+    _check(rc, "vis_spec_draft")
 
 
 STOP_STATE_INTS = 8     # int32 words of one sequence's vis_stop_scan record (stop.STATE_INTS)

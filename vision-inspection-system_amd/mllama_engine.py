@@ -669,17 +669,19 @@ class MllamaEngine(Generation):
                  frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
                  stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                  logit_bias: Optional[dict] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
-                 bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None) -> List[int]:
+                 bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None,
+                 speculative=None) -> List[int]:
         """One request through the single-sequence loop: Generation._generate describes every parameter, with
         ``stop_on_eos`` = not ignore_eos, ``chunk`` = check_every (the boundary at which a cancelled request ends) and
         ``frame`` the request's one image or None.  A reply that ended on EOS keeps its EOS token here; a ``max_new_tokens``
         the context cannot hold is clamped silently; after a stalled chained launch this engine stays on the separate
-        launches for good."""
+        launches for good.  ``speculative`` other than None is refused (ValueError): the Qwen2-VL engines only."""
         return self._generate(input_ids, frame, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
                               logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
                               frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
                               stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
-                              no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
+                              no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens,
+                              speculative=speculative)
 
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
