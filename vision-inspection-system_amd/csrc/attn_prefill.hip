@@ -99,6 +99,8 @@ __device__ __forceinline__ float att_max(float a, float b) {
 // on ~2/3 of the tiles with the strict maximum on N(0,1) scores), no per-score subtraction (the kernels keep -m as the
 // C operand of the first QK^T MFMA).  The decision is per lane = per query, a function of that query's own keys in the
 // fixed absolute tile order, so results still do not depend on what shares the wave, the launch or the batch.
+// The first tile sets m to its maximum whatever the sign: the rescale factor of that move is clamped to 1 (the accumulators are
+// still zero) - a first tile whose scores all lie below -128 would otherwise multiply them by exp2(-d) = inf: 0 * inf = NaN.
 // -DATT_LAZY=0.0f gives the strict maximum.
 #ifndef ATT_LAZY
 #define ATT_LAZY 8.0f
@@ -415,7 +417,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(AttnArgs p) {
           for (int kbk = 0; kbk < 4; ++kbk)
 #pragma unroll
             for (int r = 0; r < 4; ++r) sacc[kbk][qb][r] -= d;
-          const float alpha = att_exp2(-d);
+          const float alpha = att_exp2(fminf(-d, 0.f));   // (tile 0 may move m DOWN: O and the sums are still 0, and exp2(-d) past 2^128 would make them NaN)
           if constexpr (!MFMA_SUM) lsum[qb] *= alpha;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -703,7 +705,7 @@ __global__ __launch_bounds__(256, 3) void attn_vit32_kernel(AttnArgs p) {
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
           for (int i = 0; i < 16; ++i) sacc[kb][i] -= d;
-        const float a = att_exp2(-d);               // rescale O^T (the query is the lane: no cross-lane traffic)
+        const float a = att_exp2(fminf(-d, 0.f));   // rescale O^T (the query is the lane: no cross-lane traffic); tile 0 may move m down: see above
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -997,7 +999,7 @@ __global__ __launch_bounds__(512, 2) void attn_prefill_pair_kernel(AttnArgs p) {
           for (int kbk = 0; kbk < 4; ++kbk)
 #pragma unroll
             for (int r = 0; r < 4; ++r) sacc[kbk][qb][r] -= d;
-          const float alpha = att_exp2(-d);
+          const float alpha = att_exp2(fminf(-d, 0.f));   // (tile 0 may move m DOWN: O and the sums are still 0, and exp2(-d) past 2^128 would make them NaN)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float a = __shfl(alpha, 4 * h + r, 64);
