@@ -696,6 +696,21 @@ int vis_decode_cross_attn_batch(const void* q, const void* q_norm_w, const void*
                                 int key_tokens, int nsplit, float scale, float eps, int batch, long long q_bs,
                                 long long kv_bs, vis_stream_t stream);
 
+/* vis_decode_cross_attn over fp8 (OCP e4m3) copies of the static keys / values (csrc/cross_kv.hip): codes uint8
+ * [Hkv][key_tokens][128] and one f32 scale per (kv head, key row) [Hkv][key_tokens] for K and for V, as vis_quant_rows_fp8
+ * (no norm) writes them over the bf16 rows.  key_tokens is a multiple of 64; codes and scales are 16-byte aligned.  Same split
+ * plan, key range [0, *nkeys_m1 + 1) and partials as the bf16 entry; P stays f32, the V row scale rides in the weight. */
+int vis_decode_cross_attn_fp8(const void* q, const void* q_norm_w, const void* k_codes, const void* k_scale,
+                              const void* v_codes, const void* v_scale, const void* nkeys_m1, void* part_o, void* part_ml,
+                              void* out, int Hq, int Hkv, int HD, int key_tokens, int nsplit, float scale, float eps,
+                              vis_stream_t stream);
+/* Batch form: sequence b uses q + b * q_bs, codes + b * kv_bs, scales + b * sc_bs (element strides) and nkeys_m1[b]. */
+int vis_decode_cross_attn_fp8_batch(const void* q, const void* q_norm_w, const void* k_codes, const void* k_scale,
+                                    const void* v_codes, const void* v_scale, const void* nkeys_m1, void* part_o,
+                                    void* part_ml, void* out, int Hq, int Hkv, int HD, int key_tokens, int nsplit,
+                                    float scale, float eps, int batch, long long q_bs, long long kv_bs, long long sc_bs,
+                                    vis_stream_t stream);
+
 /* Row f4: pixel statistics of the image-quality pre-check (src/safety/image_quality.py:42-56,:118-127): exact integer
  * sums over the RGB frame - stats[0] = sum gray, stats[1] = sum Laplacian, stats[2] = sum Laplacian^2 (int64[3]) with
  * OpenCV's published 8-bit RGB2GRAY fixed-point rule and the ksize-1 Laplacian under BORDER_REFLECT_101.

@@ -24,13 +24,17 @@ ap.add_argument("--new-tokens", type=int, default=128)
 ap.add_argument("--prompt-tokens", type=int, default=700)
 ap.add_argument("--batch", type=int, default=1, help="> 1: batch inspection - that many images per step through BOTH models, "
                 "each model: per-image prompt pass + one shared decode loop (text part first: shared prefix for the Inspector)")
+ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8", "mxfp4"], help="the Auditor's decode weight format")
+ap.add_argument("--mxfp4-gemm-from", type=int, default=None, help="mxfp4 only: the MFMA projection from this many sequences on (5..64)")
+ap.add_argument("--cross-kv", default="bf16", choices=["bf16", "fp8"], help="the Auditor's decode-step cross-attention keys / values")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 qc = Qwen2VLConfig.qwen2_vl_7b()
 B = a.batch
 insp = Qwen2VLEngine(qc, random_device_weights(qc, dev, 0), dev, max_ctx=4096, max_batch=B)
 mc = MW.MllamaConfig.mllama_11b()
-aud = MllamaEngine(mc, MW.random_device_weights(mc, dev, 1), dev, max_ctx=2048, max_batch=B)
+aud = MllamaEngine(mc, MW.random_device_weights(mc, dev, 1), dev, max_ctx=2048, max_batch=B,
+                   decode_weights=a.decode_weights, mxfp4_gemm_from=a.mxfp4_gemm_from, cross_kv=a.cross_kv)
 rng = np.random.default_rng(0)
 raw = torch.from_numpy(rng.integers(0, 256, (1024, 1024, 3), dtype=np.uint8)).to(dev)
 th, tw = smart_resize(1024, 1024)

@@ -14,10 +14,13 @@ ap.add_argument("--new-tokens", type=int, default=128)
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--model", default="11b", choices=["11b", "tiny"])
 ap.add_argument("--batch", type=int, default=1, help="> 1: that many images per step, per-image prompt pass + ONE shared decode loop")
+ap.add_argument("--decode-weights", default="bf16", choices=["bf16", "fp8", "mxfp4"], help="the Auditor's decode weight format")
+ap.add_argument("--mxfp4-gemm-from", type=int, default=None, help="mxfp4 only: the MFMA projection from this many sequences on (5..64)")
+ap.add_argument("--cross-kv", default="bf16", choices=["bf16", "fp8"], help="the Auditor's decode-step cross-attention keys / values")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = MllamaConfig.mllama_11b() if a.model == "11b" else MllamaConfig.tiny()
-eng = MllamaEngine(cfg, random_device_weights(cfg, dev, 0), dev, max_ctx=2048 if a.model == "11b" else 1024, max_batch=a.batch)
+eng = MllamaEngine(cfg, random_device_weights(cfg, dev, 0), dev, max_ctx=2048 if a.model == "11b" else 1024, max_batch=a.batch, decode_weights=a.decode_weights, mxfp4_gemm_from=a.mxfp4_gemm_from, cross_kv=a.cross_kv)
 rng = np.random.default_rng(0)
 side = 1024 if a.model == "11b" else 100
 frame = torch.from_numpy(rng.integers(0, 256, (side, side, 3), dtype=np.uint8)).to(dev)

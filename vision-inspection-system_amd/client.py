@@ -258,7 +258,7 @@ class _Chat:
 TIMING_LOG: List[dict] = []
 
 # ----------------------------------------------------------------------------- engine registry
-_ENGINES: Dict[Tuple[str, str], Any] = {}
+_ENGINES: Dict[tuple, Any] = {}      # (model id, device) + an mllama engine's _auditor_settings()
 _ENGINES_LOCK = threading.Lock()
 
 
@@ -299,6 +299,9 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
     if device is None:
         with _ENGINES_LOCK:      # a model that is already loaded / registered on exactly one device: no device query needed
             hits = [k for k in _ENGINES if k[0] == model_id]
+            if any(len(k) > 2 for k in hits):      # mllama entries carry their settings: the entry of the current ones
+                aud = _auditor_settings()
+                hits = [k for k in hits if len(k) == 2 or k[2:] == aud]
             if len(hits) == 1:
                 return _ENGINES[hits[0]]
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cuda:0"
@@ -306,6 +309,12 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
     with _ENGINES_LOCK:
         if key in _ENGINES:
             return _ENGINES[key]
+        # an mllama engine is cached under its quantisation settings too (VIS_AUDITOR_*, fixed per engine); the variables are
+        # read only where an mllama model is loaded or already cached, so a malformed one cannot fail another model's load
+        if any(k[:2] == key and len(k) > 2 for k in _ENGINES):
+            akey = key + _auditor_settings()
+            if akey in _ENGINES:
+                return _ENGINES[akey]
         # KV-cache rows per sequence.  Default: the reference's request fits as the reference sends it - ~2300 prompt tokens
         # (inspection prompt + one 1024 x 1024 image) + its own default max_tokens = 2048 (/root/reference utils/config.py:50-53)
         # = 4348 -> 4608 (72 context splits: the chained decode launch stays resident up to ~6700)
@@ -313,7 +322,7 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
         max_batch = max(1, min(64, int(os.environ.get("VIS_MAX_BATCH", "64"))))
         mllama = _load_mllama(model_id, device, max_ctx, max_batch)
         if mllama is not None:
-            _ENGINES[key] = mllama
+            _ENGINES[key + _auditor_settings()] = mllama
             return mllama
         if model_id.startswith("synthetic:"):
             parts = model_id.split(":")
@@ -361,9 +370,30 @@ def _env_int_or_none(name: str) -> Optional[int]:
     return int(v) if v else None
 
 
+def _auditor_settings() -> tuple:
+    """(decode_weights, mxfp4_gemm_from, cross_kv) of an mllama engine from VIS_AUDITOR_DECODE_WEIGHTS, VIS_AUDITOR_MXFP4_GEMM_FROM
+    and VIS_AUDITOR_CROSS_KV; unset: ("bf16", None, "bf16").  VIS_DECODE_WEIGHTS is the Qwen2-VL engines' and is not read here."""
+    return (os.environ.get("VIS_AUDITOR_DECODE_WEIGHTS", "").strip() or "bf16", _env_int_or_none("VIS_AUDITOR_MXFP4_GEMM_FROM"),
+            os.environ.get("VIS_AUDITOR_CROSS_KV", "").strip() or "bf16")
+
+
+def _auditor_kwargs() -> dict:
+    """The constructor keywords the VIS_AUDITOR_* variables set; nothing set -> no keyword (the bf16 engine's call as it was)."""
+    dw, gf, xkv = _auditor_settings()
+    kw = {}
+    if dw != "bf16":
+        kw["decode_weights"] = dw
+    if gf is not None:
+        kw["mxfp4_gemm_from"] = gf
+    if xkv != "bf16":
+        kw["cross_kv"] = xkv
+    return kw
+
+
 def _load_mllama(model_id: str, device, max_ctx: int, max_batch: int = 1) -> Optional[LoadedModel]:
     """mllama family (synthetic:mllama-tiny[:seed], synthetic:mllama-11b, or a local directory whose config.json
-    says model_type "mllama"); None when ``model_id`` is not an mllama model."""
+    says model_type "mllama"); None when ``model_id`` is not an mllama model.  VIS_AUDITOR_DECODE_WEIGHTS / _MXFP4_GEMM_FROM /
+    _CROSS_KV choose the engine's decode weight format and the format of its cross-attention keys (MllamaEngine)."""
     import json
     from . import mllama_weights as MW
     from .mllama_engine import MllamaEngine
@@ -381,7 +411,7 @@ def _load_mllama(model_id: str, device, max_ctx: int, max_batch: int = 1) -> Opt
         else:
             raise ValueError(f"unknown synthetic model {parts[1]!r}")
         tok = LlamaByteTokenizer(cfg.vocab, cfg.image_token_id, cfg.eos_ids)
-        return LoadedModel(MllamaEngine(cfg, w, device, max_ctx=max_ctx, max_batch=max_batch), tok, cfg, model_id, "mllama")
+        return LoadedModel(MllamaEngine(cfg, w, device, max_ctx=max_ctx, max_batch=max_batch, **_auditor_kwargs()), tok, cfg, model_id, "mllama")
     path = resolve_model_dir(model_id)
     if path is None or not os.path.exists(os.path.join(path, "config.json")):
         return None
@@ -391,7 +421,7 @@ def _load_mllama(model_id: str, device, max_ctx: int, max_batch: int = 1) -> Opt
     cfg = MW.config_from_hf_dir(path)
     w = MW.load_safetensors_dir(cfg, path, device)
     tok = LlamaHFTokenizer(path, cfg.image_token_id, cfg.eos_ids)
-    return LoadedModel(MllamaEngine(cfg, w, device, max_ctx=max_ctx, max_batch=max_batch), tok, cfg, model_id, "mllama")
+    return LoadedModel(MllamaEngine(cfg, w, device, max_ctx=max_ctx, max_batch=max_batch, **_auditor_kwargs()), tok, cfg, model_id, "mllama")
 
 
 def _reply_text(model_id: str, decoded: str) -> str:
@@ -557,7 +587,8 @@ def register_model(model_id: str, device: str, lm: LoadedModel) -> None:
 
 def unregister_model(model_id: str, device: str) -> None:
     with _ENGINES_LOCK:
-        _ENGINES.pop((model_id, str(device)), None)
+        for k in [k for k in _ENGINES if k[:2] == (model_id, str(device))]:
+            _ENGINES.pop(k)
 
 
 SUPPORTED_MODEL_TYPES = ("qwen2_vl", "qwen2_5_vl", "mllama")

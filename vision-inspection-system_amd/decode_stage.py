@@ -348,7 +348,8 @@ class DecodeStage(PickStage):
         # default because it trades an invariant for those 6-13 %: a sequence decoded in a batch of 2 would then follow the
         # single-sequence arithmetic and in a batch of 3+ the stream-K arithmetic - its tokens could depend on the batch size
         # at near-ties (tests/test_fullsize_gpu.py::test_7b_batch_invariance_and_reproducibility).  A model with
-        # cross-attention layers has no multi-row step.
+        # cross-attention layers ignores VIS_ROWS_GEMV; with MXFP4 weights it takes the multi-row step like any other (the
+        # cross layer's q projection writes the leading columns of the packed row, a strided [B, Hq * D] view).
         if self.decode_weights == "mxfp4":
             # the multi-row GEMV at every batch size, unless mxfp4_gemm_from hands the larger ones to the MFMA projection
             # (the other arithmetic family, see Qwen2VLEngine.__init__)

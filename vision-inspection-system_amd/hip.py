@@ -102,6 +102,8 @@ _SIGS = {
     "vis_add_rows_bf16": "ppp" + "iiii" + "p",
     "vis_decode_cross_attn": "pppppppp" + "iiiii" + "ff" + "p",
     "vis_decode_cross_attn_batch": "pppppppp" + "iiiii" + "ff" + "ill" + "p",
+    "vis_decode_cross_attn_fp8": "pppppppppp" + "iiiii" + "ff" + "p",
+    "vis_decode_cross_attn_fp8_batch": "pppppppppp" + "iiiii" + "ff" + "illl" + "p",
     "vis_image_stats_u8": "p" + "ii" + "p" + "p",
     "vis_gather_rows": "ppp" + "iii" + "p",
     "vis_scatter_rows": "ppp" + "iii" + "p",
@@ -2080,6 +2082,69 @@ def decode_cross_attn_batch(q: torch.Tensor, q_norm_w: torch.Tensor, k: torch.Te
                                             _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, k.shape[2], nsplit, scale, eps,
                                             B, q.stride(0), k.stride(0), _stream())
     _check(rc, "vis_decode_cross_attn_batch")
+
+
+def quantize_cross_kv(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> None:
+    """The fp8 copy of static cross-attention keys or values: bf16 [..., 128] contiguous -> e4m3 codes (uint8, same shape) and
+    one f32 scale per row (shape without the last dim), by vis_quant_rows_fp8 without a norm: scale = max(amax / 448, 1e-12),
+    an all-zero row gets scale 1e-12 and codes 0."""
+    _bf16(x, "quantize_cross_kv x")
+    if x.shape[-1] != 128 or codes.dtype != torch.uint8 or codes.shape != x.shape or scales.dtype != torch.float32 \
+            or scales.shape != x.shape[:-1] or not (x.is_contiguous() and codes.is_contiguous() and scales.is_contiguous()):
+        raise HipLibraryError("quantize_cross_kv: bad shapes")
+    quant_rows_fp8(x.view(-1, 128), codes.view(-1, 128), scales.view(-1))
+
+
+def _cross_fp8_kv(name, kq, ksc, vq, vsc, lead, n_kv, head_dim) -> None:
+    if kq.dtype != torch.uint8 or vq.dtype != torch.uint8 or ksc.dtype != torch.float32 or vsc.dtype != torch.float32:
+        raise HipLibraryError(f"{name}: uint8 codes and f32 scales required")
+    if kq.dim() != lead + 3 or kq.shape != vq.shape or kq.shape[lead] != n_kv or kq.shape[lead + 2] != head_dim \
+            or ksc.shape != kq.shape[:-1] or vsc.shape != kq.shape[:-1] or kq.shape[lead + 1] % DECODE_KEYS_PER_SPLIT:
+        raise HipLibraryError(f"{name}: bad codes/scales")
+
+
+def decode_cross_attn_fp8(q: torch.Tensor, q_norm_w: torch.Tensor, kq: torch.Tensor, ksc: torch.Tensor, vq: torch.Tensor,
+                          vsc: torch.Tensor, nkeys_m1: torch.Tensor, part_o: torch.Tensor, part_ml: torch.Tensor,
+                          out: torch.Tensor, n_q: int, n_kv: int, head_dim: int, nsplit: int, scale: float,
+                          eps: float) -> None:
+    """decode_cross_attn over fp8 keys / values: codes kq, vq [Hkv, T, 128] uint8 with row scales ksc, vsc [Hkv, T] f32
+    (T a multiple of 64)."""
+    _bf16(q, "q")
+    _cross_fp8_kv("decode_cross_attn_fp8", kq, ksc, vq, vsc, 0, n_kv, head_dim)
+    if not (kq.is_contiguous() and vq.is_contiguous() and ksc.is_contiguous() and vsc.is_contiguous()):
+        raise HipLibraryError("decode_cross_attn_fp8: bad codes/scales")
+    if q.numel() != n_q * head_dim or out.numel() != n_q * head_dim or nkeys_m1.dtype != torch.int32:
+        raise HipLibraryError("decode_cross_attn_fp8: bad q/out/nkeys")
+    if part_o.numel() < n_q * nsplit * head_dim or part_ml.numel() < n_q * nsplit * 2:
+        raise HipLibraryError("decode_cross_attn_fp8: workspace too small")
+    rc = load().vis_decode_cross_attn_fp8(_ptr(q), _ptr(q_norm_w), _ptr(kq), _ptr(ksc), _ptr(vq), _ptr(vsc), _ptr(nkeys_m1),
+                                          _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, kq.shape[1], nsplit,
+                                          scale, eps, _stream())
+    _check(rc, "vis_decode_cross_attn_fp8")
+
+
+def decode_cross_attn_fp8_batch(q: torch.Tensor, q_norm_w: torch.Tensor, kq: torch.Tensor, ksc: torch.Tensor,
+                                vq: torch.Tensor, vsc: torch.Tensor, nkeys_m1: torch.Tensor, part_o: torch.Tensor,
+                                part_ml: torch.Tensor, out: torch.Tensor, n_q: int, n_kv: int, head_dim: int, nsplit: int,
+                                scale: float, eps: float) -> None:
+    """Batch of B new tokens, each over ITS OWN fp8 keys / values: q [B, Hq*128], codes [B, Hkv, T, 128], scales [B, Hkv, T]
+    (any batch stride, the same for K and V), nkeys_m1 [B] int32, out [B, Hq*128]."""
+    _bf16(q, "q")
+    B = q.shape[0]
+    _cross_fp8_kv("decode_cross_attn_fp8_batch", kq, ksc, vq, vsc, 1, n_kv, head_dim)
+    if kq.shape[0] != B or not (kq[0].is_contiguous() and vq[0].is_contiguous() and ksc[0].is_contiguous()
+                                and vsc[0].is_contiguous()) or kq.stride(0) != vq.stride(0) or ksc.stride(0) != vsc.stride(0):
+        raise HipLibraryError("decode_cross_attn_fp8_batch: bad codes/scales")
+    if q.shape[1] != n_q * head_dim or q.stride(1) != 1 or out.shape != (B, n_q * head_dim) or not out.is_contiguous() \
+            or nkeys_m1.dtype != torch.int32 or nkeys_m1.numel() != B:
+        raise HipLibraryError("decode_cross_attn_fp8_batch: bad q/out/nkeys")
+    if part_o.numel() < B * n_q * nsplit * head_dim or part_ml.numel() < B * n_q * nsplit * 2:
+        raise HipLibraryError("decode_cross_attn_fp8_batch: workspace too small")
+    rc = load().vis_decode_cross_attn_fp8_batch(_ptr(q), _ptr(q_norm_w), _ptr(kq), _ptr(ksc), _ptr(vq), _ptr(vsc),
+                                                _ptr(nkeys_m1), _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim,
+                                                kq.shape[2], nsplit, scale, eps, B, q.stride(0), kq.stride(0), ksc.stride(0),
+                                                _stream())
+    _check(rc, "vis_decode_cross_attn_fp8_batch")
 
 
 def patchify(img_u8: torch.Tensor, out: torch.Tensor, row0: int, mean, std) -> None:

@@ -96,8 +96,39 @@ def llama3_rope_tables(cfg: MllamaConfig, n: int) -> Tuple[np.ndarray, np.ndarra
 class MllamaEngine(Generation):
     """One mllama replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
-    def __init__(self, cfg: MllamaConfig, weights: MllamaDeviceWeights, device, max_ctx: int = 4096, max_batch: int = 1):
+    @staticmethod
+    def check_decode_weights(cfg: MllamaConfig, fmt: str) -> None:
+        """Refuse an unknown decode precision, or one the model's shapes do not fit (needs no GPU): the rules of
+        Qwen2VLEngine.check_decode_weights."""
+        from .engine import Qwen2VLEngine
+        Qwen2VLEngine.check_decode_weights(cfg, fmt)
+
+    @staticmethod
+    def check_mxfp4_gemm_from(cfg: MllamaConfig, fmt: str, mxfp4_gemm_from) -> None:
+        """The rules of Qwen2VLEngine.check_mxfp4_gemm_from (an integer in 5..64, decode_weights='mxfp4' only, multiples of 64)."""
+        from .engine import Qwen2VLEngine
+        Qwen2VLEngine.check_mxfp4_gemm_from(cfg, fmt, mxfp4_gemm_from)
+
+    @staticmethod
+    def check_cross_kv(cross_kv: str) -> None:
+        if cross_kv not in ("bf16", "fp8"):
+            raise ValueError("cross_kv must be 'bf16' or 'fp8'")
+
+    def __init__(self, cfg: MllamaConfig, weights: MllamaDeviceWeights, device, max_ctx: int = 4096, max_batch: int = 1,
+                 decode_weights: str = "bf16", mxfp4_gemm_from: Optional[int] = None, cross_kv: str = "bf16"):
+        """decode_weights="fp8" / "mxfp4" (VIS_AUDITOR_DECODE_WEIGHTS), mxfp4_gemm_from (VIS_AUDITOR_MXFP4_GEMM_FROM): the
+        decode projections of EVERY layer - a cross-attention layer's q projection too - and the lm_head are quantised at load
+        and decoded as on the Qwen2-VL engine (Qwen2VLEngine.__init__ describes the formats and the two arithmetic families
+        of mxfp4_gemm_from); a quantised engine decodes the single sequence on the un-chained step.  The prompt pass, the
+        vision tower, embedding, norms and both caches stay bf16.
+        cross_kv="fp8" (VIS_AUDITOR_CROSS_KV): the decode step reads an e4m3 copy of the image's static cross-attention keys
+        and values (codes + one f32 scale per key row, csrc/cross_kv.hip), written once per prompt pass from the bf16 rows;
+        the bf16 rows stay (the prompt pass reads them), so the copy costs half as much memory again.  Independent of
+        decode_weights.  Everything defaults to bf16: the launches of an engine built without these keywords are unchanged."""
         cfg.validate_for_kernels()
+        self.check_decode_weights(cfg, decode_weights)
+        self.check_mxfp4_gemm_from(cfg, decode_weights, mxfp4_gemm_from)
+        self.check_cross_kv(cross_kv)
         hip.load()
         if not torch.cuda.is_available():
             raise hip.HipLibraryError("MllamaEngine needs a ROCm GPU (no CPU fallback exists)")
@@ -120,6 +151,12 @@ class MllamaEngine(Generation):
         self.vcache_b = torch.zeros((Bm, self.n_self, Hkv, self.max_ctx, D), dtype=bf, device=dev)
         self.xk_b = torch.zeros((Bm, self.n_cross, Hkv, self.Tk, D), dtype=bf, device=dev)
         self.xv_b = torch.zeros((Bm, self.n_cross, Hkv, self.Tk, D), dtype=bf, device=dev)
+        self.cross_kv = cross_kv
+        if cross_kv == "fp8":       # e4m3 codes + row scales of xk_b / xv_b, what the decode step's cross-attention reads
+            self.xkq_b = torch.zeros((Bm, self.n_cross, Hkv, self.Tk, D), dtype=torch.uint8, device=dev)
+            self.xvq_b = torch.zeros((Bm, self.n_cross, Hkv, self.Tk, D), dtype=torch.uint8, device=dev)
+            self.xks_b = torch.zeros((Bm, self.n_cross, Hkv, self.Tk), dtype=torch.float32, device=dev)
+            self.xvs_b = torch.zeros((Bm, self.n_cross, Hkv, self.Tk), dtype=torch.float32, device=dev)
         cos, sin = llama3_rope_tables(cfg, self.max_ctx)
         self.cos_t = torch.from_numpy(cos).to(dev)          # plain positions: one table for every sequence
         self.sin_t = torch.from_numpy(sin).to(dev)
@@ -152,7 +189,8 @@ class MllamaEngine(Generation):
             self.b_act = torch.empty((Bm, cfg.intermediate), dtype=bf, device=dev)
         # r05 experiment, OFF by default (VIS_DECODE_FUSED=1): every batched-decode projection as ONE launch (vis_decode_proj_bf16:
         # stream + split-K reduction + epilogue; Qwen2VLEngine.__init__ says why it is not the default).
-        self.fused_proj = Bm > 1 and H % 128 == 0 and os.environ.get("VIS_DECODE_FUSED", "0") == "1"
+        # (bf16 weights only: a quantised engine's batched step is the stream-K or the rows step)
+        self.fused_proj = Bm > 1 and H % 128 == 0 and decode_weights == "bf16" and os.environ.get("VIS_DECODE_FUSED", "0") == "1"
         # batched decode: the self-attention launch finalises the qkv projection's partial slabs itself (vis_decode_attn_parts,
         # bit-identical to skinny_finalize + decode_attn); VIS_QKV_FOLD=0 keeps the two launches (A/B)
         self.fold_qkv = os.environ.get("VIS_QKV_FOLD", "1") == "1"
@@ -179,7 +217,8 @@ class MllamaEngine(Generation):
         self.chain_sync: Optional[torch.Tensor] = None
         self.chain_ctx_limit = 0
         self._chain_launches = 0
-        if os.environ.get("VIS_DECODE_CHAIN", "1") != "0" and hip.decode_chain_supported(Hq, Hkv, D, H):
+        if decode_weights == "bf16" and os.environ.get("VIS_DECODE_CHAIN", "1") != "0" \
+                and hip.decode_chain_supported(Hq, Hkv, D, H):
             lim = hip.decode_chain_ctx_limit(Hq, Hkv, H)
             if lim > 0:
                 self.chain_ws, self.chain_sync = hip.decode_chain_state(dev, Hq, Hkv, self.nsplit)
@@ -194,14 +233,45 @@ class MllamaEngine(Generation):
         self.has_image = False
         self.decode_limit = 0
         self.tokenizer = None
-        # what the decode stage needs to know of the model (decode_stage.py; bf16 weights only); it also sets up the pick stage
-        self.decode_weights, self.fp8_batched, self.mxfp4_gemm_from = "bf16", False, None
+        # what the decode stage needs to know of the model (decode_stage.py); it also sets up the pick stage.  Quantised decode
+        # weights as on the Qwen2-VL engine: every layer's four projections (a cross layer's qkv_w is its q projection) and the
+        # lm_head, quantised here once; the batched fp8 step carries its activations as e4m3 rows too.
+        self.decode_weights, self.fp8_batched, self.mxfp4_gemm_from = decode_weights, False, mxfp4_gemm_from
+        names = ("qkv_w", "o_w", "gateup_w", "down_w")
+        q8 = q4 = [None] * len(weights.layers)
+        q8_head = q4_head = None
+        if decode_weights == "fp8":
+            q8 = [{n: hip.quantize_fp8_rows(getattr(lw, n)) for n in names} for lw in weights.layers]
+            q8_head = hip.quantize_fp8_rows(weights.lm_head)
+        elif decode_weights == "mxfp4":
+            q4 = [{n: hip.quantize_mxfp4_rows(getattr(lw, n)) for n in names} for lw in weights.layers]
+            q4_head = hip.quantize_mxfp4_rows(weights.lm_head)
+        if decode_weights == "fp8" and Bm > 1 and H % 128 == 0:
+            self.fp8_batched = True
+            self.kpad = _round_up(cfg.intermediate, 128)       # fp8 MFMA needs K % 128 == 0: zero-pad down's K if necessary
+            self.b_xq = torch.zeros((Bm, H), dtype=torch.uint8, device=dev)
+            self.b_x2q = torch.zeros((Bm, H), dtype=torch.uint8, device=dev)
+            self.b_actq = torch.zeros((Bm, self.kpad), dtype=torch.uint8, device=dev)      # pad columns stay 0
+            self.b_sx = torch.zeros((3, Bm), dtype=torch.float32, device=dev)
+            if self.kpad != cfg.intermediate:
+                for q in q8:
+                    wq, sc = q["down_w"]
+                    pad = torch.zeros((wq.shape[0], self.kpad), dtype=torch.uint8, device=wq.device)
+                    pad[:, :cfg.intermediate] = wq
+                    q["down_w_pad"] = (pad, sc)
         si = ci = 0
         layers = []
-        for lw in weights.layers:
-            layers.append(DecodeLayer(lw, None, None, lw.cross, ci if lw.cross else si, None))
+        for i, lw in enumerate(weights.layers):
+            layers.append(DecodeLayer(lw, q8[i], q4[i], lw.cross, ci if lw.cross else si, None))
             ci, si = ci + lw.cross, si + (not lw.cross)
-        self._init_decode_stage(layers, weights.norm_w, weights.lm_head)
+        self._init_decode_stage(layers, weights.norm_w, weights.lm_head, q8_head=q8_head, q4_head=q4_head)
+
+    def _quantize_cross_kv(self, slot: int) -> None:
+        """cross_kv="fp8": the e4m3 copy of slot ``slot``'s cross-attention keys / values, all cross layers in one launch each -
+        once per prompt pass, after the bf16 rows of every cross layer have been written.  Every row of the buffer is
+        quantised, rows at or past the request's key count too (whatever they hold: the decode kernel never uses them)."""
+        hip.quantize_cross_kv(self.xk_b[slot], self.xkq_b[slot], self.xks_b[slot])
+        hip.quantize_cross_kv(self.xv_b[slot], self.xvq_b[slot], self.xvs_b[slot])
 
     # ------------------------------------------------------------------ preprocessing (geometry on host, pixels on GPU)
     def prepare_image(self, frame: torch.Tensor):
@@ -474,6 +544,8 @@ class MllamaEngine(Generation):
                 si += 1
             if taps is not None:
                 taps[f"layer{li}"] = x.clone()
+        if has_image and self.cross_kv == "fp8":
+            self._quantize_cross_kv(slot)
         hip.gemv(x[S - 1], w.lm_head, logits, norm_w=w.norm_w, eps=cfg.rms_eps)
         if taps is not None:
             taps["first_logits"] = logits.clone()
@@ -599,6 +671,9 @@ class MllamaEngine(Generation):
                 hip.gemm(y, lw.gateup_w, act=hip.ACT_SWIGLU, out=act)
                 proj(act, lw.down_w, ks_down)
                 si += 1
+        if self.cross_kv == "fp8":
+            for slot, _, _, _ in items:
+                self._quantize_cross_kv(slot)
         grouped = many and k <= 4 and H * 2 * (2 if k <= 2 else 4) <= 152 * 1024   # one pass over the lm_head for the group's last rows
         if grouped:
             lg = torch.empty((k, self.logits_b.shape[1]), dtype=torch.float32, device=dev)
@@ -625,11 +700,18 @@ class MllamaEngine(Generation):
     def _decode_cross_attn(self, L, q: torch.Tensor, att: torch.Tensor, B: int) -> None:
         """Attention of the new token(s) over the image's static keys / values of cross layer ``L`` (DecodeStage hook)."""
         cfg = self.cfg
-        if B:
-            fn, xk, xv, nkeys = hip.decode_cross_attn_batch, self.xk_b[:B, L.idx], self.xv_b[:B, L.idx], self.nkeys_b[:B]
+        if self.cross_kv == "fp8":      # the e4m3 copy the prompt pass left (csrc/cross_kv.hip)
+            if B:
+                fn, nkeys = hip.decode_cross_attn_fp8_batch, self.nkeys_b[:B]
+                kv = (self.xkq_b[:B, L.idx], self.xks_b[:B, L.idx], self.xvq_b[:B, L.idx], self.xvs_b[:B, L.idx])
+            else:
+                fn, nkeys = hip.decode_cross_attn_fp8, self.nkeys_m1
+                kv = (self.xkq_b[0, L.idx], self.xks_b[0, L.idx], self.xvq_b[0, L.idx], self.xvs_b[0, L.idx])
+        elif B:
+            fn, kv, nkeys = hip.decode_cross_attn_batch, (self.xk_b[:B, L.idx], self.xv_b[:B, L.idx]), self.nkeys_b[:B]
         else:
-            fn, xk, xv, nkeys = hip.decode_cross_attn, self.xk[L.idx], self.xv[L.idx], self.nkeys_m1
-        fn(q, L.w.q_norm, xk, xv, nkeys, self.part_o, self.part_ml, att, cfg.heads, cfg.kv_heads, cfg.head_dim, self.xsplit,
+            fn, kv, nkeys = hip.decode_cross_attn, (self.xk[L.idx], self.xv[L.idx]), self.nkeys_m1
+        fn(q, L.w.q_norm, *kv, nkeys, self.part_o, self.part_ml, att, cfg.heads, cfg.kv_heads, cfg.head_dim, self.xsplit,
            cfg.head_dim ** -0.5, cfg.rms_eps)
 
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
@@ -706,6 +788,9 @@ class MllamaEngine(Generation):
         """A further choice attends to its root's image: the cross-attention keys / values, whole (DecodeStage hook)."""
         self.xk_b[child].copy_(self.xk_b[root])
         self.xv_b[child].copy_(self.xv_b[root])
+        if self.cross_kv == "fp8":
+            for t in (self.xkq_b, self.xvq_b, self.xks_b, self.xvs_b):
+                t[child].copy_(t[root])
         self.nkeys_b[child:child + 1].copy_(self.nkeys_b[root:root + 1])
 
     def prefill_many(self, requests: Sequence, temperature: float = 0.0, seed: int = 0, max_new_tokens: Optional[int] = None,
