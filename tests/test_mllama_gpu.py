@@ -195,11 +195,11 @@ def test_stacked_prompt_passes_equal_one_pass_per_request(device, monkeypatch):
     monkeypatch.setattr(eng, "_prefill_group", lambda items, *a, **k: (calls.append(len(items)), real(items, *a, **k))[1])
     stacked = eng.generate_batch(reqs, max_new_tokens=10, stop_on_eos=False)
     logits = eng.logits_b[:5].clone()
-    assert calls == [4]                                                  # groups of four: [4 stacked] + [1 alone]
+    assert calls == [4, 1]                                               # groups of four: [4 stacked] + [1 alone, a group of one]
     monkeypatch.setenv("VIS_MERGE_PREFILL", "0")
     monkeypatch.setenv("VIS_VIT_BATCH", "1")
     apart = eng.generate_batch(reqs, max_new_tokens=10, stop_on_eos=False)
-    assert calls == [4] and apart == stacked and torch.equal(logits, eng.logits_b[:5])
+    assert calls == [4, 1] + [1] * 5 and apart == stacked and torch.equal(logits, eng.logits_b[:5])      # no stack now
     assert stacked[0] == stacked[3] and stacked[1] == stacked[4]
     for b in range(3):
         assert eng.generate(ids, frames[b], max_new_tokens=10, stop_on_eos=False)[0] == stacked[b][0]

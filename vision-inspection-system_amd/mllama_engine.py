@@ -314,73 +314,25 @@ class MllamaEngine(Generation):
         return plan
 
     def vision_forward(self, frame: torch.Tensor, taps: Optional[dict] = None) -> Tuple[torch.Tensor, int]:
-        """uint8 device frame [H, W, 3] -> (cross-attention states [max_tiles*tile_tokens, hidden] bf16, n_tiles)."""
-        cfg, w, dev, bf = self.cfg, self.w, self.device, torch.bfloat16
-        frame, th, tw, ar_id = self.prepare_image(frame)
-        n_tiles = th * tw
-        T, P, E, Hh, D = cfg.max_tiles, cfg.tile_tokens, cfg.v_hidden, cfg.v_heads, cfg.v_head_dim
-        npad = (8 - P % 8) % 8
-        TP, N, nR = T * P, T * (P + npad), n_tiles * P
-        patches = torch.zeros((TP, w.patch_w.shape[1]), dtype=bf, device=dev)
-        hip.patchify_tiles(frame, patches, th, tw, cfg.image_size, cfg.image_mean, cfg.image_std)
-        x = torch.zeros((N, E), dtype=bf, device=dev)                      # pad rows start as exact zeros
-        hip.gemm(patches, w.patch_w, residual=w.cls_pos[ar_id].view(TP, E), out=x[:TP])
-        hip.layernorm(x[:TP], w.ln_pre_w, w.ln_pre_b, 1e-5, out=x[:TP])
-        plan = self._vision_plan([(0, nR, N)])
-        ld = _round_up(N, 64)
-        y = torch.empty((N, E), dtype=bf, device=dev)
-        qkv = torch.empty((N, 3 * E), dtype=bf, device=dev)
-        q = torch.empty((Hh, N, D), dtype=bf, device=dev)
-        k = torch.empty((Hh, N, D), dtype=bf, device=dev)
-        vt = torch.empty((Hh, D, ld), dtype=bf, device=dev)
-        att = torch.empty((N, E), dtype=bf, device=dev)
-        hmid = torch.empty((N, cfg.v_mlp), dtype=bf, device=dev)
-        feats = torch.empty((TP, cfg.v_out), dtype=bf, device=dev)
-        scale = D ** -0.5
+        """uint8 device frame [H, W, 3] -> (cross-attention states [max_tiles*tile_tokens, hidden] bf16, n_tiles): a stack of one."""
+        return self.vision_forward_many([frame], taps)[0]
 
-        def layer(b):
-            hip.layernorm(x, b.ln1_w, b.ln1_b, cfg.v_eps, out=y)
-            hip.gemm(y, b.qkv_w, out=qkv)
-            hip.qkv_rope_split(qkv, None, None, q, k, None, vt, Hh, Hh, D)
-            hip.attn_prefill_plan(q, k, vt, att, plan, scale)
-            hip.gemm(att, b.o_w, residual=x, out=x)
-            hip.layernorm(x, b.ln2_w, b.ln2_b, cfg.v_eps, out=y)
-            hip.gemm(y, b.fc1_w, bias=b.fc1_b, act=hip.ACT_GELU_ERF, out=hmid)
-            hip.gemm(hmid, b.fc2_w, bias=b.fc2_b, residual=x, out=x)
-
-        j = 0
-        for i, b in enumerate(w.v_layers):
-            layer(b)
-            if i in cfg.v_inter:
-                feats[:, E * (1 + j):E * (2 + j)].copy_(x[:TP])
-                j += 1
-        hip.layernorm(x, w.ln_post_w, w.ln_post_b, 1e-5, out=x)
-        tile_of = np.concatenate([np.repeat(np.arange(T), P), np.repeat(np.arange(T), npad)]).astype(np.int32)
-        idx = hip.upload(ar_id * T + tile_of, dev)
-        hip.add_rows(x, w.post_tile.view(-1, E), idx)
-        for b in w.v_global:
-            layer(b)
-        feats[:, :E].copy_(x[:TP])
-        if taps is not None:
-            taps["vision_features"] = feats
-        return hip.gemm(feats, w.proj_w, bias=w.proj_b), n_tiles
-
-    def vision_forward_many(self, frames: Sequence[torch.Tensor]) -> List[Tuple[torch.Tensor, int]]:
-        """The tower over SEVERAL requests' images in one pass (the batch seam: verify_many).  One image is 6432 rows:
-        its projections are 1 - 2 rounds of the chip (qkv 390 tiles, fc1 520) and its attention list 816 workgroups for 768
-        slots - two rounds, the second 6 % full; four images stacked make whole rounds of all of them.  Every image
-        starts on a 64-row boundary (the attention kernel walks keys in absolute 64-row tiles), so its features - and with
-        them the whole answer - are bit-identical to the single-image pass
-        (test_batched_decode_matches_single_and_is_batch_invariant).  Row order inside an image as in vision_forward."""
+    def vision_forward_many(self, frames: Sequence[torch.Tensor], taps: Optional[dict] = None) -> List[Tuple[torch.Tensor, int]]:
+        """The tower over a stack of k >= 1 images in one pass -> [(cross-attention states [max_tiles*tile_tokens, hidden] bf16,
+        n_tiles)] (k > 1 is the batch seam: verify_many).  One image is 6432 rows: its projections are 1 - 2 rounds of the chip
+        (qkv 390 tiles, fc1 520) and its attention list 816 workgroups for 768 slots - two rounds, the second 6 % full; four
+        images stacked make whole rounds of all of them.  Every image owns round_up(6432, 64) rows of the stack, whatever k: it
+        starts on a 64-row boundary (the attention kernel walks keys in absolute 64-row tiles) and its rows see the same launches
+        alone as stacked, so its features - and with them the whole answer - do not depend on what it is stacked with
+        (test_batched_decode_matches_single_and_is_batch_invariant).  Row order inside an image: the module docstring.
+        ``taps["vision_features"]``: the features of a single image in front of the projection."""
         k = len(frames)
-        if k == 1:
-            return [self.vision_forward(frames[0])]
         cfg, w, dev, bf = self.cfg, self.w, self.device, torch.bfloat16
         T, P, E, Hh, D = cfg.max_tiles, cfg.tile_tokens, cfg.v_hidden, cfg.v_heads, cfg.v_head_dim
         npad = (8 - P % 8) % 8
         TP, N = T * P, T * (P + npad)
         NS = _round_up(N, 64)                         # rows per image in the stack
-        x = torch.zeros((k * NS, E), dtype=bf, device=dev)
+        x = torch.zeros((k * NS, E), dtype=bf, device=dev)                 # pad rows start as exact zeros
         layout, n_tiles_of = [], []
         tile_of = np.concatenate([np.repeat(np.arange(T), P), np.repeat(np.arange(T), npad),
                                   np.zeros(NS - N, dtype=np.int64)]).astype(np.int32)
@@ -433,170 +385,86 @@ class MllamaEngine(Generation):
         for b in w.v_global:
             layer(b)
         take(0)
+        if taps is not None and k == 1:
+            taps["vision_features"] = feats[0]
         cross = hip.gemm(feats.view(k * TP, cfg.v_out), w.proj_w, bias=w.proj_b)
         return [(cross[i * TP:(i + 1) * TP], n_tiles_of[i]) for i in range(k)]
 
     # ------------------------------------------------------------------ prefill
-    def prefill(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, taps: Optional[dict] = None,
-                temperature: float = 0.0, seed: int = 0, slot: int = 0,
-                cross_states: Optional[Tuple[torch.Tensor, int]] = None) -> None:
-        cfg, w, dev, bf = self.cfg, self.w, self.device, torch.bfloat16
+    def _check_prompt(self, input_ids: Sequence[int], has_frame: bool, slot: int) -> Tuple[np.ndarray, int]:
+        """The argument checks of a prompt pass, before anything is launched -> (ids as int64, index of the image token; 0
+        without an image)."""
         if not 0 <= slot < self.max_batch:
             raise ValueError("slot out of range")
-        self.temperature, self.seed = float(temperature), int(seed)
-        kcache, vcache, xk, xv = self.kcache_b[slot], self.vcache_b[slot], self.xk_b[slot], self.xv_b[slot]
-        step, cur_token, nkeys_m1 = self.step_b[slot:slot + 1], self.cur_b[slot:slot + 1], self.nkeys_b[slot:slot + 1]
-        tokens, logits = self.tokens_b[slot], self.logits_b[slot]
         S = len(input_ids)
         if S < 1 or S + 1 > self.max_ctx:
             raise ValueError(f"prompt of {S} tokens does not fit the context of {self.max_ctx}")
         ids_np = np.asarray(list(input_ids), dtype=np.int64)
-        if ids_np.min() < 0 or ids_np.max() >= cfg.vocab + 8:
+        if ids_np.min() < 0 or ids_np.max() >= self.cfg.vocab + 8:
             raise ValueError("token id out of range")
-        locs = np.nonzero(ids_np == cfg.image_token_id)[0]
+        locs = np.nonzero(ids_np == self.cfg.image_token_id)[0]
         if len(locs) > 1:
             raise ValueError("one image per prompt")
-        if (frame is None) != (len(locs) == 0):
+        if has_frame != (len(locs) == 1):
             raise ValueError("image token and image frame must come together")
-        H, Hq, Hkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
-        P, TP = cfg.tile_tokens, self.TP
-        has_image = frame is not None
-        if slot == 0:
-            self.has_image = has_image
-        nm = int(locs[0]) if has_image else 0
-        cross = None
-        if has_image:
-            # cross_states: the tower's output for this frame computed elsewhere (generate_batch stacks several requests' images)
+        return ids_np, int(locs[0]) if has_frame else 0
+
+    def prefill(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, taps: Optional[dict] = None,
+                temperature: float = 0.0, seed: int = 0, slot: int = 0,
+                cross_states: Optional[Tuple[torch.Tensor, int]] = None) -> None:
+        """One request's prompt pass into ``slot``: the tower over its image, then the text pass as a group of one.
+        cross_states: the tower's output for this frame computed elsewhere (prefill_many stacks several requests' images).
+        taps: cross_states, layer{i} of every layer that ran, first_logits (and the tower's vision_features)."""
+        self._check_prompt(input_ids, frame is not None, slot)
+        cross, n_tiles = None, 0
+        if frame is not None:
             cross, n_tiles = cross_states if cross_states is not None else self.vision_forward(frame, taps)
-            nR = n_tiles * P
-            nkeys_m1.fill_(nR - 1)
-            if taps is not None:
-                taps["cross_states"] = cross
-            xitems = [(q0, min(128, nm - q0), 0, TP) for q0 in range(0, nm, 128)] + \
-                     [(q0, min(128, S - q0), 0, nR) for q0 in range(nm, S, 128)]
-            xwork = torch.tensor(xitems, dtype=torch.int32, device=dev).reshape(-1, 4).contiguous()
-            kvbuf = torch.empty((TP, 2 * Hkv * D), dtype=bf, device=dev)
-            xvt = torch.empty((Hkv, D, self.Tk), dtype=bf, device=dev)
-            q2 = torch.empty((S, Hq * D), dtype=bf, device=dev)
-        x = torch.empty((S, H), dtype=bf, device=dev)
-        ids_dev = hip.upload(ids_np.astype(np.int32), dev)
-        hip.gather_rows(w.embed, ids_dev, x)
-        cos, sin = self.cos_t[:S], self.sin_t[:S]
-        work = hip.make_attn_pairs(0, S, dev)        # causal self-attention: paired query blocks (hip.attn_prefill_pairs)
-        ld = _round_up(S, 64)
-        nq = (Hq + 2 * Hkv) * D
-        y = torch.empty((S, H), dtype=bf, device=dev)
-        qkv = torch.empty((S, nq), dtype=bf, device=dev)
-        q = torch.empty((Hq, S, D), dtype=bf, device=dev)
-        vt = torch.empty((Hkv, D, ld), dtype=bf, device=dev)
-        att = torch.empty((S, Hq * D), dtype=bf, device=dev)
-        act = torch.empty((S, cfg.intermediate), dtype=bf, device=dev)
-        scale = D ** -0.5
-        si = ci = 0
-        # Long-K projections at a prompt's few hundred rows (o: 3 x 16 tiles of 256^2 at K = 4096; down: the same tiles at
-        # K = 14336) leave most of the chip idle as plain tiles: they run as K-slices (f32 slabs + fixed-order finalisation
-        # with the residual, vis_gemm_bf16_splitk).  The slice count is a function of the LAYER shape only, never of the row
-        # count, so a row's summation order - and slot / batch invariance - does not depend on the prompt (A/B: VIS_MLLAMA_SPLITK=0).
-        ks_down = int(os.environ.get("VIS_MLLAMA_SPLITK", "4")) if cfg.intermediate >= 8192 else 0
-        ks_o = int(os.environ.get("VIS_MLLAMA_SPLITK_O", "4")) if H >= 4096 else 0
-        ks_qkv = int(os.environ.get("VIS_MLLAMA_SPLITK_QKV", "0"))
-        swork = torch.empty(max(ks_down, ks_o, 1) * S * max(H, nq if ks_qkv else 0), dtype=torch.float32, device=dev) if (ks_down or ks_o or ks_qkv) else None
+        self._prefill_group([(slot, input_ids, cross, n_tiles)], temperature, seed, taps)
 
-        def proj(a, wt, ks):        # x += a @ wt.T
-            if ks >= 2:
-                hip.gemm_splitk(a, wt, swork, ks, residual=x, out=x)
-            else:
-                hip.gemm(a, wt, residual=x, out=x)
-
-        for li, lw in enumerate(w.layers):
-            if lw.cross:
-                if not has_image:
-                    ci += 1
-                    continue                      # text-only prompt: cross layers are skipped (TF:...:1128-1138)
-                hip.gemm(cross, lw.kv_w, out=kvbuf)
-                hip.rmsnorm_heads(kvbuf, lw.k_norm, Hkv, cfg.rms_eps)     # k_norm on the Hkv key heads of every row (one launch)
-                hip.qkv_rope_split(kvbuf, None, None, None, xk[ci], xv[ci], xvt, 0, Hkv, D, k_pos0=0)
-                hip.rmsnorm(x, lw.ln1_w, cfg.rms_eps, out=y)
-                hip.gemm(y, lw.qkv_w, out=q2)
-                hip.rmsnorm(q2.view(S * Hq, D), lw.q_norm, cfg.rms_eps, out=q2.view(S * Hq, D))
-                hip.qkv_rope_split(q2, None, None, q, None, None, None, Hq, 0, D)
-                hip.attn_prefill(q, xk[ci], xvt, att, xwork, False, scale)
-                proj(att, lw.o_w, ks_o)
-                keep = x[:nm].clone() if nm > 0 else None
-                hip.rmsnorm(x, lw.ln2_w, cfg.rms_eps, out=y)
-                hip.gemm(y, lw.gateup_w, act=hip.ACT_SWIGLU, out=act)
-                proj(act, lw.down_w, ks_down)
-                if keep is not None:              # rows before the image: MLP contribution zeroed (TF:...:697-699)
-                    x[:nm].copy_(keep)
-                ci += 1
-            else:
-                hip.rmsnorm(x, lw.ln1_w, cfg.rms_eps, out=y)
-                if ks_qkv >= 2:
-                    hip.gemm_splitk(y, lw.qkv_w, swork, ks_qkv, out=qkv)
-                else:
-                    hip.gemm(y, lw.qkv_w, out=qkv)
-                hip.qkv_rope_split(qkv, cos, sin, q, kcache[si], vcache[si], vt, Hq, Hkv, D, k_pos0=0)
-                hip.attn_prefill_pairs(q, kcache[si], vt, att, work, scale)
-                proj(att, lw.o_w, ks_o)
-                hip.rmsnorm(x, lw.ln2_w, cfg.rms_eps, out=y)
-                hip.gemm(y, lw.gateup_w, act=hip.ACT_SWIGLU, out=act)
-                proj(act, lw.down_w, ks_down)
-                si += 1
-            if taps is not None:
-                taps[f"layer{li}"] = x.clone()
-        if has_image and self.cross_kv == "fp8":
-            self._quantize_cross_kv(slot)
-        hip.gemv(x[S - 1], w.lm_head, logits, norm_w=w.norm_w, eps=cfg.rms_eps)
-        if taps is not None:
-            taps["first_logits"] = logits.clone()
-        step.fill_(S - 1)
-        self._prompt_pick(slot, ids_dev, logits, tokens, cur_token, step)
-        self.slot_prompt_len[slot] = S
-        if slot == 0:
-            self.prompt_len, self._decoded = S, 0
-            self.decode_limit = self.max_ctx
-
-    def _prefill_group(self, items: Sequence[tuple], temperature: float, seed: int) -> None:
-        """The text decoder's prompt pass of SEVERAL requests with one prompt layout (verify_many: the same Auditor prompt in
-        front of every image) over their stacked rows.  items: [(slot, ids, cross_states, n_tiles)], all prompts S tokens
-        long with the image token at the same index.  At S ~ 700 a request is 2.75 row tiles of 256: stacked, four give 11
-        (gate/up 112 x 3 = 1.3 rounds per request -> 4.8 for four).  Only the row-independent kernels see the stack
-        (projections, norms); K / V projection of the image, rope / cache write and both attentions run per request.  The
-        K order of every projection is M-independent and the K-slice counts are a function of the layer shape, so a
-        request's tokens are those of its own pass (test_batched_decode_matches_single_and_is_batch_invariant)."""
+    def _prefill_group(self, items: Sequence[tuple], temperature: float, seed: int, taps: Optional[dict] = None) -> None:
+        """The text decoder's prompt pass of k >= 1 requests with one prompt layout over their stacked rows - the engine's only
+        text pass: ``prefill`` is a group of one, verify_many (the same Auditor prompt in front of every image) one of several.
+        items: [(slot, ids, cross_states, n_tiles)], all prompts S tokens long with the image token at the same index; a group of
+        one may come without an image (cross_states None): its cross layers are skipped.  At S ~ 700 a request is 2.75 row tiles
+        of 256: stacked, four give 11 (gate/up 112 x 3 = 1.3 rounds per request -> 4.8 for four).  Only the row-independent
+        kernels see the stack (projections, norms); K / V projection of the image, rope / cache write and both attentions run per
+        request, and a group of one issues exactly one request's launches.  The K order of every projection is M-independent and
+        the K-slice counts are a function of the layer shape, so a request's tokens do not depend on its group
+        (test_batched_decode_matches_single_and_is_batch_invariant).  taps (a group of one only): see ``prefill``."""
         cfg, w, dev, bf = self.cfg, self.w, self.device, torch.bfloat16
         self.temperature, self.seed = float(temperature), int(seed)
         k = len(items)
         S = len(items[0][1])
+        has_image = items[0][2] is not None
+        if (k > 1 and not has_image) or (taps is not None and k != 1):
+            raise ValueError("_prefill_group: a prompt without an image, and taps, need a group of one")
         H, Hq, Hkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
         P, TP = cfg.tile_tokens, self.TP
-        ids0 = np.asarray(list(items[0][1]), dtype=np.int64)
-        nm = int(np.nonzero(ids0 == cfg.image_token_id)[0][0])
         M = k * S
         x = torch.empty((M, H), dtype=bf, device=dev)
-        xworks, xvts, ids_devs = [], [], []
+        nm, xworks, ids_devs = 0, [], []
         for j, (slot, ids, cross, n_tiles) in enumerate(items):
-            ids_np = np.asarray(list(ids), dtype=np.int64)
-            locs = np.nonzero(ids_np == cfg.image_token_id)[0]
-            if len(ids_np) != S or len(locs) != 1 or int(locs[0]) != nm:
+            ids_np, nm_j = self._check_prompt(ids, cross is not None, slot)
+            if j == 0:
+                nm = nm_j
+            if len(ids_np) != S or (cross is not None) != has_image or nm_j != nm:
                 raise ValueError("_prefill_group: the prompts of a group must share length and image-token position")
-            if ids_np.min() < 0 or ids_np.max() >= cfg.vocab + 8:
-                raise ValueError("token id out of range")
             ids_devs.append(hip.upload(ids_np.astype(np.int32), dev))
             hip.gather_rows(w.embed, ids_devs[j], x[j * S:(j + 1) * S])
-            nR = n_tiles * P
-            self.nkeys_b[slot:slot + 1].fill_(nR - 1)
-            xitems = [(q0, min(128, nm - q0), 0, TP) for q0 in range(0, nm, 128)] + \
-                     [(q0, min(128, S - q0), 0, nR) for q0 in range(nm, S, 128)]
-            xworks.append(xitems)
-        xvt_all = torch.empty((k, Hkv, D, self.Tk), dtype=bf, device=dev)
-        xvts = [xvt_all[j] for j in range(k)]
-        xwork_all = torch.tensor(xworks, dtype=torch.int32, device=dev).reshape(k, -1, 4).contiguous()   # same item count: same S, nm
-        xworks = [xwork_all[j] for j in range(k)]
-        kvbuf = torch.empty((TP, 2 * Hkv * D), dtype=bf, device=dev)
-        q2 = torch.empty((M, Hq * D), dtype=bf, device=dev)
+            if has_image:
+                nR = n_tiles * P
+                self.nkeys_b[slot:slot + 1].fill_(nR - 1)
+                xworks.append([(q0, min(128, nm - q0), 0, TP) for q0 in range(0, nm, 128)] +
+                              [(q0, min(128, S - q0), 0, nR) for q0 in range(nm, S, 128)])
+        if has_image:
+            if taps is not None:
+                taps["cross_states"] = items[0][2]
+            xvt_all = torch.empty((k, Hkv, D, self.Tk), dtype=bf, device=dev)
+            xwork_all = torch.tensor(xworks, dtype=torch.int32, device=dev).reshape(k, -1, 4).contiguous()   # same item count: same S, nm
+            kvbuf = torch.empty((TP, 2 * Hkv * D), dtype=bf, device=dev)
+            q2 = torch.empty((M, Hq * D), dtype=bf, device=dev)
         cos, sin = self.cos_t[:S], self.sin_t[:S]
-        work = hip.make_attn_pairs(0, S, dev)
+        work = hip.make_attn_pairs(0, S, dev)        # causal self-attention: paired query blocks (hip.attn_prefill_pairs)
         ld = _round_up(S, 64)
         nq = (Hq + 2 * Hkv) * D
         y = torch.empty((M, H), dtype=bf, device=dev)
@@ -606,6 +474,10 @@ class MllamaEngine(Generation):
         att = torch.empty((M, Hq * D), dtype=bf, device=dev)
         act = torch.empty((M, cfg.intermediate), dtype=bf, device=dev)
         scale = D ** -0.5
+        # Long-K projections at a prompt's few hundred rows (o: 3 x 16 tiles of 256^2 at K = 4096; down: the same tiles at
+        # K = 14336) leave most of the chip idle as plain tiles: they run as K-slices (f32 slabs + fixed-order finalisation
+        # with the residual, vis_gemm_bf16_splitk).  The slice count is a function of the LAYER shape only, never of the row
+        # count, so a row's summation order - and slot / batch invariance - does not depend on the prompt (A/B: VIS_MLLAMA_SPLITK=0).
         ks_down = int(os.environ.get("VIS_MLLAMA_SPLITK", "4")) if cfg.intermediate >= 8192 else 0
         ks_o = int(os.environ.get("VIS_MLLAMA_SPLITK_O", "4")) if H >= 4096 else 0
         ks_qkv = int(os.environ.get("VIS_MLLAMA_SPLITK_QKV", "0"))
@@ -621,12 +493,15 @@ class MllamaEngine(Generation):
         Tc = self.kcache_b.shape[3]
         many = os.environ.get("VIS_GROUP_ATTN", "1") == "1" and 1 < k <= hip.MAX_GROUP_REQUESTS and self.kcache_b.is_contiguous()
         si = ci = 0
-        for lw in w.layers:
+        for li, lw in enumerate(w.layers):
             if lw.cross:
+                if not has_image:
+                    ci += 1
+                    continue                      # text-only prompt: cross layers are skipped (TF:...:1128-1138)
                 for j, (slot, _, cross, _) in enumerate(items):
                     hip.gemm(cross, lw.kv_w, out=kvbuf)
-                    hip.rmsnorm_heads(kvbuf, lw.k_norm, Hkv, cfg.rms_eps)
-                    hip.qkv_rope_split(kvbuf, None, None, None, self.xk_b[slot][ci], self.xv_b[slot][ci], xvts[j], 0, Hkv, D,
+                    hip.rmsnorm_heads(kvbuf, lw.k_norm, Hkv, cfg.rms_eps)     # k_norm on the Hkv key heads of every row (one launch)
+                    hip.qkv_rope_split(kvbuf, None, None, None, self.xk_b[slot][ci], self.xv_b[slot][ci], xvt_all[j], 0, Hkv, D,
                                        k_pos0=0)
                 hip.rmsnorm(x, lw.ln1_w, cfg.rms_eps, out=y)
                 hip.gemm(y, lw.qkv_w, out=q2)
@@ -640,7 +515,7 @@ class MllamaEngine(Generation):
                     for j, (slot, _, _, _) in enumerate(items):
                         rows = slice(j * S, (j + 1) * S)
                         hip.qkv_rope_split(q2[rows], None, None, q[j], None, None, None, Hq, 0, D)
-                        hip.attn_prefill(q[j], self.xk_b[slot][ci], xvts[j], att[rows], xworks[j], False, scale)
+                        hip.attn_prefill(q[j], self.xk_b[slot][ci], xvt_all[j], att[rows], xwork_all[j], False, scale)
                 proj(att, lw.o_w, ks_o)
                 keep = [x[j * S:j * S + nm].clone() for j in range(k)] if nm > 0 else None
                 hip.rmsnorm(x, lw.ln2_w, cfg.rms_eps, out=y)
@@ -671,7 +546,9 @@ class MllamaEngine(Generation):
                 hip.gemm(y, lw.gateup_w, act=hip.ACT_SWIGLU, out=act)
                 proj(act, lw.down_w, ks_down)
                 si += 1
-        if self.cross_kv == "fp8":
+            if taps is not None:
+                taps[f"layer{li}"] = x.clone()
+        if has_image and self.cross_kv == "fp8":
             for slot, _, _, _ in items:
                 self._quantize_cross_kv(slot)
         grouped = many and k <= 4 and H * 2 * (2 if k <= 2 else 4) <= 152 * 1024   # one pass over the lm_head for the group's last rows
@@ -684,11 +561,13 @@ class MllamaEngine(Generation):
                 logits.copy_(lg[j])
             else:
                 hip.gemv(x[(j + 1) * S - 1], w.lm_head, logits, norm_w=w.norm_w, eps=cfg.rms_eps)
+            if taps is not None:
+                taps["first_logits"] = logits.clone()
             self.step_b[slot:slot + 1].fill_(S - 1)
             self._prompt_pick(slot, ids_devs[j], logits, self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1])
             self.slot_prompt_len[slot] = S
             if slot == 0:
-                self.has_image = True
+                self.has_image = has_image
                 self.prompt_len, self._decoded = S, 0
                 self.decode_limit = self.max_ctx
 
@@ -817,6 +696,12 @@ class MllamaEngine(Generation):
         if n_streams > 1 and len(getattr(self, "_prefill_streams", [])) < n_streams:
             self._prefill_streams = [torch.cuda.Stream(device=self.device) for _ in range(n_streams)]
         vb = max(1, int(os.environ.get("VIS_VIT_BATCH", "4"))) if n_streams > 1 else 1
+
+        def place(slot, b):      # request b's switch rows into its slot, before its prompt pass picks the first token
+            for name, rows in (("_slot_seed", seeds), ("_slot_pen", penalties), ("_slot_shape", shaping), ("_slot_ban", ban)):
+                if rows is not None:
+                    getattr(self, name)[slot] = rows[b]
+
         for g0 in range(0, n_req, vb):
             grp = []                                     # (request index, ids, frame) of the requests that resolved
             for b in range(g0, min(n_req, g0 + vb)):
@@ -854,14 +739,7 @@ class MllamaEngine(Generation):
                         items = []
                         for (b, ids, fr), cs in zip(grp, crosses):
                             cs[0].record_stream(st)
-                            if seeds is not None:
-                                self._slot_seed[B + len(items)] = seeds[b]
-                            if penalties is not None:
-                                self._slot_pen[B + len(items)] = penalties[b]
-                            if shaping is not None:
-                                self._slot_shape[B + len(items)] = shaping[b]
-                            if ban is not None:
-                                self._slot_ban[B + len(items)] = ban[b]
+                            place(B + len(items), b)
                             items.append((B + len(items), ids, cs[0], cs[1]))
                         self._prefill_group(items, temperature, seed)
                     for (b, _, _) in grp:
@@ -874,14 +752,7 @@ class MllamaEngine(Generation):
                         errors[b] = e
                 continue
             for (b, ids, fr), cs in zip(grp, crosses):
-                if seeds is not None:
-                    self._slot_seed[B] = seeds[b]
-                if penalties is not None:
-                    self._slot_pen[B] = penalties[b]
-                if shaping is not None:
-                    self._slot_shape[B] = shaping[b]
-                if ban is not None:
-                    self._slot_ban[B] = ban[b]
+                place(B, b)
                 try:
                     if n_streams > 1:
                         st = self._prefill_streams[B % n_streams]
