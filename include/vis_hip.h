@@ -671,6 +671,22 @@ int vis_spec_draft(const void* prompt_ids, int ld_prompt, const void* prompt_len
                    const void* gen_start, const void* step_ptr, int k, int lookup_max, int lookup_min, int vocab,
                    void* draft, void* n_draft, vis_stream_t stream);
 
+/* vis_spec_draft_pred: the drafter of a request that came with a prediction (OpenAI's Predicted Outputs): exactly one
+ * spec.propose_pred() call on device memory.  The arguments of vis_spec_draft, plus pred_ids [ld_pred] with *pred_len of
+ * them valid (clamped to 0..ld_pred) and state, 7 ints (spec.PredState): cursor (index into pred_ids of the id expected
+ * next, -1 = lost), last (the cursor before it was lost), seen (reply tokens consumed), src / n_out (source - 0 none,
+ * 1 prompt lookup, 2 prediction - and count of the drafts of the previous call), accepted, rejected.  The reply is
+ * tokens[*gen_start .. *step_ptr).  The new reply tokens settle the previous drafts (accepted += min(new - 1, n_out),
+ * rejected += the rest, prediction-sourced drafts only) and move the cursor; a lost cursor is looked for again: for m =
+ * lookup_max down to lookup_min, e in [m, *pred_len) with pred_ids[e-m .. e) == the reply's last m ids, the smallest
+ * e >= last, else the largest e < last.  Draft: pred_ids[cursor .. cursor + min(k, *pred_len - cursor)) while the cursor
+ * stands inside the prediction, else vis_spec_draft's lookup over prompt + reply.  Ids clamped into [0, vocab).  One
+ * workgroup, one launch, no host round trip: a captured step serves any prediction up to ld_pred ids. */
+int vis_spec_draft_pred(const void* prompt_ids, int ld_prompt, const void* prompt_len, const void* tokens, int max_tokens,
+                        const void* gen_start, const void* step_ptr, int k, int lookup_max, int lookup_min, int vocab,
+                        const void* pred_ids, int ld_pred, const void* pred_len, void* state, void* draft, void* n_draft,
+                        vis_stream_t stream);
+
 /* ---- Row f2: Llama-3.2-11B-Vision ("mllama") Auditor, reference src/agents/vlm_auditor.py:81-83,:152-158 ---- */
 
 /* Resized RGB frame -> patch rows of the tile canvas (zero padding applied to RAW pixels, then rescale/normalise;

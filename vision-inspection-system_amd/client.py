@@ -219,14 +219,24 @@ class _Completions:
                stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                logit_bias: Optional[dict] = None, n: Optional[int] = None, stream: Optional[bool] = None,
                stream_options: Optional[dict] = None, no_repeat_ngram_size: Optional[int] = None,
-               bad_words: Optional[list] = None, min_tokens: Optional[int] = None, speculative=None, **kwargs):
+               bad_words: Optional[list] = None, min_tokens: Optional[int] = None, speculative=None,
+               prediction: Optional[dict] = None, **kwargs):
         """``stream=True``: an iterator of ChatCompletionChunk instead of a ChatCompletion (``stream_options``: OpenAI's
         {"include_usage": True}); None or False: the call of before.
         ``speculative`` (extension; vLLM's names): {"method": "ngram", "num_speculative_tokens": k in 1..3[,
         "prompt_lookup_max": 4, "prompt_lookup_min": 2]} - lossless n-gram speculative decoding (spec.py): the same text
         and usage in fewer weight passes where the reply repeats earlier text.  A greedy single request of a Qwen2-VL model
         only: ValueError with a temperature, a seed, ``n`` > 1 or any other sampling / constraint / stop / stream / logprobs
-        keyword.  None: the call of before."""
+        keyword.  None: the call of before.
+        ``prediction`` (OpenAI's Predicted Outputs): {"type": "content", "content": text} - or content as a list of {"type":
+        "text", "text": ...} parts - text the reply will probably repeat: the previous reply of a retry, the report of an
+        earlier inspection of the same part, a fixed template.  The speculative step drafts from it (vis_spec_draft_pred) and
+        from prompt lookup where the reply leaves it; the text and finish_reason are those of the call without it, and
+        ``usage["completion_tokens_details"]`` = {"accepted_prediction_tokens", "rejected_prediction_tokens"} counts the
+        prediction's drafts the steps kept and did not keep (over every step issued: those of a poll interval that ran past
+        an EOS included).  Alone it implies speculative = {"method": "ngram", "num_speculative_tokens": 3,
+        "prompt_lookup_max": 4, "prompt_lookup_min": 2}; ``speculative`` next to it sets k and the window.  The conditions
+        and refusals of ``speculative``; an empty text is no prediction.  None: the call of before."""
         from .stream import check_stream, check_stream_options
         if check_stream(stream):
             if logprobs:
@@ -243,6 +253,8 @@ class _Completions:
         kwargs.update({name: v for name, v in given.items() if v is not None})
         if speculative is not None:
             kwargs["speculative"] = speculative
+        if prediction is not None:
+            kwargs["prediction"] = prediction
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
                                      top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
                                      **kwargs)
@@ -464,12 +476,15 @@ def logprobs_k(logprobs, top_logprobs) -> Optional[int]:
     return int(top_logprobs or 0)
 
 
-def check_speculative_request(speculative, temperature=None, seed=None, **switches):
-    """``speculative`` of one ``create`` call, checked without a model: spec.check_speculative's record, or ValueError when
-    the dict is malformed or the request carries something a speculative step cannot (spec.check_exclusive names it)."""
+def check_speculative_request(speculative, temperature=None, seed=None, *, prediction=None, **switches):
+    """``speculative`` and ``prediction`` of one ``create`` call, checked without a model: spec.check_speculative's record
+    (what a prediction alone implies: spec.PRED_DEFAULT; None when neither is on), or ValueError when a dict is malformed or
+    the request carries something a speculative step cannot (spec.check_exclusive names it)."""
     from . import spec
-    sp = spec.check_speculative(speculative)
-    spec.check_exclusive(sp, float(temperature) if temperature else 0.0, seed, **switches)
+    text = spec.check_prediction(prediction)
+    sp = spec.with_prediction(speculative, text is not None)
+    spec.check_exclusive(sp, float(temperature) if temperature else 0.0, seed,
+                         what="speculative" if text is None else "prediction (speculative decoding)", **switches)
     return sp
 
 
@@ -559,8 +574,11 @@ def _completion(model_id: str, tok, n_ids: int, toks, rec, fin, timing: dict, ne
                        logprobs=_choice_logprobs(tok, t, r) if r is not None else None)
                for i, (t, r, f) in enumerate(zip(toks, rec, fin))]
     done = sum(len(t) for t in toks)
-    return ChatCompletion(choices, model=model_id,
-                          usage={"prompt_tokens": n_ids, "completion_tokens": done, "total_tokens": n_ids + done}, timings=timing)
+    usage = {"prompt_tokens": n_ids, "completion_tokens": done, "total_tokens": n_ids + done}
+    if "pred_accepted" in timing:      # the request came with a prediction (OpenAI's Predicted Outputs)
+        usage["completion_tokens_details"] = {"accepted_prediction_tokens": timing["pred_accepted"],
+                                              "rejected_prediction_tokens": timing["pred_rejected"]}
+    return ChatCompletion(choices, model=model_id, usage=usage, timings=timing)
 
 
 def _choice_logprobs(tok, toks: List[int], rec) -> ChoiceLogprobs:
@@ -672,17 +690,20 @@ class LocalVLMClient:
     def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
                   top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
                   stop=None, top_k=None, min_p=None, logit_bias=None, n=None, stream=None, stream_options=None,
-                  no_repeat_ngram_size=None, bad_words=None, min_tokens=None, speculative=None, **kwargs):
-        if speculative is not None:
+                  no_repeat_ngram_size=None, bad_words=None, min_tokens=None, speculative=None, prediction=None, **kwargs):
+        from .spec import check_prediction
+        text = check_prediction(prediction)
+        if speculative is not None or text is not None:
             sp = check_speculative_request(
-                speculative, temperature, seed, logprobs=logprobs, top_logprobs=top_logprobs, response_format=response_format,
+                speculative, temperature, seed, prediction=prediction, logprobs=logprobs, top_logprobs=top_logprobs, response_format=response_format,
                 top_p=top_p, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
                 repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n,
                 stream=stream, no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
             if is_mllama_model(model or self.default_model):
-                raise ValueError("speculative decoding is offered for Qwen2-VL / Qwen2.5-VL models only: the Mllama engine's "
-                                 "cross-attention rows have no multi-row form")
-            return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp)[0]
+                raise ValueError(("speculative decoding is" if text is None else "prediction (speculative decoding) is") +
+                                 " offered for Qwen2-VL / Qwen2.5-VL models only: the Mllama engine's cross-attention rows "
+                                 "have no multi-row form")
+            return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp, prediction=text)[0]
         out = self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
                                  response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
                                  presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop,
@@ -698,7 +719,7 @@ class LocalVLMClient:
                       min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
                       n: Optional[int] = None, stream: Optional[bool] = None, stream_options: Optional[dict] = None,
                       no_repeat_ngram_size: Optional[int] = None, bad_words: Optional[list] = None,
-                      min_tokens: Optional[int] = None):
+                      min_tokens: Optional[int] = None, prediction=None):
         """As ``_complete_many`` (the keywords are described there), plus ``stream`` (OpenAI's): True returns ONE
         ChatCompletionStream over the chunks of all requests instead of the list - each chunk carries its request's index
         as ``request_index`` - while the engine call runs on a worker thread.  Every token is published from the GPU into
@@ -709,8 +730,11 @@ class LocalVLMClient:
         ``finish_reason``; ``stream_options={"include_usage": True}`` adds a chunk with ``choices=[]`` and the ``usage``
         per request.  Not together with ``logprobs``.  With VIS_SYNTHETIC_REPLY the substituted text comes as one content
         chunk after the generation.  Closing or dropping the iterator cancels the call at the loop's next poll; an exception
-        of a request is raised from ``next()``.  None or False: the list, as before."""
+        of a request is raised from ``next()``.  None or False: the list, as before.
+        ``prediction`` other than None is refused (ValueError): it belongs to the one request of ``create``."""
+        from .spec import refuse_batch_prediction
         from .stream import StreamReader, check_stream, check_stream_options
+        refuse_batch_prediction(prediction)
         kw = dict(logprobs=logprobs, top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
                   frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
                   repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n,
@@ -759,7 +783,7 @@ class LocalVLMClient:
                        min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
                        n: Optional[int] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
                        bad_words: Optional[list] = None, min_tokens: Optional[int] = None,
-                       speculative=None) -> List[ChatCompletion]:
+                       speculative=None, prediction: Optional[str] = None) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -809,7 +833,10 @@ class LocalVLMClient:
         = off.  Not together with a ``response_format`` of json_object or json_schema: ValueError.  Checked before any GPU
         work.  Logprobs keep their meaning.
         ``speculative`` (a spec.SpecConfig, from ``create`` only - ``complete_many`` does not offer it): the ONE request of the
-        call goes through the engine's ``generate(.., speculative=)``; every other keyword is off then (create checks)."""
+        call goes through the engine's ``generate(.., speculative=)``; every other keyword is off then (create checks).
+        ``prediction`` (the text of create's ``prediction``, next to ``speculative``): tokenised without special tokens, at
+        most the engine's max_ctx ids, handed to ``generate(.., prediction=)``; the completion's usage then carries
+        ``completion_tokens_details``."""
         from .penalties import check_penalties
         from .sampling import check_seed, check_top_p
         from .shaping import check_shaping, shaping_kwargs
@@ -854,7 +881,8 @@ class LocalVLMClient:
                     on_stream.requests = list(idx)      # which requests of the call this engine call serves
                 if speculative is not None:      # one greedy request, no other switch: the single-sequence loop, speculating
                     ids, frames = request_of(idx[0])()
-                    outs = [eng.generate(ids, frames, speculative=speculative, **gen)]
+                    pred = {} if not prediction else {"prediction": tok.encode(prediction)[:eng.max_ctx]}
+                    outs = [eng.generate(ids, frames, speculative=speculative, **pred, **gen)]
                 else:
                     outs = eng.generate_batch([request_of(j) for j in idx], seed=self.seed, **gen,
                                               **({"seeds": [seed] * len(idx)} if seed is not None else {}))
@@ -1013,11 +1041,13 @@ class CannedResponseClient:
     def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
                   frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None, top_k=None, min_p=None,
                   logit_bias=None, n=None, stream=None, stream_options=None, no_repeat_ngram_size=None, bad_words=None,
-                  min_tokens=None, speculative=None, **kwargs):
+                  min_tokens=None, speculative=None, prediction=None, **kwargs):
         check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
-        if speculative is not None:
+        if speculative is not None or prediction is not None:
+            if prediction is not None and is_mllama_model(model):
+                raise ValueError("prediction (speculative decoding) is offered for Qwen2-VL / Qwen2.5-VL models only")
             check_speculative_request(
-                speculative, temperature, seed, response_format=response_format, top_p=top_p,
+                speculative, temperature, seed, prediction=prediction, response_format=response_format, top_p=top_p,
                 frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, repetition_penalty=repetition_penalty,
                 stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n, stream=stream,
                 no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens, **kwargs)
@@ -1026,7 +1056,7 @@ class CannedResponseClient:
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
                  "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
                  "logit_bias": logit_bias, "n": n, "no_repeat_ngram_size": no_repeat_ngram_size, "bad_words": bad_words,
-                 "min_tokens": min_tokens, "speculative": speculative}
+                 "min_tokens": min_tokens, "speculative": speculative, "prediction": prediction}
         self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
         reply = self.reply(messages) if callable(self.reply) else self.reply
         done = ChatCompletion([_Choice(_Message(reply), index=i) for i in range(check_n(n, 64) or 1)], model=model or "")

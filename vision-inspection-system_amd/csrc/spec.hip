@@ -1,7 +1,7 @@
 // Lossless n-gram speculative decoding of ONE greedy sequence (spec.py, DecodeStage._decode_step_spec): a step runs R = 1 + k
 // rows - the current token and up to k drafted ones - through every projection in one pass over the weights
 // (vis_gemv_*_rows, each row bit-identical to the single-row kernel), and keeps the longest prefix of the drafts the model
-// itself would have picked.  The three pieces that did not exist:
+// itself would have picked.  The pieces that did not exist:
 //
 //  * vis_decode_attn_draft: vis_decode_attn for the R rows of one sequence.  Row r sits at position *step_ptr + r: it takes
 //    that rope row, its K / V go to that cache row, it attends over keys [0, *step_ptr + r].  Three launches behind the one
@@ -16,6 +16,9 @@
 //    and the bookkeeping of a step that produced a + 1 tokens.
 //  * vis_spec_draft: prompt lookup - the latest earlier occurrence of the last m ids of the history (m from lookup_max down
 //    to lookup_min) and the ids that followed it.  spec.propose() is its definition.
+//  * vis_spec_draft_pred: the drafter of a request with a prediction (spec.propose_pred() is its definition): a cursor into
+//    the caller's predicted reply, found again from the reply's tail after a deviation, with the prompt lookup above as
+//    its fallback.
 //
 // Every index that comes from device memory (*step_ptr, the draft count, the limit, lengths, token ids) is clamped before it
 // forms an address.
@@ -186,18 +189,11 @@ extern "C" int vis_spec_accept(const void* logits, int V, int ld_logits, int row
 // lookup_max down to lookup_min with L > m: the largest j < L - m with h[j .. j + m) == h[L - m .. L); the first m that has
 // one wins: draft = h[j + m .. min(j + m + k, L)), *n_draft its length.  No match: *n_draft = 0 and draft is left alone.
 // One workgroup: 256 lanes take the candidate starts j in strides, the largest matching j is reduced through LDS.
-__global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__ prompt, int ld_prompt, const int* __restrict__ plen,
-                                                         const int* __restrict__ tokens, int max_tokens,
-                                                         const int* __restrict__ gen0, const int* __restrict__ step_ptr, int k,
-                                                         int lookup_max, int lookup_min, int vocab, int* __restrict__ draft,
-                                                         int* __restrict__ n_draft) {
-  __shared__ int wbest[4];
+// The lookup itself, shared with vis_spec_draft_pred (its fallback): returns d (uniform) and writes draft[0 .. d); d = 0 leaves
+// draft alone.  ``wbest``: four ints of LDS.  Every lane of the workgroup calls it.
+__device__ __forceinline__ int sp_prompt_lookup(const int* __restrict__ prompt, int P, const int* __restrict__ gn, int L, int k,
+                                                int lookup_max, int lookup_min, int vocab, int* __restrict__ draft, int* wbest) {
   const int tid = threadIdx.x;
-  const int P = min(max(*plen, 0), ld_prompt);
-  const int end = min(max(*step_ptr, 0), max_tokens);
-  const int s0 = min(max(*gen0, 0), end);
-  const int L = P + (end - s0);
-  const int* __restrict__ gn = tokens + s0;
 #define SP_H(i) ((i) < P ? prompt[(i)] : gn[(i) - P])
   for (int m = lookup_max; m >= lookup_min; --m) {
     if (L <= m) continue;     // (uniform) no room for the pattern and one id after an earlier copy of it
@@ -221,12 +217,24 @@ __global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__
     if (best >= 0) {            // uniform
       const int from = best + m, d = min(k, L - from);
       if (tid < d) draft[tid] = min(max(SP_H(from + tid), 0), vocab - 1);
-      if (tid == 0) *n_draft = d;
-      return;
+      return d;
     }
   }
 #undef SP_H
-  if (tid == 0) *n_draft = 0;
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void spec_draft_kernel(const int* __restrict__ prompt, int ld_prompt, const int* __restrict__ plen,
+                                                         const int* __restrict__ tokens, int max_tokens,
+                                                         const int* __restrict__ gen0, const int* __restrict__ step_ptr, int k,
+                                                         int lookup_max, int lookup_min, int vocab, int* __restrict__ draft,
+                                                         int* __restrict__ n_draft) {
+  __shared__ int wbest[4];
+  const int P = min(max(*plen, 0), ld_prompt);
+  const int end = min(max(*step_ptr, 0), max_tokens);
+  const int s0 = min(max(*gen0, 0), end);
+  const int d = sp_prompt_lookup(prompt, P, tokens + s0, P + (end - s0), k, lookup_max, lookup_min, vocab, draft, wbest);
+  if (threadIdx.x == 0) *n_draft = d;
 }
 
 extern "C" int vis_spec_draft(const void* prompt_ids, int ld_prompt, const void* prompt_len, const void* tokens, int max_tokens,
@@ -242,5 +250,125 @@ extern "C" int vis_spec_draft(const void* prompt_ids, int ld_prompt, const void*
   hipLaunchKernelGGL(spec_draft_kernel, dim3(1), dim3(256), 0, stream, (const int*)prompt_ids, ld_prompt, (const int*)prompt_len,
                      (const int*)tokens, max_tokens, (const int*)gen_start, (const int*)step_ptr, k, lookup_max, lookup_min,
                      vocab, (int*)draft, (int*)n_draft);
+  return vis_check_launch();
+}
+
+// -------------------------------------------------------------------------------------------------- vis_spec_draft_pred
+// One spec.propose_pred() call on device memory: the drafter of a request that came with a prediction (OpenAI's Predicted
+// Outputs).  A cursor walks the prediction while the reply follows it; a reply token that differs loses the cursor, and the
+// last lookup_max .. lookup_min ids of the reply find it again - forward of where it was lost first, else the nearest place
+// behind.  While the cursor is lost or past the prediction's end the draft is vis_spec_draft's prompt lookup.
+// state: cursor, last, seen, src, n_out, accepted, rejected (spec.PredState).  One workgroup, one pass over the prediction:
+// every lane keeps, per match length, the smallest candidate >= last and the largest one < last of its stride; the
+// longest match length is reduced first (a maximum), then that length's two candidates (a minimum and a maximum), so the
+// result does not depend on which lane saw what.
+#define SP_ST_INTS 7
+
+__device__ __forceinline__ int sp_block_max(int v, int* lds) {      // lds: four ints nobody else uses
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return max(max(lds[0], lds[1]), max(lds[2], lds[3]));
+}
+
+__global__ __launch_bounds__(256) void spec_draft_pred_kernel(const int* __restrict__ prompt, int ld_prompt,
+                                                              const int* __restrict__ plen, const int* __restrict__ tokens,
+                                                              int max_tokens, const int* __restrict__ gen0,
+                                                              const int* __restrict__ step_ptr, int k, int lookup_max,
+                                                              int lookup_min, int vocab, const int* __restrict__ pred, int ld_pred,
+                                                              const int* __restrict__ pred_len, int* __restrict__ state,
+                                                              int* __restrict__ draft, int* __restrict__ n_draft) {
+  __shared__ int wbest[4], rmax[4], rfwd[4], rbwd[4];
+  const int tid = threadIdx.x;
+  const int PL = min(max(*plen, 0), ld_prompt);
+  const int end = min(max(*step_ptr, 0), max_tokens);
+  const int s0 = min(max(*gen0, 0), end);
+  const int Lr = end - s0;                  // the reply so far, the newest pick included
+  const int* __restrict__ gn = tokens + s0;
+  const int P = min(max(*pred_len, 0), ld_pred);
+  int cursor = state[0], last = state[1];
+  const int seen = min(max(state[2], 0), Lr), src = state[3], n_out = max(state[4], 0);
+  int acc = state[5], rej = state[6];
+  __syncthreads();                          // every lane holds the state before lane 0 replaces it
+  // 1. what the accept step kept of the drafts of the previous call (a step behind the limit brought nothing: no count)
+  if (Lr > seen && src == 2) {
+    const int a = min(Lr - seen - 1, n_out);
+    acc += a;
+    rej += n_out - a;
+  }
+  // 2. the cursor follows the new tokens (every lane, the same few compares)
+  for (int i = seen; i < Lr && cursor >= 0; ++i) {
+    if (cursor < P && pred[cursor] == gn[i]) ++cursor;
+    else { last = cursor; cursor = -1; }
+  }
+  // 3. lost: the longest tail of the reply that stands in the prediction with an id behind it
+  if (cursor < 0 && P > 0) {                // uniform
+    const int mtop = min(lookup_max, Lr);
+    int tail[SP_MAXLOOKUP], fmin[SP_MAXLOOKUP], bmax[SP_MAXLOOKUP];
+#pragma unroll
+    for (int i = 0; i < SP_MAXLOOKUP; ++i) {
+      tail[i] = (i < mtop) ? gn[Lr - 1 - i] : 0;      // backwards: tail[0] is the newest id
+      fmin[i] = 0x7fffffff;
+      bmax[i] = -1;
+    }
+    int mine = 0;
+    for (int e = 1 + tid; e < P; e += 256) {           // candidate: pred[e] would be drafted next
+      const int cap = min(mtop, e);
+      int ml = 0;
+#pragma unroll
+      for (int i = 0; i < SP_MAXLOOKUP; ++i)
+        if (i == ml && i < cap && pred[e - 1 - i] == tail[i]) ml = i + 1;
+      mine = max(mine, ml);
+#pragma unroll
+      for (int i = 0; i < SP_MAXLOOKUP; ++i)
+        if (i < ml) {
+          if (e >= last) fmin[i] = min(fmin[i], e);
+          else bmax[i] = max(bmax[i], e);
+        }
+    }
+    const int M = sp_block_max(mine, rmax);            // uniform: the first m of the definition that has a candidate
+    if (M >= lookup_min) {
+      int f = 0x7fffffff, b = -1;
+#pragma unroll
+      for (int i = 0; i < SP_MAXLOOKUP; ++i)
+        if (i == M - 1) { f = fmin[i]; b = bmax[i]; }
+      f = -sp_block_max(-f, rfwd);                     // the minimum (f >= 1, so -f has no overflow)
+      b = sp_block_max(b, rbwd);
+      cursor = (f != 0x7fffffff) ? f : b;
+    }
+  }
+  // 4. the draft
+  int d, nsrc;
+  if (cursor >= 0 && cursor < P) {
+    d = min(k, P - cursor);
+    if (tid < d) draft[tid] = min(max(pred[cursor + tid], 0), vocab - 1);
+    nsrc = 2;
+  } else {
+    d = sp_prompt_lookup(prompt, PL, gn, PL + Lr, k, lookup_max, lookup_min, vocab, draft, wbest);
+    nsrc = d > 0 ? 1 : 0;
+  }
+  if (tid == 0) {
+    *n_draft = d;
+    state[0] = cursor; state[1] = last; state[2] = Lr; state[3] = nsrc; state[4] = d; state[5] = acc; state[6] = rej;
+  }
+}
+
+extern "C" int vis_spec_draft_pred(const void* prompt_ids, int ld_prompt, const void* prompt_len, const void* tokens,
+                                   int max_tokens, const void* gen_start, const void* step_ptr, int k, int lookup_max,
+                                   int lookup_min, int vocab, const void* pred_ids, int ld_pred, const void* pred_len, void* state,
+                                   void* draft, void* n_draft, hipStream_t stream) {
+  if (!prompt_ids || !prompt_len || !tokens || !gen_start || !step_ptr || !pred_ids || !pred_len || !state || !draft || !n_draft)
+    return VIS_ERR_ARG;
+  if (ld_prompt <= 0 || ld_pred <= 0 || max_tokens <= 0 || vocab <= 0 || k < 1 || k > SP_MAXROWS - 1) return VIS_ERR_ARG;
+  if (lookup_max < 1 || lookup_max > SP_MAXLOOKUP || lookup_min < 1 || lookup_min > lookup_max) return VIS_ERR_ARG;
+  if (((uintptr_t)prompt_ids | (uintptr_t)prompt_len | (uintptr_t)tokens | (uintptr_t)gen_start | (uintptr_t)step_ptr |
+       (uintptr_t)pred_ids | (uintptr_t)pred_len | (uintptr_t)state | (uintptr_t)draft | (uintptr_t)n_draft) & 3)
+    return VIS_ERR_ARG;
+  vis_clear_error();
+  hipLaunchKernelGGL(spec_draft_pred_kernel, dim3(1), dim3(256), 0, stream, (const int*)prompt_ids, ld_prompt,
+                     (const int*)prompt_len, (const int*)tokens, max_tokens, (const int*)gen_start, (const int*)step_ptr, k,
+                     lookup_max, lookup_min, vocab, (const int*)pred_ids, ld_pred, (const int*)pred_len, (int*)state, (int*)draft,
+                     (int*)n_draft);
   return vis_check_launch();
 }

@@ -80,6 +80,7 @@ class DecodeStage(PickStage):
         # speculative decoding of the single sequence (generate(.., speculative=)): buffers and graphs on first use
         self._spec: Optional[spec.SpecBuffers] = None
         self._spec_cfg: Optional[spec.SpecConfig] = None
+        self._spec_pred = False      # the request in flight came with a prediction: its steps end with vis_spec_draft_pred
         self._spec_graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
 
     def _attn_share(self, B: int, shared: int) -> dict:
@@ -256,25 +257,38 @@ class DecodeStage(PickStage):
         self._stream_after_pick(B or 1)
 
     # ---- speculative decode of the single sequence (spec.py): 1..R tokens per weight pass
-    def _spec_begin(self, cfg: "spec.SpecConfig", max_new_tokens: int) -> "spec.SpecBuffers":
+    def _spec_begin(self, cfg: "spec.SpecConfig", max_new_tokens: int,
+                    prediction: Optional[Sequence[int]] = None) -> "spec.SpecBuffers":
         """Behind the prompt pass of a speculative request (its rope rows prepared for max_new_tokens + R - 1 further
         positions): the step's buffers take over the first token and the prompt's ids; ``limit`` is the index of the token
-        row the reply's last token goes to, so the reply has exactly max_new_tokens tokens however a step's run ends."""
+        row the reply's last token goes to, so the reply has exactly max_new_tokens tokens however a step's run ends.
+        ``prediction`` (ids): uploaded, and the prediction drafter is issued once behind the prompt pass's pick, so the
+        first step already carries drafts; every step of the request then ends with that drafter."""
         if self.dec_n_self != len(self.dec_layers):
             raise ValueError("speculative decoding is not supported on a model with cross-attention layers")
         spec.check_rows_fit(self.cfg, cfg.rows)
         if self._spec is None:
             self._spec = spec.SpecBuffers(self.cfg, self.nsplit, self.max_ctx, self.device)
         self._spec_cfg = cfg
+        self._spec_pred = bool(prediction)
         start = self.prompt_len - 1
-        self._spec.begin(self.cur_token, self._slot_ids[0], start, min(start + max_new_tokens - 1, self.max_ctx - 2))
+        self._spec.begin(self.cur_token, self._slot_ids[0], start, min(start + max_new_tokens - 1, self.max_ctx - 2),
+                         prediction)
+        if self._spec_pred:
+            self._spec_draft_pred(cfg.k)
         return self._spec
+
+    def _spec_draft_pred(self, k: int) -> None:
+        sp, c = self._spec, self._spec_cfg
+        hip.spec_draft_pred(sp.prompt, sp.prompt_len, self.tokens, sp.gen_start, self.step, k, c.lookup_max, c.lookup_min,
+                            self.cfg.vocab, sp.pred, sp.pred_len, sp.pred_state, sp.draft, sp.n_draft)
 
     def _decode_step_spec(self, R: int, propose: bool = True) -> None:
         """One speculative step of the single sequence: rows [cur, draft 0 .. draft R-2] at positions step .. step + R - 1
         through the multi-row GEMVs (one pass over the weights, every row the single-row kernel's bits), the draft
         attention (row r = the plain launch at step + r, bit for bit), the lm_head into [R, V] f32, then vis_spec_accept -
-        which keeps the drafts the picks confirm and advances ``step`` by 1..R - and vis_spec_draft for the next step.
+        which keeps the drafts the picks confirm and advances ``step`` by 1..R - and vis_spec_draft for the next step
+        (vis_spec_draft_pred instead when the request came with a prediction).
         Never the chained launch: the chain is bit-identical to the four launches, so the tokens are the chained step's.
         ``propose`` False leaves the draft row and its count alone (a test plants them)."""
         cfg, fmt, sp = self.cfg, self.decode_weights, self._spec
@@ -294,16 +308,19 @@ class DecodeStage(PickStage):
         gemv_rows(x, *self.dec_head[fmt], logits, norm_w=self.dec_norm_w, eps=eps)
         hip.spec_accept(logits, sp.draft, sp.n_draft, sp.limit, sp.ws_val, sp.ws_idx, self.tokens, sp.cur, self.step,
                         sp.counters)
-        if propose and R > 1:
+        if propose and R > 1 and self._spec_pred:
+            self._spec_draft_pred(R - 1)
+        elif propose and R > 1:
             c = self._spec_cfg
             hip.spec_draft(sp.prompt, sp.prompt_len, self.tokens, sp.gen_start, self.step, R - 1, c.lookup_max, c.lookup_min,
                            cfg.vocab, sp.draft, sp.n_draft)
 
     def _spec_graph(self, R: int) -> torch.cuda.CUDAGraph:
-        """The captured speculative step, keyed by (R, weight format, the lookup window): its launches read everything else
-        from device memory.  The warm-up step advances the request's counters; they are put back before the capture."""
+        """The captured speculative step, keyed by (R, weight format, the lookup window, and "pred" when the step ends with
+        the prediction drafter): its launches read everything else - the prediction, its length, the drafter's state - from
+        device memory.  The warm-up step advances the request's counters; they are put back before the capture."""
         c = self._spec_cfg
-        key = ("spec", R, self.decode_weights, c.lookup_max, c.lookup_min)
+        key = ("spec", R, self.decode_weights, c.lookup_max, c.lookup_min) + (("pred",) if self._spec_pred else ())
         if key in self._spec_graphs:
             return self._spec_graphs[key]
         sp = self._spec

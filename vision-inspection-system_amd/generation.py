@@ -81,7 +81,8 @@ class Generation(DecodeStage):
     def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, *,
                   logprobs=None, json_mode=False, top_p=None, repetition_penalty=None, frequency_penalty=None,
                   presence_penalty=None, json_schema=None, stop=None, top_k=None, min_p=None, logit_bias=None,
-                  on_stream=None, no_repeat_ngram_size=None, bad_words=None, min_tokens=None, speculative=None) -> List[int]:
+                  on_stream=None, no_repeat_ngram_size=None, bad_words=None, min_tokens=None, speculative=None,
+                  prediction=None) -> List[int]:
         """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
         ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
         first EOS (exclusive; inclusive for an engine with ``keep_eos``).  ``logprobs`` = k in 0..20: afterwards
@@ -125,13 +126,22 @@ class Generation(DecodeStage):
         keeps the drafts the model's own greedy picks confirm - the reply is the plain reply token for token, in fewer
         weight passes where the reply repeats earlier text.  Greedy single requests of the Qwen2-VL engines only: ValueError
         with a temperature, a seed or any switch above (they advance one token at a time).  Afterwards ``last_timing`` holds
-        ``spec_steps`` / ``spec_proposed`` / ``spec_accepted``."""
-        sp = spec.check_speculative(speculative)
+        ``spec_steps`` / ``spec_proposed`` / ``spec_accepted``.
+        ``prediction``: a sequence of token ids the reply will probably repeat (OpenAI's Predicted Outputs; at most max_ctx
+        are kept, none = off): the drafts come from it while the reply follows it, and from prompt lookup where it does not
+        (spec.propose_pred, vis_spec_draft_pred).  Alone it implies speculative = k 3, window 4..2; ``speculative`` next to it
+        sets k and the window.  The same conditions and refusals as ``speculative``; the reply is the plain reply.  Afterwards
+        ``last_timing`` also holds ``pred_accepted`` / ``pred_rejected``: the prediction's drafts the steps kept and did not
+        keep, over every step issued."""
+        pred = spec.check_prediction_ids(prediction, getattr(self, "max_ctx", None))
+        sp = spec.with_prediction(speculative, pred is not None)
         if sp is not None:
+            what = "speculative" if pred is None else "prediction (speculative decoding)"
             if not self.speculative_supported:
-                raise ValueError("speculative decoding is offered by the Qwen2-VL / Qwen2.5-VL engine only: this engine's "
-                                 "cross-attention rows have no multi-row form")
-            spec.check_exclusive(sp, temperature, seed, logprobs=logprobs, json_mode=json_mode, top_p=top_p,
+                raise ValueError(("speculative decoding is" if pred is None else "prediction (speculative decoding) is") +
+                                 " offered by the Qwen2-VL / Qwen2.5-VL engine only: this engine's cross-attention rows "
+                                 "have no multi-row form")
+            spec.check_exclusive(sp, temperature, seed, what=what, logprobs=logprobs, json_mode=json_mode, top_p=top_p,
                                  repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
                                  presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
                                  min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
@@ -146,7 +156,7 @@ class Generation(DecodeStage):
             self._stream_bind([[0]])
             max_new_tokens = self._clamp_request(input_ids, max_new_tokens)
             if sp is not None:      # no chained launch in a speculative step: nothing of the stall handling below applies
-                return self._run_single_spec(sp, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every)
+                return self._run_single_spec(sp, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, pred)
             try:
                 out = self._run_single(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
                 self._maybe_reenable_chain()
@@ -191,7 +201,7 @@ class Generation(DecodeStage):
         return toks
 
     def _run_single_spec(self, sp: "spec.SpecConfig", input_ids, frames, max_new_tokens, ignore_eos, use_graph,
-                         check_every) -> List[int]:
+                         check_every, prediction=None) -> List[int]:
         """_run_single with speculative steps: ``check_every`` steps are issued ahead as there, then the poll reads the device
         step counter together with the token row - a step has produced 1..R tokens.  Ends at EOS or when the reply has
         max_new_tokens tokens (the device ``limit`` cuts the last step's run there; steps issued past it change nothing)."""
@@ -201,7 +211,7 @@ class Generation(DecodeStage):
         self._prompt_pass(input_ids, frames, max_new_tokens + R - 1, 0.0, 0)      # rope rows for the rows past the last token
         ev[1].record()
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - len(input_ids) - 1))
-        buf = self._spec_begin(sp, max_new_tokens)
+        buf = self._spec_begin(sp, max_new_tokens, prediction)
         start, eos = self.prompt_len - 1, set(self.cfg.eos_ids)
 
         def poll():      # one D2H each: the step counter, then the tokens it covers
@@ -221,6 +231,9 @@ class Generation(DecodeStage):
         self.last_timing = {"prompt_tokens": len(input_ids), "prefill_ms": ev[0].elapsed_time(ev[1]),
                             "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": steps, "sequences": 1,
                             "spec_steps": c[0], "spec_proposed": c[1], "spec_accepted": c[2]}
+        if prediction:
+            st = buf.read_pred_state()
+            self.last_timing.update(pred_accepted=st.accepted, pred_rejected=st.rejected)
         toks = self._finish([(0, toks)], eos, ignore_eos, keep_eos=self.keep_eos)[0]
         self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
         return toks

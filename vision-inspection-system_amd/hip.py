@@ -78,6 +78,7 @@ _SIGS = {
     "vis_decode_attn_draft": "ppppppppp" + "iiiii" + "f" + "i" + "l" + "p",
     "vis_spec_accept": "p" + "iii" + "pppppp" + "i" + "ppp" + "p",
     "vis_spec_draft": "pi" + "pp" + "i" + "pp" + "iiii" + "pp" + "p",
+    "vis_spec_draft_pred": "pi" + "pp" + "i" + "pp" + "iiii" + "pi" + "pp" + "pp" + "p",
     "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
     "vis_stream_publish": "pp" + "i" + "pp" + "i" + "pp" + "i" + "pp" + "i" + "p",
     "vis_host_coherent_alloc": "ppl",
@@ -1616,6 +1617,28 @@ def spec_draft(prompt_ids: torch.Tensor, prompt_len: torch.Tensor, tokens: torch
                                _ptr(gen_start), _ptr(step), int(k), int(lookup_max), int(lookup_min), int(vocab), _ptr(draft),
                                _ptr(n_draft), _stream())
     _check(rc, "vis_spec_draft")
+
+
+SPEC_PRED_STATE_INTS = 7     # cursor, last, seen, src, n_out, accepted, rejected (spec.PredState; SP_ST_INTS of csrc/spec.hip)
+
+
+def spec_draft_pred(prompt_ids: torch.Tensor, prompt_len: torch.Tensor, tokens: torch.Tensor, gen_start: torch.Tensor,
+                    step: torch.Tensor, k: int, lookup_max: int, lookup_min: int, vocab: int, pred_ids: torch.Tensor,
+                    pred_len: torch.Tensor, state: torch.Tensor, draft: torch.Tensor, n_draft: torch.Tensor) -> None:
+    """The drafter of a request with a prediction (vis_spec_draft_pred): one spec.propose_pred() call over the reply
+    tokens[gen_start[0]:step[0]], the prediction pred_ids[:pred_len[0]] and the 7 state ints - all device memory, read and
+    written at run time.  Up to k ids into draft int32 [>= k], their count into n_draft.  Equals spec.propose_pred() exactly."""
+    ints = (prompt_ids, prompt_len, tokens, gen_start, step, pred_ids, pred_len, state, draft, n_draft)
+    if any(t.dtype != torch.int32 for t in ints) or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("spec_draft_pred: contiguous int32 tensors required")
+    if any(t.numel() != 1 for t in (prompt_len, gen_start, step, pred_len, n_draft)) or prompt_ids.numel() == 0 \
+            or pred_ids.numel() == 0 or state.numel() != SPEC_PRED_STATE_INTS or draft.numel() < k:
+        raise HipLibraryError("spec_draft_pred: bad parameter shapes")
+    rc = load().vis_spec_draft_pred(_ptr(prompt_ids), prompt_ids.numel(), _ptr(prompt_len), _ptr(tokens), tokens.numel(),
+                                    _ptr(gen_start), _ptr(step), int(k), int(lookup_max), int(lookup_min), int(vocab),
+                                    _ptr(pred_ids), pred_ids.numel(), _ptr(pred_len), _ptr(state), _ptr(draft), _ptr(n_draft),
+                                    _stream())
+    _check(rc, "vis_spec_draft_pred")
 
 
 STOP_STATE_INTS = 8     # int32 words of one sequence's vis_stop_scan record (stop.STATE_INTS)

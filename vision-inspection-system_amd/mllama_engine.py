@@ -30,7 +30,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, spec
 from .decode_stage import DecodeLayer
 from .generation import Generation
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
@@ -631,18 +631,18 @@ class MllamaEngine(Generation):
                  stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                  logit_bias: Optional[dict] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
                  bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None,
-                 speculative=None) -> List[int]:
+                 speculative=None, prediction=None) -> List[int]:
         """One request through the single-sequence loop: Generation._generate describes every parameter, with
         ``stop_on_eos`` = not ignore_eos, ``chunk`` = check_every (the boundary at which a cancelled request ends) and
         ``frame`` the request's one image or None.  A reply that ended on EOS keeps its EOS token here; a ``max_new_tokens``
         the context cannot hold is clamped silently; after a stalled chained launch this engine stays on the separate
-        launches for good.  ``speculative`` other than None is refused (ValueError): the Qwen2-VL engines only."""
+        launches for good.  ``speculative`` or ``prediction`` other than None is refused (ValueError): the Qwen2-VL engines only."""
         return self._generate(input_ids, frame, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
                               logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
                               frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
                               stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
                               no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens,
-                              speculative=speculative)
+                              speculative=speculative, prediction=prediction)
 
     def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
                        temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
@@ -650,12 +650,13 @@ class MllamaEngine(Generation):
                        top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
                        repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
                        stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None,
-                       no_repeat_ngram_size=None, bad_words=None, min_tokens=None) -> list:
+                       no_repeat_ngram_size=None, bad_words=None, min_tokens=None, prediction=None) -> list:
         """Up to max_batch requests through one shared decode loop: Generation._generate_batch describes every parameter
-        (``stop_on_eos`` / ``chunk`` as in generate).  requests: [(input_ids, frame)]; every request of a batch carries an
+        (``stop_on_eos`` / ``chunk`` as in generate; ``prediction`` other than None is refused).  requests: [(input_ids, frame)]; every request of a batch carries an
         image - one text-only request alone takes the single-sequence path.  A reply that ended on EOS keeps its EOS token.
         With ``n``, the image's cross-attention keys / values are copied whole into every further choice's slot and the
         forked attention serves the self-attention layers."""
+        spec.refuse_batch_prediction(prediction)
         return self._generate_batch(requests, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
                                     logprobs=logprobs, json_mode=json_mode, top_p=top_p, seeds=seeds,
                                     repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,

@@ -6,7 +6,11 @@ A step feeds R = 1 + k rows - the current token and up to k drafted ones - throu
 weights (vis_gemv_*_rows: each row's arithmetic is the single-row kernel's, bit for bit) and through
 vis_decode_attn_draft (row r bit-identical to a plain attention launch at its position).  Row r's logits therefore are
 the logits the plain step would have computed after the drafts in front of it - when those drafts are what the plain
-step would have picked.  The accept step keeps exactly that prefix, so the reply is the plain reply token for token."""
+step would have picked.  The accept step keeps exactly that prefix, so the reply is the plain reply token for token.
+
+A request may bring a second source of drafts, the caller's prediction of the reply (OpenAI's Predicted Outputs:
+``check_prediction``): ``propose_pred`` is that drafter's definition (vis_spec_draft_pred equals it exactly), and
+``simulate_prediction`` the model-free walk that gives the counters a run must report."""
 from __future__ import annotations
 
 import os
@@ -61,16 +65,75 @@ def check_speculative(speculative) -> Optional[SpecConfig]:
     return SpecConfig(k, hi, lo)
 
 
-def check_exclusive(cfg: Optional[SpecConfig], temperature: float = 0.0, seed=None, **switches) -> None:
+PRED_DEFAULT = SpecConfig(3, 4, 2)      # what ``prediction`` alone implies: four rows per step, vLLM's lookup window
+
+
+def check_prediction(prediction) -> Optional[str]:
+    """OpenAI's Predicted Outputs argument -> its text: {"type": "content", "content": str}, or content as a list of
+    {"type": "text", "text": str} parts (concatenated).  None, or a prediction without text: None (no prediction).
+    ValueError for any other type, a missing content or a part that is not text."""
+    if prediction is None:
+        return None
+    if not isinstance(prediction, dict):
+        raise ValueError("prediction must be a dict {'type': 'content', 'content': ...}")
+    unknown = set(prediction) - {"type", "content"}
+    if unknown:
+        raise ValueError(f"prediction: unknown keys {sorted(unknown)}")
+    if prediction.get("type") != "content":
+        raise ValueError("prediction: the only type is 'content'")
+    if "content" not in prediction:
+        raise ValueError("prediction: content is required")
+    content = prediction["content"]
+    if isinstance(content, (list, tuple)):
+        for part in content:
+            if not isinstance(part, dict) or set(part) != {"type", "text"} or part["type"] != "text" \
+                    or not isinstance(part["text"], str):
+                raise ValueError("prediction: every content part must be {'type': 'text', 'text': str}")
+        content = "".join(part["text"] for part in content)
+    if not isinstance(content, str):
+        raise ValueError("prediction: content must be a string or a list of text parts")
+    return content or None
+
+
+def check_prediction_ids(prediction, max_ids: Optional[int] = None) -> Optional[List[int]]:
+    """The engine-level form: a sequence of token ids (>= 0), at most ``max_ids`` kept.  None or empty: None."""
+    if prediction is None:
+        return None
+    if isinstance(prediction, (str, bytes, dict)) or not hasattr(prediction, "__len__"):
+        raise ValueError("prediction must be a sequence of token ids")
+    ids = []
+    for t in (prediction if max_ids is None else prediction[:max_ids]):
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < 2 ** 31:
+            raise ValueError("prediction must be a sequence of token ids (integers >= 0)")
+        ids.append(int(t))
+    return ids or None
+
+
+def refuse_batch_prediction(prediction) -> None:
+    """generate_batch / complete_many: a prediction belongs to ONE greedy request (the speculative step carries one sequence)."""
+    if prediction is not None:
+        raise ValueError("prediction (speculative decoding) serves one request per call: chat.completions.create / generate, "
+                         "not a batch")
+
+
+def with_prediction(speculative, has_prediction: bool) -> Optional[SpecConfig]:
+    """The step configuration of a request: ``speculative`` as check_speculative reads it; a prediction alone implies
+    PRED_DEFAULT (k = 3: with a prediction that holds, the four-row step is the cheapest per token in every weight format)."""
+    sp = check_speculative(speculative)
+    return PRED_DEFAULT if sp is None and has_prediction else sp
+
+
+def check_exclusive(cfg: Optional[SpecConfig], temperature: float = 0.0, seed=None, *, what: str = "speculative",
+                    **switches) -> None:
     """What a speculative request may not carry: every switch that is a per-step device state machine advancing one token
     at a time, and everything that samples.  ``switches``: name -> value as the caller got it (None / neutral = off).
-    ValueError naming the conflict."""
+    ValueError naming the conflict.  ``what``: how the messages name the request's argument."""
     if cfg is None:
         return
     if temperature:
-        raise ValueError("speculative together with temperature > 0 is not supported: acceptance is defined for the greedy pick")
+        raise ValueError(f"{what} together with temperature > 0 is not supported: acceptance is defined for the greedy pick")
     if seed:
-        raise ValueError("speculative together with a seed is not supported: a greedy request has nothing to seed")
+        raise ValueError(f"{what} together with a seed is not supported: a greedy request has nothing to seed")
     neutral = {"top_p": (None, 1, 1.0), "repetition_penalty": (None, 1, 1.0), "frequency_penalty": (None, 0, 0.0),
                "presence_penalty": (None, 0, 0.0), "top_k": (None, 0), "min_p": (None, 0, 0.0), "logit_bias": (None, {}),
                "no_repeat_ngram_size": (None, 0), "bad_words": (None, [], ()), "min_tokens": (None, 0),
@@ -80,7 +143,7 @@ def check_exclusive(cfg: Optional[SpecConfig], temperature: float = 0.0, seed=No
     for name, value in switches.items():
         off = neutral.get(name, (None,))
         if not any(value is o or (type(value) is type(o) and value == o) for o in off):
-            raise ValueError(f"speculative together with {name} is not supported: it is a per-step state of the pick, and a "
+            raise ValueError(f"{what} together with {name} is not supported: it is a per-step state of the pick, and a "
                              "speculative step yields several tokens")
 
 
@@ -120,6 +183,87 @@ def propose(history: Sequence[int], k: int, lookup_max: int = 4, lookup_min: int
     return []
 
 
+class PredState(NamedTuple):
+    """What the prediction drafter keeps between two calls (the 7 device ints of vis_spec_draft_pred, in this order)."""
+    cursor: int = 0      # index into pred of the id expected next; -1 = lost
+    last: int = 0        # the last cursor value held before a loss
+    seen: int = 0        # reply tokens consumed so far
+    src: int = 0         # source of the drafts outstanding from the previous call: 0 none, 1 prompt lookup, 2 prediction
+    n_out: int = 0       # their count
+    accepted: int = 0    # prediction-sourced drafts the accept step kept
+    rejected: int = 0    # ... and did not keep
+
+
+def propose_pred(state: PredState, prompt: Sequence[int], reply: Sequence[int], pred: Sequence[int], k: int,
+                 lookup_max: int = 4, lookup_min: int = 2, vocab: Optional[int] = None):
+    """The drafter of a request with a prediction; vis_spec_draft_pred equals it exactly.  ``reply``: everything picked so
+    far, the newest pick included.  Returns (draft, state).
+
+    1. new = reply[seen:]; a = min(len(new) - 1, n_out) is what the accept step kept of the outstanding drafts (a step
+       yields the kept drafts and one more token).  Drafts that came from the prediction count: accepted += a, rejected +=
+       n_out - a - also those the request's token limit cut off.  No new token (a step issued behind the limit): no count.
+    2. Every new token moves the cursor on when it is the id the prediction expected; the first one that is not loses the
+       cursor (last = where it stood), and it stays lost for the rest of ``new``.
+    3. A lost cursor is looked for again: for m = lookup_max down to lookup_min (the reply holds m ids), the candidates are
+       e in [m, P) with pred[e-m:e] == reply[-m:].  The smallest candidate >= last wins - the reply went on in the
+       prediction behind a substituted, skipped or inserted piece; without one the largest candidate < last - a report
+       whose list entries repeat the template's keys.  The first m with a candidate decides.
+    4. With the cursor inside the prediction the draft is pred[cursor:cursor + k] (src 2); else it is the prompt lookup
+       ``propose(prompt + reply, ..)`` (src 1, or 0 when that has nothing).  Ids are clamped into [0, vocab)."""
+    reply, pred = [int(t) for t in reply], [int(t) for t in pred]
+    P = len(pred)
+    cursor, last, seen, src, n_out, accepted, rejected = state
+    new = reply[seen:]
+    if new and src == 2:
+        a = min(len(new) - 1, n_out)
+        accepted, rejected = accepted + a, rejected + n_out - a
+    for t in new:
+        if 0 <= cursor < P and pred[cursor] == t:
+            cursor += 1
+        elif cursor >= 0:
+            last, cursor = cursor, -1
+    if cursor == -1 and P > 0:
+        for m in range(lookup_max, lookup_min - 1, -1):
+            if len(reply) < m:
+                continue
+            cand = [e for e in range(m, P) if pred[e - m:e] == reply[-m:]]
+            if cand:
+                fwd = [e for e in cand if e >= last]
+                cursor = fwd[0] if fwd else cand[-1]
+                break
+    if 0 <= cursor < P:
+        draft, src = pred[cursor:cursor + min(k, P - cursor)], 2
+    else:
+        draft = propose(list(prompt) + reply, k, lookup_max, lookup_min)
+        src = 1 if draft else 0
+    if vocab is not None:
+        draft = [min(max(t, 0), vocab - 1) for t in draft]
+    return draft, PredState(cursor, last, len(reply), src, len(draft), accepted, rejected)
+
+
+def simulate_prediction(plain_reply: Sequence[int], prompt: Sequence[int], pred: Sequence[int], k: int, lookup_max: int = 4,
+                        lookup_min: int = 2, max_new_tokens: Optional[int] = None, vocab: Optional[int] = None) -> dict:
+    """What a run with ``prediction=pred`` must report, without a model: the scheme is lossless, so the pick behind any
+    accepted prefix is the plain reply's next token.  ``plain_reply``: the reply of the plain request run to its length
+    limit (ignore_eos), at least max_new_tokens ids.  Walks the steps as vis_spec_accept takes them (a draft counts while it
+    equals the pick in front of it; the limit cuts the last step's run) and returns the reply and the five counters:
+    {"reply", "spec_steps", "spec_proposed", "spec_accepted", "pred_accepted", "pred_rejected"}."""
+    plain = [int(t) for t in plain_reply]
+    N = len(plain) if max_new_tokens is None else min(len(plain), max_new_tokens)
+    reply = plain[:1]
+    draft, state = propose_pred(PredState(), prompt, reply, pred, k, lookup_max, lookup_min, vocab)
+    steps = proposed = accepted = 0
+    while len(reply) < N:
+        n, d, a = len(reply), len(draft), 0
+        while a < d and n + a < N - 1 and draft[a] == plain[n + a]:
+            a += 1
+        reply = plain[:n + a + 1]
+        steps, proposed, accepted = steps + 1, proposed + d, accepted + a
+        draft, state = propose_pred(state, prompt, reply, pred, k, lookup_max, lookup_min, vocab)
+    return {"reply": reply, "spec_steps": steps, "spec_proposed": proposed, "spec_accepted": accepted,
+            "pred_accepted": state.accepted, "pred_rejected": state.rejected}
+
+
 def accept_ref(logits: np.ndarray, draft: Sequence[int], d: int, step: int, limit: int, tokens: np.ndarray,
                counters: Sequence[int]):
     """vis_spec_accept restated: returns (tokens, cur_token or None, step, counters) after the call."""
@@ -147,7 +291,7 @@ class SpecBuffers:
     """What the speculative step of one engine owns: its own activation rows (an engine built with max_batch=1 has no
     batched buffers), the attention workspace for 4 rows, the f32 logits of 4 rows, the id row [cur, drafts], the request's
     prompt ids and the small device ints the launches read (draft count, limit, prompt length, start of the reply in the
-    token row, counters)."""
+    token row, counters), and for a request with a prediction its ids (max_ctx int32), their count and the drafter's state."""
 
     def __init__(self, cfg, n_split: int, max_ctx: int, device):
         bf, dev, R = torch.bfloat16, device, MAX_K + 1
@@ -164,9 +308,11 @@ class SpecBuffers:
         self.ws_idx = torch.empty(256 * R, dtype=torch.int32, device=dev)
         self.ids = torch.zeros(R, dtype=torch.int32, device=dev)           # [cur, draft 0 .. draft k-1]
         self.prompt = torch.zeros(max_ctx, dtype=torch.int32, device=dev)
-        ints = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.pred = torch.zeros(max_ctx, dtype=torch.int32, device=dev)    # the request's prediction (vis_spec_draft_pred)
+        ints = torch.zeros(16, dtype=torch.int32, device=dev)
         self.n_draft, self.limit, self.prompt_len, self.gen_start = ints[0:1], ints[1:2], ints[2:3], ints[3:4]
         self.counters = ints[4:7]                                           # steps, proposed, accepted
+        self.pred_len, self.pred_state = ints[8:9], ints[9:16]              # ... and the PredState ints behind its length
         self._ints = ints
 
     @property
@@ -177,14 +323,23 @@ class SpecBuffers:
     def draft(self) -> torch.Tensor:
         return self.ids[1:]
 
-    def begin(self, cur_token: torch.Tensor, prompt_ids: torch.Tensor, step0: int, limit: int) -> None:
+    def begin(self, cur_token: torch.Tensor, prompt_ids: torch.Tensor, step0: int, limit: int,
+              prediction: Optional[Sequence[int]] = None) -> None:
         """A request starts behind its prompt pass: the first token, the prompt's ids, no drafts yet, counters at zero.
-        ``step0``: the index of the token row the prompt pass's pick went to; ``limit``: the last one the reply may use."""
+        ``step0``: the index of the token row the prompt pass's pick went to; ``limit``: the last one the reply may use.
+        ``prediction``: the ids of the request's predicted reply (at most the buffer's size is kept), its drafter state zeroed."""
         n = prompt_ids.numel()
         self.prompt[:n].copy_(prompt_ids)
         self.ids.zero_()
         self.ids[0:1].copy_(cur_token)
-        self._ints.copy_(torch.tensor([0, limit, n, step0, 0, 0, 0, 0], dtype=torch.int32), non_blocking=False)
+        p = list(prediction or ())[:self.pred.numel()]
+        if p:
+            self.pred[:len(p)].copy_(torch.tensor(p, dtype=torch.int32))
+        self._ints.copy_(torch.tensor([0, limit, n, step0, 0, 0, 0, 0, len(p)] + list(PredState()), dtype=torch.int32),
+                         non_blocking=False)
 
     def read_counters(self) -> List[int]:
         return [int(v) for v in self.counters.cpu().tolist()]
+
+    def read_pred_state(self) -> PredState:
+        return PredState(*(int(v) for v in self.pred_state.cpu().tolist()))
