@@ -652,6 +652,24 @@ int vis_decode_attn_draft(const void* qkv, const void* cos_t, const void* sin_t,
                           const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
                           int cache_tokens, int nsplit, float scale, int rows, long long qkv_ld, vis_stream_t stream);
 
+/* vis_decode_cross_attn_draft: vis_decode_cross_attn (below) for the `rows` (1..4) rows of ONE sequence's speculative step.
+ * Row r's q is q + r * q_ld (q_ld >= Hq * 128, a multiple of 8: the leading columns of a wider projection row may be passed);
+ * all rows attend the same static keys [0, *nkeys_m1 + 1) - one count, read from device memory and clamped into
+ * [.., key_tokens).  One workgroup per (kv head, split of 64 keys) loads the split's K / V once and serves every row: row r's
+ * normalised heads take columns r G .. r G + G - 1 of the score MFMA's 16, hence rows * G <= 16 (G = Hq / Hkv; G = 7, 8: rows
+ * <= 2).  Workspaces part_o [rows][Hq][nsplit][128] / part_ml [rows][Hq][nsplit][2] f32, out [rows][Hq*128].  Output row r is
+ * bit-identical to vis_decode_cross_attn on q row r alone and does not depend on `rows` or on the other rows.  Argument checks:
+ * vis_decode_cross_attn's, rows, q_ld and rows * G <= 16; VIS_ERR_ARG launches nothing. */
+int vis_decode_cross_attn_draft(const void* q, const void* q_norm_w, const void* k, const void* v, const void* nkeys_m1,
+                                void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD, int key_tokens, int nsplit,
+                                float scale, float eps, int rows, long long q_ld, vis_stream_t stream);
+/* The same over the fp8 copies of the keys / values (vis_decode_cross_attn_fp8's operands and checks; csrc/cross_kv.hip):
+ * output row r is bit-identical to vis_decode_cross_attn_fp8 on q row r alone. */
+int vis_decode_cross_attn_fp8_draft(const void* q, const void* q_norm_w, const void* k_codes, const void* k_scale,
+                                    const void* v_codes, const void* v_scale, const void* nkeys_m1, void* part_o,
+                                    void* part_ml, void* out, int Hq, int Hkv, int HD, int key_tokens, int nsplit,
+                                    float scale, float eps, int rows, long long q_ld, vis_stream_t stream);
+
 /* vis_spec_accept: p_r = the greedy pick of logits row r ([rows][ld_logits] f32; vis_argmax_f32's comparison: ties to the
  * lowest id, a row without a comparable logit picks 0); d = *n_draft clamped to 0..rows-1; a = the number of leading
  * r < d with draft[r] == p_r, clamped so that *step_ptr + a <= *limit (the last index of `tokens` the request may

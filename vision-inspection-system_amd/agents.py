@@ -154,12 +154,17 @@ def speculative_kwargs(client, model_id, temperature, others: dict) -> dict:
     "ngram", "num_speculative_tokens": k} - lossless n-gram speculative decoding (spec.py): the report's JSON template
     stands in the prompt, and what the reply copies of it costs fewer weight passes; the reply itself is unchanged.  Only
     on requests that carry none of the switches it excludes (``others``: the keywords of the VIS_* switches above; a
-    temperature), only to this package's own clients, and not to an mllama model.  Unset: the calls are as before."""
+    temperature) and only to this package's own clients.  VIS_SPECULATIVE means the Qwen2-VL engines: a request to an mllama
+    model (the Auditor's Llama-3.2-11B-Vision) passes VIS_AUDITOR_SPECULATIVE=k instead, under the same exclusions - that
+    variable also has the engine built for it (client._auditor_kwargs).  Unset: the calls are as before."""
     from .client import CannedResponseClient, LocalVLMClient, is_mllama_model
-    from .spec import from_env
+    from .spec import auditor_from_env, from_env
     sp = from_env()
-    if sp is None or others or temperature or not isinstance(client, (LocalVLMClient, CannedResponseClient)) \
-            or is_mllama_model(model_id):
+    if others or temperature or not isinstance(client, (LocalVLMClient, CannedResponseClient)):
+        return {}
+    if is_mllama_model(model_id):
+        sp = auditor_from_env()
+    if sp is None:
         return {}
     return {"speculative": {"method": "ngram", "num_speculative_tokens": sp.k}}
 

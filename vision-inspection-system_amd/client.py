@@ -270,7 +270,7 @@ class _Chat:
 TIMING_LOG: List[dict] = []
 
 # ----------------------------------------------------------------------------- engine registry
-_ENGINES: Dict[tuple, Any] = {}      # (model id, device) + an mllama engine's _auditor_settings()
+_ENGINES: Dict[tuple, Any] = {}      # (model id, device) + an mllama engine's _auditor_key()
 _ENGINES_LOCK = threading.Lock()
 
 
@@ -312,7 +312,7 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
         with _ENGINES_LOCK:      # a model that is already loaded / registered on exactly one device: no device query needed
             hits = [k for k in _ENGINES if k[0] == model_id]
             if any(len(k) > 2 for k in hits):      # mllama entries carry their settings: the entry of the current ones
-                aud = _auditor_settings()
+                aud = _auditor_key()
                 hits = [k for k in hits if len(k) == 2 or k[2:] == aud]
             if len(hits) == 1:
                 return _ENGINES[hits[0]]
@@ -324,7 +324,7 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
         # an mllama engine is cached under its quantisation settings too (VIS_AUDITOR_*, fixed per engine); the variables are
         # read only where an mllama model is loaded or already cached, so a malformed one cannot fail another model's load
         if any(k[:2] == key and len(k) > 2 for k in _ENGINES):
-            akey = key + _auditor_settings()
+            akey = key + _auditor_key()
             if akey in _ENGINES:
                 return _ENGINES[akey]
         # KV-cache rows per sequence.  Default: the reference's request fits as the reference sends it - ~2300 prompt tokens
@@ -334,7 +334,7 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
         max_batch = max(1, min(64, int(os.environ.get("VIS_MAX_BATCH", "64"))))
         mllama = _load_mllama(model_id, device, max_ctx, max_batch)
         if mllama is not None:
-            _ENGINES[key + _auditor_settings()] = mllama
+            _ENGINES[key + _auditor_key()] = mllama
             return mllama
         if model_id.startswith("synthetic:"):
             parts = model_id.split(":")
@@ -389,10 +389,25 @@ def _auditor_settings() -> tuple:
             os.environ.get("VIS_AUDITOR_CROSS_KV", "").strip() or "bf16")
 
 
+def _auditor_speculative() -> bool:
+    """VIS_AUDITOR_SPECULATIVE=k (1..3) is set: the mllama engine is built with speculative=True and the clients accept
+    ``speculative`` / ``prediction`` for one request of an mllama model.  Read at every call; a malformed value is a ValueError."""
+    from .spec import auditor_from_env
+    return auditor_from_env() is not None
+
+
+def _auditor_key() -> tuple:
+    """What an mllama engine is cached under behind (model id, device): _auditor_settings(), and one further element while
+    VIS_AUDITOR_SPECULATIVE is set (the engine built for speculative requests is another engine).  Unset: today's key."""
+    return _auditor_settings() + (("speculative",) if _auditor_speculative() else ())
+
+
 def _auditor_kwargs() -> dict:
     """The constructor keywords the VIS_AUDITOR_* variables set; nothing set -> no keyword (the bf16 engine's call as it was)."""
     dw, gf, xkv = _auditor_settings()
     kw = {}
+    if _auditor_speculative():
+        kw["speculative"] = True
     if dw != "bf16":
         kw["decode_weights"] = dw
     if gf is not None:
@@ -405,7 +420,8 @@ def _auditor_kwargs() -> dict:
 def _load_mllama(model_id: str, device, max_ctx: int, max_batch: int = 1) -> Optional[LoadedModel]:
     """mllama family (synthetic:mllama-tiny[:seed], synthetic:mllama-11b, or a local directory whose config.json
     says model_type "mllama"); None when ``model_id`` is not an mllama model.  VIS_AUDITOR_DECODE_WEIGHTS / _MXFP4_GEMM_FROM /
-    _CROSS_KV choose the engine's decode weight format and the format of its cross-attention keys (MllamaEngine)."""
+    _CROSS_KV choose the engine's decode weight format and the format of its cross-attention keys, VIS_AUDITOR_SPECULATIVE
+    whether it serves speculative requests (MllamaEngine)."""
     import json
     from . import mllama_weights as MW
     from .mllama_engine import MllamaEngine
@@ -699,10 +715,10 @@ class LocalVLMClient:
                 top_p=top_p, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
                 repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n,
                 stream=stream, no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
-            if is_mllama_model(model or self.default_model):
+            if is_mllama_model(model or self.default_model) and not _auditor_speculative():
                 raise ValueError(("speculative decoding is" if text is None else "prediction (speculative decoding) is") +
-                                 " offered for Qwen2-VL / Qwen2.5-VL models only: the Mllama engine's cross-attention rows "
-                                 "have no multi-row form")
+                                 " offered for Qwen2-VL / Qwen2.5-VL models only, unless VIS_AUDITOR_SPECULATIVE=k (1..3) "
+                                 "has the Mllama engine built for it")
             return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp, prediction=text)[0]
         out = self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
                                  response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
@@ -859,8 +875,10 @@ class LocalVLMClient:
         temp = float(temperature) if temperature else 0.0
         n = check_n(n, eng.max_batch)
         n = None if n == 1 else n
-        if speculative is not None and (len(batch_of_messages) != 1 or lm.family == "mllama"):
-            raise ValueError("speculative decoding serves one request of a Qwen2-VL / Qwen2.5-VL model per call")
+        if speculative is not None and (len(batch_of_messages) != 1 or
+                                        (lm.family == "mllama" and not _auditor_speculative())):
+            raise ValueError("speculative decoding serves one request of a Qwen2-VL / Qwen2.5-VL model per call (an mllama "
+                             "model: with VIS_AUDITOR_SPECULATIVE=k set)")
         # What every engine call of this request group gets, built once: the switches that are on (an engine call without a
         # keyword is the call of before the keyword existed) and the ignore-EOS switch in the engine's spelling.
         ignore_eos = os.environ.get("VIS_IGNORE_EOS") == "1"
@@ -895,7 +913,7 @@ class LocalVLMClient:
                 yield idx, outs, recs, fins, timing
 
         if lm.family == "mllama":
-            return self._complete_mllama_many(lm, batch_of_messages, gen, seed, serve)
+            return self._complete_mllama_many(lm, batch_of_messages, gen, seed, serve, speculative, prediction)
         # Service-side decode (base64 + JPEG) of every request on the ingest pool.  A request may arrive as a Future of
         # its messages (the agents' prepare_many: the request-side encode is still running on the same pool); its decode
         # is queued the moment that encode finishes, ahead of the encodes still waiting (ingest.then).  The engine receives the
@@ -961,11 +979,14 @@ class LocalVLMClient:
             raise ValueError("the mllama backend takes one image per request (what the reference sends)")
         return build_llama_chat_ids(lm.tokenizer, messages, len(frames)), (frames[0] if frames else None)
 
-    def _complete_mllama_many(self, lm, batch_of_messages, gen: dict, seed: Optional[int], serve) -> List[ChatCompletion]:
+    def _complete_mllama_many(self, lm, batch_of_messages, gen: dict, seed: Optional[int], serve, speculative=None,
+                              prediction: Optional[str] = None) -> List[ChatCompletion]:
         """Requests with an image share ONE decode loop in groups of the engine's max_batch (MllamaEngine.generate_batch:
         per-request prompt pass, weights streamed once per generated token for the whole group); text-only requests
         (the agents' health check) take the single-sequence path.  ``gen`` / ``seed`` / ``serve``: the engine keywords, the
-        call's seed and the chunked generate_batch of _complete_many."""
+        call's seed and the chunked generate_batch of _complete_many.  ``speculative`` / ``prediction`` (VIS_AUDITOR_SPECULATIVE
+        set, one request, no other switch - _complete_many has checked): the request goes through ``generate(.., speculative=)``
+        with or without an image."""
         from concurrent.futures import Future
         eng, tok = lm.engine, lm.tokenizer
         from . import ingest
@@ -976,6 +997,15 @@ class LocalVLMClient:
             return _completion(lm.model_id, tok, n_ids, t, rec, fin, dict(getattr(eng, "last_timing", {})), n is not None)
 
         futs = [ingest.then(m, lambda msgs: self._prepare_mllama(lm, msgs)) for m in batch_of_messages]
+        if speculative is not None:
+            ids, f = futs[0].result()
+            pred = {} if not prediction else {"prediction": tok.encode(prediction)[:eng.max_ctx]}
+            with eng.lock:
+                t = eng.generate(ids, _frame_to_device(f, eng.device) if f is not None else None, speculative=speculative,
+                                 **pred, **one)
+                TIMING_LOG.append({"model": lm.model_id, **eng.last_timing})
+                del TIMING_LOG[:-4096]
+                return [completion(len(ids), t, None, eng.last_finish[0])]
         if any(isinstance(m, Future) for m in batch_of_messages):
             # the batch seam (verify_many): every request carries an image; requests are resolved in order by the engine
             # while it already runs the earlier prompt passes; a failed request keeps its exception as its result
@@ -1044,8 +1074,9 @@ class CannedResponseClient:
                   min_tokens=None, speculative=None, prediction=None, **kwargs):
         check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
         if speculative is not None or prediction is not None:
-            if prediction is not None and is_mllama_model(model):
-                raise ValueError("prediction (speculative decoding) is offered for Qwen2-VL / Qwen2.5-VL models only")
+            if prediction is not None and is_mllama_model(model) and not _auditor_speculative():
+                raise ValueError("prediction (speculative decoding) is offered for Qwen2-VL / Qwen2.5-VL models only (an mllama "
+                                 "model: with VIS_AUDITOR_SPECULATIVE=k set)")
             check_speculative_request(
                 speculative, temperature, seed, prediction=prediction, response_format=response_format, top_p=top_p,
                 frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, repetition_penalty=repetition_penalty,

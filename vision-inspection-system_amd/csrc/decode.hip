@@ -714,7 +714,7 @@ __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float* _
                                                                   bf16_t* __restrict__ out, int nsplit,
                                                                   const int* __restrict__ step_ptr,
                                                                   int cache_tokens) {
-  decode_attn_combine_body(part_o, part_ml, out, nsplit, step_ptr, cache_tokens, false);
+  decode_attn_combine_body(part_o, part_ml, out, nsplit, step_ptr, cache_tokens, 0);
 }
 
 static int decode_attn_launch(const DecAttnArgs& p, void* out, int batch, hipStream_t stream) {

@@ -679,13 +679,14 @@ __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<
 // merge the per-split partials of one query head (only the splits that ran): 256 threads = 128 dims x 2
 // split-halves; the first partial loads are issued before the position is known
 #define CB_PRE 32   // partial rows preloaded per thread: covers 64 splits = 4096 cached keys
-// (the body of decode_attn_combine_kernel; vis_decode_attn_draft's combine calls it with `row_pos` = 1: the grid's y index
-// is then row r of ONE sequence, at position *step_ptr + r, instead of sequence r at step_ptr[r])
+// (the body of decode_attn_combine_kernel; `pos_mode` says what the grid's y index is: 0 = sequence r at step_ptr[r];
+// 1 = row r of ONE sequence at position *step_ptr + r (vis_decode_attn_draft's combine); 2 = row r of ONE sequence over the
+// one shared key count *step_ptr (vis_decode_cross_attn_draft / _fp8_draft: every row attends the same static keys))
 __device__ __forceinline__ void decode_attn_combine_body(const float* __restrict__ part_o,
                                                          const float* __restrict__ part_ml,
                                                          bf16_t* __restrict__ out, int nsplit,
                                                          const int* __restrict__ step_ptr,
-                                                         int cache_tokens, const bool row_pos) {
+                                                         int cache_tokens, const int pos_mode) {
   constexpr int HD = 128;
   __shared__ float wgt[256];
   __shared__ float osum[2][HD];
@@ -694,7 +695,7 @@ __device__ __forceinline__ void decode_attn_combine_body(const float* __restrict
   part_o += (size_t)seq * gridDim.x * nsplit * HD;
   part_ml += (size_t)seq * gridDim.x * nsplit * 2;
   out += (size_t)seq * gridDim.x * HD;
-  if (!row_pos) step_ptr += seq;
+  if (pos_mode == 0) step_ptr += seq;
   const float* po = part_o + (size_t)hq * nsplit * HD + d;
   const float* ml = part_ml + (size_t)hq * nsplit * 2;
   // ONE level of loads: the partials of the first 2 x CB_PRE split slots, the statistics of every slot and the position
@@ -706,7 +707,7 @@ __device__ __forceinline__ void decode_attn_combine_body(const float* __restrict
   for (int j = 0; j < CB_PRE; ++j) v[j] = po[(size_t)min(half + 2 * j, nsplit - 1) * HD];
   const int sl = min(tid, nsplit - 1);
   const float m_raw = ml[sl * 2], l_raw = ml[sl * 2 + 1];
-  const int ctx = min(row_pos ? max(*step_ptr, 0) + seq : *step_ptr, cache_tokens - 1) + 1;
+  const int ctx = min(pos_mode == 1 ? max(*step_ptr, 0) + seq : *step_ptr, cache_tokens - 1) + 1;
   const int active = min((ctx + DA_MAXKEYS - 1) / DA_MAXKEYS, nsplit);  // splits that ran
   const float m = (tid < active) ? m_raw : -1.0e30f;
   const float l = (tid < active) ? l_raw : 0.f;

@@ -61,6 +61,8 @@ class DecodeStage(PickStage):
     What the models do differently is behind two hooks: ``_decode_rope(B)`` -> (cos, sin, shared_len), the rope tables
     [B, T, D] of the batched self-attention and the number of leading keys every sequence reads from slot 0, and
     ``_decode_cross_attn(L, q, att, B)``, the cross-attention launch of layer L for the single sequence (B == 0) or B slots.
+    An engine with cross-attention layers that offers speculative decoding (``speculative_supported``) also supplies
+    ``_decode_cross_attn_draft(L, q, att, R)``, that launch for the R rows of a speculative step, and ``xsplit``, its split count.
     An engine supplies ``_ensure_graph(chained=)`` with its own graph key (see ``_captured_step``) and checks its own bounds
     in ``decode()`` before ``_decode_ordered``."""
 
@@ -264,11 +266,16 @@ class DecodeStage(PickStage):
         row the reply's last token goes to, so the reply has exactly max_new_tokens tokens however a step's run ends.
         ``prediction`` (ids): uploaded, and the prediction drafter is issued once behind the prompt pass's pick, so the
         first step already carries drafts; every step of the request then ends with that drafter."""
-        if self.dec_n_self != len(self.dec_layers):
-            raise ValueError("speculative decoding is not supported on a model with cross-attention layers")
+        cross = self.dec_n_self != len(self.dec_layers)
+        if cross and not self.speculative_supported:
+            raise ValueError("speculative decoding is not supported on a model with cross-attention layers unless its engine "
+                             "was built for it (MllamaEngine(.., speculative=True))")
         spec.check_rows_fit(self.cfg, cfg.rows)
-        if self._spec is None:
-            self._spec = spec.SpecBuffers(self.cfg, self.nsplit, self.max_ctx, self.device)
+        if cross:
+            spec.check_cross_rows_fit(self.cfg, cfg.rows)
+        if self._spec is None:      # one attention workspace serves the self and the cross launches: the larger split count
+            self._spec = spec.SpecBuffers(self.cfg, max(self.nsplit, self.xsplit) if cross else self.nsplit, self.max_ctx,
+                                          self.device)
         self._spec_cfg = cfg
         self._spec_pred = bool(prediction)
         start = self.prompt_len - 1
@@ -286,7 +293,9 @@ class DecodeStage(PickStage):
     def _decode_step_spec(self, R: int, propose: bool = True) -> None:
         """One speculative step of the single sequence: rows [cur, draft 0 .. draft R-2] at positions step .. step + R - 1
         through the multi-row GEMVs (one pass over the weights, every row the single-row kernel's bits), the draft
-        attention (row r = the plain launch at step + r, bit for bit), the lm_head into [R, V] f32, then vis_spec_accept -
+        attention (row r = the plain launch at step + r, bit for bit; a cross-attention layer: the q projection into the
+        leading columns of the packed rows and ``_decode_cross_attn_draft``, row r = the plain cross launch on row r, skipped
+        while the request has no image as in the plain step), the lm_head into [R, V] f32, then vis_spec_accept -
         which keeps the drafts the picks confirm and advances ``step`` by 1..R - and vis_spec_draft for the next step
         (vis_spec_draft_pred instead when the request came with a prediction).
         Never the chained launch: the chain is bit-identical to the four launches, so the tokens are the chained step's.
@@ -299,9 +308,16 @@ class DecodeStage(PickStage):
         hip.gather_rows(self.w.embed, sp.ids[:R], x)
         for L in self.dec_layers:
             lw = L.w
-            gemv_rows(x, *_wt(L, "qkv_w", fmt), qkv, bias=L.bias, norm_w=lw.ln1_w, eps=eps)
-            hip.decode_attn_draft(qkv, self.cos_t, self.sin_t, self.kcache[L.idx], self.vcache[L.idx], self.step, sp.part_o,
-                                  sp.part_ml, att, Hq, Hkv, D, self.nsplit, scale)
+            if L.cross:
+                if not self.has_image:
+                    continue
+                q = qkv[:, :Hq * D]
+                gemv_rows(x, *_wt(L, "qkv_w", fmt), q, norm_w=lw.ln1_w, eps=eps)
+                self._decode_cross_attn_draft(L, q, att, R)
+            else:
+                gemv_rows(x, *_wt(L, "qkv_w", fmt), qkv, bias=L.bias, norm_w=lw.ln1_w, eps=eps)
+                hip.decode_attn_draft(qkv, self.cos_t, self.sin_t, self.kcache[L.idx], self.vcache[L.idx], self.step,
+                                      sp.part_o, sp.part_ml, att, Hq, Hkv, D, self.nsplit, scale)
             gemv_rows(att, *_wt(L, "o_w", fmt), x2, residual=x)
             gemv_rows(x2, *_wt(L, "gateup_w", fmt), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
             gemv_rows(act, *_wt(L, "down_w", fmt), x, residual=x2)
@@ -315,12 +331,19 @@ class DecodeStage(PickStage):
             hip.spec_draft(sp.prompt, sp.prompt_len, self.tokens, sp.gen_start, self.step, R - 1, c.lookup_max, c.lookup_min,
                            cfg.vocab, sp.draft, sp.n_draft)
 
+    def _decode_cross_attn_draft(self, L: DecodeLayer, q: torch.Tensor, att: torch.Tensor, R: int) -> None:
+        """Hook: the cross-attention of layer L for the R rows q [R, Hq * D] (a column view of the packed rows) into att[:R],
+        with the step's workspace ``self._spec.part_o`` / ``part_ml``; every row bit-identical to ``_decode_cross_attn`` alone."""
+        raise NotImplementedError("this engine has no draft form of its cross-attention")
+
     def _spec_graph(self, R: int) -> torch.cuda.CUDAGraph:
-        """The captured speculative step, keyed by (R, weight format, the lookup window, and "pred" when the step ends with
-        the prediction drafter): its launches read everything else - the prediction, its length, the drafter's state - from
-        device memory.  The warm-up step advances the request's counters; they are put back before the capture."""
+        """The captured speculative step, keyed by (R, weight format, the lookup window, whether the cross-attention layers run,
+        and "pred" when the step ends with the prediction drafter): its launches read everything else - the prediction, its
+        length, the drafter's state - from device memory.  The warm-up step advances the request's counters; they are put back
+        before the capture."""
         c = self._spec_cfg
-        key = ("spec", R, self.decode_weights, c.lookup_max, c.lookup_min) + (("pred",) if self._spec_pred else ())
+        cross = (("image" if self.has_image else "text"),) if self.dec_n_self != len(self.dec_layers) else ()
+        key = ("spec", R, self.decode_weights, c.lookup_max, c.lookup_min) + cross + (("pred",) if self._spec_pred else ())
         if key in self._spec_graphs:
             return self._spec_graphs[key]
         sp = self._spec

@@ -49,8 +49,9 @@ class Generation(DecodeStage):
     # generate_batch with ONE request takes the single-sequence loop: polled at the call's own interval (None, Qwen2-VL) or
     # at this one whatever the call said (Mllama: 32, the default ``chunk`` of its ``generate``).
     single_route_check_every = None
-    # generate(.., speculative=): the Qwen2-VL / Qwen2.5-VL engine only.  Mllama's cross-attention rows would need a
-    # draft form of their own (the static keys are shared, but the q_norm rows and the has_image skip are per step).
+    # generate(.., speculative=): the Qwen2-VL / Qwen2.5-VL engine, and an MllamaEngine built with speculative=True (its
+    # cross-attention rows take vis_decode_cross_attn_draft / _fp8_draft; the instance then sets this).  The class default -
+    # and with it an engine built without the keyword - refuses.
     speculative_supported = False
 
     # ------------------------------------------------------------------ hooks with a default
@@ -124,7 +125,8 @@ class Generation(DecodeStage):
         "num_speculative_tokens": k, "prompt_lookup_max": 4, "prompt_lookup_min": 2} (spec.py): a decode step carries the
         current token and up to k ids drafted by prompt lookup over prompt + reply through ONE pass over the weights and
         keeps the drafts the model's own greedy picks confirm - the reply is the plain reply token for token, in fewer
-        weight passes where the reply repeats earlier text.  Greedy single requests of the Qwen2-VL engines only: ValueError
+        weight passes where the reply repeats earlier text.  Greedy single requests of the Qwen2-VL engines, or of an
+        MllamaEngine built with speculative=True, only: ValueError
         with a temperature, a seed or any switch above (they advance one token at a time).  Afterwards ``last_timing`` holds
         ``spec_steps`` / ``spec_proposed`` / ``spec_accepted``.
         ``prediction``: a sequence of token ids the reply will probably repeat (OpenAI's Predicted Outputs; at most max_ctx
@@ -139,8 +141,9 @@ class Generation(DecodeStage):
             what = "speculative" if pred is None else "prediction (speculative decoding)"
             if not self.speculative_supported:
                 raise ValueError(("speculative decoding is" if pred is None else "prediction (speculative decoding) is") +
-                                 " offered by the Qwen2-VL / Qwen2.5-VL engine only: this engine's cross-attention rows "
-                                 "have no multi-row form")
+                                 " offered by the Qwen2-VL / Qwen2.5-VL engine only, unless an MllamaEngine is built for it: "
+                                 "MllamaEngine(.., speculative=True), or VIS_AUDITOR_SPECULATIVE=k (1..3) where the client "
+                                 "loads it")
             spec.check_exclusive(sp, temperature, seed, what=what, logprobs=logprobs, json_mode=json_mode, top_p=top_p,
                                  repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
                                  presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,

@@ -76,6 +76,8 @@ _SIGS = {
     "vis_shape_f32": "p" + "ii" + "p" + "i" + "ppppp" + "p" + "i" + "pp" + "i" + "p",
     "vis_ban_f32": "p" + "ii" + "p" + "i" + "pp" + "i" + "pppppp" + "i" + "p" + "i" + "p" + "ii" + "p",
     "vis_decode_attn_draft": "ppppppppp" + "iiiii" + "f" + "i" + "l" + "p",
+    "vis_decode_cross_attn_draft": "pppppppp" + "iiiii" + "ff" + "il" + "p",
+    "vis_decode_cross_attn_fp8_draft": "pppppppppp" + "iiiii" + "ff" + "il" + "p",
     "vis_spec_accept": "p" + "iii" + "pppppp" + "i" + "ppp" + "p",
     "vis_spec_draft": "pi" + "pp" + "i" + "pp" + "iiii" + "pp" + "p",
     "vis_spec_draft_pred": "pi" + "pp" + "i" + "pp" + "iiii" + "pi" + "pp" + "pp" + "p",
@@ -2168,6 +2170,54 @@ def decode_cross_attn_fp8_batch(q: torch.Tensor, q_norm_w: torch.Tensor, kq: tor
                                                 kq.shape[2], nsplit, scale, eps, B, q.stride(0), kq.stride(0), ksc.stride(0),
                                                 _stream())
     _check(rc, "vis_decode_cross_attn_fp8_batch")
+
+
+def _cross_draft_rows(name, q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit) -> int:
+    """The checks the two draft forms share -> the number of rows R."""
+    _bf16(q, "q"); _bf16(out, "out")
+    if q.dim() != 2 or not 1 <= q.shape[0] <= SPEC_MAX_ROWS or q.shape[1] != n_q * head_dim or q.stride(1) != 1 \
+            or (q.shape[0] > 1 and q.stride(0) < n_q * head_dim):
+        raise HipLibraryError(f"{name}: q must be [1..4, Hq * D] (rows of a wider buffer allowed)")
+    R = q.shape[0]
+    if out.shape != (R, n_q * head_dim) or not out.is_contiguous() or nkeys_m1.dtype != torch.int32 or nkeys_m1.numel() != 1:
+        raise HipLibraryError(f"{name}: bad out/nkeys")
+    if part_o.numel() < R * n_q * nsplit * head_dim or part_ml.numel() < R * n_q * nsplit * 2:
+        raise HipLibraryError(f"{name}: workspace too small")
+    return R
+
+
+def decode_cross_attn_draft(q: torch.Tensor, q_norm_w: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                            nkeys_m1: torch.Tensor, part_o: torch.Tensor, part_ml: torch.Tensor, out: torch.Tensor,
+                            n_q: int, n_kv: int, head_dim: int, nsplit: int, scale: float, eps: float) -> None:
+    """decode_cross_attn for the R = 1..4 rows of ONE sequence's speculative step (vis_decode_cross_attn_draft): q [R, Hq*128]
+    (a column slice of wider rows is fine), all rows over the same keys / values k, v [Hkv, T, 128] and the one count
+    nkeys_m1 [1]; out [R, Hq*128]; workspaces R x the single-row ones.  R * (Hq / Hkv) <= 16, or the library refuses.  Row r
+    is bit-identical to decode_cross_attn on q[r] alone."""
+    _bf16(k, "k"); _bf16(v, "v")
+    if k.dim() != 3 or k.shape != v.shape or k.shape[0] != n_kv or k.shape[2] != head_dim \
+            or not (k.is_contiguous() and v.is_contiguous()):
+        raise HipLibraryError("decode_cross_attn_draft: bad k/v")
+    R = _cross_draft_rows("decode_cross_attn_draft", q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit)
+    rc = load().vis_decode_cross_attn_draft(_ptr(q), _ptr(q_norm_w), _ptr(k), _ptr(v), _ptr(nkeys_m1), _ptr(part_o),
+                                            _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, k.shape[1], nsplit, scale, eps,
+                                            R, q.stride(0), _stream())
+    _check(rc, "vis_decode_cross_attn_draft")
+
+
+def decode_cross_attn_fp8_draft(q: torch.Tensor, q_norm_w: torch.Tensor, kq: torch.Tensor, ksc: torch.Tensor,
+                                vq: torch.Tensor, vsc: torch.Tensor, nkeys_m1: torch.Tensor, part_o: torch.Tensor,
+                                part_ml: torch.Tensor, out: torch.Tensor, n_q: int, n_kv: int, head_dim: int, nsplit: int,
+                                scale: float, eps: float) -> None:
+    """decode_cross_attn_draft over fp8 keys / values (decode_cross_attn_fp8's operands): row r is bit-identical to
+    decode_cross_attn_fp8 on q[r] alone."""
+    _cross_fp8_kv("decode_cross_attn_fp8_draft", kq, ksc, vq, vsc, 0, n_kv, head_dim)
+    if not (kq.is_contiguous() and vq.is_contiguous() and ksc.is_contiguous() and vsc.is_contiguous()):
+        raise HipLibraryError("decode_cross_attn_fp8_draft: bad codes/scales")
+    R = _cross_draft_rows("decode_cross_attn_fp8_draft", q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit)
+    rc = load().vis_decode_cross_attn_fp8_draft(_ptr(q), _ptr(q_norm_w), _ptr(kq), _ptr(ksc), _ptr(vq), _ptr(vsc),
+                                                _ptr(nkeys_m1), _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim,
+                                                kq.shape[1], nsplit, scale, eps, R, q.stride(0), _stream())
+    _check(rc, "vis_decode_cross_attn_fp8_draft")
 
 
 def patchify(img_u8: torch.Tensor, out: torch.Tensor, row0: int, mean, std) -> None:

@@ -115,7 +115,8 @@ class MllamaEngine(Generation):
             raise ValueError("cross_kv must be 'bf16' or 'fp8'")
 
     def __init__(self, cfg: MllamaConfig, weights: MllamaDeviceWeights, device, max_ctx: int = 4096, max_batch: int = 1,
-                 decode_weights: str = "bf16", mxfp4_gemm_from: Optional[int] = None, cross_kv: str = "bf16"):
+                 decode_weights: str = "bf16", mxfp4_gemm_from: Optional[int] = None, cross_kv: str = "bf16",
+                 speculative: bool = False):
         """decode_weights="fp8" / "mxfp4" (VIS_AUDITOR_DECODE_WEIGHTS), mxfp4_gemm_from (VIS_AUDITOR_MXFP4_GEMM_FROM): the
         decode projections of EVERY layer - a cross-attention layer's q projection too - and the lm_head are quantised at load
         and decoded as on the Qwen2-VL engine (Qwen2VLEngine.__init__ describes the formats and the two arithmetic families
@@ -124,11 +125,18 @@ class MllamaEngine(Generation):
         cross_kv="fp8" (VIS_AUDITOR_CROSS_KV): the decode step reads an e4m3 copy of the image's static cross-attention keys
         and values (codes + one f32 scale per key row, csrc/cross_kv.hip), written once per prompt pass from the bf16 rows;
         the bf16 rows stay (the prompt pass reads them), so the copy costs half as much memory again.  Independent of
-        decode_weights.  Everything defaults to bf16: the launches of an engine built without these keywords are unchanged."""
+        decode_weights.  Everything defaults to bf16: the launches of an engine built without these keywords are unchanged.
+        speculative=True (VIS_AUDITOR_SPECULATIVE): ``generate`` accepts ``speculative=`` / ``prediction=`` for one greedy
+        request - the lossless speculative step of the Qwen2-VL engines (DecodeStage._decode_step_spec), its cross-attention
+        layers on vis_decode_cross_attn_draft / _fp8_draft according to cross_kv; every decode_weights format.  Nothing is
+        allocated until the first such request, and a request without either argument issues the launches of before."""
         cfg.validate_for_kernels()
         self.check_decode_weights(cfg, decode_weights)
         self.check_mxfp4_gemm_from(cfg, decode_weights, mxfp4_gemm_from)
         self.check_cross_kv(cross_kv)
+        if not isinstance(speculative, bool):
+            raise ValueError("speculative must be True or False (the per-request k goes to generate)")
+        self.speculative_supported = speculative
         hip.load()
         if not torch.cuda.is_available():
             raise hip.HipLibraryError("MllamaEngine needs a ROCm GPU (no CPU fallback exists)")
@@ -593,6 +601,18 @@ class MllamaEngine(Generation):
         fn(q, L.w.q_norm, *kv, nkeys, self.part_o, self.part_ml, att, cfg.heads, cfg.kv_heads, cfg.head_dim, self.xsplit,
            cfg.head_dim ** -0.5, cfg.rms_eps)
 
+    def _decode_cross_attn_draft(self, L, q: torch.Tensor, att: torch.Tensor, R: int) -> None:
+        """The R rows of a speculative step over the image's static keys / values of cross layer ``L``: one pass over K / V for
+        all rows, row r bit-identical to ``_decode_cross_attn`` on row r (DecodeStage hook)."""
+        cfg, sp = self.cfg, self._spec
+        if self.cross_kv == "fp8":
+            fn = hip.decode_cross_attn_fp8_draft
+            kv = (self.xkq_b[0, L.idx], self.xks_b[0, L.idx], self.xvq_b[0, L.idx], self.xvs_b[0, L.idx])
+        else:
+            fn, kv = hip.decode_cross_attn_draft, (self.xk[L.idx], self.xv[L.idx])
+        fn(q, L.w.q_norm, *kv, self.nkeys_m1, sp.part_o, sp.part_ml, att[:R], cfg.heads, cfg.kv_heads, cfg.head_dim,
+           self.xsplit, cfg.head_dim ** -0.5, cfg.rms_eps)
+
     def _ensure_graph(self, chained: bool = False) -> torch.cuda.CUDAGraph:
         chained = chained and self.chain_sync is not None
         key = (self.temperature, self.seed, self.has_image, chained) + self._pick_key() + self._stop_key() + self._shape_key() + self._stream_key() + self._ban_key()
@@ -636,7 +656,8 @@ class MllamaEngine(Generation):
         ``stop_on_eos`` = not ignore_eos, ``chunk`` = check_every (the boundary at which a cancelled request ends) and
         ``frame`` the request's one image or None.  A reply that ended on EOS keeps its EOS token here; a ``max_new_tokens``
         the context cannot hold is clamped silently; after a stalled chained launch this engine stays on the separate
-        launches for good.  ``speculative`` or ``prediction`` other than None is refused (ValueError): the Qwen2-VL engines only."""
+        launches for good.  ``speculative`` or ``prediction`` other than None needs an engine built with speculative=True
+        (else ValueError: by default they are the Qwen2-VL engines'); the reply is then the plain reply, EOS token included."""
         return self._generate(input_ids, frame, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
                               logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
                               frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,

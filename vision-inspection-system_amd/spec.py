@@ -166,6 +166,31 @@ def check_rows_fit(cfg_model, rows: int) -> None:
         raise ValueError(f"speculative: {rows} rows of {width} inputs do not fit the multi-row GEMV's LDS")
 
 
+def check_cross_rows_fit(cfg_model, rows: int) -> None:
+    """The draft cross-attention kernels place every row's G = heads / kv_heads query heads of a kv group in the 16 columns of
+    one score MFMA (vis_decode_cross_attn_draft): rows * G <= 16."""
+    g = cfg_model.heads // cfg_model.kv_heads
+    if rows * g > 16:
+        raise ValueError(f"speculative: {rows} rows of {g} query heads per kv head do not fit the draft cross-attention "
+                         f"(rows * heads per kv head <= 16: at most k = {16 // g - 1})")
+
+
+def auditor_from_env() -> Optional[SpecConfig]:
+    """VIS_AUDITOR_SPECULATIVE=k (1..3; unset, empty or 0 = off; anything else: ValueError): the Auditor's (Mllama) engine is
+    built with speculative=True, the clients accept ``speculative`` / ``prediction`` for one request of an mllama model, and
+    the agents pass k on a single request to one.  VIS_SPECULATIVE is the Qwen2-VL engines' and is not read here."""
+    v = os.environ.get("VIS_AUDITOR_SPECULATIVE", "").strip()
+    if v in ("", "0"):
+        return None
+    try:
+        k = int(v)
+    except ValueError:
+        k = -1
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"VIS_AUDITOR_SPECULATIVE must be an integer in 0..{MAX_K}")
+    return check_speculative(k)
+
+
 # ----------------------------------------------------------------------------------------------------- references
 def propose(history: Sequence[int], k: int, lookup_max: int = 4, lookup_min: int = 2) -> List[int]:
     """Prompt lookup: for m from lookup_max down to lookup_min, the LATEST earlier occurrence of the last m ids of
@@ -289,7 +314,8 @@ def accept_ref(logits: np.ndarray, draft: Sequence[int], d: int, step: int, limi
 # --------------------------------------------------------------------------------------------------- device buffers
 class SpecBuffers:
     """What the speculative step of one engine owns: its own activation rows (an engine built with max_batch=1 has no
-    batched buffers), the attention workspace for 4 rows, the f32 logits of 4 rows, the id row [cur, drafts], the request's
+    batched buffers), the attention workspace for 4 rows (``n_split``: the largest split count of the launches that share
+    it - a model with cross-attention layers: max(nsplit, xsplit)), the f32 logits of 4 rows, the id row [cur, drafts], the request's
     prompt ids and the small device ints the launches read (draft count, limit, prompt length, start of the reply in the
     token row, counters), and for a request with a prediction its ids (max_ctx int32), their count and the drafter's state."""
 
