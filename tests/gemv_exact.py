@@ -15,6 +15,8 @@ doubled or misplaced 16-byte chunk shows as a wrong integer.
   dense, with eight of those columns adjusted so that the up sum of output i is non-zero and congruent to i modulo 32 (in
   units of 1, fp8: 1/4): any 32 consecutive outputs have different up values, so a wrong gate-up pairing or output index is
   off by far more than the one bf16 ulp silu_fast is allowed.
+* fused RMSNorm: x = +-c with c a power of two and integer norm weights, so that the staged row is sign * norm_w exactly
+  whatever rsqrtf's last bit (`norm_operands`, shared with tests/mxfp4_exact.py).
 * `walk` restates the kernels' task walk (p_begin / p_end, nseg, the A / B register ring) so that the CPU tests can check
   that every shape reaches the edge it was chosen for.
 
@@ -192,6 +194,69 @@ def padded(w, pad):
         wide = torch.full((N, K + pad), NAN_E4M3, dtype=torch.uint8)
     wide[:, :K] = w
     return wide
+
+
+# ----------------------------------------------------------------------------- exact RMSNorm prologue
+NORM_EPS = 1e-6
+
+
+def norm_operands(K, B, rng):
+    """Operands for which the fused RMSNorm prologue (gv_stage_x_rmsnorm) stages an EXACT row: x[b, k] = +-c_b with c_b a
+    power of two (1, 2, 1/2, 4 by row), norm_w integers in [-8, 8] (zeros included).  The sum of squares K c^2 is exact in
+    any order (every partial sum is n c^2, n <= K < 2^24), so is the division by K; rstd = rsqrt(c^2 + eps) misses 1 / c by
+    eps / 2 c^3 and a few f32 ulps, so x * rstd is +-1 up to far less than half a bf16 ulp (2^-9 below 1) - proved here in
+    float64 with 16 f32 ulps of slack for rsqrtf, the division and the product - and the staged row is sign * norm_w exactly.
+    Returns x [B, K] bf16, norm_w [K] bf16, staged [B, K] float64 (pairwise different sign patterns)."""
+    c = torch.tensor([1.0, 2.0, 0.5, 4.0], dtype=torch.float64)[torch.arange(B) % 4]
+    while True:
+        sign = torch.from_numpy(rng.integers(0, 2, (B, K)) * 2.0 - 1)
+        if len({r.numpy().tobytes() for r in sign}) == B:
+            break
+    nw = _draw(BF16_VALUES, (K,), rng)
+    x = sign * c[:, None]
+    ssq = (x * x).sum(1)
+    assert K < 2 ** 24 and torch.equal(ssq, K * c * c) and torch.equal((ssq.float() / float(K)).double(), c * c)
+    eps32 = float(np.float32(NORM_EPS))
+    rstd = 1.0 / torch.sqrt((c * c + eps32).float().double())       # the f32 argument, then float64
+    off = (c * rstd - 1.0).abs() + 16 * 2.0 ** -24
+    assert float(off.max()) < 2.0 ** -12, "x * rstd could leave the bf16 rounding interval of +-1"
+    assert torch.equal((x * rstd[:, None]).to(torch.bfloat16).double(), sign)
+    staged = sign * nw[None, :]
+    assert torch.equal(staged.to(torch.bfloat16).double(), staged)
+    return x.to(torch.bfloat16), nw.to(torch.bfloat16), staged
+
+
+@functools.lru_cache(maxsize=None)
+def bf16_norm_case(N, K, B=1):
+    """bf16_case behind the exact RMSNorm prologue: ref / ref_br = W @ (sign * norm_w) (+ bias + R), float64."""
+    rng = _rng(6, N, K, B)
+    w = _draw(BF16_VALUES, (N, K), rng).to(torch.bfloat16)
+    x, nw, staged = norm_operands(K, B, rng)
+    assert float(_matvec(w.float().abs(), staged.abs()).max()) < 2 ** 24
+    acc = _matvec(w, staged)
+    bias, R = _quarters((N,), rng), _quarters((B, N), rng)
+    return dict(x=x, norm_w=nw, W=w, bias=bias.to(torch.bfloat16), R=R.to(torch.bfloat16), ref=_exact_f32(acc, "sum"),
+                ref_br=_epilogue(acc, None, bias, R))
+
+
+@functools.lru_cache(maxsize=None)
+def fp8_norm_case(N, K, B=1):
+    """fp8_case behind the exact RMSNorm prologue."""
+    rng = _rng(7, N, K, B)
+    wq = _draw(FP8_CODES, (N, K), rng)
+    deq = E4M3[wq.long()]
+    x, nw, staged = norm_operands(K, B, rng)
+    assert float(_matvec(deq.abs(), staged.abs()).max()) * 4 < 2 ** 24
+    acc = _matvec(deq, staged)
+    scale = fp8_scales(N)
+    bias, R = _quarters((N,), rng), _quarters((B, N), rng)
+    zero = torch.zeros_like(bias)
+    return dict(x=x, norm_w=nw, Wq=wq, scale=scale.float(), bias=bias.to(torch.bfloat16), R=R.to(torch.bfloat16),
+                ref=_epilogue(acc, scale, zero, torch.zeros_like(R)), ref_br=_epilogue(acc, scale, bias, R))
+
+
+BF16_NORM_SHAPE = (6, 4104)      # 513 x-chunks: the re-reading loop of gv_stage_x_rmsnorm<false> (more than 512 chunks)
+FP8_NORM_SHAPE = (6, 8208)       # 1026 x-chunks: five passes of that loop
 
 
 # ----------------------------------------------------------------------------- f32 evaluation in a given order

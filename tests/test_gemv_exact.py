@@ -54,6 +54,25 @@ def test_rows_reference_is_order_independent(kind, N, K, B):
     assert len({tuple(r.tolist()) for r in c["x"]}) == B, "the input rows must differ"
 
 
+@pytest.mark.parametrize("kind", ["bf16", "fp8"])
+def test_norm_case_stages_sign_times_weight(kind):
+    """norm_operands proves in float64 that bf16(x * rstd) is +-1 (it asserts); here: the reference is the plain product with
+    sign * norm_w in two f32 orders, the shape takes the loop path of gv_stage_x_rmsnorm (more than 512 x-chunks), the norm
+    weights use all of -8 .. 8 and |x| is one power of two."""
+    N, K = G.BF16_NORM_SHAPE if kind == "bf16" else G.FP8_NORM_SHAPE
+    c = G.bf16_norm_case(N, K) if kind == "bf16" else G.fp8_norm_case(N, K)
+    assert K // 8 > 512 and (N, K) in (G.BF16_SHAPES if kind == "bf16" else G.FP8_SHAPES)
+    x, nw = c["x"][0].double(), c["norm_w"].double()
+    assert len(torch.unique(x.abs())) == 1 and float(torch.log2(x.abs()[0])) % 1 == 0
+    assert set(nw.tolist()) == set(range(-8, 9)) and len(torch.unique(torch.sign(x))) == 2
+    staged = torch.sign(x) * nw
+    w = c["W"].float() if kind == "bf16" else G.E4M3[c["Wq"].long()]
+    sc = 1.0 if kind == "bf16" else c["scale"].double()
+    for reverse in (False, True):
+        assert torch.equal(G.f32_sum(w, staged, 8 if kind == "bf16" else 16, reverse) * sc, c["ref"][0])
+    assert torch.equal(c["ref_br"][0], c["ref"][0] + c["bias"].double() + c["R"][0].double())
+
+
 def test_one_hot_columns_are_in_range():
     N, K = G.ONE_HOT_SHAPE
     assert (N, K) in G.BF16_SHAPES and max(G.ONE_HOT_K) == K - 1 and all(0 <= k < K for k in G.ONE_HOT_K)

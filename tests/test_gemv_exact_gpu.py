@@ -224,6 +224,28 @@ def test_fp8_rows_exact(hip, device, N, K, B):
         _check_rows(c, ob, B, N, dtype, f"gemv_fp8_rows B={B} {N}x{K} {dtype}")
 
 
+# ----------------------------------------------------------------------------- 6b. the fused RMSNorm prologue, exactly
+@pytest.mark.parametrize("kind", ["bf16", "fp8"])
+def test_fused_rmsnorm_stages_an_exact_row(hip, device, kind):
+    """gv_stage_x_rmsnorm<false> on gemv_exact.norm_operands: x = +-c, integer norm weights, so the staged row is
+    sign * norm_w whatever rsqrtf's last bit and the output equals float64 bit for bit.  (6, 4104) / (6, 8208): 513 / 1026
+    x-chunks, the loop path (more than 512 chunks) that no tolerance test runs with a norm."""
+    N, K = G.BF16_NORM_SHAPE if kind == "bf16" else G.FP8_NORM_SHAPE
+    c = G.bf16_norm_case(N, K) if kind == "bf16" else G.fp8_norm_case(N, K)
+    x, nw = c["x"][0].to(device), c["norm_w"].to(device)
+    bias, r = c["bias"].to(device), c["R"][0].to(device)
+    for dtype in (torch.float32, torch.bfloat16):
+        for full in (False, True):
+            kw = dict(bias=bias, residual=r) if full else {}
+            want = _expect((c["ref_br"] if full else c["ref"])[0], dtype)
+            y = _sentinel((N,), dtype, device)
+            if kind == "bf16":
+                hip.gemv(x, c["W"].to(device), y, norm_w=nw, eps=G.NORM_EPS, **kw)
+            else:
+                hip.gemv_fp8(x, c["Wq"].to(device), c["scale"].to(device), y, norm_w=nw, eps=G.NORM_EPS, **kw)
+            _same(y, want, f"{kind} gemv with norm {N}x{K} {dtype} bias+residual={full}")
+
+
 # ----------------------------------------------------------------------------- 7. ties in the fused argmax
 @pytest.mark.parametrize("N,K", G.ARGMAX_SHAPES, ids=_ids(G.ARGMAX_SHAPES))
 def test_argmax_ties_take_the_first_index(hip, device, N, K):
