@@ -202,15 +202,15 @@ def vis_env(env: dict):
 _WEIGHTS: dict = {}
 
 
-def _qwen(device, **kw):
+def _qwen(device, cfg=None, max_ctx: int = 256, **kw):
     from vision_inspection_system_amd.config import Qwen2VLConfig
     from vision_inspection_system_amd.engine import Qwen2VLEngine
     from vision_inspection_system_amd.tokenizer import ByteTokenizer
     from vision_inspection_system_amd.weights import pack_device_weights, synth_state_dict
-    cfg = Qwen2VLConfig.tiny()
-    if ("qwen", str(device)) not in _WEIGHTS:
-        _WEIGHTS[("qwen", str(device))] = pack_device_weights(cfg, synth_state_dict(cfg, seed=0), device)
-    eng = Qwen2VLEngine(cfg, _WEIGHTS[("qwen", str(device))], device, max_ctx=256, **kw)
+    cfg = cfg or Qwen2VLConfig.tiny()
+    if ("qwen", cfg, str(device)) not in _WEIGHTS:
+        _WEIGHTS[("qwen", cfg, str(device))] = pack_device_weights(cfg, synth_state_dict(cfg, seed=0), device)
+    eng = Qwen2VLEngine(cfg, _WEIGHTS[("qwen", cfg, str(device))], device, max_ctx=max_ctx, **kw)
     eng.tokenizer = ByteTokenizer(cfg.vocab, cfg.image_token_id, cfg.vision_start_id, cfg.vision_end_id, cfg.eos_ids)
     return cfg, eng
 

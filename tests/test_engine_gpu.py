@@ -306,7 +306,8 @@ def test_shared_text_prefix_is_bit_identical(device, monkeypatch, dtype):
     assert calls == [4]
     monkeypatch.setenv("VIS_MERGE_PREFILL", "0")
     apart = eng.generate_batch(four, max_new_tokens=8, ignore_eos=True)
-    assert calls == [4] and stacked == apart and torch.equal(logits_stacked, eng.logits_b[:4])
+    # (every text pass is a group now: forced apart, the four ran as four groups of one - and the prefix came from the cache)
+    assert calls == [4, 1, 1, 1, 1] and stacked == apart and torch.equal(logits_stacked, eng.logits_b[:4])
     assert stacked[0] == stacked[3] == shared[0]
     monkeypatch.delenv("VIS_MERGE_PREFILL")
     # prompts without a common text prefix, or with the image first, fall back to the plain pass

@@ -549,36 +549,26 @@ class Qwen2VLEngine(Generation):
                 slot: int = 0, split_vit: bool = True, image_embeds: Optional[torch.Tensor] = None,
                 prefix: Optional[dict] = None, collect_prefix: bool = False) -> Optional[dict]:
         """Run the prompt through the LLM, fill the KV cache of ``slot`` and pick the first token
-        (greedy when temperature == 0, Gumbel-max sampled otherwise).
-
-        ``prefix`` (from ``collect_prefix``): K / V / V^T of the first P tokens (P a multiple of 64, text only) computed by
-        another pass over the SAME leading tokens - the reference puts the ~1000-token inspection prompt in front of the
-        image (src/agents/vlm_inspector.py:462-470), so the images of a batch share it.  They are copied into this slot
-        and only rows P.. are computed; every row's arithmetic is unchanged (row-independent GEMMs, attention key tiles
-        on absolute 64-key boundaries), so the result is bit-identical to the full pass.
-        ``collect_prefix``: run rows 0..S-1 only (no lm_head, no token) and return that bundle."""
-        cfg, w, dev, bf = self.cfg, self.w, self.device, torch.bfloat16
+        (greedy when temperature == 0, Gumbel-max sampled otherwise): the tower over the request's frames, then the text
+        pass as a group of one (_prefill_group describes ``prefix``, ``collect_prefix`` and ``taps``).
+        image_embeds: the merged ViT output of these frames computed elsewhere (prefill_many batches the tower over
+        several requests' images)."""
         if not 0 <= slot < self.max_batch:
             raise ValueError("slot out of range")
-        self.temperature, self.seed = float(temperature), int(seed)
-        kcache, vcache = self.kcache_b[slot], self.vcache_b[slot]
-        cos_t, sin_t = self.cos_b[slot], self.sin_b[slot]
-        step, cur_token = self.step_b[slot:slot + 1], self.cur_b[slot:slot + 1]
-        tokens, logits = self.tokens_b[slot], self.logits_b[slot]
-        S = len(input_ids)
-        if S < 1 or S + 1 > self.max_ctx:
-            raise ValueError(f"prompt of {S} tokens does not fit the context of {self.max_ctx}")
-        ids_np = np.asarray(list(input_ids), dtype=np.int64)
-        if ids_np.min() < 0 or ids_np.max() >= cfg.vocab:
-            raise ValueError("token id out of range")
-        grids = [(1, f.shape[0] // cfg.patch, f.shape[1] // cfg.patch) for f in frames]
-        # decode rows: slot S + t carries rope position next_pos + t on all three axes
-        n_dec = self.max_ctx - S if max_new_tokens is None else min(self.max_ctx - S, max_new_tokens + 1)
-        # The M-RoPE tables (and the image-token scatter index) depend only on WHERE the image tokens sit, not on the
-        # text: the images of a batch inspection - and every request with the same prompt template and frame size -
-        # share them, so they are built once (host trigonometry + H2D) and kept on the device.
+        img = None
+        if len(frames):
+            img = image_embeds if image_embeds is not None else self.vision_forward(frames, split_rows=split_vit)
+        return self._prefill_group([(slot, input_ids, ids_dev, img)], prefix, temperature, seed, max_new_tokens, frames,
+                                   taps, collect_prefix)
+
+    def _rope_tables(self, ids_np: np.ndarray, grids: Sequence[tuple], n_dec: int) -> tuple:
+        """(cos, sin [S + n_dec, head_dim] f32, image-token scatter index) of a prompt structure, on the device.  The M-RoPE
+        tables depend only on WHERE the image tokens sit, not on the text: the images of a batch inspection - and every
+        request with the same prompt template and frame size - share them, so they are built once (host trigonometry + H2D)
+        and kept.  Decode rows: slot S + t carries rope position next_pos + t on all three axes."""
+        cfg, dev = self.cfg, self.device
         is_img = ids_np == cfg.image_token_id
-        key = (S, n_dec, tuple(grids), bool(is_img[0]), np.flatnonzero(np.diff(is_img.view(np.int8))).tobytes())
+        key = (len(ids_np), n_dec, tuple(grids), bool(is_img[0]), np.flatnonzero(np.diff(is_img.view(np.int8))).tobytes())
         hit = self._rope_cache.get(key)
         if hit is None:
             pos3, next_pos = rope_index(cfg, ids_np, grids)
@@ -591,247 +581,33 @@ class Qwen2VLEngine(Generation):
             if len(self._rope_cache) >= 16:
                 self._rope_cache.pop(next(iter(self._rope_cache)))
             self._rope_cache[key] = hit
-        cos_t[:S + n_dec].copy_(hit[0], non_blocking=True)
-        sin_t[:S + n_dec].copy_(hit[1], non_blocking=True)
-        img_idx_dev = hit[2]
-        if slot == 0:
-            self.decode_limit = S + n_dec
-        if ids_dev is None:
-            ids_dev = hip.upload(ids_np.astype(np.int32), dev)
-        H, Hq, Hkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
+        return hit
+
+    def _llm_layers(self, x: torch.Tensor, qkv: torch.Tensor, att: torch.Tensor, attend, taps: Optional[dict] = None) -> None:
+        """The decoder layers of the prompt pass over the M stacked rows of ``x`` (updated in place): bf16, or with every
+        projection on the fp8 MFMA and the norms fused into the per-row activation quantiser (prefill_dtype="fp8",
+        configs[4]).  ``attend(li)`` does rope / KV write / attention of layer li: it reads ``qkv`` and fills ``att``."""
+        cfg, w, dev, bf = self.cfg, self.w, self.device, torch.bfloat16
+        M, H = x.shape
         L = len(w.llm)
-        P = 0
-        if prefix is not None:
-            P = int(prefix["len"])
-            if P % 64 or not 0 < P < S or collect_prefix:
-                raise ValueError("bad shared prefix")
-            if not np.array_equal(ids_np[:P], prefix["ids"]):
-                raise ValueError("the shared prefix does not match this prompt")
-            if (ids_np[:P] == cfg.image_token_id).any():
-                raise ValueError("a shared prefix must be text only")
-        n = S - P                                   # rows computed here
-        x = torch.empty((n, H), dtype=bf, device=dev)
-        hip.gather_rows(w.embed, ids_dev[P:] if P else ids_dev, x)
-        if len(frames):
-            # image_embeds: the merged ViT output of these frames computed elsewhere (prefill_many batches the tower
-            # over several requests' images)
-            img = image_embeds if image_embeds is not None else self.vision_forward(frames, split_rows=split_vit)
-            if img_idx_dev.shape[0] != img.shape[0]:
-                raise ValueError(f"image tokens ({img_idx_dev.shape[0]}) and image features ({img.shape[0]}) do not match")
-            hip.scatter_rows(img, (img_idx_dev - P) if P else img_idx_dev, x)
-            if taps is not None:
-                taps["image_embeds"] = img
-        cos, sin = cos_t[P:S], sin_t[P:S]
-        # causal pass over rows P..S-1: 128-row query blocks paired latest-with-earliest, one pair per workgroup
-        # (hip.attn_prefill_pairs); VIS_ATTN_PAIRS=0 keeps one block per workgroup (A/B: same results, bit for bit)
-        pairs = os.environ.get("VIS_ATTN_PAIRS", "1") != "0"
-        if pairs:
-            work = self._pairs_cache.get((P, S))
-            if work is None:
-                if len(self._pairs_cache) >= 64:
-                    self._pairs_cache.clear()
-                work = self._pairs_cache[(P, S)] = hip.make_attn_pairs(P, S, dev)
-        elif P:
-            items = [(q0, min(128, S - q0), 0, S) for q0 in range(P, S, 128)]
-            items.sort(key=lambda it: -(it[0] + it[1]))
-            work = torch.tensor(items, dtype=torch.int32, device=dev).reshape(-1, 4).contiguous()
-        else:
-            work = hip.make_attn_work([(0, S)], True, dev)
-        self._causal_pairs = pairs
-        ld = _round_up(S, 64)
-        nq = (Hq + 2 * Hkv) * D
-        y = torch.empty((n, H), dtype=bf, device=dev)
-        qkv = torch.empty((n, nq), dtype=bf, device=dev)
-        q = torch.empty((Hq, n, D), dtype=bf, device=dev)
-        # V^T per layer: one buffer re-used by all layers, or - when a prefix is involved - one per layer, so that the
-        # prefix columns can be copied in (or handed out) in one go
-        per_layer_vt = bool(P) or collect_prefix
-        vt_all = torch.empty((L if per_layer_vt else 1, Hkv, D, ld), dtype=bf, device=dev)
-        if P:
-            kcache[:, :, :P].copy_(prefix["k"])
-            vcache[:, :, :P].copy_(prefix["v"])
-            vt_all[:, :, :, :P].copy_(prefix["vt"])
-        att = torch.empty((n, Hq * D), dtype=bf, device=dev)
-        act = torch.empty((n, cfg.intermediate), dtype=bf, device=dev)
-        scale = D ** -0.5
+        fp8 = self.prefill_dtype == "fp8"
+        act = torch.empty((M, cfg.intermediate), dtype=bf, device=dev)
         # The long-K down projection always runs as two K-slices (f32 partials, fixed-order sum): at S = 2249 its 126
         # 256x256 tiles would leave half the chip idle, and making the choice a function of the LAYER only (never of the
-        # row count) keeps every row's summation order the same in the full, the prefix and the suffix pass.
-        splitk_work = None
-        if cfg.intermediate >= 8192 and H % 8 == 0:
-            splitk_work = torch.empty(2 * n * H, dtype=torch.float32, device=dev)
-        if self.prefill_dtype == "fp8":
-            self._llm_layers_fp8(x, qkv, q, vt_all, att, act, cos, sin, kcache, vcache, work, n, taps, P)
-        else:
-            hip.rmsnorm(x, w.llm[0].ln1_w, cfg.rms_eps, out=y)
-            for li, lw in enumerate(w.llm):
-                vt = vt_all[li if per_layer_vt else 0]
-                hip.gemm(y, lw.qkv_w, bias=lw.qkv_b, out=qkv)
-                hip.qkv_rope_split(qkv, cos, sin, q, kcache[li], vcache[li], vt, Hq, Hkv, D, k_pos0=P, vt_col0=P)
-                if pairs:
-                    hip.attn_prefill_pairs(q, kcache[li], vt, att, work, scale, q_row0=P)
-                else:
-                    hip.attn_prefill(q, kcache[li], vt, att, work, True, scale, q_row0=P)
-                hip.gemm(att, lw.o_w, residual=x, out=x)
-                hip.rmsnorm(x, lw.ln2_w, cfg.rms_eps, out=y)
-                hip.gemm(y, lw.gateup_w, act=hip.ACT_SWIGLU, out=act)
-                nxt = w.llm[li + 1].ln1_w if li + 1 < L else None      # the next layer's input norm rides on the finalisation
-                if splitk_work is not None:      # long K, too few 256x256 tiles for the chip: two K-slices per tile
-                    hip.gemm_splitk_part(act, lw.down_w, splitk_work, 2)
-                    hip.splitk_finalize_norm(splitk_work, 2, x, residual=x, norm_w=nxt, y_out=y if nxt is not None else None,
-                                             eps=cfg.rms_eps)
-                else:
-                    hip.gemm(act, lw.down_w, residual=x, out=x)
-                    if nxt is not None:
-                        hip.rmsnorm(x, nxt, cfg.rms_eps, out=y)
-                if taps is not None and li == 0:
-                    taps["layer0"] = x.clone()
-        if collect_prefix:
-            Pn = (S // 64) * 64
-            return {"len": Pn, "ids": ids_np[:Pn].copy(), "k": kcache[:, :, :Pn].clone(), "v": vcache[:, :, :Pn].clone(),
-                    "vt": vt_all[:, :, :, :Pn].clone()}
-        # first token: final norm fused into the lm_head GEMV of the last position only
-        hip.gemv(x[n - 1], w.lm_head, logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
-        if taps is not None:
-            taps["first_logits"] = logits.clone()
-        step.fill_(S - 1)
-        self._prompt_pick(slot, ids_dev, logits, tokens, cur_token, step)
-        self.slot_prompt_len[slot] = S
-        if slot == 0:
-            self.prompt_len = S
-            self._decoded = 0
-        return None
-
-    def _llm_layers_fp8(self, x, qkv, q, vt_all, att, act, cos, sin, kcache, vcache, work, S, taps, P: int = 0) -> None:
-        """The decoder layers of the prompt pass with every projection on the fp8 MFMA (configs[4]).  S = rows computed
-        here, P = rows of a shared prefix already in the cache (vt_all: one V^T buffer per layer when it has > 1)."""
-        cfg, w, dev = self.cfg, self.w, self.device
-        H, Hq, Hkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
-        scale = D ** -0.5
-        xq = torch.empty((S, H), dtype=torch.uint8, device=dev)
-        aq = torch.empty((S, Hq * D), dtype=torch.uint8, device=dev)
-        hq = torch.zeros((S, self.kpad), dtype=torch.uint8, device=dev)      # pad columns stay 0 (= +0.0 in e4m3)
-        sx = torch.empty(S, dtype=torch.float32, device=dev)
-        dwork = torch.empty(2 * S * H, dtype=torch.float32, device=dev) \
-            if (self.kpad >= 8192 and H % 8 == 0) else None      # as in the bf16 pass: a function of the layer only
-        for li, lw in enumerate(w.llm):
-            q8 = self.q8[li]
-            vt = vt_all[li if vt_all.shape[0] > 1 else 0]
-            hip.quant_rows_fp8(x, xq, sx, norm_w=lw.ln1_w, eps=cfg.rms_eps)
-            hip.gemm_fp8(xq, sx, *q8["qkv_w"], bias=lw.qkv_b, out=qkv)
-            hip.qkv_rope_split(qkv, cos, sin, q, kcache[li], vcache[li], vt, Hq, Hkv, D, k_pos0=P, vt_col0=P)
-            if self._causal_pairs:
-                hip.attn_prefill_pairs(q, kcache[li], vt, att, work, scale, q_row0=P)
-            else:
-                hip.attn_prefill(q, kcache[li], vt, att, work, True, scale, q_row0=P)
-            hip.quant_rows_fp8(att, aq, sx)
-            hip.gemm_fp8(aq, sx, *q8["o_w"], residual=x, out=x)
-            hip.quant_rows_fp8(x, xq, sx, norm_w=lw.ln2_w, eps=cfg.rms_eps)
-            hip.gemm_fp8(xq, sx, *q8["gateup_w"], act=hip.ACT_SWIGLU, out=act)
-            hip.quant_rows_fp8(act, hq[:, :cfg.intermediate], sx)
-            hip.gemm_fp8(hq, sx, *q8.get("down_w_pad", q8["down_w"]), residual=x, out=x, work=dwork, ksplit=2)
-            if taps is not None and li == 0:
-                taps["layer0"] = x.clone()
-
-    def _prefill_group(self, items: Sequence[tuple], prefix: dict, temperature: float, seed: int,
-                       max_new_tokens: Optional[int]) -> None:
-        """The prompt pass of SEVERAL requests that share one text prefix and one prompt structure (the images of a batch
-        inspection: same template, same frame size) as ONE pass over their stacked suffix rows.
-
-        items: [(slot, input_ids, ids_dev or None, image_embeds)] - all prompts have the same length S and the image tokens
-        in the same places.  Per request n = S - P rows (7B bench prompt: 1289 = 5.04 row tiles of 256: a sixth of the LLM
-        GEMM tiles is padding, and the qkv / o projections fill 0.42 / 0.33 of a round of the chip); stacked, k requests
-        give k n rows (four: 20.1 tiles, 1.5 / 1.15 rounds).  Only the row-independent kernels see the stack - embedding
-        gather, projections, norms, finalisations; rope / KV write / attention run per request on its own rows, KV-cache
-        slot and V^T buffer.  Every row's arithmetic is what the single-request pass does (a projection's K order does
-        not depend on M, the down projection is two K-slices either way, key tiles are absolute), so tokens and logits
-        are bit-identical to it (tests/test_engine_gpu.py, test_fullsize_gpu.py)."""
-        cfg, w, dev, bf = self.cfg, self.w, self.device, torch.bfloat16
-        self.temperature, self.seed = float(temperature), int(seed)
-        k = len(items)
-        S = len(items[0][1])
-        P = int(prefix["len"])
-        n = S - P
-        H, Hq, Hkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
-        L = len(w.llm)
-        ids0 = np.asarray(list(items[0][1]), dtype=np.int64)
-        is_img = ids0 == cfg.image_token_id
-        grids_n = int(is_img.sum())
-        n_dec = self.max_ctx - S if max_new_tokens is None else min(self.max_ctx - S, max_new_tokens + 1)
-        ld = _round_up(S, 64)
-        nq = (Hq + 2 * Hkv) * D
-        x = torch.empty((k * n, H), dtype=bf, device=dev)
-        tabs = None
-        ids_devs = []
-        for j, (slot, ids, ids_dev, img) in enumerate(items):
-            ids_np = np.asarray(list(ids), dtype=np.int64)
-            if len(ids_np) != S or not np.array_equal(ids_np == cfg.image_token_id, is_img) or \
-                    not np.array_equal(ids_np[:P], prefix["ids"]) or img.shape[0] != grids_n:
-                raise ValueError("_prefill_group: the prompts of a group must share length, image positions and prefix")
-            if ids_np.min() < 0 or ids_np.max() >= cfg.vocab:
-                raise ValueError("token id out of range")
-            if tabs is None:     # rope tables / scatter index: one structure for the whole group (cached per structure)
-                key = ("grp", S, n_dec, grids_n, bool(is_img[0]), np.flatnonzero(np.diff(is_img.view(np.int8))).tobytes())
-                tabs = self._rope_cache.get(key)
-                if tabs is None:
-                    raise ValueError("_prefill_group: rope tables missing (prefill_many prepares them)")
-            self.cos_b[slot][:S + n_dec].copy_(tabs[0], non_blocking=True)
-            self.sin_b[slot][:S + n_dec].copy_(tabs[1], non_blocking=True)
-            if ids_dev is None:
-                ids_dev = hip.upload(ids_np.astype(np.int32), dev)
-            ids_devs.append(ids_dev)
-            xj = x[j * n:(j + 1) * n]
-            hip.gather_rows(w.embed, ids_dev[P:], xj)
-            hip.scatter_rows(img, tabs[2] - P, xj)
-            self.kcache_b[slot][:, :, :P].copy_(prefix["k"])
-            self.vcache_b[slot][:, :, :P].copy_(prefix["v"])
-        s0 = items[0][0]                      # every slot of the group now holds the same (contiguous) tables
-        cos, sin = self.cos_b[s0][P:S], self.sin_b[s0][P:S]
-        work = self._pairs_cache.get((P, S))
-        if work is None:
-            if len(self._pairs_cache) >= 64:
-                self._pairs_cache.clear()
-            work = self._pairs_cache[(P, S)] = hip.make_attn_pairs(P, S, dev)
-        y = torch.empty((k * n, H), dtype=bf, device=dev)
-        qkv = torch.empty((k * n, nq), dtype=bf, device=dev)
-        q = torch.empty((k, Hq, n, D), dtype=bf, device=dev)
-        vt_all = torch.empty((k, L, Hkv, D, ld), dtype=bf, device=dev)
-        for j in range(k):
-            vt_all[j][:, :, :, :P].copy_(prefix["vt"])
-        att = torch.empty((k * n, Hq * D), dtype=bf, device=dev)
-        act = torch.empty((k * n, cfg.intermediate), dtype=bf, device=dev)
-        scale = D ** -0.5
-        splitk_work = torch.empty(2 * k * n * H, dtype=torch.float32, device=dev) \
-            if (cfg.intermediate >= 8192 and H % 8 == 0 and self.prefill_dtype != "fp8") else None
-
-        slots = [it[0] for it in items]
-        T = self.kcache_b.shape[3]
-        many = self.group_attn and k > 1 and k <= hip.MAX_GROUP_REQUESTS and self.kcache_b.is_contiguous()
-
-        def attend(li):        # rope / KV write / attention: per request, on its rows, cache slot and V^T buffer
-            if many:           # ... as ONE launch each for the whole group (r05: a 1289-row suffix alone fills a third of the chip)
-                kv_off = [sl * self.kcache_b.stride(0) + li * self.kcache_b.stride(1) for sl in slots]
-                vt_l = vt_all[:, li]
-                hip.qkv_rope_split_many(qkv, cos, sin, q, self.kcache_b, self.vcache_b, vt_l, Hq, Hkv, D, kv_off, T,
-                                        k_pos0=P, vt_col0=P)
-                hip.attn_prefill_pairs_many(q, self.kcache_b, vt_l, att, work, scale, kv_off, T, q_row0=P)
-                return
-            for j, (slot, _, _, _) in enumerate(items):
-                rows = slice(j * n, (j + 1) * n)
-                kc, vc, vt = self.kcache_b[slot][li], self.vcache_b[slot][li], vt_all[j][li]
-                hip.qkv_rope_split(qkv[rows], cos, sin, q[j], kc, vc, vt, Hq, Hkv, D, k_pos0=P, vt_col0=P)
-                hip.attn_prefill_pairs(q[j], kc, vt, att[rows], work, scale, q_row0=P)
-
-        if self.prefill_dtype == "fp8":
-            # configs[4]: every projection on the fp8 MFMA; the per-token activation quantiser is row-wise, so it stacks
-            # like the projections do (the layer body of _llm_layers_fp8 over k n rows)
-            M = k * n
+        # row count) keeps every row's summation order the same alone, in a group, and in the full, prefix and suffix pass.
+        swork = None
+        if (self.kpad if fp8 else cfg.intermediate) >= 8192 and H % 8 == 0:
+            swork = torch.empty(2 * M * H, dtype=torch.float32, device=dev)
+        if fp8:
             xq = torch.empty((M, H), dtype=torch.uint8, device=dev)
-            aq = torch.empty((M, Hq * D), dtype=torch.uint8, device=dev)
-            hq = torch.zeros((M, self.kpad), dtype=torch.uint8, device=dev)
+            aq = torch.empty((M, att.shape[1]), dtype=torch.uint8, device=dev)
+            hq = torch.zeros((M, self.kpad), dtype=torch.uint8, device=dev)      # pad columns stay 0 (= +0.0 in e4m3)
             sx = torch.empty(M, dtype=torch.float32, device=dev)
-            dwork = torch.empty(2 * M * H, dtype=torch.float32, device=dev) if (self.kpad >= 8192 and H % 8 == 0) else None
-            for li, lw in enumerate(w.llm):
+        else:
+            y = torch.empty((M, H), dtype=bf, device=dev)
+            hip.rmsnorm(x, w.llm[0].ln1_w, cfg.rms_eps, out=y)
+        for li, lw in enumerate(w.llm):
+            if fp8:
                 q8 = self.q8[li]
                 hip.quant_rows_fp8(x, xq, sx, norm_w=lw.ln1_w, eps=cfg.rms_eps)
                 hip.gemm_fp8(xq, sx, *q8["qkv_w"], bias=lw.qkv_b, out=qkv)
@@ -841,64 +617,178 @@ class Qwen2VLEngine(Generation):
                 hip.quant_rows_fp8(x, xq, sx, norm_w=lw.ln2_w, eps=cfg.rms_eps)
                 hip.gemm_fp8(xq, sx, *q8["gateup_w"], act=hip.ACT_SWIGLU, out=act)
                 hip.quant_rows_fp8(act, hq[:, :cfg.intermediate], sx)
-                hip.gemm_fp8(hq, sx, *q8.get("down_w_pad", q8["down_w"]), residual=x, out=x, work=dwork, ksplit=2)
-        else:
-            hip.rmsnorm(x, w.llm[0].ln1_w, cfg.rms_eps, out=y)
-        for li, lw in enumerate(w.llm if self.prefill_dtype != "fp8" else ()):
-            hip.gemm(y, lw.qkv_w, bias=lw.qkv_b, out=qkv)
-            attend(li)
-            hip.gemm(att, lw.o_w, residual=x, out=x)
-            hip.rmsnorm(x, lw.ln2_w, cfg.rms_eps, out=y)
-            hip.gemm(y, lw.gateup_w, act=hip.ACT_SWIGLU, out=act)
-            nxt = w.llm[li + 1].ln1_w if li + 1 < L else None
-            if splitk_work is not None:
-                hip.gemm_splitk_part(act, lw.down_w, splitk_work, 2)
-                hip.splitk_finalize_norm(splitk_work, 2, x, residual=x, norm_w=nxt, y_out=y if nxt is not None else None,
-                                         eps=cfg.rms_eps)
+                hip.gemm_fp8(hq, sx, *q8.get("down_w_pad", q8["down_w"]), residual=x, out=x, work=swork, ksplit=2)
             else:
-                hip.gemm(act, lw.down_w, residual=x, out=x)
-                if nxt is not None:
-                    hip.rmsnorm(x, nxt, cfg.rms_eps, out=y)
-        # lm_head over the last rows of the whole group in ONE pass over its 1.09 GB (vis_gemv_bf16_rows: every row bit-identical to
-        # the single-row GEMV) instead of one pass per request; VIS_GROUP_ATTN=0 keeps the per-request calls
+                hip.gemm(y, lw.qkv_w, bias=lw.qkv_b, out=qkv)
+                attend(li)
+                hip.gemm(att, lw.o_w, residual=x, out=x)
+                hip.rmsnorm(x, lw.ln2_w, cfg.rms_eps, out=y)
+                hip.gemm(y, lw.gateup_w, act=hip.ACT_SWIGLU, out=act)
+                nxt = w.llm[li + 1].ln1_w if li + 1 < L else None      # the next layer's input norm rides on the finalisation
+                if swork is not None:
+                    hip.gemm_splitk_part(act, lw.down_w, swork, 2)
+                    hip.splitk_finalize_norm(swork, 2, x, residual=x, norm_w=nxt, y_out=y if nxt is not None else None,
+                                             eps=cfg.rms_eps)
+                else:
+                    hip.gemm(act, lw.down_w, residual=x, out=x)
+                    if nxt is not None:
+                        hip.rmsnorm(x, nxt, cfg.rms_eps, out=y)
+            if taps is not None and li == 0:
+                taps["layer0"] = x.clone()
+
+    def _prefill_group(self, items: Sequence[tuple], prefix: Optional[dict], temperature: float, seed: int,
+                       max_new_tokens: Optional[int], frames: Sequence[torch.Tensor] = (), taps: Optional[dict] = None,
+                       collect_prefix: bool = False) -> Optional[dict]:
+        """The text prompt pass of k >= 1 requests with one prompt structure over their stacked rows - the engine's only
+        text pass: ``prefill`` is a group of one, the images of a batch inspection (same template, same frame size, one
+        text prefix) are a group of several.
+
+        items: [(slot, input_ids, ids_dev or None, image_embeds or None)] - all prompts have the same length S and the
+        image tokens in the same places; ``frames``: the first request's (the sizes are the group's).
+        ``prefix`` (from ``collect_prefix``): K / V / V^T of the first P tokens (P a multiple of 64, text only) computed by
+        another pass over the SAME leading tokens - the reference puts the ~1000-token inspection prompt in front of the
+        image (src/agents/vlm_inspector.py:462-470), so the images of a batch share it.  They are copied into every slot
+        and only rows P.. are computed; every row's arithmetic is unchanged (row-independent GEMMs, attention key tiles
+        on absolute 64-key boundaries), so the result is bit-identical to the full pass.
+        ``collect_prefix`` (a group of one): run rows 0..S-1 only (no lm_head, no token) and return that bundle.
+        ``taps`` (a group of one): image_embeds, layer0, first_logits.
+
+        Per request n = S - P rows (7B bench prompt: 1289 = 5.04 row tiles of 256: a sixth of the LLM GEMM tiles is
+        padding, and the qkv / o projections fill 0.42 / 0.33 of a round of the chip); stacked, k requests give k n rows
+        (four: 20.1 tiles, 1.5 / 1.15 rounds).  Only the row-independent kernels see the stack - embedding gather,
+        projections, norms, finalisations; rope / KV write / attention run per request on its own rows, KV-cache slot and
+        V^T buffer, and a group of one issues exactly one request's launches.  A projection's K order does not depend on
+        M, the down projection is two K-slices either way and key tiles are absolute, so a request's tokens and logits do
+        not depend on its group (tests/test_engine_gpu.py, test_fullsize_gpu.py, test_qwen_prompt_pass_gpu.py)."""
+        cfg, w, dev, bf = self.cfg, self.w, self.device, torch.bfloat16
+        self.temperature, self.seed = float(temperature), int(seed)
+        k = len(items)
+        if k > 1 and (taps is not None or collect_prefix):
+            raise ValueError("_prefill_group: taps and collect_prefix need a group of one")
+        ids0 = np.asarray(list(items[0][1]), dtype=np.int64)
+        S = len(ids0)
+        if S < 1 or S + 1 > self.max_ctx:
+            raise ValueError(f"prompt of {S} tokens does not fit the context of {self.max_ctx}")
+        P = 0
+        if prefix is not None:
+            P = int(prefix["len"])
+            if P % 64 or not 0 < P < S or collect_prefix:
+                raise ValueError("bad shared prefix")
+            if (ids0[:P] == cfg.image_token_id).any():
+                raise ValueError("a shared prefix must be text only")
+        n = S - P                                   # rows computed here, per request
+        H, Hq, Hkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
+        L = len(w.llm)
+        n_dec = self.max_ctx - S if max_new_tokens is None else min(self.max_ctx - S, max_new_tokens + 1)
+        grids = [(1, f.shape[0] // cfg.patch, f.shape[1] // cfg.patch) for f in frames]
+        cos_all, sin_all, img_idx = self._rope_tables(ids0, grids, n_dec)
+        is_img = ids0 == cfg.image_token_id
+        ld = _round_up(S, 64)
+        x = torch.empty((k * n, H), dtype=bf, device=dev)
+        # V^T per layer: one buffer re-used by all layers, or - when a prefix is involved - one per layer, so that the
+        # prefix columns can be copied in (or handed out) in one go
+        per_layer_vt = bool(P) or collect_prefix
+        vt_all = torch.empty((k, L if per_layer_vt else 1, Hkv, D, ld), dtype=bf, device=dev)
+        ids_devs = []
+        for j, (slot, ids, ids_dev, img) in enumerate(items):
+            ids_np = np.asarray(list(ids), dtype=np.int64)
+            if len(ids_np) != S or not np.array_equal(ids_np == cfg.image_token_id, is_img):
+                raise ValueError("_prefill_group: the prompts of a group must share length and image positions")
+            if P and not np.array_equal(ids_np[:P], prefix["ids"]):
+                raise ValueError("the shared prefix does not match this prompt")
+            if ids_np.min() < 0 or ids_np.max() >= cfg.vocab:
+                raise ValueError("token id out of range")
+            n_feat = 0 if img is None else img.shape[0]
+            if n_feat != img_idx.shape[0]:
+                raise ValueError(f"image tokens ({img_idx.shape[0]}) and image features ({n_feat}) do not match")
+            self.cos_b[slot][:S + n_dec].copy_(cos_all, non_blocking=True)
+            self.sin_b[slot][:S + n_dec].copy_(sin_all, non_blocking=True)
+            if slot == 0:
+                self.decode_limit = S + n_dec
+            if ids_dev is None:
+                ids_dev = hip.upload(ids_np.astype(np.int32), dev)
+            ids_devs.append(ids_dev)
+            xj = x[j * n:(j + 1) * n]
+            hip.gather_rows(w.embed, ids_dev[P:] if P else ids_dev, xj)
+            if img is not None:
+                hip.scatter_rows(img, (img_idx - P) if P else img_idx, xj)
+            if P:
+                self.kcache_b[slot][:, :, :P].copy_(prefix["k"])
+                self.vcache_b[slot][:, :, :P].copy_(prefix["v"])
+                vt_all[j][:, :, :, :P].copy_(prefix["vt"])
+        if taps is not None and items[0][3] is not None:
+            taps["image_embeds"] = items[0][3]
+        slots = [it[0] for it in items]
+        s0 = slots[0]                         # every slot of the group now holds the same (contiguous) tables
+        cos, sin = self.cos_b[s0][P:S], self.sin_b[s0][P:S]
+        # causal pass over rows P..S-1: 128-row query blocks paired latest-with-earliest, one pair per workgroup
+        # (hip.attn_prefill_pairs); VIS_ATTN_PAIRS=0 keeps one block per workgroup (A/B: same results, bit for bit) - for a
+        # group of one, the only pass there was when the switch was measured; a group of several ignores it
+        pairs = k > 1 or os.environ.get("VIS_ATTN_PAIRS", "1") != "0"
+        if pairs:
+            work = self._pairs_cache.get((P, S))
+            if work is None:
+                if len(self._pairs_cache) >= 64:
+                    self._pairs_cache.clear()
+                work = self._pairs_cache[(P, S)] = hip.make_attn_pairs(P, S, dev)
+        elif P:
+            blocks = [(q0, min(128, S - q0), 0, S) for q0 in range(P, S, 128)]
+            blocks.sort(key=lambda it: -(it[0] + it[1]))
+            work = torch.tensor(blocks, dtype=torch.int32, device=dev).reshape(-1, 4).contiguous()
+        else:
+            work = hip.make_attn_work([(0, S)], True, dev)
+        qkv = torch.empty((k * n, (Hq + 2 * Hkv) * D), dtype=bf, device=dev)
+        q = torch.empty((k, Hq, n, D), dtype=bf, device=dev)
+        att = torch.empty((k * n, Hq * D), dtype=bf, device=dev)
+        scale = D ** -0.5
+        T = self.kcache_b.shape[3]
+        many = self.group_attn and 1 < k <= hip.MAX_GROUP_REQUESTS and self.kcache_b.is_contiguous()
+
+        def attend(li):        # rope / KV write / attention: per request, on its rows, cache slot and V^T buffer
+            lv = li if per_layer_vt else 0
+            if many:           # ... as ONE launch each for the whole group (r05: a 1289-row suffix alone fills a third of the chip)
+                kv_off = [sl * self.kcache_b.stride(0) + li * self.kcache_b.stride(1) for sl in slots]
+                vt_l = vt_all[:, lv]
+                hip.qkv_rope_split_many(qkv, cos, sin, q, self.kcache_b, self.vcache_b, vt_l, Hq, Hkv, D, kv_off, T,
+                                        k_pos0=P, vt_col0=P)
+                hip.attn_prefill_pairs_many(q, self.kcache_b, vt_l, att, work, scale, kv_off, T, q_row0=P)
+                return
+            for j, slot in enumerate(slots):
+                rows = slice(j * n, (j + 1) * n)
+                kc, vc, vt = self.kcache_b[slot][li], self.vcache_b[slot][li], vt_all[j][lv]
+                hip.qkv_rope_split(qkv[rows], cos, sin, q[j], kc, vc, vt, Hq, Hkv, D, k_pos0=P, vt_col0=P)
+                if pairs:
+                    hip.attn_prefill_pairs(q[j], kc, vt, att[rows], work, scale, q_row0=P)
+                else:
+                    hip.attn_prefill(q[j], kc, vt, att[rows], work, True, scale, q_row0=P)
+
+        self._llm_layers(x, qkv, att, attend, taps)
+        if collect_prefix:
+            Pn = (S // 64) * 64
+            return {"len": Pn, "ids": ids0[:Pn].copy(), "k": self.kcache_b[s0][:, :, :Pn].clone(),
+                    "v": self.vcache_b[s0][:, :, :Pn].clone(), "vt": vt_all[0][:, :, :, :Pn].clone()}
+        # first token: final norm fused into the lm_head GEMV of every request's last position only - for a group of 2..4 in
+        # ONE pass over its 1.09 GB (vis_gemv_bf16_rows: every row bit-identical to the single-row GEMV) instead of one pass
+        # per request; VIS_GROUP_ATTN=0 keeps the per-request calls
         grouped = self.group_attn and 1 < k <= 4 and H * 2 * (2 if k <= 2 else 4) <= 152 * 1024
         if grouped:
             lg = torch.empty((k, self.logits_b.shape[1]), dtype=torch.float32, device=dev)
             hip.gemv_rows(x[n - 1::n], w.lm_head, lg, norm_w=w.final_norm_w, eps=cfg.rms_eps)
-        for j, (slot, _, _, _) in enumerate(items):
+        for j, slot in enumerate(slots):
             logits = self.logits_b[slot]
             if grouped:
                 logits.copy_(lg[j])
             else:
                 hip.gemv(x[(j + 1) * n - 1], w.lm_head, logits, norm_w=w.final_norm_w, eps=cfg.rms_eps)
+            if taps is not None:
+                taps["first_logits"] = logits.clone()
             self.step_b[slot:slot + 1].fill_(S - 1)
             self._prompt_pick(slot, ids_devs[j], logits, self.tokens_b[slot], self.cur_b[slot:slot + 1], self.step_b[slot:slot + 1])
             self.slot_prompt_len[slot] = S
             if slot == 0:
                 self.prompt_len = S
                 self._decoded = 0
-                self.decode_limit = S + n_dec
-
-    def _group_tables(self, ids: Sequence[int], n_img_tokens: int, max_new_tokens: Optional[int], frames) -> None:
-        """Rope tables + image-token scatter index of a prompt structure, under the key _prefill_group looks up."""
-        cfg, dev = self.cfg, self.device
-        ids_np = np.asarray(list(ids), dtype=np.int64)
-        S = len(ids_np)
-        is_img = ids_np == cfg.image_token_id
-        n_dec = self.max_ctx - S if max_new_tokens is None else min(self.max_ctx - S, max_new_tokens + 1)
-        key = ("grp", S, n_dec, n_img_tokens, bool(is_img[0]), np.flatnonzero(np.diff(is_img.view(np.int8))).tobytes())
-        if key in self._rope_cache:
-            return
-        grids = [(1, f.shape[0] // cfg.patch, f.shape[1] // cfg.patch) for f in frames]
-        pos3, next_pos = rope_index(cfg, ids_np, grids)
-        cos_np, sin_np = mrope_cos_sin(cfg, pos3)
-        dpos = np.broadcast_to((next_pos + np.arange(n_dec))[None, :], (3, n_dec))
-        dcos, dsin = mrope_cos_sin(cfg, dpos)
-        img_idx = np.nonzero(is_img)[0].astype(np.int32)
-        if len(self._rope_cache) >= 16:
-            self._rope_cache.pop(next(iter(self._rope_cache)))
-        self._rope_cache[key] = (torch.from_numpy(np.concatenate([cos_np, dcos])).to(dev),
-                                 torch.from_numpy(np.concatenate([sin_np, dsin])).to(dev), torch.from_numpy(img_idx).to(dev))
+        return None
 
     def prefill_many(self, requests: Sequence, temperature: float = 0.0,
                      seed: int = 0, max_new_tokens: Optional[int] = None,
@@ -961,6 +851,12 @@ class Qwen2VLEngine(Generation):
                 unshared[0] = True
             return shared if hit else None
 
+        def place(slot, b):       # request b's own switches, where the picks of its slot read them
+            for table, rows in ((self._slot_seed, seeds), (self._slot_pen, penalties), (self._slot_shape, shaping),
+                                (self._slot_ban, ban)):
+                if rows is not None:
+                    table[slot] = rows[b]
+
         self.batch_shared_len = 0
 
         next_slot = 0
@@ -969,14 +865,7 @@ class Qwen2VLEngine(Generation):
                 r = get(b)
                 if r is None:
                     continue
-                if seeds is not None:
-                    self._slot_seed[next_slot] = seeds[b]
-                if penalties is not None:
-                    self._slot_pen[next_slot] = penalties[b]
-                if shaping is not None:
-                    self._slot_shape[next_slot] = shaping[b]
-                if ban is not None:
-                    self._slot_ban[next_slot] = ban[b]
+                place(next_slot, b)
                 self.prefill(r[0], r[1], ids_dev=ids_dev[b] if ids_dev else None, temperature=temperature, seed=seed,
                              max_new_tokens=max_new_tokens, slot=next_slot, prefix=prefix_for(r[0]))
                 slots[b] = next_slot
@@ -1019,14 +908,8 @@ class Qwen2VLEngine(Generation):
                     if len(same) >= 2:
                         merged = same
             slot_of = {b: next_slot + i for i, b in enumerate(grp_all)}       # slots follow the request order
-            if seeds is not None:
-                self._slot_seed.update({slot_of[b]: seeds[b] for b in grp_all})
-            if penalties is not None:
-                self._slot_pen.update({slot_of[b]: penalties[b] for b in grp_all})
-            if shaping is not None:
-                self._slot_shape.update({slot_of[b]: shaping[b] for b in grp_all})
-            if ban is not None:
-                self._slot_ban.update({slot_of[b]: ban[b] for b in grp_all})
+            for b in grp_all:
+                place(slot_of[b], b)
             next_slot += len(grp_all)
             if merged:
                 st = streams[(g0 // vb) % n_streams]         # consecutive groups alternate streams
@@ -1040,9 +923,7 @@ class Qwen2VLEngine(Generation):
                         embeds[b].record_stream(st)
                         items.append((slot_of[b], ids, ids_dev[b] if ids_dev else None, embeds[b]))
                         slots[b] = slot_of[b]
-                    self._group_tables(resolved[merged[0]][0], int(embeds[merged[0]].shape[0]), max_new_tokens,
-                                       resolved[merged[0]][1])
-                    self._prefill_group(items, shared, temperature, seed, max_new_tokens)
+                    self._prefill_group(items, shared, temperature, seed, max_new_tokens, resolved[merged[0]][1])
             for b in grp_all:
                 if b in merged:
                     continue
