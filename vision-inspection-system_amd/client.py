@@ -221,22 +221,22 @@ class _Completions:
                stream_options: Optional[dict] = None, no_repeat_ngram_size: Optional[int] = None,
                bad_words: Optional[list] = None, min_tokens: Optional[int] = None, speculative=None,
                prediction: Optional[dict] = None, **kwargs):
-        """``stream=True``: an iterator of ChatCompletionChunk instead of a ChatCompletion (``stream_options``: OpenAI's
+        """One request; LocalVLMClient._complete_many describes the keywords not described here.
+        ``stream=True``: an iterator of ChatCompletionChunk instead of a ChatCompletion (``stream_options``: OpenAI's
         {"include_usage": True}); None or False: the call of before.
         ``speculative`` (extension; vLLM's names): {"method": "ngram", "num_speculative_tokens": k in 1..3[,
-        "prompt_lookup_max": 4, "prompt_lookup_min": 2]} - lossless n-gram speculative decoding (spec.py): the same text
-        and usage in fewer weight passes where the reply repeats earlier text.  A greedy single request of a Qwen2-VL model
-        only: ValueError with a temperature, a seed, ``n`` > 1 or any other sampling / constraint / stop / stream / logprobs
-        keyword.  None: the call of before.
+        "prompt_lookup_max": 4, "prompt_lookup_min": 2]} - lossless n-gram speculative decoding (request.Switches says how):
+        the same text and usage in fewer weight passes where the reply repeats earlier text.  A greedy single request of a
+        Qwen2-VL model only: ValueError with a temperature, a seed, ``n`` > 1 or any other sampling / constraint / stop /
+        stream / logprobs keyword.  None: the call of before.
         ``prediction`` (OpenAI's Predicted Outputs): {"type": "content", "content": text} - or content as a list of {"type":
         "text", "text": ...} parts - text the reply will probably repeat: the previous reply of a retry, the report of an
-        earlier inspection of the same part, a fixed template.  The speculative step drafts from it (vis_spec_draft_pred) and
-        from prompt lookup where the reply leaves it; the text and finish_reason are those of the call without it, and
-        ``usage["completion_tokens_details"]`` = {"accepted_prediction_tokens", "rejected_prediction_tokens"} counts the
-        prediction's drafts the steps kept and did not keep (over every step issued: those of a poll interval that ran past
-        an EOS included).  Alone it implies speculative = {"method": "ngram", "num_speculative_tokens": 3,
-        "prompt_lookup_max": 4, "prompt_lookup_min": 2}; ``speculative`` next to it sets k and the window.  The conditions
-        and refusals of ``speculative``; an empty text is no prediction.  None: the call of before."""
+        earlier inspection of the same part, a fixed template.  The speculative step drafts from it; the text and
+        finish_reason are those of the call without it, and ``usage["completion_tokens_details"]`` = {"accepted_prediction_tokens",
+        "rejected_prediction_tokens"} counts the prediction's drafts the steps kept and did not keep (over every step issued:
+        those of a poll interval that ran past an EOS included).  Alone it implies k = 3 and the lookup window 4..2;
+        ``speculative`` next to it sets them.  The conditions and refusals of ``speculative``; an empty text is no
+        prediction.  None: the call of before."""
         from .stream import check_stream, check_stream_options
         if check_stream(stream):
             if logprobs:
@@ -249,12 +249,8 @@ class _Completions:
         given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
                  "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
                  "logit_bias": logit_bias, "n": n, "no_repeat_ngram_size": no_repeat_ngram_size, "bad_words": bad_words,
-                 "min_tokens": min_tokens}
+                 "min_tokens": min_tokens, "speculative": speculative, "prediction": prediction}
         kwargs.update({name: v for name, v in given.items() if v is not None})
-        if speculative is not None:
-            kwargs["speculative"] = speculative
-        if prediction is not None:
-            kwargs["prediction"] = prediction
         return self._owner._complete(model, messages or [], temperature, max_tokens, logprobs=logprobs,
                                      top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
                                      **kwargs)
@@ -579,6 +575,66 @@ def schema_of(response_format):
     return dfa
 
 
+# The one list of the request keywords of ``create`` / ``complete_many`` (_complete_many describes each; ``speculative`` and
+# ``prediction`` are ``create``'s own), in the order in which a speculative request names its conflicts.
+REQUEST_KEYWORDS = ("logprobs", "top_logprobs", "response_format", "top_p", "seed", "frequency_penalty", "presence_penalty",
+                    "repetition_penalty", "stop", "top_k", "min_p", "logit_bias", "n", "stream", "stream_options",
+                    "no_repeat_ngram_size", "bad_words", "min_tokens")
+
+
+def _request_keywords(kwargs: dict, where: Optional[str] = None) -> dict:
+    """The REQUEST_KEYWORDS among ``kwargs``, in the list's order; with ``where``, any other one is that function's TypeError."""
+    for name in kwargs if where else ():
+        if name not in REQUEST_KEYWORDS:
+            raise TypeError(f"{where}() got an unexpected keyword argument {name!r}")
+    return {name: kwargs[name] for name in REQUEST_KEYWORDS if name in kwargs}
+
+
+def engine_keywords(max_tokens=None, **kw) -> Tuple[dict, Optional[int]]:
+    """The request keywords of one call (REQUEST_KEYWORDS; another one is a TypeError), checked without a model - ValueError
+    for the first one that is malformed - and translated: (the engine keywords that are on, the checked ``seed``).  Not
+    looked at here: ``n`` (it needs the engine's max_batch) and ``stream`` / ``stream_options`` (the caller's)."""
+    from .penalties import check_penalties
+    from .request import PENALTY_NAMES
+    from .sampling import check_seed, check_top_p
+    from .shaping import check_shaping, shaping_kwargs
+    from .stop import check_stop
+    kw = _request_keywords(kw, "engine_keywords")
+    response_format = kw.get("response_format")
+    on = {"logprobs": logprobs_k(kw.get("logprobs", False), kw.get("top_logprobs")), "json_schema": schema_of(response_format)}
+    on["json_mode"] = (json_mode_of(response_format) if on["json_schema"] is None else False) or None
+    on["top_p"] = check_top_p(kw.get("top_p"))
+    on["stop"] = check_stop(kw.get("stop"))
+    seed = check_seed(kw.get("seed"))
+    pen = check_penalties(*(kw.get(name) for name in PENALTY_NAMES), 1)
+    on.update({} if pen is None else zip(PENALTY_NAMES, pen[0]))
+    on.update(shaping_kwargs(check_shaping(kw.get("top_k"), kw.get("min_p"), kw.get("logit_bias"), 1)))
+    on.update(check_ban_keywords(kw.get("no_repeat_ngram_size"), kw.get("bad_words"), kw.get("min_tokens"), max_tokens,
+                                 response_format))
+    return {name: v for name, v in on.items() if v is not None}, seed
+
+
+def _prediction_ids(lm: "LoadedModel", prediction: Optional[str]) -> dict:
+    """The text of a request's prediction as ``generate``'s keyword: tokenised without special tokens, at most the engine's
+    max_ctx ids; {} without one."""
+    return {"prediction": lm.tokenizer.encode(prediction)[:lm.engine.max_ctx]} if prediction else {}
+
+
+def _log_timing(model_id: str, timing: dict) -> None:
+    TIMING_LOG.append({"model": model_id, **timing})
+    del TIMING_LOG[:-4096]
+
+
+def _image_urls(messages):
+    """The URL of every ``image_url`` part of ``messages``, in order."""
+    for m in messages:
+        content = m.get("content")
+        if isinstance(content, list):
+            for part in content:
+                if part.get("type") == "image_url":
+                    yield part["image_url"]["url"] if isinstance(part.get("image_url"), dict) else part["image_url"]
+
+
 def _completion(model_id: str, tok, n_ids: int, toks, rec, fin, timing: dict, nested: bool) -> ChatCompletion:
     """One request's ChatCompletion from what the engine returned for it: a token list with its logprob record and (reason,
     cut) - or, ``nested`` (the request asked for n choices), a list of each.  The prompt is counted once."""
@@ -681,64 +737,39 @@ class LocalVLMClient:
         cfg = lm.cfg
         gpu_resize = os.environ.get("VIS_GPU_RESIZE", "1") != "0"
         frames = []
-        for m in messages:
-            content = m.get("content")
-            if isinstance(content, list):
-                for part in content:
-                    if part.get("type") == "image_url":
-                        url = part["image_url"]["url"] if isinstance(part.get("image_url"), dict) else part["image_url"]
-                        # baseline JPEG (what the reference's agents send): Huffman decode here, on this pool thread;
-                        # IDCT / upsampling / colour conversion on the GPU (jpeg.py).  Other flavours: PIL.
-                        jc = jpeg.parse_data_uri(url) if (gpu_resize and jpeg.enabled()) else None
-                        if jc is not None:
-                            frames.append((jc, target_size(jc.size, cfg.patch, cfg.merge, cfg.min_pixels, cfg.max_pixels)))
-                            continue
-                        img = decode_data_uri(url)
-                        th, tw = target_size(img.size, cfg.patch, cfg.merge, cfg.min_pixels, cfg.max_pixels)
-                        if gpu_resize:
-                            frames.append((np.array(img, dtype=np.uint8), (th, tw)))
-                        else:
-                            frames.append((resize_for_model(img, cfg.patch, cfg.merge, cfg.min_pixels,
-                                                            cfg.max_pixels), (th, tw)))
+        for url in _image_urls(messages):
+            # baseline JPEG (what the reference's agents send): Huffman decode here, on this pool thread;
+            # IDCT / upsampling / colour conversion on the GPU (jpeg.py).  Other flavours: PIL.
+            jc = jpeg.parse_data_uri(url) if (gpu_resize and jpeg.enabled()) else None
+            if jc is not None:
+                frames.append((jc, target_size(jc.size, cfg.patch, cfg.merge, cfg.min_pixels, cfg.max_pixels)))
+                continue
+            img = decode_data_uri(url)
+            th, tw = target_size(img.size, cfg.patch, cfg.merge, cfg.min_pixels, cfg.max_pixels)
+            frames.append((np.array(img, dtype=np.uint8) if gpu_resize else
+                           resize_for_model(img, cfg.patch, cfg.merge, cfg.min_pixels, cfg.max_pixels), (th, tw)))
         counts = [(th // cfg.patch) * (tw // cfg.patch) // cfg.merge ** 2 for _, (th, tw) in frames]
         return build_chat_ids(lm.tokenizer, messages, counts), frames
 
-    def _complete(self, model, messages, temperature, max_tokens, logprobs=False, top_logprobs=None, response_format=None,
-                  top_p=None, seed=None, frequency_penalty=None, presence_penalty=None, repetition_penalty=None,
-                  stop=None, top_k=None, min_p=None, logit_bias=None, n=None, stream=None, stream_options=None,
-                  no_repeat_ngram_size=None, bad_words=None, min_tokens=None, speculative=None, prediction=None, **kwargs):
+    def _complete(self, model, messages, temperature, max_tokens, speculative=None, prediction=None, **kwargs):
         from .spec import check_prediction
+        kw = _request_keywords(kwargs)      # an OpenAI keyword ``create`` swallowed and this client does not know ends here
         text = check_prediction(prediction)
         if speculative is not None or text is not None:
-            sp = check_speculative_request(
-                speculative, temperature, seed, prediction=prediction, logprobs=logprobs, top_logprobs=top_logprobs, response_format=response_format,
-                top_p=top_p, frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
-                repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n,
-                stream=stream, no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
+            sp = check_speculative_request(speculative, temperature, prediction=prediction,
+                                           **{name: v for name, v in kw.items() if name != "stream_options"})
             if is_mllama_model(model or self.default_model) and not _auditor_speculative():
                 raise ValueError(("speculative decoding is" if text is None else "prediction (speculative decoding) is") +
                                  " offered for Qwen2-VL / Qwen2.5-VL models only, unless VIS_AUDITOR_SPECULATIVE=k (1..3) "
                                  "has the Mllama engine built for it")
             return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp, prediction=text)[0]
-        out = self.complete_many(model, [messages], temperature, max_tokens, logprobs=logprobs, top_logprobs=top_logprobs,
-                                 response_format=response_format, top_p=top_p, seed=seed, frequency_penalty=frequency_penalty,
-                                 presence_penalty=presence_penalty, repetition_penalty=repetition_penalty, stop=stop,
-                                 top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n, stream=stream, stream_options=stream_options,
-                                 no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
+        out = self.complete_many(model, [messages], temperature, max_tokens, **kw)
         return out if isinstance(out, ChatCompletionStream) else out[0]
 
-    def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
-                      top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
-                      top_p: Optional[float] = None, seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
-                      presence_penalty: Optional[float] = None,
-                      repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
-                      min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
-                      n: Optional[int] = None, stream: Optional[bool] = None, stream_options: Optional[dict] = None,
-                      no_repeat_ngram_size: Optional[int] = None, bad_words: Optional[list] = None,
-                      min_tokens: Optional[int] = None, prediction=None):
-        """As ``_complete_many`` (the keywords are described there), plus ``stream`` (OpenAI's): True returns ONE
-        ChatCompletionStream over the chunks of all requests instead of the list - each chunk carries its request's index
-        as ``request_index`` - while the engine call runs on a worker thread.  Every token is published from the GPU into
+    def complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, *, prediction=None, **kw):
+        """As ``_complete_many`` (``kw``: the REQUEST_KEYWORDS, described there; any other is a TypeError), plus ``stream``
+        (OpenAI's): True returns ONE ChatCompletionStream over the chunks of all requests instead of the list - each chunk
+        carries its request's index as ``request_index`` - while the engine call runs on a worker thread.  Every token is published from the GPU into
         host memory as it is picked (vis_stream_publish, stream.py), so text arrives while the decode loop runs and the
         loop keeps its launch-ahead; text that may still turn out to be the start of a stop string is held back.  The
         streamed text of a choice, its finish_reason and the usage are those of the same call not streamed.  Per choice:
@@ -746,60 +777,32 @@ class LocalVLMClient:
         ``finish_reason``; ``stream_options={"include_usage": True}`` adds a chunk with ``choices=[]`` and the ``usage``
         per request.  Not together with ``logprobs``.  With VIS_SYNTHETIC_REPLY the substituted text comes as one content
         chunk after the generation.  Closing or dropping the iterator cancels the call at the loop's next poll; an exception
-        of a request is raised from ``next()``.  None or False: the list, as before.
+        of a request is raised from ``next()``; one of its arguments from this call.  None or False: the list, as before.
         ``prediction`` other than None is refused (ValueError): it belongs to the one request of ``create``."""
         from .spec import refuse_batch_prediction
         from .stream import StreamReader, check_stream, check_stream_options
+        kw = _request_keywords(kw, "complete_many")
         refuse_batch_prediction(prediction)
-        kw = dict(logprobs=logprobs, top_logprobs=top_logprobs, response_format=response_format, top_p=top_p, seed=seed,
-                  frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
-                  repetition_penalty=repetition_penalty, stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n,
-                  no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
+        stream, stream_options = kw.pop("stream", None), kw.pop("stream_options", None)
         if not check_stream(stream):
             check_stream_options(stream_options, False)
             return self._complete_many(model, batch_of_messages, temperature, max_tokens, **kw)
         include_usage = check_stream_options(stream_options, True)
-        if logprobs:
+        if kw.get("logprobs"):
             raise ValueError("stream=True together with logprobs=True is not supported: chunks carry no logprobs")
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
-        self._check_keywords(max_tokens=max_tokens, **kw)
+        checked = engine_keywords(max_tokens, **kw)      # here, not on the worker: a bad argument raises from this call
         lm = get_model(model_id, self.device)
         hold = model_id.startswith("synthetic:") and bool(os.environ.get("VIS_SYNTHETIC_REPLY"))
         return ChatCompletionStream(
-            lambda reader: self._complete_many(model, batch_of_messages, temperature, max_tokens, on_stream=reader, **kw),
+            lambda reader: self._complete_many(model, batch_of_messages, temperature, max_tokens, on_stream=reader,
+                                               checked=checked, **kw),
             StreamReader(lm.tokenizer), model_id, include_usage, hold)
 
-    @staticmethod
-    def _check_keywords(logprobs, top_logprobs, response_format, top_p, seed, frequency_penalty, presence_penalty,
-                        repetition_penalty, stop, top_k, min_p, logit_bias, n, no_repeat_ngram_size=None, bad_words=None,
-                        min_tokens=None, max_tokens=None) -> None:
-        """The argument checks of _complete_many that need no model: a streamed call raises them from create(), not from
-        the first next()."""
-        from .penalties import check_penalties
-        from .sampling import check_seed, check_top_p
-        from .shaping import check_shaping
-        from .stop import check_stop
-        logprobs_k(logprobs, top_logprobs)
-        if schema_of(response_format) is None:
-            json_mode_of(response_format)
-        check_top_p(top_p)
-        check_stop(stop)
-        check_seed(seed)
-        check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        check_shaping(top_k, min_p, logit_bias, 1)
-        check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
-
-    def _complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, logprobs: bool = False,
-                       top_logprobs: Optional[int] = None, response_format: Optional[dict] = None,
-                       top_p: Optional[float] = None, seed: Optional[int] = None, frequency_penalty: Optional[float] = None,
-                       presence_penalty: Optional[float] = None,
-                       repetition_penalty: Optional[float] = None, stop=None, top_k: Optional[int] = None,
-                       min_p: Optional[float] = None, logit_bias: Optional[dict] = None,
-                       n: Optional[int] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
-                       bad_words: Optional[list] = None, min_tokens: Optional[int] = None,
-                       speculative=None, prediction: Optional[str] = None) -> List[ChatCompletion]:
+    def _complete_many(self, model, batch_of_messages, temperature=None, max_tokens=None, on_stream=None, speculative=None,
+                       prediction: Optional[str] = None, checked=None, **kw) -> List[ChatCompletion]:
         """Several independent requests in one go: per-request prefill, then ONE shared decode loop in which every
         weight is streamed once per step for all of them (engine.generate_batch).  Groups larger than the
         engine's max_batch are processed in consecutive chunks.  Extension of the reference's call shape used by
@@ -853,19 +856,8 @@ class LocalVLMClient:
         ``prediction`` (the text of create's ``prediction``, next to ``speculative``): tokenised without special tokens, at
         most the engine's max_ctx ids, handed to ``generate(.., prediction=)``; the completion's usage then carries
         ``completion_tokens_details``."""
-        from .penalties import check_penalties
-        from .sampling import check_seed, check_top_p
-        from .shaping import check_shaping, shaping_kwargs
-        from .stop import check_stop
-        k = logprobs_k(logprobs, top_logprobs)
-        dfa = schema_of(response_format)
-        jm = json_mode_of(response_format) if dfa is None else False
-        top_p = check_top_p(top_p)
-        stop = check_stop(stop)
-        seed = check_seed(seed)
-        pen = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        shp = shaping_kwargs(check_shaping(top_k, min_p, logit_bias, 1))
-        bans = check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
+        on, seed = checked or engine_keywords(max_tokens, **kw)
+        k = on.get("logprobs")
         model_id = model or self.default_model
         if not model_id:
             raise ValueError("no model given")
@@ -873,7 +865,7 @@ class LocalVLMClient:
         eng, tok = lm.engine, lm.tokenizer
         max_new = int(max_tokens) if max_tokens else 512
         temp = float(temperature) if temperature else 0.0
-        n = check_n(n, eng.max_batch)
+        n = check_n(kw.get("n"), eng.max_batch)
         n = None if n == 1 else n
         if speculative is not None and (len(batch_of_messages) != 1 or
                                         (lm.family == "mllama" and not _auditor_speculative())):
@@ -882,12 +874,9 @@ class LocalVLMClient:
         # What every engine call of this request group gets, built once: the switches that are on (an engine call without a
         # keyword is the call of before the keyword existed) and the ignore-EOS switch in the engine's spelling.
         ignore_eos = os.environ.get("VIS_IGNORE_EOS") == "1"
-        gen = dict(max_new_tokens=max_new, temperature=temp,
+        gen = dict(max_new_tokens=max_new, temperature=temp, **on,
                    **({"stop_on_eos": not ignore_eos} if lm.family == "mllama" else {"ignore_eos": ignore_eos}))
-        gen.update({name: v for name, v in dict(logprobs=k, json_mode=jm or None, json_schema=dfa, top_p=top_p, stop=stop,
-                                                **({} if pen is None else dict(zip(
-                                                    ("repetition_penalty", "frequency_penalty", "presence_penalty"), pen[0]))),
-                                                **shp, **bans, n=n, on_stream=on_stream).items() if v is not None})
+        gen.update({name: v for name, v in (("n", n), ("on_stream", on_stream)) if v is not None})
 
         def serve(indices, request_of):
             """The requests ``indices`` of this call through generate_batch, in chunks filled by choices (max_batch // n
@@ -899,8 +888,7 @@ class LocalVLMClient:
                     on_stream.requests = list(idx)      # which requests of the call this engine call serves
                 if speculative is not None:      # one greedy request, no other switch: the single-sequence loop, speculating
                     ids, frames = request_of(idx[0])()
-                    pred = {} if not prediction else {"prediction": tok.encode(prediction)[:eng.max_ctx]}
-                    outs = [eng.generate(ids, frames, speculative=speculative, **pred, **gen)]
+                    outs = [eng.generate(ids, frames, speculative=speculative, **_prediction_ids(lm, prediction), **gen)]
                 else:
                     outs = eng.generate_batch([request_of(j) for j in idx], seed=self.seed, **gen,
                                               **({"seeds": [seed] * len(idx)} if seed is not None else {}))
@@ -908,8 +896,7 @@ class LocalVLMClient:
                 fins = getattr(eng, "last_finish", None) or [None] * len(idx)
                 timing = dict(getattr(eng, "last_timing", None) or {})
                 if timing:
-                    TIMING_LOG.append({"model": model_id, **timing})
-                    del TIMING_LOG[:-4096]
+                    _log_timing(model_id, timing)
                 yield idx, outs, recs, fins, timing
 
         if lm.family == "mllama":
@@ -967,14 +954,9 @@ class LocalVLMClient:
         from .image_processing import decode_data_uri
         from .tokenizer import build_llama_chat_ids
         frames = []
-        for m in messages:
-            content = m.get("content")
-            if isinstance(content, list):
-                for part in content:
-                    if part.get("type") == "image_url":
-                        url = part["image_url"]["url"] if isinstance(part.get("image_url"), dict) else part["image_url"]
-                        jc = jpeg.parse_data_uri(url) if jpeg.enabled() else None
-                        frames.append(jc if jc is not None else np.array(decode_data_uri(url), dtype=np.uint8))
+        for url in _image_urls(messages):
+            jc = jpeg.parse_data_uri(url) if jpeg.enabled() else None
+            frames.append(jc if jc is not None else np.array(decode_data_uri(url), dtype=np.uint8))
         if len(frames) > 1:
             raise ValueError("the mllama backend takes one image per request (what the reference sends)")
         return build_llama_chat_ids(lm.tokenizer, messages, len(frames)), (frames[0] if frames else None)
@@ -999,12 +981,10 @@ class LocalVLMClient:
         futs = [ingest.then(m, lambda msgs: self._prepare_mllama(lm, msgs)) for m in batch_of_messages]
         if speculative is not None:
             ids, f = futs[0].result()
-            pred = {} if not prediction else {"prediction": tok.encode(prediction)[:eng.max_ctx]}
             with eng.lock:
                 t = eng.generate(ids, _frame_to_device(f, eng.device) if f is not None else None, speculative=speculative,
-                                 **pred, **one)
-                TIMING_LOG.append({"model": lm.model_id, **eng.last_timing})
-                del TIMING_LOG[:-4096]
+                                 **_prediction_ids(lm, prediction), **one)
+                _log_timing(lm.model_id, eng.last_timing)
                 return [completion(len(ids), t, None, eng.last_finish[0])]
         if any(isinstance(m, Future) for m in batch_of_messages):
             # the batch seam (verify_many): every request carries an image; requests are resolved in order by the engine
@@ -1068,32 +1048,27 @@ class CannedResponseClient:
         self.calls: List[dict] = []
         self.chat = _Chat(self)
 
-    def _complete(self, model, messages, temperature, max_tokens, response_format=None, top_p=None, seed=None,
-                  frequency_penalty=None, presence_penalty=None, repetition_penalty=None, stop=None, top_k=None, min_p=None,
-                  logit_bias=None, n=None, stream=None, stream_options=None, no_repeat_ngram_size=None, bad_words=None,
-                  min_tokens=None, speculative=None, prediction=None, **kwargs):
-        check_ban_keywords(no_repeat_ngram_size, bad_words, min_tokens, max_tokens, response_format)
+    def _complete(self, model, messages, temperature, max_tokens, speculative=None, prediction=None, **kwargs):
+        kw = _request_keywords(kwargs)
+        check_ban_keywords(kw.get("no_repeat_ngram_size"), kw.get("bad_words"), kw.get("min_tokens"), max_tokens,
+                           kw.get("response_format"))
         if speculative is not None or prediction is not None:
             if prediction is not None and is_mllama_model(model) and not _auditor_speculative():
                 raise ValueError("prediction (speculative decoding) is offered for Qwen2-VL / Qwen2.5-VL models only (an mllama "
                                  "model: with VIS_AUDITOR_SPECULATIVE=k set)")
-            check_speculative_request(
-                speculative, temperature, seed, prediction=prediction, response_format=response_format, top_p=top_p,
-                frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, repetition_penalty=repetition_penalty,
-                stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, n=n, stream=stream,
-                no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens, **kwargs)
+            # whatever else ``create`` swallowed goes along, as before: check_exclusive names an unknown keyword as a conflict
+            check_speculative_request(speculative, temperature, prediction=prediction,
+                                      **{name: v for name, v in {**kw, **kwargs}.items() if name != "stream_options"})
         self.calls.append({"model": model, "messages": messages, "temperature": temperature, "max_tokens": max_tokens,
-                           "response_format": response_format, "top_p": top_p, "seed": seed})
-        given = {"frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty,
-                 "repetition_penalty": repetition_penalty, "stop": stop, "top_k": top_k, "min_p": min_p,
-                 "logit_bias": logit_bias, "n": n, "no_repeat_ngram_size": no_repeat_ngram_size, "bad_words": bad_words,
-                 "min_tokens": min_tokens, "speculative": speculative, "prediction": prediction}
-        self.calls[-1].update({name: v for name, v in given.items() if v is not None})     # only the keywords that were given
+                           "response_format": kw.get("response_format"), "top_p": kw.get("top_p"), "seed": kw.get("seed")})
+        given = {**kw, "speculative": speculative, "prediction": prediction}      # only the keywords that were given
+        self.calls[-1].update({name: v for name, v in given.items()
+                               if v is not None and name not in ("logprobs", "top_logprobs", "stream", "stream_options")})
         reply = self.reply(messages) if callable(self.reply) else self.reply
-        done = ChatCompletion([_Choice(_Message(reply), index=i) for i in range(check_n(n, 64) or 1)], model=model or "")
-        if stream:      # the reply as its chunk sequence: role, one content chunk, the finish chunk (and the usage, if asked for)
+        done = ChatCompletion([_Choice(_Message(reply), index=i) for i in range(check_n(kw.get("n"), 64) or 1)], model=model or "")
+        if kw.get("stream"):      # the reply as its chunk sequence: role, one content chunk, the finish chunk (and the usage, if asked for)
             from .stream import check_stream_options
-            return _chunks_of(done, 0, check_stream_options(stream_options, True))
+            return _chunks_of(done, 0, check_stream_options(kw.get("stream_options"), True))
         return done
 
 

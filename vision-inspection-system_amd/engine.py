@@ -25,9 +25,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import hip, spec
+from . import hip
 from .decode_stage import DecodeLayer
 from .generation import Generation
+from .request import Switches
 from .config import Qwen2VLConfig
 from .weights import DeviceWeights, PATCH_K_PAD
 
@@ -1070,40 +1071,21 @@ class Qwen2VLEngine(Generation):
 
     def generate(self, input_ids: Sequence[int], frames: Sequence[torch.Tensor] = (), max_new_tokens: int = 128,
                  ignore_eos: bool = False, use_graph: bool = True, check_every: int = 16,
-                 temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
-                 json_mode: bool = False, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
-                 stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 logit_bias: Optional[dict] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
-                 bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None,
-                 speculative=None, prediction: Optional[Sequence[int]] = None) -> List[int]:
-        """One request through the single-sequence loop: Generation._generate describes every parameter.  Here a reply that
-        ended on EOS is cut in front of it, and a ``max_new_tokens`` the context cannot hold is clamped with a warning, once
-        per engine (_clamp_request)."""
+                 temperature: float = 0.0, seed: int = 0, **switches) -> List[int]:
+        """One request through the single-sequence loop (Generation._generate); ``switches``: the keywords request.Switches
+        describes.  Here a reply that ended on EOS is cut in front of it, and a ``max_new_tokens`` the context cannot hold is
+        clamped with a warning, once per engine (_clamp_request)."""
         return self._generate(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                              logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
-                              frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
-                              stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
-                              no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens,
-                              speculative=speculative, prediction=prediction)
+                              Switches.single(**switches))
 
-    def generate_batch(self, requests: Sequence,
-                       max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
-                       check_every: int = 16, temperature: float = 0.0, seed: int = 0, logprobs: Optional[int] = None,
-                       json_mode: bool = False, top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
-                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None,
-                       no_repeat_ngram_size=None, bad_words=None, min_tokens=None, prediction=None) -> list:
-        """Up to max_batch requests through one shared decode loop: Generation._generate_batch describes every parameter.
-        The requests are [(input_ids, frames)], text-only ones included; prompts that start with the same text share its
-        keys / values (prefill_many).  ``prediction`` other than None is refused (ValueError): ``generate`` only."""
-        spec.refuse_batch_prediction(prediction)
+    def generate_batch(self, requests: Sequence, max_new_tokens: int = 128, ignore_eos: bool = False, use_graph: bool = True,
+                       check_every: int = 16, temperature: float = 0.0, seed: int = 0, **switches) -> list:
+        """Up to max_batch requests through one shared decode loop (Generation._generate_batch); ``switches``: the keywords
+        request.Switches describes.  The requests are [(input_ids, frames)], text-only ones included; prompts that start with
+        the same text share its keys / values (prefill_many).  A prediction other than None is refused (ValueError):
+        ``generate`` only."""
         return self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                                    logprobs=logprobs, json_mode=json_mode, top_p=top_p, seeds=seeds,
-                                    repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
-                                    presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
-                                    min_p=min_p, logit_bias=logit_bias, n=n, on_stream=on_stream,
-                                    no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
+                                    Switches.group(**switches))
 
     def _fork_model_state(self, root: int, child: int) -> None:
         """A further choice decodes at its root's M-RoPE positions (DecodeStage hook)."""

@@ -5,23 +5,24 @@ engines derive from ``Generation`` and keep only what their models do differentl
 from __future__ import annotations
 
 import logging
+from dataclasses import replace
 from typing import List, Sequence
 
 import torch
 
 from . import hip, spec
-from .ban import ban_kwargs, check_ban
+from .ban import check_ban
 from .decode_stage import DecodeStage
 from .fork import check_n_list
 from .json_mode import JsonModeError, check_schema
 from .logprobs import check_k
 from .penalties import check_penalties
+from .request import Switches
 from .sampling import check_seeds, check_top_p
-from .shaping import check_shaping, shaping_kwargs
+from .shaping import check_shaping
 from .stop import check_stop
 
 _LOG = logging.getLogger("vision_inspection_system_amd.engine")
-_PENALTY_NAMES = ("repetition_penalty", "frequency_penalty", "presence_penalty")
 
 
 class Generation(DecodeStage):
@@ -29,7 +30,8 @@ class Generation(DecodeStage):
 
     The engines' public ``generate`` / ``generate_batch`` keep their own spellings (Qwen2-VL: ``ignore_eos`` / ``check_every``
     / ``frames``; Mllama: ``stop_on_eos`` / ``chunk`` / ``frame``) and hand over to ``_generate`` / ``_generate_batch`` here,
-    which know one spelling: ``ignore_eos``, ``check_every``, ``frames`` (whatever the engine's prompt pass takes as images).
+    which know one spelling: ``ignore_eos``, ``check_every``, ``frames`` (whatever the engine's prompt pass takes as images),
+    and take every further keyword of theirs as one request.Switches.
     What an engine supplies:
       ``_prompt_pass(input_ids, frames, max_new_tokens, temperature, seed)``: the single sequence's prompt pass into slot 0;
       ``prefill_many(requests, temperature=, seed=, max_new_tokens=, seeds=, penalties=, shaping=[, ban=]) -> (slots,
@@ -79,64 +81,13 @@ class Generation(DecodeStage):
         """After a single-sequence request served without a stall.  Only Qwen2-VL switches the chain back on."""
 
     # ------------------------------------------------------------------ the single sequence
-    def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, *,
-                  logprobs=None, json_mode=False, top_p=None, repetition_penalty=None, frequency_penalty=None,
-                  presence_penalty=None, json_schema=None, stop=None, top_k=None, min_p=None, logit_bias=None,
-                  on_stream=None, no_repeat_ngram_size=None, bad_words=None, min_tokens=None, speculative=None,
-                  prediction=None) -> List[int]:
-        """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every
-        ``check_every`` tokens so the decode loop itself never synchronises; output is truncated at the
-        first EOS (exclusive; inclusive for an engine with ``keep_eos``).  ``logprobs`` = k in 0..20: afterwards
-        ``last_logprobs`` holds one TokenLogprobs record
-        (log-softmax of the raw logits - independent of temperature and seed - for every returned token, plus its k most
-        likely alternatives); None = off, no extra launch.  ``json_mode``: every pick is restricted to the tokens that
-        continue a JSON object (json_grammar; needs ``self.tokenizer``): the reply is a prefix of one, complete when it
-        ended on EOS; JsonModeError when the vocabulary could not continue it.  Logprobs keep their meaning (raw logits),
-        so top_logprobs may list tokens the mask forbade.  ``top_p`` in [0, 1]: nucleus sampling (sampling.py) - each pick
-        draws from the shortest most-likely prefix holding top_p of the temperature-scaled mass; None or 1 = off.
-        ``repetition_penalty`` > 0 (transformers' meaning: over prompt and generated ids), ``frequency_penalty`` /
-        ``presence_penalty`` in [-2, 2] (OpenAI's: over generated ids): penalties.py - applied to the raw logits ahead of
-        everything above; None or 1 / 0 / 0 = off.  Logprobs keep their meaning (raw logits).
-        ``json_schema`` (a json_schema.SchemaDFA): as ``json_mode``, with the schema's compiled DFA as the grammar
-        (vis_schema_mask): a reply that ended on EOS is a document of the schema.  Not together with ``json_mode``.
-        ``stop``: a string or 1..4 of them (stop.py): the reply ends with the token that completes the first occurrence of
-        one in its bytes (vis_stop_scan after every pick; the poll then reads its records, not the token row), also in an
-        ``ignore_eos`` run.  Afterwards, always, ``last_finish`` = [(reason, cut)]: "eos", "stop" (cut = the byte offset in
-        the returned tokens' bytes where the stop string starts) or "length" (max_new_tokens, the context clamp, or an
-        ``ignore_eos`` run that matched nothing).
-        ``top_k`` >= 1, ``min_p`` in [0, 1] (transformers' TopKLogitsWarper / MinPLogitsWarper) and ``logit_bias`` {token id:
-        bias in [-100, 100]}, at most 300 entries (OpenAI's): shaping.py - one launch ahead of the pick adds the biases to
-        the (penalised) logits, then takes out every token below the k-th largest allowed one or less likely than min_p
-        times the most likely one; top_p and the draw see the rest.  None / 0 / {} = off; a greedy request is affected by
-        logit_bias only.  Logprobs keep their meaning (raw logits).
-        ``on_stream`` (a stream.StreamReader the caller polls from another thread): every token is published to it while the
-        loop runs - vis_stream_publish after every pick, behind the stop scan, which is then on with or without ``stop`` -
-        and the loop keeps its launch-ahead.  ``on_stream.cancel()`` ends the loop at its next ``check_every`` boundary (the
-        reply then ended as "length").  Not together with ``logprobs``.  A request served again after a stalled chained
-        launch resets the reader's slot; the reader continues behind what it had handed out (stream.py).
-        ``no_repeat_ngram_size`` in 1..64 (transformers' NoRepeatNGramLogitsProcessor: no n-gram of prompt + reply occurs
-        twice), ``bad_words``, up to 16 strings of 1..8 token ids each (transformers' NoBadWordsLogitsProcessor / vLLM's: the
-        token that would complete one is never picked; a word the tokenizer spells differently behind a space is banned in
-        both spellings) and ``min_tokens`` <= max_new_tokens (vLLM's: no EOS id before that many tokens): ban.py - one launch
-        after the penalties takes the banned ids out of the pick.  None / 0 / [] = off.  Not together with ``json_mode`` /
-        ``json_schema`` (ValueError: a ban could leave the grammar no token).  ``min_tokens`` holds back EOS ids only: a
-        ``stop`` string may still end the reply earlier.  Logprobs keep their meaning (raw logits).
-        ``speculative``: None (off: exactly the launches of before), the integer k in 1..3 or {"method": "ngram",
-        "num_speculative_tokens": k, "prompt_lookup_max": 4, "prompt_lookup_min": 2} (spec.py): a decode step carries the
-        current token and up to k ids drafted by prompt lookup over prompt + reply through ONE pass over the weights and
-        keeps the drafts the model's own greedy picks confirm - the reply is the plain reply token for token, in fewer
-        weight passes where the reply repeats earlier text.  Greedy single requests of the Qwen2-VL engines, or of an
-        MllamaEngine built with speculative=True, only: ValueError
-        with a temperature, a seed or any switch above (they advance one token at a time).  Afterwards ``last_timing`` holds
-        ``spec_steps`` / ``spec_proposed`` / ``spec_accepted``.
-        ``prediction``: a sequence of token ids the reply will probably repeat (OpenAI's Predicted Outputs; at most max_ctx
-        are kept, none = off): the drafts come from it while the reply follows it, and from prompt lookup where it does not
-        (spec.propose_pred, vis_spec_draft_pred).  Alone it implies speculative = k 3, window 4..2; ``speculative`` next to it
-        sets k and the window.  The same conditions and refusals as ``speculative``; the reply is the plain reply.  Afterwards
-        ``last_timing`` also holds ``pred_accepted`` / ``pred_rejected``: the prediction's drafts the steps kept and did not
-        keep, over every step issued."""
-        pred = spec.check_prediction_ids(prediction, getattr(self, "max_ctx", None))
-        sp = spec.with_prediction(speculative, pred is not None)
+    def _generate(self, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
+                  sw: Switches) -> List[int]:
+        """Generate up to max_new_tokens (greedy at temperature 0).  EOS is checked on the host every ``check_every`` tokens so
+        the decode loop itself never synchronises; output is truncated at the first EOS (exclusive; inclusive for an engine
+        with ``keep_eos``).  ``sw``: what the request switches on (request.Switches describes every switch)."""
+        pred = spec.check_prediction_ids(sw.prediction, getattr(self, "max_ctx", None))
+        sp = spec.with_prediction(sw.speculative, pred is not None)
         if sp is not None:
             what = "speculative" if pred is None else "prediction (speculative decoding)"
             if not self.speculative_supported:
@@ -144,17 +95,13 @@ class Generation(DecodeStage):
                                  " offered by the Qwen2-VL / Qwen2.5-VL engine only, unless an MllamaEngine is built for it: "
                                  "MllamaEngine(.., speculative=True), or VIS_AUDITOR_SPECULATIVE=k (1..3) where the client "
                                  "loads it")
-            spec.check_exclusive(sp, temperature, seed, what=what, logprobs=logprobs, json_mode=json_mode, top_p=top_p,
-                                 repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
-                                 presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
-                                 min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
-                                 no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
-        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, 1)
-        shaping = check_shaping(top_k, min_p, logit_bias, 1)
-        ban = check_ban(no_repeat_ngram_size, bad_words, min_tokens, 1, max_new_tokens, json_mode=json_mode,
-                        json_schema=json_schema)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, False, penalties, stop=stop, shaping=shaping,
-                                on_stream=on_stream, **({} if ban is None else {"ban": ban})):
+            spec.check_exclusive(sp, temperature, seed, what=what, **sw.exclusive())
+        penalties = check_penalties(sw.repetition_penalty, sw.frequency_penalty, sw.presence_penalty, 1)
+        shaping = check_shaping(sw.top_k, sw.min_p, sw.logit_bias, 1)
+        ban = check_ban(sw.no_repeat_ngram_size, sw.bad_words, sw.min_tokens, 1, max_new_tokens, json_mode=sw.json_mode,
+                        json_schema=sw.json_schema)
+        with self._pick_request(sw.logprobs, sw.json_mode, sw.json_schema, sw.top_p, False, penalties, stop=sw.stop,
+                                shaping=shaping, on_stream=sw.on_stream, **({} if ban is None else {"ban": ban})):
             self.stop_eos = not ignore_eos
             self._stream_bind([[0]])
             max_new_tokens = self._clamp_request(input_ids, max_new_tokens)
@@ -246,57 +193,31 @@ class Generation(DecodeStage):
         return JsonModeError("json_mode: the vocabulary could not continue the JSON text")
 
     # ------------------------------------------------------------------ a batch
-    def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed, *,
-                        logprobs=None, json_mode=False, top_p=None, seeds=None, repetition_penalty=None,
-                        frequency_penalty=None, presence_penalty=None, json_schema=None, stop=None, top_k=None, min_p=None,
-                        logit_bias=None, n=None, on_stream=None, no_repeat_ngram_size=None, bad_words=None,
-                        min_tokens=None) -> list:
+    def _generate_batch(self, requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
+                        sw: Switches) -> list:
         """requests: [(input_ids, frames)] for up to max_batch images - or zero-argument callables returning that pair
         (see prefill_many: resolved in order while the GPU already works on the earlier ones).  Prefill runs per image
         (M = S rows is already MFMA-efficient); the decode steps are shared: one weight pass per step for all sequences.
         Returns one token list per request; for a lazy request whose callable raised, the exception object instead.
-        ``logprobs``: as in generate; ``last_logprobs`` then holds one record per request (None for a failed one).
-        ``json_mode``: as in generate; a request whose JSON text could not be continued gets a JsonModeError.
-        ``top_p``: as in generate.  ``seeds``: one integer per request, its own sampling seed in place of the slot-derived
-        one, so a request's sampled reply does not depend on its slot or on what shares the batch.
-        ``repetition_penalty``, ``frequency_penalty``, ``presence_penalty``: as in generate, each a number or a sequence
-        with one value per request.  ``json_schema``: as in generate, one schema for the whole group.  ``stop``: as in
-        generate, one set for the whole group; the shared loop ends when every row has ended.  ``last_finish`` holds one
-        (reason, cut) per request, None for a failed one.  ``top_k``, ``min_p``, ``logit_bias``: as in generate, each one
-        value for the group or a sequence with one value (or None) per request.
-        ``n``: None, an integer >= 1 or one integer per request - that many sampled choices of each request from ONE prompt
-        pass (fork.py): the further choices take slots behind the requests', read the prompt's keys / values from the slot
-        that ran the prompt pass (vis_decode_attn_forked) and sample with seeds[j] + i (without seeds: the slot-derived seed
-        of the slot they land in).  All choices together must fit max_batch.  With ``n`` given, the entry of a request is a
-        list of n[j] token lists (for a failed request the exception object, as without), and ``last_logprobs`` /
-        ``last_finish`` nest the same way.  At temperature 0 all choices of a request are equal; they are decoded all the
-        same.  A slot is still a full-size cache: ``n`` saves prompt passes and attention traffic, not cache memory.
-        ``on_stream``: as in generate, one reader for the whole group; its events name the request and the choice.
-        ``no_repeat_ngram_size``, ``min_tokens``: as in generate, each one value for the group or a sequence with one value
-        per request; ``bad_words``: as in generate, one list for the whole group.  The choices of a request (``n``) inherit
-        its values."""
+        ``sw``: what the group switches on (request.Switches: every switch, and which take one value per request)."""
         n_req = len(requests)
         if not 1 <= n_req <= self.max_batch:
             raise ValueError(f"batch of {n_req} does not fit max_batch={self.max_batch}")
-        check_k(logprobs)
-        if not isinstance(json_mode, bool):
+        check_k(sw.logprobs)
+        if not isinstance(sw.json_mode, bool):
             raise ValueError("json_mode must be True or False")
-        check_schema(json_mode, json_schema)
-        check_top_p(top_p)
-        seeds = check_seeds(seeds, n_req)
-        penalties = check_penalties(repetition_penalty, frequency_penalty, presence_penalty, n_req)
-        shaping = check_shaping(top_k, min_p, logit_bias, n_req)
-        ban = check_ban(no_repeat_ngram_size, bad_words, min_tokens, n_req, max_new_tokens, json_mode=json_mode,
-                        json_schema=json_schema)
-        check_stop(stop)
-        ns = check_n_list(n, n_req, self.max_batch)
-        switches = dict(logprobs=logprobs, json_mode=json_mode, json_schema=json_schema, top_p=top_p, stop=stop,
-                        on_stream=on_stream, **ban_kwargs(ban))
+        check_schema(sw.json_mode, sw.json_schema)
+        check_top_p(sw.top_p)
+        seeds = check_seeds(sw.seeds, n_req)
+        penalties = check_penalties(sw.repetition_penalty, sw.frequency_penalty, sw.presence_penalty, n_req)
+        shaping = check_shaping(sw.top_k, sw.min_p, sw.logit_bias, n_req)
+        ban = check_ban(sw.no_repeat_ngram_size, sw.bad_words, sw.min_tokens, n_req, max_new_tokens, json_mode=sw.json_mode,
+                        json_schema=sw.json_schema)
+        check_stop(sw.stop)
+        ns = check_n_list(sw.n, n_req, self.max_batch)
         if n_req == 1 and ns is not None and ns[0] == 1:      # one choice: the route without n, the results nested
             out = self._generate_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,
-                                       seeds=seeds, repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
-                                       presence_penalty=presence_penalty, top_k=top_k, min_p=min_p, logit_bias=logit_bias,
-                                       **switches)
+                                       replace(sw, n=None))
             if not isinstance(out[0], Exception):
                 out = [[out[0]]]
                 self.last_finish = [[self.last_finish[0]]]
@@ -309,7 +230,7 @@ class Generation(DecodeStage):
             r, own = requests[0], False
 
             def failed(e):
-                self.last_logprobs = [None] if logprobs is not None else None
+                self.last_logprobs = [None] if sw.logprobs is not None else None
                 self.last_finish = [None]
                 return [e]
 
@@ -322,8 +243,7 @@ class Generation(DecodeStage):
             try:
                 return [self._generate(r[0], r[1], max_new_tokens, ignore_eos, use_graph,
                                        self.single_route_check_every or check_every, temperature,
-                                       seed if seeds is None else seeds[0], **switches, **shaping_kwargs(shaping),
-                                       **({} if penalties is None else dict(zip(_PENALTY_NAMES, penalties[0]))))]
+                                       seed if seeds is None else seeds[0], sw.request(0))]
             except Exception as e:      # noqa: BLE001
                 if own:
                     return failed(e)
@@ -331,8 +251,8 @@ class Generation(DecodeStage):
                     return [e]
                 raise
         self._check_batch(requests)
-        with self._pick_request(logprobs, json_mode, json_schema, top_p, seeds is not None, penalties, stop=stop,
-                                shaping=shaping, on_stream=on_stream, **({} if ban is None else {"ban": ban})):
+        with self._pick_request(sw.logprobs, sw.json_mode, sw.json_schema, sw.top_p, seeds is not None, penalties,
+                                stop=sw.stop, shaping=shaping, on_stream=sw.on_stream, **({} if ban is None else {"ban": ban})):
             self.stop_eos = not ignore_eos
             try:
                 return self._run_batch(requests, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed,

@@ -30,9 +30,10 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import hip, spec
+from . import hip
 from .decode_stage import DecodeLayer
 from .generation import Generation
+from .request import Switches
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
 
 
@@ -645,45 +646,26 @@ class MllamaEngine(Generation):
 
     def generate(self, input_ids: Sequence[int], frame: Optional[torch.Tensor] = None, max_new_tokens: int = 128,
                  temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                 chunk: int = 32, logprobs: Optional[int] = None, json_mode: bool = False,
-                 top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                 frequency_penalty: Optional[float] = None, presence_penalty: Optional[float] = None, json_schema=None,
-                 stop=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                 logit_bias: Optional[dict] = None, on_stream=None, no_repeat_ngram_size: Optional[int] = None,
-                 bad_words: Optional[Sequence[str]] = None, min_tokens: Optional[int] = None,
-                 speculative=None, prediction=None) -> List[int]:
-        """One request through the single-sequence loop: Generation._generate describes every parameter, with
-        ``stop_on_eos`` = not ignore_eos, ``chunk`` = check_every (the boundary at which a cancelled request ends) and
-        ``frame`` the request's one image or None.  A reply that ended on EOS keeps its EOS token here; a ``max_new_tokens``
-        the context cannot hold is clamped silently; after a stalled chained launch this engine stays on the separate
-        launches for good.  ``speculative`` or ``prediction`` other than None needs an engine built with speculative=True
+                 chunk: int = 32, **switches) -> List[int]:
+        """One request through the single-sequence loop (Generation._generate), with ``stop_on_eos`` = not ignore_eos,
+        ``chunk`` = check_every (the boundary at which a cancelled request ends) and ``frame`` the request's one image or
+        None; ``switches``: the keywords request.Switches describes.  A reply that ended on EOS keeps its EOS token here; a
+        ``max_new_tokens`` the context cannot hold is clamped silently; after a stalled chained launch this engine stays on
+        the separate launches for good.  A speculative request or a prediction needs an engine built with speculative=True
         (else ValueError: by default they are the Qwen2-VL engines'); the reply is then the plain reply, EOS token included."""
         return self._generate(input_ids, frame, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
-                              logprobs=logprobs, json_mode=json_mode, top_p=top_p, repetition_penalty=repetition_penalty,
-                              frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, json_schema=json_schema,
-                              stop=stop, top_k=top_k, min_p=min_p, logit_bias=logit_bias, on_stream=on_stream,
-                              no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens,
-                              speculative=speculative, prediction=prediction)
+                              Switches.single(**switches))
 
-    def generate_batch(self, requests: Sequence, max_new_tokens: int = 128,
-                       temperature: float = 0.0, seed: int = 0, stop_on_eos: bool = True, use_graph: bool = True,
-                       chunk: int = 16, logprobs: Optional[int] = None, json_mode: bool = False,
-                       top_p: Optional[float] = None, seeds: Optional[Sequence[int]] = None,
-                       repetition_penalty=None, frequency_penalty=None, presence_penalty=None, json_schema=None,
-                       stop=None, top_k=None, min_p=None, logit_bias=None, n=None, on_stream=None,
-                       no_repeat_ngram_size=None, bad_words=None, min_tokens=None, prediction=None) -> list:
-        """Up to max_batch requests through one shared decode loop: Generation._generate_batch describes every parameter
-        (``stop_on_eos`` / ``chunk`` as in generate; ``prediction`` other than None is refused).  requests: [(input_ids, frame)]; every request of a batch carries an
-        image - one text-only request alone takes the single-sequence path.  A reply that ended on EOS keeps its EOS token.
-        With ``n``, the image's cross-attention keys / values are copied whole into every further choice's slot and the
-        forked attention serves the self-attention layers."""
-        spec.refuse_batch_prediction(prediction)
+    def generate_batch(self, requests: Sequence, max_new_tokens: int = 128, temperature: float = 0.0, seed: int = 0,
+                       stop_on_eos: bool = True, use_graph: bool = True, chunk: int = 16, **switches) -> list:
+        """Up to max_batch requests through one shared decode loop (Generation._generate_batch; ``stop_on_eos`` / ``chunk`` as
+        in generate, ``switches``: the keywords request.Switches describes; a prediction other than None is refused).
+        requests: [(input_ids, frame)]; every request of a batch carries an image - one text-only request alone takes the
+        single-sequence path.  A reply that ended on EOS keeps its EOS token.  With several choices per request, the image's
+        cross-attention keys / values are copied whole into every further choice's slot and the forked attention serves the
+        self-attention layers."""
         return self._generate_batch(requests, max_new_tokens, not stop_on_eos, use_graph, chunk, temperature, seed,
-                                    logprobs=logprobs, json_mode=json_mode, top_p=top_p, seeds=seeds,
-                                    repetition_penalty=repetition_penalty, frequency_penalty=frequency_penalty,
-                                    presence_penalty=presence_penalty, json_schema=json_schema, stop=stop, top_k=top_k,
-                                    min_p=min_p, logit_bias=logit_bias, n=n, on_stream=on_stream,
-                                    no_repeat_ngram_size=no_repeat_ngram_size, bad_words=bad_words, min_tokens=min_tokens)
+                                    Switches.group(**switches))
 
     def _fork_model_state(self, root: int, child: int) -> None:
         """A further choice attends to its root's image: the cross-attention keys / values, whole (DecodeStage hook)."""
