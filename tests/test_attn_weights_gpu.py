@@ -132,6 +132,72 @@ def test_prefill80_key_split(hip, device):
     _prefill_check(c, out, "attn_prefill_plan key-split")
 
 
+# ----------------------------------------------------------------------------- prefill: operands inside poisoned buffers
+# The cases above again, with the memory AROUND the operands hostile.  K is a contiguous view whose last head is followed, in
+# the same allocation, by GUARD_ROWS rows of bf16 NaN - what a ragged last key tile brings into LDS if its load reaches past the
+# head (tests/test_buffer_range_gpu.py measures whether it does); Q is followed by NaN rows too; `out` is a view (rows
+# GUARD_ROWS .., the first Hq * D columns) of a wider and taller buffer filled with a canary word.  The V^T pad columns stay
+# ZERO: csrc/rope.hip documents that vis_qkv_rope_split zeroes them and the kernels rely on it (the probability of a masked key
+# is 0, and 0 x pad must stay 0), so that is a contract of the input, not memory behind it.
+# Pinned: masking stays a SELECT (an additive mask would turn a NaN score into a NaN output), and a launch writes its own rows
+# and columns of `out` and nothing else.
+GUARD_ROWS = 64
+CANARY = 0x4B1D                  # as bf16 about 1.0e7: an output element left unwritten also fails check's |out| < 64
+
+
+def _nan_tailed(t, device):
+    """t [H, n, D] -> the same values as a contiguous view at the start of one allocation whose last GUARD_ROWS x D are NaN."""
+    H, n, D = t.shape
+    flat = torch.full(((H * n + GUARD_ROWS) * D,), float("nan"), dtype=torch.bfloat16, device=device)
+    flat[:H * n * D] = t.to(device).reshape(-1)
+    assert bool(flat[H * n * D:].isnan().all())
+    return flat[:H * n * D].view(H, n, D)
+
+
+def _embedded(hip, device, c, launch, what):
+    """launch(Q, K, vt, out) on the plain layout, then on the embedded one: same `check`, same bits, canary untouched."""
+    Hq, S, D = c.Q.shape
+    vt = _vt(hip, c.V.to(device), device)
+    plain = _blank(S, Hq * D, device)
+    launch(c.Q.to(device), c.K.to(device), vt, plain)
+    _prefill_check(c, plain, f"{what}, plain layout")
+    buf = torch.full((S + 2 * GUARD_ROWS, Hq * D + 64), CANARY, dtype=torch.int16, device=device)
+    out = buf.view(torch.bfloat16)[GUARD_ROWS:GUARD_ROWS + S, :Hq * D]
+    launch(_nan_tailed(c.Q, device), _nan_tailed(c.K, device), vt, out)
+    _prefill_check(c, out, f"{what}, operands inside poisoned buffers")
+    assert torch.equal(out.contiguous().view(torch.int16), plain.view(torch.int16)), f"{what}: bits differ from the plain-layout run"
+    guard = buf.clone()
+    guard[GUARD_ROWS:GUARD_ROWS + S, :Hq * D] = CANARY
+    touched = int((guard != CANARY).sum())
+    assert touched == 0, f"{what}: {touched} canary words outside `out` were written"
+
+
+def test_prefill80_poisoned_surroundings(hip, device):
+    """attn_vit32_kernel on the head_dim 80 case whose key count is no multiple of 64 (S = 2945 through the key-split plan: the
+    whole items and the second halves end in a tile with ONE key and 63 rows past the head)."""
+    c = W.prefill80_split(W.SPLIT_S, W.SPLIT_MID)
+    assert W.SPLIT_S % 64 == 1
+    plan = hip.make_vit_attn_plan([(0, W.SPLIT_S)], device, 3)
+    assert plan.n_pairs > 0
+    _embedded(hip, device, c, lambda Q, K, vt, out: hip.attn_prefill_plan(Q, K, vt, out, plan, W.SCALE), "attn_prefill_plan key-split")
+
+
+@pytest.mark.parametrize("entry", ["rows", "pairs"])
+def test_prefill128_causal_poisoned_surroundings(hip, device, entry):
+    """The smallest causal head_dim 128 case, S = 65 (heads 2 / 2: the first head's ragged tile reaches into the second head's
+    rows, the second head's into the NaN rows), through vis_attn_prefill_rows and through attn_prefill_pair_kernel."""
+    S = W.PREFILL_S[0]
+    assert S % 64 and S == min(W.PREFILL_S)
+    c = W.prefill128(S, True, 2, 2)
+    if entry == "rows":
+        work = hip.make_attn_work(c.segments, True, device, heads=2)
+        launch = lambda Q, K, vt, out: hip.attn_prefill(Q, K, vt, out, work, True, W.SCALE)
+    else:
+        work = hip.make_attn_pairs(0, S, device)
+        launch = lambda Q, K, vt, out: hip.attn_prefill_pairs(Q, K, vt, out, work, W.SCALE)
+    _embedded(hip, device, c, launch, f"attn_prefill {entry}")
+
+
 # ----------------------------------------------------------------------------- decode
 def _decode_launch(hip, device, c, T, seqs, batched, shared_len=0, fork=None, parts=None):
     """seqs: the sequences of case c to run (one launch).  -> (out [len(seqs), Hq * D], k cache, v cache after)."""

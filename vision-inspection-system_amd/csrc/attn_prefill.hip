@@ -43,6 +43,7 @@
 // Output O[s][head*HD + d] is staged through LDS and written as whole 16-B
 // chunks so the following projection GEMM reads a plain row-major matrix.
 #include "common.hip.h"
+#include "attn_tile_dma.hip.h"
 #include <type_traits>
 
 struct AttnArgs {
@@ -605,9 +606,16 @@ __global__ __launch_bounds__(256, 3) void attn_vit32_kernel(AttnArgs p) {
   // LDS-DMA through BUFFER instructions (r05): the per-lane offsets above are loop constants in VGPRs, the tile's position is
   // the instruction's SCALAR offset, the head's base lives in the resource descriptor - no per-tile vector address arithmetic
   // (the global_load_lds form rebuilt a 64-bit address per piece and tile: 14 v_lshl_add_u64 + ~40 other VALU / SALU
-  // instructions per tile, profiles/r05_vit_attention_isa.txt), and rows past the head's last key read as zeros by the
-  // descriptor's range check (the ragged last tile needed a second code path with clamped rows; its scores are masked anyway).
+  // instructions per tile, profiles/r05_vit_attention_isa.txt).
+  // Rows past the head's last key (the ragged last tile) read as zeros by the descriptor's range check.  LLVM's and the ISA
+  // text's wording excludes the scalar offset from that check; on the MI355X it was MEASURED to take part in it
+  // (tools/probes/buffer_range_probe.hip on att_tile_dma16 itself, profiles/buffer_range_probe.txt: with the tile's position in
+  // the scalar offset, every 16-byte piece at or past num_records arrives as zeros, never as the memory behind the buffer) - so
+  // the ragged tile needs no second code path with clamped rows, and no load leaves the head.  Its scores are masked anyway.
   const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc((void*)Kh, 0, p.k_tokens * (HD * 2), 0x00020000);
+  // V^T loads stay inside their descriptor by construction, in the scalar form: a lane reads 16 bytes at
+  // d * vt_ld * 2 + kt * 2 + 16 c, d < HD, c < 8, i.e. columns kt .. kt + 63 of row d; kt is a multiple of 64 below the last key,
+  // and the wrappers (hip.py: vt_col0 + ceil64(S) <= vt_ld; the entry points: vt_ld % 64 == 0) guarantee kt + 64 <= vt_ld.
   const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc((void*)Vh, 0, HD * p.vt_ld * 2, 0x00020000);
   auto load_tile = [&](int kt, int buf) {
     __attribute__((address_space(3))) char* base = (__attribute__((address_space(3))) char*)(lds + buf * BUF + dma_base);
@@ -615,11 +623,11 @@ __global__ __launch_bounds__(256, 3) void attn_vit32_kernel(AttnArgs p) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
       if (i < 2 || wave < 2)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (__attribute__((address_space(3))) void*)(base + i * 4096), 16, dk_off[i], ko, 0, 0);
+        att_tile_dma16(rs_k, (att_lds_void*)(base + i * 4096), dk_off[i], ko);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
       if (i < 2 || wave < 2)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (__attribute__((address_space(3))) void*)(base + K_BYTES + i * 4096), 16, dv_off[i], vo, 0, 0);
+        att_tile_dma16(rs_v, (att_lds_void*)(base + K_BYTES + i * 4096), dv_off[i], vo);
   };
 
   // fragment read addresses: one per-lane base for K (the chunk XOR only touches bit 0: (2 ks + hh) ^ sw = 2 ks + (hh ^ sw)),
@@ -898,7 +906,9 @@ __global__ __launch_bounds__(512, 2) void attn_prefill_pair_kernel(AttnArgs p) {
   // loads of tile t + 1 parked in 16 VGPRs over the whole body of tile t and written behind it): K tile 64 rows x 16 chunks,
   // V^T tile 128 rows x 8 chunks = 1024 16-byte slots each = two 8 KiB pieces per image (512 threads x 16 B).  The LDS images
   // are lane-linear, so the XOR swizzles sit on the per-lane SOURCE offsets (loop constants); the tile's position is the
-  // instruction's scalar offset; rows past the head's last key read as zeros by the descriptor's range check (masked below).
+  // instruction's scalar offset; rows past the head's last key read as zeros by the descriptor's range check, which was measured to
+  // cover the scalar offset (profiles/buffer_range_probe.txt; see attn_vit32_kernel) - masked below.  V^T: in range by
+  // construction, as there.
   uint32_t dk_off[2], dv_off[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -916,10 +926,10 @@ __global__ __launch_bounds__(512, 2) void attn_prefill_pair_kernel(AttnArgs p) {
     const int ko = kt * (HD * 2), vo = kt * 2;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (__attribute__((address_space(3))) void*)(base + i * 8192), 16, dk_off[i], ko, 0, 0);
+      att_tile_dma16(rs_k, (att_lds_void*)(base + i * 8192), dk_off[i], ko);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (__attribute__((address_space(3))) void*)(base + K_BYTES + i * 8192), 16, dv_off[i], vo, 0, 0);
+      att_tile_dma16(rs_v, (att_lds_void*)(base + K_BYTES + i * 8192), dv_off[i], vo);
   };
 
   f32x4 oacc[2][ND + 1];
