@@ -680,6 +680,18 @@ int vis_spec_accept(const void* logits, int V, int ld_logits, int rows, const vo
                     const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
                     void* step_ptr, void* counters, vis_stream_t stream);
 
+/* vis_spec_accept_sampled: vis_spec_accept for a sampled request.  params: 8 bytes of device memory {float inv_temp,
+ * uint32 seed}, read when the launch runs (a captured step serves every temperature and seed).  p_r = the Gumbel-max pick
+ * of row r at hash counter s = (unsigned)(*step_ptr + r): argmax_i of logits[r][i] * inv_temp + gumbel_noise(seed, s, i),
+ * the expression and tie rule of vis_argmax_f32 (a larger value wins, an equal one goes to the lower id, NaN is never
+ * picked, a row without a comparable value picks 0) - bit for bit the token vis_argmax_f32 (batch 1) stores for that row
+ * with *step_ptr = s and that seed.  An inv_temp that is not > 0 gives vis_spec_accept's picks.  Everything behind the
+ * picks - d, a, limit, tokens, *cur_token, *step_ptr, counters - is vis_spec_accept's.  Argument checks: vis_spec_accept's,
+ * and params non-null and 4-byte aligned; VIS_ERR_ARG launches nothing.  Two launches. */
+int vis_spec_accept_sampled(const void* logits, int V, int ld_logits, int rows, const void* draft, const void* n_draft,
+                            const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
+                            void* step_ptr, void* counters, const void* params, vis_stream_t stream);
+
 /* vis_spec_draft: prompt lookup over the history h = prompt_ids[0 .. *prompt_len) followed by tokens[*gen_start ..
  * *step_ptr) (vis_ban_f32's reading), length L.  For m = lookup_max down to lookup_min (1 <= min <= max <= 8) with
  * L > m: the LATEST j < L - m with h[j .. j+m) == h[L-m .. L); the first m with a match writes draft[0 .. d) =

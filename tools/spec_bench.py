@@ -8,6 +8,13 @@
                                                    # t_R / t_1 - 1 = the drafts a step must get accepted, on average, to break
                                                    # even; tokens per step on a synthetic prompt that repeats itself
     python tools/spec_bench.py all [out.json]      # both; default out: profiles/speculative.json
+    python tools/spec_bench.py sampled [out.json] [formats]   # the sampled speculative step (spec.SpecConfig.sampled): kernel -
+                                                   # vis_spec_accept_sampled next to vis_spec_accept at R = 2, 3, 4 - and step,
+                                                   # per format of the comma-separated list (default: all three; "-": none), in
+                                                   # one process: the plain SAMPLED step at T = 0.1, the greedy speculative step
+                                                   # and the sampled speculative step at T = 0.1; the break-even of the last is
+                                                   # t_R / t_1 - 1 against the plain sampled step; every time with the spread
+                                                   # (min .. max) of its repeats; default out: profiles/spec_sampled.json
 
 Every measurement runs in a child process of its own under a time limit (step: one child per format); this process never
 opens the GPU.  A child that fails or runs out of time ends the run: nothing more is started on the GPU.  Times are device
@@ -26,7 +33,7 @@ HQ, HKV, HD, CTX, T, V = 28, 4, 128, 2304, 2560, 152064
 FORMATS = ("bf16", "fp8", "mxfp4")
 
 
-def _time(run, n=20, reps=10) -> float:
+def _time(run, n=20, reps=10, spread=False):
     import numpy as np
     import torch
     run()
@@ -45,10 +52,13 @@ def _time(run, n=20, reps=10) -> float:
         e.record()
         torch.cuda.synchronize()
         ts.append(s.elapsed_time(e) * 1e3 / n)
+    if spread:
+        return [round(float(v), 2) for v in (np.median(ts), min(ts), max(ts))]
     return float(np.median(ts))
 
 
-def kernel_times() -> list:
+def kernel_times(sampled: bool = False) -> list:
+    import numpy as np
     import torch
     from vision_inspection_system_amd import hip
     dev = torch.device("cuda:0")
@@ -71,6 +81,14 @@ def kernel_times() -> list:
         logits = torch.randn((R, V), device=dev)
         wv, wi = torch.empty(256 * R, device=dev), torch.empty(256 * R, dtype=torch.int32, device=dev)
         draft, nd, lim, cur, cnt = ints(1, 2, 3), ints(R - 1), ints(-1), ints(0), ints(0, 0, 0)      # limit -1: no state moves
+        if sampled:      # the same logits through both accepts, each [median, min, max] of the repeats; T = 0.1, seed 1
+            params = torch.from_numpy(np.array([np.float32(10.0).view(np.uint32), 1], dtype=np.uint32).view(np.int32)).to(dev)
+            rows.append({"R": R, "V": V,
+                         "accept_us": _time(lambda: hip.spec_accept(logits, draft, nd, lim, wv, wi, tokens, cur, step, cnt), spread=True),
+                         "accept_sampled_us": _time(lambda: hip.spec_accept_sampled(logits, draft, nd, lim, wv, wi, tokens, cur, step,
+                                                                                    cnt, params), spread=True)})
+            print(json.dumps(rows[-1]), flush=True)
+            continue
         row = {"R": R, "context": CTX,
                "attn_draft_us": round(_time(lambda: hip.decode_attn_draft(qkv, cos, sin, kc, vc, step, po, pml, out, HQ, HKV, HD,
                                                                           ns, HD ** -0.5)), 2),
@@ -86,7 +104,7 @@ def kernel_times() -> list:
     return rows
 
 
-def step_times(fmt: str) -> list:
+def step_times(fmt: str, sampled: bool = False) -> list:
     import numpy as np
     import torch
     from vision_inspection_system_amd import weights as W
@@ -100,7 +118,7 @@ def step_times(fmt: str) -> list:
     ids = [9] + phrase * 16                                      # 385 ids that repeat themselves every 24
     n, reps = 16, 5
 
-    def timed(run) -> float:
+    def timed(run, spread=False):
         ts = []
         for _ in range(reps):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -109,9 +127,13 @@ def step_times(fmt: str) -> list:
             e.record()
             torch.cuda.synchronize()
             ts.append(s.elapsed_time(e) / n)
+        if spread:
+            return [round(float(v), 4) for v in (np.median(ts), min(ts), max(ts))]
         return float(np.median(ts))
 
     rows = []
+    if sampled:
+        return sampled_step_times(eng, fmt, ids, n, timed)
     eng.prefill(ids, [], max_new_tokens=500)
     eng.decode(4)                                                # graph capture and warm-up
     t1 = timed(lambda: eng.decode(n))
@@ -132,19 +154,49 @@ def step_times(fmt: str) -> list:
     return rows
 
 
+def sampled_step_times(eng, fmt, ids, n, timed) -> list:
+    """One process: the plain sampled step (T = 0.1, seed 1), then per R the greedy speculative step and the sampled one; each
+    time [median, min, max] ms."""
+    from vision_inspection_system_amd.spec import SpecConfig
+    T, seed = 0.1, 1
+    eng.prefill(ids, [], max_new_tokens=500, temperature=T, seed=seed)
+    eng.decode(4)
+    t1 = timed(lambda: eng.decode(n), spread=True)
+    rows = [{"format": fmt, "R": 1, "step": "plain sampled" + (" (chained)" if eng.chain_sync is not None else ""),
+             "temperature": T, "step_ms": t1}]
+    print(json.dumps(rows[-1]), flush=True)
+    for R in (2, 3, 4):
+        ts = {}
+        for name, cfg, draw in (("greedy", SpecConfig(R - 1, 4, 2), {}),
+                                ("sampled", SpecConfig(R - 1, 4, 2, True), dict(temperature=T, seed=seed))):
+            eng.prefill(ids, [], max_new_tokens=500, **draw)
+            eng._spec_begin(cfg, 10 ** 6)
+            eng._decode_steps_spec(4, R, True)
+            ts[name] = timed(lambda: eng._decode_steps_spec(n, R, True), spread=True)
+        rows.append({"format": fmt, "R": R, "temperature": T, "speculative_greedy_step_ms": ts["greedy"],
+                     "speculative_sampled_step_ms": ts["sampled"],
+                     "sampled_minus_greedy_ms": round(ts["sampled"][0] - ts["greedy"][0], 4),
+                     "break_even_accepted_per_step_vs_plain_sampled": round(ts["sampled"][0] / t1[0] - 1, 4)})
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def _child(what: str, arg: str) -> None:
     from vision_inspection_system_amd import hip
     hip.load()
-    rows = kernel_times() if what == "kernel" else step_times(arg)
+    if what.endswith("_sampled"):
+        rows = kernel_times(True) if what == "kernel_sampled" else step_times(arg, True)
+    else:
+        rows = kernel_times() if what == "kernel" else step_times(arg)
     print("RESULT " + json.dumps(rows), flush=True)
 
 
 def _run_child(what: str, arg: str = "-") -> list:
     try:
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", what, arg], stdout=subprocess.PIPE, text=True,
-                           timeout=LIMITS[what])
+                           timeout=LIMITS[what.split("_")[0]])
     except subprocess.TimeoutExpired:
-        raise SystemExit(f"spec_bench {what} {arg}: no result within {LIMITS[what]} s - stopping")
+        raise SystemExit(f"spec_bench {what} {arg}: no result within {LIMITS[what.split('_')[0]]} s - stopping")
     sys.stdout.write(p.stdout)
     if p.returncode != 0:
         raise SystemExit(f"spec_bench {what} {arg}: the child ended with status {p.returncode} - stopping")
@@ -156,10 +208,18 @@ if __name__ == "__main__":
         _child(sys.argv[2], sys.argv[3])
         sys.exit(0)
     what = sys.argv[1] if len(sys.argv) > 1 else "kernel"
-    if what not in ("kernel", "step", "all"):
+    if what not in ("kernel", "step", "all", "sampled"):
         raise SystemExit(__doc__)
-    out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "speculative.json")
+    out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "spec_sampled.json" if what == "sampled" else "speculative.json")
     result = {}
+    if what == "sampled":
+        fmts = [f for f in (sys.argv[3].split(",") if len(sys.argv) > 3 else FORMATS) if f != "-"]
+        if any(f not in FORMATS for f in fmts):
+            raise SystemExit(__doc__)
+        result["times"] = "[median, min, max] of the repeats: kernel 10 x 20 replayed launches (us), step 5 x 16 replayed steps (ms)"
+        result["kernel"] = [r for r in _run_child("kernel_sampled") if r["R"] > 1]
+        result["step"] = [row for fmt in fmts for row in _run_child("step_sampled", fmt)]
+        result["step_formats_not_measured"] = [f for f in FORMATS if f not in fmts]
     if what in ("kernel", "all"):
         result["kernel"] = _run_child("kernel")
     if what in ("step", "all"):

@@ -156,17 +156,22 @@ def speculative_kwargs(client, model_id, temperature, others: dict) -> dict:
     on requests that carry none of the switches it excludes (``others``: the keywords of the VIS_* switches above; a
     temperature) and only to this package's own clients.  VIS_SPECULATIVE means the Qwen2-VL engines: a request to an mllama
     model (the Auditor's Llama-3.2-11B-Vision) passes VIS_AUDITOR_SPECULATIVE=k instead, under the same exclusions - that
-    variable also has the engine built for it (client._auditor_kwargs).  Unset: the calls are as before."""
+    variable also has the engine built for it (client._auditor_kwargs).  Unset: the calls are as before.
+    VIS_SPECULATIVE_SAMPLED=1 next to either: the dict carries "sampled": True, and it is passed also at a temperature and
+    when ``others`` holds nothing but ``seed`` (VIS_SEED) - the reference's requests run at temperature 0.1 / 0.2, so this
+    is what turns the step on for them; the reply is the plain sampled reply (spec.check_exclusive).  Any other keyword in
+    ``others`` still means no speculation."""
     from .client import CannedResponseClient, LocalVLMClient, is_mllama_model
-    from .spec import auditor_from_env, from_env
+    from .spec import auditor_from_env, from_env, sampled_from_env
     sp = from_env()
-    if others or temperature or not isinstance(client, (LocalVLMClient, CannedResponseClient)):
+    excluded = set(others) - {"seed"} if sampled_from_env() else (others or temperature)
+    if excluded or not isinstance(client, (LocalVLMClient, CannedResponseClient)):
         return {}
     if is_mllama_model(model_id):
         sp = auditor_from_env()
     if sp is None:
         return {}
-    return {"speculative": {"method": "ngram", "num_speculative_tokens": sp.k}}
+    return {"speculative": {"method": "ngram", "num_speculative_tokens": sp.k, **({"sampled": True} if sp.sampled else {})}}
 
 
 def _logger(name: str) -> logging.Logger:

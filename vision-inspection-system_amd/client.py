@@ -224,11 +224,11 @@ class _Completions:
         """One request; LocalVLMClient._complete_many describes the keywords not described here.
         ``stream=True``: an iterator of ChatCompletionChunk instead of a ChatCompletion (``stream_options``: OpenAI's
         {"include_usage": True}); None or False: the call of before.
-        ``speculative`` (extension; vLLM's names): {"method": "ngram", "num_speculative_tokens": k in 1..3[,
-        "prompt_lookup_max": 4, "prompt_lookup_min": 2]} - lossless n-gram speculative decoding (request.Switches says how):
-        the same text and usage in fewer weight passes where the reply repeats earlier text.  A greedy single request of a
-        Qwen2-VL model only: ValueError with a temperature, a seed, ``n`` > 1 or any other sampling / constraint / stop /
-        stream / logprobs keyword.  None: the call of before.
+        ``speculative`` (extension; vLLM's names): {"method": "ngram", "num_speculative_tokens": k in 1..3[, "prompt_lookup_max": 4,
+        "prompt_lookup_min": 2, "sampled": False]} - lossless n-gram speculative decoding (request.Switches says how): the same
+        text and usage in fewer weight passes where the reply repeats earlier text.  A single request of a Qwen2-VL model only:
+        ValueError with ``n`` > 1 or any other sampling / constraint / stop / stream / logprobs keyword, and with a temperature
+        or a seed unless ``"sampled": True`` opts in (the reply is then the plain sampled reply).  None: the call of before.
         ``prediction`` (OpenAI's Predicted Outputs): {"type": "content", "content": text} - or content as a list of {"type":
         "text", "text": ...} parts - text the reply will probably repeat: the previous reply of a retry, the report of an
         earlier inspection of the same part, a fixed template.  The speculative step drafts from it; the text and
@@ -752,7 +752,7 @@ class LocalVLMClient:
         return build_chat_ids(lm.tokenizer, messages, counts), frames
 
     def _complete(self, model, messages, temperature, max_tokens, speculative=None, prediction=None, **kwargs):
-        from .spec import check_prediction
+        from .spec import check_prediction, sampled_seed
         kw = _request_keywords(kwargs)      # an OpenAI keyword ``create`` swallowed and this client does not know ends here
         text = check_prediction(prediction)
         if speculative is not None or text is not None:
@@ -762,7 +762,8 @@ class LocalVLMClient:
                 raise ValueError(("speculative decoding is" if text is None else "prediction (speculative decoding) is") +
                                  " offered for Qwen2-VL / Qwen2.5-VL models only, unless VIS_AUDITOR_SPECULATIVE=k (1..3) "
                                  "has the Mllama engine built for it")
-            return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp, prediction=text)[0]
+            return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp, prediction=text,
+                                       checked=sampled_seed(sp, kw.get("seed"), self.seed))[0]      # no other keyword is on
         out = self.complete_many(model, [messages], temperature, max_tokens, **kw)
         return out if isinstance(out, ChatCompletionStream) else out[0]
 
@@ -852,7 +853,7 @@ class LocalVLMClient:
         = off.  Not together with a ``response_format`` of json_object or json_schema: ValueError.  Checked before any GPU
         work.  Logprobs keep their meaning.
         ``speculative`` (a spec.SpecConfig, from ``create`` only - ``complete_many`` does not offer it): the ONE request of the
-        call goes through the engine's ``generate(.., speculative=)``; every other keyword is off then (create checks).
+        call goes through the engine's ``generate(.., speculative=)``; every other keyword is off then (create checks; a sampled one keeps its seed).
         ``prediction`` (the text of create's ``prediction``, next to ``speculative``): tokenised without special tokens, at
         most the engine's max_ctx ids, handed to ``generate(.., prediction=)``; the completion's usage then carries
         ``completion_tokens_details``."""

@@ -16,6 +16,7 @@
 //  * vis_spec_accept: the greedy pick of every row (vis_argmax_f32's comparison: larger value, ties to the lower id, a row
 //    without a comparable logit picks id 0), the count `a` of leading drafts that equal the pick of the row in front of them,
 //    and the bookkeeping of a step that produced a + 1 tokens.
+//  * vis_spec_accept_sampled: the same with the Gumbel-max pick of a sampled request, row r at hash counter *step_ptr + r.
 //  * vis_spec_draft: prompt lookup - the latest earlier occurrence of the last m ids of the history (m from lookup_max down
 //    to lookup_min) and the ids that followed it.  spec.propose() is its definition.
 //  * vis_spec_draft_pred: the drafter of a request with a prediction (spec.propose_pred() is its definition): a cursor into
@@ -373,6 +374,65 @@ extern "C" int vis_spec_accept(const void* logits, int V, int ld_logits, int row
   vis_clear_error();
   hipLaunchKernelGGL(spec_pick_kernel, dim3(nb, rows), dim3(256), 0, stream, (const float*)logits, V, ld_logits,
                      (float*)ws_val, (int*)ws_idx);
+  hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx, nb, rows,
+                     (const int*)draft, (const int*)n_draft, (const int*)limit, (int*)tokens, max_tokens, (int*)cur_token,
+                     (int*)step_ptr, (int*)counters);
+  return vis_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------- vis_spec_accept_sampled
+// vis_spec_accept with the SAMPLED pick of every row: row r perturbs id i with gumbel_noise(seed, *step_ptr + r, i) - the
+// hash counter the plain loop has when it picks from these logits - in argmax_stage1_body's source expression and under its
+// tie rule, so row r's pick is the token vis_argmax_f32 stores for that row at step *step_ptr + r, bit for bit.  inv_temp and
+// seed come from device memory (8 bytes, read at run time): one captured step serves every temperature and seed.  An
+// inv_temp that is not > 0 (0, negative, NaN) leaves the logits alone: vis_spec_accept's picks.  The step only feeds the
+// hash, never an address.  Stage 2 is spec_accept_kernel itself.
+struct SpSampleParams {
+  float inv_temp;
+  unsigned seed;
+};
+
+__global__ __launch_bounds__(256) void spec_pick_sampled_kernel(const float* __restrict__ logits, int V, int ld,
+                                                                const int* __restrict__ step_ptr,
+                                                                const SpSampleParams* __restrict__ params,
+                                                                float* __restrict__ bval, int* __restrict__ bidx) {
+  const int tid = threadIdx.x, row = blockIdx.y;
+  const float* __restrict__ x = logits + (size_t)row * ld;
+  const float inv_temp = params->inv_temp;
+  const unsigned seed = params->seed;
+  const unsigned step = (unsigned)*step_ptr + (unsigned)row;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = blockIdx.x * 256 + tid; i < V; i += gridDim.x * 256) {
+    float v = x[i];
+    if (inv_temp > 0.f) v = v * inv_temp + gumbel_noise(seed, step, (unsigned)i);
+    sp_better(best, bi, v, i);
+  }
+  sp_wave_best(best, bi);
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) sp_better(best, bi, sv[w], si[w]);
+    bval[row * 256 + blockIdx.x] = best;
+    bidx[row * 256 + blockIdx.x] = bi;
+  }
+}
+
+extern "C" int vis_spec_accept_sampled(const void* logits, int V, int ld_logits, int rows, const void* draft, const void* n_draft,
+                                       const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens,
+                                       void* cur_token, void* step_ptr, void* counters, const void* params, hipStream_t stream) {
+  if (!logits || !draft || !n_draft || !limit || !ws_val || !ws_idx || !tokens || !cur_token || !step_ptr || !counters || !params)
+    return VIS_ERR_ARG;
+  if (V <= 0 || rows < 1 || rows > SP_MAXROWS || ld_logits < V || max_tokens <= 0) return VIS_ERR_ARG;
+  if (((uintptr_t)logits | (uintptr_t)draft | (uintptr_t)n_draft | (uintptr_t)limit | (uintptr_t)ws_val | (uintptr_t)ws_idx |
+       (uintptr_t)tokens | (uintptr_t)cur_token | (uintptr_t)step_ptr | (uintptr_t)counters | (uintptr_t)params) & 3)
+    return VIS_ERR_ARG;
+  const int nb = min(256, (V + 255) / 256);
+  vis_clear_error();
+  hipLaunchKernelGGL(spec_pick_sampled_kernel, dim3(nb, rows), dim3(256), 0, stream, (const float*)logits, V, ld_logits,
+                     (const int*)step_ptr, (const SpSampleParams*)params, (float*)ws_val, (int*)ws_idx);
   hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx, nb, rows,
                      (const int*)draft, (const int*)n_draft, (const int*)limit, (int*)tokens, max_tokens, (int*)cur_token,
                      (int*)step_ptr, (int*)counters);

@@ -281,6 +281,8 @@ class DecodeStage(PickStage):
         start = self.prompt_len - 1
         self._spec.begin(self.cur_token, self._slot_ids[0], start, min(start + max_new_tokens - 1, self.max_ctx - 2),
                          prediction)
+        if cfg.sampled:      # the row seed the prompt pass's pick just drew with (PickStage._seed_slot's choice for slot 0)
+            self._spec.set_params(self.temperature, self._slot_seed.get(0, self.seed))
         if self._spec_pred:
             self._spec_draft_pred(cfg.k)
         return self._spec
@@ -296,7 +298,8 @@ class DecodeStage(PickStage):
         attention (row r = the plain launch at step + r, bit for bit; a cross-attention layer: the q projection into the
         leading columns of the packed rows and ``_decode_cross_attn_draft``, row r = the plain cross launch on row r, skipped
         while the request has no image as in the plain step), the lm_head into [R, V] f32, then vis_spec_accept -
-        which keeps the drafts the picks confirm and advances ``step`` by 1..R - and vis_spec_draft for the next step
+        which keeps the drafts the picks confirm and advances ``step`` by 1..R (vis_spec_accept_sampled, the same with the
+        sampled pick, when the request's configuration opted in; the only launch that differs) - and vis_spec_draft for the next step
         (vis_spec_draft_pred instead when the request came with a prediction).
         Never the chained launch: the chain is bit-identical to the four launches, so the tokens are the chained step's.
         ``propose`` False leaves the draft row and its count alone (a test plants them)."""
@@ -322,8 +325,12 @@ class DecodeStage(PickStage):
             gemv_rows(x2, *_wt(L, "gateup_w", fmt), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
             gemv_rows(act, *_wt(L, "down_w", fmt), x, residual=x2)
         gemv_rows(x, *self.dec_head[fmt], logits, norm_w=self.dec_norm_w, eps=eps)
-        hip.spec_accept(logits, sp.draft, sp.n_draft, sp.limit, sp.ws_val, sp.ws_idx, self.tokens, sp.cur, self.step,
-                        sp.counters)
+        if self._spec_cfg.sampled:      # row r's pick: the plain loop's sampled pick at step + r; 1 / T and the seed from params
+            hip.spec_accept_sampled(logits, sp.draft, sp.n_draft, sp.limit, sp.ws_val, sp.ws_idx, self.tokens, sp.cur,
+                                    self.step, sp.counters, sp.params)
+        else:
+            hip.spec_accept(logits, sp.draft, sp.n_draft, sp.limit, sp.ws_val, sp.ws_idx, self.tokens, sp.cur, self.step,
+                            sp.counters)
         if propose and R > 1 and self._spec_pred:
             self._spec_draft_pred(R - 1)
         elif propose and R > 1:
@@ -338,12 +345,13 @@ class DecodeStage(PickStage):
 
     def _spec_graph(self, R: int) -> torch.cuda.CUDAGraph:
         """The captured speculative step, keyed by (R, weight format, the lookup window, whether the cross-attention layers run,
-        and "pred" when the step ends with the prediction drafter): its launches read everything else - the prediction, its
-        length, the drafter's state - from device memory.  The warm-up step advances the request's counters; they are put back
-        before the capture."""
+        "pred" when the step ends with the prediction drafter, and "sampled" when its accept is the sampled one): its launches
+        read everything else - the prediction, its length, the drafter's state, the inverse temperature and the seed - from
+        device memory.  The warm-up step advances the request's counters; they are put back before the capture."""
         c = self._spec_cfg
         cross = (("image" if self.has_image else "text"),) if self.dec_n_self != len(self.dec_layers) else ()
-        key = ("spec", R, self.decode_weights, c.lookup_max, c.lookup_min) + cross + (("pred",) if self._spec_pred else ())
+        key = ("spec", R, self.decode_weights, c.lookup_max, c.lookup_min) + cross + (("pred",) if self._spec_pred else ()) + \
+            (("sampled",) if c.sampled else ())
         if key in self._spec_graphs:
             return self._spec_graphs[key]
         sp = self._spec

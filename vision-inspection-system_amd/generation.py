@@ -106,7 +106,7 @@ class Generation(DecodeStage):
             self._stream_bind([[0]])
             max_new_tokens = self._clamp_request(input_ids, max_new_tokens)
             if sp is not None:      # no chained launch in a speculative step: nothing of the stall handling below applies
-                return self._run_single_spec(sp, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, pred)
+                return self._run_single_spec(sp, input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, pred, temperature, seed)
             try:
                 out = self._run_single(input_ids, frames, max_new_tokens, ignore_eos, use_graph, check_every, temperature, seed)
                 self._maybe_reenable_chain()
@@ -151,14 +151,14 @@ class Generation(DecodeStage):
         return toks
 
     def _run_single_spec(self, sp: "spec.SpecConfig", input_ids, frames, max_new_tokens, ignore_eos, use_graph,
-                         check_every, prediction=None) -> List[int]:
+                         check_every, prediction=None, temperature=0.0, seed=0) -> List[int]:
         """_run_single with speculative steps: ``check_every`` steps are issued ahead as there, then the poll reads the device
         step counter together with the token row - a step has produced 1..R tokens.  Ends at EOS or when the reply has
         max_new_tokens tokens (the device ``limit`` cuts the last step's run there; steps issued past it change nothing)."""
         R = sp.rows
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
-        self._prompt_pass(input_ids, frames, max_new_tokens + R - 1, 0.0, 0)      # rope rows for the rows past the last token
+        self._prompt_pass(input_ids, frames, max_new_tokens + R - 1, temperature or 0.0, seed or 0)      # + rope rows past the last token
         ev[1].record()
         max_new_tokens = max(1, min(max_new_tokens, self.max_ctx - len(input_ids) - 1))
         buf = self._spec_begin(sp, max_new_tokens, prediction)

@@ -79,6 +79,7 @@ _SIGS = {
     "vis_decode_cross_attn_draft": "pppppppp" + "iiiii" + "ff" + "il" + "p",
     "vis_decode_cross_attn_fp8_draft": "pppppppppp" + "iiiii" + "ff" + "il" + "p",
     "vis_spec_accept": "p" + "iii" + "pppppp" + "i" + "ppp" + "p",
+    "vis_spec_accept_sampled": "p" + "iii" + "pppppp" + "i" + "ppp" + "p" + "p",
     "vis_spec_draft": "pi" + "pp" + "i" + "pp" + "iiii" + "pp" + "p",
     "vis_spec_draft_pred": "pi" + "pp" + "i" + "pp" + "iiii" + "pi" + "pp" + "pp" + "p",
     "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
@@ -1602,6 +1603,28 @@ def spec_accept(logits: torch.Tensor, draft: torch.Tensor, n_draft: torch.Tensor
                                 _ptr(ws_idx), _ptr(tokens), tokens.numel(), _ptr(cur_token), _ptr(step), _ptr(counters),
                                 _stream())
     _check(rc, "vis_spec_accept")
+
+
+def spec_accept_sampled(logits: torch.Tensor, draft: torch.Tensor, n_draft: torch.Tensor, limit: torch.Tensor,
+                        ws_val: torch.Tensor, ws_idx: torch.Tensor, tokens: torch.Tensor, cur_token: torch.Tensor,
+                        step: torch.Tensor, counters: torch.Tensor, params: torch.Tensor) -> None:
+    """spec_accept with the sampled pick (vis_spec_accept_sampled): row r's pick is argmax's token for that row at step[0] + r.
+    params int32 [2] in device memory: the bits of the f32 inv_temp (1 / temperature; 0 = greedy) and the uint32 seed,
+    read when the launch runs.  Everything else as spec_accept."""
+    ints = (draft, n_draft, limit, ws_idx, tokens, cur_token, step, counters, params)
+    if logits.dtype != torch.float32 or ws_val.dtype != torch.float32 or any(t.dtype != torch.int32 for t in ints):
+        raise HipLibraryError("spec_accept_sampled: f32 logits, ws_val / int32 everything else required")
+    if logits.dim() != 2 or not 1 <= logits.shape[0] <= SPEC_MAX_ROWS or logits.stride(1) != 1:
+        raise HipLibraryError("spec_accept_sampled: logits must be [1..4, V] with unit column stride")
+    R, V = logits.shape
+    if draft.numel() < max(1, R - 1) or any(t.numel() != 1 for t in (n_draft, limit, cur_token, step)) or counters.numel() != 3 \
+            or params.numel() != 2 or ws_val.numel() < 256 * R or ws_idx.numel() < 256 * R \
+            or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("spec_accept_sampled: bad parameter shapes")
+    rc = load().vis_spec_accept_sampled(_ptr(logits), V, logits.stride(0), R, _ptr(draft), _ptr(n_draft), _ptr(limit),
+                                        _ptr(ws_val), _ptr(ws_idx), _ptr(tokens), tokens.numel(), _ptr(cur_token), _ptr(step),
+                                        _ptr(counters), _ptr(params), _stream())
+    _check(rc, "vis_spec_accept_sampled")
 
 
 def spec_draft(prompt_ids: torch.Tensor, prompt_len: torch.Tensor, tokens: torch.Tensor, gen_start: torch.Tensor,

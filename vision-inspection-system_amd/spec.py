@@ -10,7 +10,12 @@ step would have picked.  The accept step keeps exactly that prefix, so the reply
 
 A request may bring a second source of drafts, the caller's prediction of the reply (OpenAI's Predicted Outputs:
 ``check_prediction``): ``propose_pred`` is that drafter's definition (vis_spec_draft_pred equals it exactly), and
-``simulate_prediction`` the model-free walk that gives the counters a run must report."""
+``simulate_prediction`` the model-free walk that gives the counters a run must report.
+
+A request that opts in (``"sampled": True``) may sample: the engines' pick at a temperature is Gumbel-max over a counter hash
+of (seed, step, id), so the token is a pure function of (logits row, seed, step), and row r of a step carries the logits of
+step + r.  vis_spec_accept_sampled takes every row's pick with that counter (``accept_ref_sampled`` walks given picks); the
+reply is then the plain SAMPLED reply token for token - equality, not rejection sampling's equality in distribution."""
 from __future__ import annotations
 
 import os
@@ -24,14 +29,28 @@ MAX_LOOKUP = 8       # hip.SPEC_MAX_LOOKUP
 ROWS_LDS_MAX = 152 * 1024      # GV_ROWS_LDS_MAX of csrc/decode.hip: the input rows of a multi-row GEMV live in LDS
 
 
-class SpecConfig(NamedTuple):
-    k: int               # num_speculative_tokens
-    lookup_max: int      # prompt_lookup_max
-    lookup_min: int      # prompt_lookup_min
+class SpecConfig(tuple):
+    """(k, lookup_max, lookup_min[, True]): num_speculative_tokens, prompt_lookup_max, prompt_lookup_min and ``sampled`` - the
+    request's own opt-in: the accept step takes the sampled pick (vis_spec_accept_sampled).  The fourth value stands in the
+    tuple only when it is set, so the record of a request that did not opt in is, value for value, the three-field record
+    of before (what the engines are handed and what a recorded call compares against); SpecConfig(2, 4, 2) ==
+    SpecConfig(2, 4, 2, False)."""
+    __slots__ = ()
+
+    def __new__(cls, k: int, lookup_max: int, lookup_min: int, sampled: bool = False):
+        return tuple.__new__(cls, (k, lookup_max, lookup_min) + ((True,) if sampled else ()))
+
+    k = property(lambda self: self[0])
+    lookup_max = property(lambda self: self[1])
+    lookup_min = property(lambda self: self[2])
+    sampled = property(lambda self: len(self) > 3)
 
     @property
     def rows(self) -> int:
         return self.k + 1
+
+    def __repr__(self) -> str:
+        return f"SpecConfig(k={self.k}, lookup_max={self.lookup_max}, lookup_min={self.lookup_min}, sampled={self.sampled})"
 
 
 def _int(v, name: str, lo: int, hi: int) -> int:
@@ -42,17 +61,18 @@ def _int(v, name: str, lo: int, hi: int) -> int:
 
 def check_speculative(speculative) -> Optional[SpecConfig]:
     """None (off), the integer k, or {"method": "ngram", "num_speculative_tokens": k[, "prompt_lookup_max": 4,
-    "prompt_lookup_min": 2]} (vLLM's names) -> SpecConfig or None; ValueError otherwise."""
+    "prompt_lookup_min": 2][, "sampled": False]} (vLLM's names; ``sampled`` is this package's: the request may carry a
+    temperature and a seed, see check_exclusive) -> SpecConfig or None; ValueError otherwise."""
     if speculative is None:
         return None
     if isinstance(speculative, SpecConfig):
         speculative = {"method": "ngram", "num_speculative_tokens": speculative.k, "prompt_lookup_max": speculative.lookup_max,
-                       "prompt_lookup_min": speculative.lookup_min}
+                       "prompt_lookup_min": speculative.lookup_min, "sampled": speculative.sampled}
     if isinstance(speculative, int) and not isinstance(speculative, bool):
         speculative = {"method": "ngram", "num_speculative_tokens": speculative}
     if not isinstance(speculative, dict):
         raise ValueError("speculative must be None, an integer k or a dict with 'method' and 'num_speculative_tokens'")
-    unknown = set(speculative) - {"method", "num_speculative_tokens", "prompt_lookup_max", "prompt_lookup_min"}
+    unknown = set(speculative) - {"method", "num_speculative_tokens", "prompt_lookup_max", "prompt_lookup_min", "sampled"}
     if unknown:
         raise ValueError(f"speculative: unknown keys {sorted(unknown)}")
     if speculative.get("method", "ngram") != "ngram":
@@ -62,7 +82,10 @@ def check_speculative(speculative) -> Optional[SpecConfig]:
     k = _int(speculative["num_speculative_tokens"], "num_speculative_tokens", 1, MAX_K)
     hi = _int(speculative.get("prompt_lookup_max", 4), "prompt_lookup_max", 1, MAX_LOOKUP)
     lo = _int(speculative.get("prompt_lookup_min", min(2, hi)), "prompt_lookup_min", 1, hi)
-    return SpecConfig(k, hi, lo)
+    sampled = speculative.get("sampled", False)
+    if not isinstance(sampled, bool):
+        raise ValueError("speculative: sampled must be True or False")
+    return SpecConfig(k, hi, lo, sampled)
 
 
 PRED_DEFAULT = SpecConfig(3, 4, 2)      # what ``prediction`` alone implies: four rows per step, vLLM's lookup window
@@ -127,9 +150,14 @@ def check_exclusive(cfg: Optional[SpecConfig], temperature: float = 0.0, seed=No
                     **switches) -> None:
     """What a speculative request may not carry: every switch that is a per-step device state machine advancing one token
     at a time, and everything that samples.  ``switches``: name -> value as the caller got it (None / neutral = off).
-    ValueError naming the conflict.  ``what``: how the messages name the request's argument."""
+    ValueError naming the conflict.  ``what``: how the messages name the request's argument.
+    A request that opted in (``cfg.sampled``) may carry ``temperature`` and ``seed``: its pick is Gumbel-max over a counter
+    hash, a pure function of (logits row, seed, step), so "the draft equals the pick of the row in front of it" stays exact
+    with the sampled pick at hash counter step + r (vis_spec_accept_sampled).  ``top_p`` and everything else stay refused."""
     if cfg is None:
         return
+    if cfg.sampled:
+        temperature = seed = None
     if temperature:
         raise ValueError(f"{what} together with temperature > 0 is not supported: acceptance is defined for the greedy pick")
     if seed:
@@ -147,8 +175,31 @@ def check_exclusive(cfg: Optional[SpecConfig], temperature: float = 0.0, seed=No
                              "speculative step yields several tokens")
 
 
+def sampled_seed(cfg: SpecConfig, seed, default: int):
+    """The client's checked keywords of ONE speculative request (client.engine_keywords' pair: the engine keywords that are
+    on, the call's seed).  No other keyword is on; a request that opted in hands ``generate`` the seed the plain single
+    request draws with - its own ``seed`` where it brought one, else the client's ``default``.  A request that did not is
+    the call of before: nothing on."""
+    from .sampling import check_seed
+    if not cfg.sampled:
+        return {}, None
+    seed = check_seed(seed)
+    return {"seed": default if seed is None else seed}, None
+
+
+def sampled_from_env() -> bool:
+    """VIS_SPECULATIVE_SAMPLED (unset, empty or 0 = off; 1 = on; anything else: ValueError): the configurations from_env and
+    auditor_from_env return carry ``sampled``, so the agents' requests keep speculating at their temperature and seed."""
+    v = os.environ.get("VIS_SPECULATIVE_SAMPLED", "").strip()
+    if v not in ("", "0", "1"):
+        raise ValueError("VIS_SPECULATIVE_SAMPLED must be 0 or 1")
+    return v == "1"
+
+
 def from_env() -> Optional[SpecConfig]:
-    """VIS_SPECULATIVE=k (1..3; unset, empty or 0 = off): the agents pass it on requests without an excluded switch."""
+    """VIS_SPECULATIVE=k (1..3; unset, empty or 0 = off): the agents pass it on requests without an excluded switch.
+    VIS_SPECULATIVE_SAMPLED=1 next to it sets ``sampled`` on the configuration."""
+    sampled = sampled_from_env()
     v = os.environ.get("VIS_SPECULATIVE", "").strip()
     if v in ("", "0"):
         return None
@@ -156,7 +207,7 @@ def from_env() -> Optional[SpecConfig]:
         k = int(v)
     except ValueError:
         raise ValueError("VIS_SPECULATIVE must be an integer in 0..3") from None
-    return check_speculative(k)
+    return check_speculative({"num_speculative_tokens": k, "sampled": sampled})
 
 
 def check_rows_fit(cfg_model, rows: int) -> None:
@@ -178,7 +229,9 @@ def check_cross_rows_fit(cfg_model, rows: int) -> None:
 def auditor_from_env() -> Optional[SpecConfig]:
     """VIS_AUDITOR_SPECULATIVE=k (1..3; unset, empty or 0 = off; anything else: ValueError): the Auditor's (Mllama) engine is
     built with speculative=True, the clients accept ``speculative`` / ``prediction`` for one request of an mllama model, and
-    the agents pass k on a single request to one.  VIS_SPECULATIVE is the Qwen2-VL engines' and is not read here."""
+    the agents pass k on a single request to one.  VIS_SPECULATIVE is the Qwen2-VL engines' and is not read here;
+    VIS_SPECULATIVE_SAMPLED=1 sets ``sampled`` on the configuration as in from_env."""
+    sampled = sampled_from_env()
     v = os.environ.get("VIS_AUDITOR_SPECULATIVE", "").strip()
     if v in ("", "0"):
         return None
@@ -188,7 +241,7 @@ def auditor_from_env() -> Optional[SpecConfig]:
         k = -1
     if not 1 <= k <= MAX_K:
         raise ValueError(f"VIS_AUDITOR_SPECULATIVE must be an integer in 0..{MAX_K}")
-    return check_speculative(k)
+    return check_speculative({"num_speculative_tokens": k, "sampled": sampled})
 
 
 # ----------------------------------------------------------------------------------------------------- references
@@ -311,6 +364,25 @@ def accept_ref(logits: np.ndarray, draft: Sequence[int], d: int, step: int, limi
     return tokens, picks[a], step + a + 1, [counters[0] + 1, counters[1] + d, counters[2] + a]
 
 
+def accept_ref_sampled(picks: Sequence[int], draft: Sequence[int], d: int, step: int, limit: int, tokens: np.ndarray,
+                       counters: Sequence[int]):
+    """The model-free half of accept_ref, which vis_spec_accept and vis_spec_accept_sampled share: the walk over GIVEN per-row
+    picks (row r's pick, however it was made - the sampled one at hash counter step + r).  Returns (tokens, cur_token or
+    None, step, counters) after the call."""
+    tokens, counters, picks = np.array(tokens), list(counters), [int(p) for p in picks]
+    R = len(picks)
+    lim = min(limit, len(tokens) - 1)
+    if step < 0 or step > lim:
+        return tokens, None, step, counters
+    d = min(max(d, 0), R - 1)
+    a = 0
+    while a < d and draft[a] == picks[a]:
+        a += 1
+    a = min(a, lim - step)
+    tokens[step:step + a + 1] = picks[:a + 1]
+    return tokens, picks[a], step + a + 1, [counters[0] + 1, counters[1] + d, counters[2] + a]
+
+
 # --------------------------------------------------------------------------------------------------- device buffers
 class SpecBuffers:
     """What the speculative step of one engine owns: its own activation rows (an engine built with max_batch=1 has no
@@ -340,6 +412,8 @@ class SpecBuffers:
         self.counters = ints[4:7]                                           # steps, proposed, accepted
         self.pred_len, self.pred_state = ints[8:9], ints[9:16]              # ... and the PredState ints behind its length
         self._ints = ints
+        # what vis_spec_accept_sampled reads at run time: the bits of the f32 inv_temp, the uint32 seed (8 bytes)
+        self.params = torch.zeros(2, dtype=torch.int32, device=dev)
 
     @property
     def cur(self) -> torch.Tensor:
@@ -363,6 +437,13 @@ class SpecBuffers:
             self.pred[:len(p)].copy_(torch.tensor(p, dtype=torch.int32))
         self._ints.copy_(torch.tensor([0, limit, n, step0, 0, 0, 0, 0, len(p)] + list(PredState()), dtype=torch.int32),
                          non_blocking=False)
+
+    def set_params(self, temperature: float, seed: int) -> None:
+        """The sampled accept's parameters of the request starting: inv_temp as hip.argmax forms it (the double quotient
+        narrowed to f32; 0 at temperature 0 = the greedy pick) and the seed modulo 2^32."""
+        inv_temp = np.float32((1.0 / temperature) if temperature > 0 else 0.0)
+        raw = np.array([inv_temp.view(np.uint32), int(seed) & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)
+        self.params.copy_(torch.from_numpy(raw))
 
     def read_counters(self) -> List[int]:
         return [int(v) for v in self.counters.cpu().tolist()]
