@@ -652,7 +652,8 @@ int vis_decode_attn_draft(const void* qkv, const void* cos_t, const void* sin_t,
                           const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
                           int cache_tokens, int nsplit, float scale, int rows, long long qkv_ld, vis_stream_t stream);
 
-/* vis_decode_cross_attn_draft: vis_decode_cross_attn (below) for the `rows` (1..4) rows of ONE sequence's speculative step.
+/* vis_decode_cross_attn_draft (csrc/cross_attn.hip): vis_decode_cross_attn (below) for the `rows` (1..4) rows of ONE sequence's
+ * speculative step.
  * Row r's q is q + r * q_ld (q_ld >= Hq * 128, a multiple of 8: the leading columns of a wider projection row may be passed);
  * all rows attend the same static keys [0, *nkeys_m1 + 1) - one count, read from device memory and clamped into
  * [.., key_tokens).  One workgroup per (kv head, split of 64 keys) loads the split's K / V once and serves every row: row r's
@@ -663,7 +664,7 @@ int vis_decode_attn_draft(const void* qkv, const void* cos_t, const void* sin_t,
 int vis_decode_cross_attn_draft(const void* q, const void* q_norm_w, const void* k, const void* v, const void* nkeys_m1,
                                 void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD, int key_tokens, int nsplit,
                                 float scale, float eps, int rows, long long q_ld, vis_stream_t stream);
-/* The same over the fp8 copies of the keys / values (vis_decode_cross_attn_fp8's operands and checks; csrc/cross_kv.hip):
+/* The same over the fp8 copies of the keys / values (vis_decode_cross_attn_fp8's operands and checks; csrc/cross_attn.hip):
  * output row r is bit-identical to vis_decode_cross_attn_fp8 on q row r alone. */
 int vis_decode_cross_attn_fp8_draft(const void* q, const void* q_norm_w, const void* k_codes, const void* k_scale,
                                     const void* v_codes, const void* v_scale, const void* nkeys_m1, void* part_o,
@@ -742,7 +743,7 @@ int vis_decode_cross_attn_batch(const void* q, const void* q_norm_w, const void*
                                 int key_tokens, int nsplit, float scale, float eps, int batch, long long q_bs,
                                 long long kv_bs, vis_stream_t stream);
 
-/* vis_decode_cross_attn over fp8 (OCP e4m3) copies of the static keys / values (csrc/cross_kv.hip): codes uint8
+/* vis_decode_cross_attn over fp8 (OCP e4m3) copies of the static keys / values (csrc/cross_attn.hip): codes uint8
  * [Hkv][key_tokens][128] and one f32 scale per (kv head, key row) [Hkv][key_tokens] for K and for V, as vis_quant_rows_fp8
  * (no norm) writes them over the bf16 rows.  key_tokens is a multiple of 64; codes and scales are 16-byte aligned.  Same split
  * plan, key range [0, *nkeys_m1 + 1) and partials as the bf16 entry; P stays f32, the V row scale rides in the weight. */

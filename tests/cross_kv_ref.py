@@ -1,4 +1,4 @@
-"""Restatements, from the stated definition, of the fp8 cross-attention keys / values (csrc/cross_kv.hip, MllamaEngine
+"""Restatements, from the stated definition, of the fp8 cross-attention keys / values (csrc/cross_attn.hip, MllamaEngine
 cross_kv="fp8"): the row quantiser, the attention over codes and scales in float64, a float32 emulation of the kernel's
 order of operations, and the slack the comparison allows.
 

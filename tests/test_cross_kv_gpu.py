@@ -1,4 +1,4 @@
-"""fp8 (e4m3) cross-attention keys / values at kernel level (csrc/cross_kv.hip): the row quantiser bit for bit against the
+"""fp8 (e4m3) cross-attention keys / values at kernel level (csrc/cross_attn.hip): the row quantiser bit for bit against the
 numpy restatement, vis_decode_cross_attn_fp8 against float64 on the SAME codes and scales inside the derived slack of
 tests/cross_kv_ref.py (no element excluded), an exact mean, poisoned rows past the key count, the batch form against the
 single launch, and the refusals."""

@@ -717,48 +717,29 @@ __global__ __launch_bounds__(256) void decode_attn_combine_kernel(const float* _
   decode_attn_combine_body(part_o, part_ml, out, nsplit, step_ptr, cache_tokens, 0);
 }
 
-static int decode_attn_launch(const DecAttnArgs& p, void* out, int batch, hipStream_t stream) {
-  const int G = p.Hq / p.Hkv;
+// the streaming form: one workgroup per (kv head, sequence); non-static: vis_decode_cross_attn_batch (cross_attn.hip) launches it too
+int decode_attn_stream_launch(const DecAttnArgs& p, void* out, int batch, hipStream_t stream) {
   const bool fork = p.fork_parent != nullptr;     // the forked entry points: their own instantiations, same plan
   vis_clear_error();
-  // Enough (kv head, sequence) pairs to fill the chip on their own: the streaming form - one workgroup per pair, the
-  // whole context in one pass, no partials, no combine.  VIS_DECODE_ATTN_STREAM=0 keeps the split form (A/B).
-  // (read per launch - not cached - so that a test can compare both forms in one process; graph capture bakes it in)
-  const char* se = getenv("VIS_DECODE_ATTN_STREAM");
-  const int stream_env = se ? atoi(se) : 1;
-  if (stream_env == 2 || (stream_env && p.Hkv * batch >= 128)) {   // 2: force (tests at small batch)
-    const dim3 grid(p.Hkv, batch), block(512);
-    if (fork) switch (G) {
-      case 1: hipLaunchKernelGGL((decode_attn_stream_kernel<1, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
-      case 2: hipLaunchKernelGGL((decode_attn_stream_kernel<2, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
-      case 4: hipLaunchKernelGGL((decode_attn_stream_kernel<4, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
-      case 7: hipLaunchKernelGGL((decode_attn_stream_kernel<7, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
-      default: hipLaunchKernelGGL((decode_attn_stream_kernel<8, true>), grid, block, 0, stream, p, (bf16_t*)out); break;
-    }
-    else switch (G) {
-      case 1: hipLaunchKernelGGL(decode_attn_stream_kernel<1>, grid, block, 0, stream, p, (bf16_t*)out); break;
-      case 2: hipLaunchKernelGGL(decode_attn_stream_kernel<2>, grid, block, 0, stream, p, (bf16_t*)out); break;
-      case 4: hipLaunchKernelGGL(decode_attn_stream_kernel<4>, grid, block, 0, stream, p, (bf16_t*)out); break;
-      case 7: hipLaunchKernelGGL(decode_attn_stream_kernel<7>, grid, block, 0, stream, p, (bf16_t*)out); break;
-      default: hipLaunchKernelGGL(decode_attn_stream_kernel<8>, grid, block, 0, stream, p, (bf16_t*)out); break;
-    }
-    return vis_check_launch();
-  }
+  const dim3 grid(p.Hkv, batch), block(512);
+  da_dispatch_g(p.Hq / p.Hkv, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    if (fork) hipLaunchKernelGGL((decode_attn_stream_kernel<G, true>), grid, block, 0, stream, p, (bf16_t*)out);
+    else hipLaunchKernelGGL(decode_attn_stream_kernel<G>, grid, block, 0, stream, p, (bf16_t*)out);
+  });
+  return vis_check_launch();
+}
+
+static int decode_attn_launch(const DecAttnArgs& p, void* out, int batch, hipStream_t stream) {
+  if (da_use_stream_form(p.Hkv, batch)) return decode_attn_stream_launch(p, out, batch, stream);
+  const bool fork = p.fork_parent != nullptr;
+  vis_clear_error();
   const dim3 grid(p.Hkv, p.nsplit, batch), block(256);
-  if (fork) switch (G) {
-    case 1: hipLaunchKernelGGL((decode_attn_fused_kernel<1, true>), grid, block, 0, stream, p); break;
-    case 2: hipLaunchKernelGGL((decode_attn_fused_kernel<2, true>), grid, block, 0, stream, p); break;
-    case 4: hipLaunchKernelGGL((decode_attn_fused_kernel<4, true>), grid, block, 0, stream, p); break;
-    case 7: hipLaunchKernelGGL((decode_attn_fused_kernel<7, true>), grid, block, 0, stream, p); break;
-    default: hipLaunchKernelGGL((decode_attn_fused_kernel<8, true>), grid, block, 0, stream, p); break;
-  }
-  else switch (G) {
-    case 1: hipLaunchKernelGGL(decode_attn_fused_kernel<1>, grid, block, 0, stream, p); break;
-    case 2: hipLaunchKernelGGL(decode_attn_fused_kernel<2>, grid, block, 0, stream, p); break;
-    case 4: hipLaunchKernelGGL(decode_attn_fused_kernel<4>, grid, block, 0, stream, p); break;
-    case 7: hipLaunchKernelGGL(decode_attn_fused_kernel<7>, grid, block, 0, stream, p); break;
-    default: hipLaunchKernelGGL(decode_attn_fused_kernel<8>, grid, block, 0, stream, p); break;
-  }
+  da_dispatch_g(p.Hq / p.Hkv, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    if (fork) hipLaunchKernelGGL((decode_attn_fused_kernel<G, true>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL(decode_attn_fused_kernel<G>, grid, block, 0, stream, p);
+  });
   hipLaunchKernelGGL(decode_attn_combine_kernel, dim3(p.Hq, batch), dim3(256), 0, stream, (const float*)p.part_o,
                      (const float*)p.part_ml, (bf16_t*)out, p.nsplit, p.step_ptr, p.cache_tokens);
   return vis_check_launch();
@@ -914,51 +895,6 @@ extern "C" int vis_decode_attn_parts_forked(const void* part, int ksplit, int sl
   return decode_attn_parts_impl(part, ksplit, slab_rows, bias, sx, sw, cos_t, sin_t, k_cache, v_cache, step_ptr, part_o, part_ml,
                                 out, Hq, Hkv, HD, cache_tokens, nsplit, scale, batch, cache_bs, tab_bs, 0, parent, fork_len,
                                 stream);
-}
-
-// Cross-attention of one new token over a static key/value set (mllama cross layers, decode): q [Hq*128] straight
-// from the q projection (q_norm applied inside), keys/values [Hkv][key_tokens][128] written once per request by
-// the prefill; *nkeys_m1 (device int) = number of valid keys - 1.  Same split/combine machinery as vis_decode_attn.
-static int decode_cross_attn_impl(const void* q, const void* q_norm_w, const void* k, const void* v,
-                                  const void* nkeys_m1, void* part_o, void* part_ml, void* out, int Hq, int Hkv,
-                                  int HD, int key_tokens, int nsplit, float scale, float eps, int batch, long long q_bs,
-                                  long long kv_bs, hipStream_t stream) {
-  if (!q || !q_norm_w || !k || !v || !nkeys_m1 || !part_o || !part_ml || !out) return VIS_ERR_ARG;
-  if (HD != 128 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) return VIS_ERR_ARG;
-  const int G = Hq / Hkv;
-  if (G != 1 && G != 2 && G != 4 && G != 7 && G != 8) return VIS_ERR_ARG;
-  if (nsplit <= 0 || nsplit > 256 || key_tokens <= 0 || (long long)nsplit * DA_MAXKEYS < key_tokens) return VIS_ERR_ARG;
-  if (batch <= 0 || batch > 64 || (batch > 1 && (q_bs <= 0 || kv_bs <= 0)) || (q_bs % 8) || (kv_bs % 8)) return VIS_ERR_ARG;
-  if (((uintptr_t)k | (uintptr_t)v) & 15) return VIS_ERR_ARG;
-  DecAttnArgs p;
-  p.qkv = (const bf16_t*)q; p.cos_t = nullptr; p.sin_t = nullptr;
-  p.k_cache = (bf16_t*)k; p.v_cache = (bf16_t*)v; p.step_ptr = (const int*)nkeys_m1;
-  p.part_o = (float*)part_o; p.part_ml = (float*)part_ml;
-  p.Hq = Hq; p.Hkv = Hkv; p.cache_tokens = key_tokens; p.nsplit = nsplit;
-  p.scale_log2 = scale * 1.4426950408889634f;
-  p.qkv_bs = q_bs; p.cache_bs = kv_bs; p.tab_bs = 0;
-  p.q_norm_w = (const bf16_t*)q_norm_w; p.q_eps = eps;
-  p.shared_len = 0;
-  p.fork_parent = nullptr; p.fork_len = nullptr;
-  da_no_parts(p);
-  return decode_attn_launch(p, out, batch, stream);
-}
-
-extern "C" int vis_decode_cross_attn(const void* q, const void* q_norm_w, const void* k, const void* v,
-                                     const void* nkeys_m1, void* part_o, void* part_ml, void* out, int Hq, int Hkv,
-                                     int HD, int key_tokens, int nsplit, float scale, float eps, hipStream_t stream) {
-  return decode_cross_attn_impl(q, q_norm_w, k, v, nkeys_m1, part_o, part_ml, out, Hq, Hkv, HD, key_tokens, nsplit, scale,
-                                eps, 1, 0, 0, stream);
-}
-
-// Batch form (mllama batched decode): sequence b reads q + b * q_bs, its own static keys / values k, v + b * kv_bs
-// (element strides) and nkeys_m1[b]; out [batch][Hq * 128]; workspaces sized batch x the single-sequence ones.
-extern "C" int vis_decode_cross_attn_batch(const void* q, const void* q_norm_w, const void* k, const void* v,
-                                           const void* nkeys_m1, void* part_o, void* part_ml, void* out, int Hq,
-                                           int Hkv, int HD, int key_tokens, int nsplit, float scale, float eps,
-                                           int batch, long long q_bs, long long kv_bs, hipStream_t stream) {
-  return decode_cross_attn_impl(q, q_norm_w, k, v, nkeys_m1, part_o, part_ml, out, Hq, Hkv, HD, key_tokens, nsplit, scale,
-                                eps, batch, q_bs, kv_bs, stream);
 }
 
 // ---------------------------------------------------------------------------

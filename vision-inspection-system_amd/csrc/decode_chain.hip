@@ -445,24 +445,14 @@ extern "C" int vis_decode_chain(const void* x, const void* x_idx, int x_rows, co
   if (No / 2 > p.n_gv * 4) return VIS_ERR_UNSUPPORTED; // every o row pair needs a wave
   const int grid = p.n_gv + p.n_att + Hq;
   size_t lds = 0;
-  switch (G) {
-    case 1: lds = chain_lds_bytes<1>(K > Ko ? K : Ko); break;
-    case 2: lds = chain_lds_bytes<2>(K > Ko ? K : Ko); break;
-    case 4: lds = chain_lds_bytes<4>(K > Ko ? K : Ko); break;
-    case 7: lds = chain_lds_bytes<7>(K > Ko ? K : Ko); break;
-    default: lds = chain_lds_bytes<8>(K > Ko ? K : Ko); break;
-  }
+  da_dispatch_g(G, [&](auto g) { lds = chain_lds_bytes<decltype(g)::value>(K > Ko ? K : Ko); });
   const int bound = (ctx_bound > 0 && ctx_bound < cache_tokens) ? ctx_bound : cache_tokens;
   int active = (bound + DA_MAXKEYS - 1) / DA_MAXKEYS;
   if (active > nsplit) active = nsplit;
   if (lds > 64 * 1024 || active > chain_split_limit(Hq, Hkv, K)) return VIS_ERR_UNSUPPORTED;
   vis_clear_error();
-  switch (G) {
-    case 1: hipLaunchKernelGGL(decode_chain_kernel<1>, dim3(grid), dim3(256), lds, stream, p); break;
-    case 2: hipLaunchKernelGGL(decode_chain_kernel<2>, dim3(grid), dim3(256), lds, stream, p); break;
-    case 4: hipLaunchKernelGGL(decode_chain_kernel<4>, dim3(grid), dim3(256), lds, stream, p); break;
-    case 7: hipLaunchKernelGGL(decode_chain_kernel<7>, dim3(grid), dim3(256), lds, stream, p); break;
-    default: hipLaunchKernelGGL(decode_chain_kernel<8>, dim3(grid), dim3(256), lds, stream, p); break;
-  }
+  da_dispatch_g(G, [&](auto g) {
+    hipLaunchKernelGGL(decode_chain_kernel<decltype(g)::value>, dim3(grid), dim3(256), lds, stream, p);
+  });
   return vis_check_launch();
 }

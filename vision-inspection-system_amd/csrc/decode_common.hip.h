@@ -2,6 +2,8 @@
 // the weight-streaming GEMV building blocks and one work item of the split decode attention.
 #pragma once
 #include "common.hip.h"
+#include <stdlib.h>
+#include <type_traits>
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
@@ -282,6 +284,7 @@ __device__ __forceinline__ bool gr_poll_abort(const int* status, int it) {
 // decode_attn_combine_kernel.
 #define DA_ITERS 4                  // 16 keys per block iteration
 #define DA_MAXKEYS (16 * DA_ITERS)  // keys per split
+#define SP_MAXROWS 4                // rows of one speculative step (spec.hip, the draft forms of cross_attn.hip)
 
 struct DecAttnArgs {
   const bf16_t* qkv;      // [(Hq + 2 Hkv) * 128] packed projection row of the new token (bias added)
@@ -296,10 +299,11 @@ struct DecAttnArgs {
   float scale_log2;
   // batch (blockIdx.z = sequence): element strides between sequences
   long long qkv_bs, cache_bs, tab_bs;
-  // cross-attention mode (mllama, TF:models/mllama/modeling_mllama.py:384-466): `qkv` holds only the Hq query heads,
-  // the cache is a static set of keys/values (no rope, no append), *step_ptr = number of keys - 1, and the
-  // per-head RMSNorm of q (q_norm) is applied while q is staged.
-  const bf16_t* q_norm_w;  // [128] or null (self-attention mode)
+  // streaming form only (decode_attn_stream_kernel, decode.hip): cross-attention mode of vis_decode_cross_attn_batch at
+  // Hkv * batch >= 128 (mllama, TF:models/mllama/modeling_mllama.py:384-466) - `qkv` holds only the Hq query heads, the cache is
+  // a static set of keys/values (no rope, no append), *step_ptr = number of keys - 1, and the per-head RMSNorm of q (q_norm) is
+  // applied while q is staged.  The split item below is self-attention only; the split cross-attention is csrc/cross_attn.hip.
+  const bf16_t* q_norm_w;  // [128] or null (self-attention)
   float q_eps;
   // batched streaming form only: keys [0, shared_len) (a multiple of 16) are the same in every sequence of the batch (the
   // text prefix a batch inspection shares, copied into every slot by the prompt passes) and are read from sequence 0's
@@ -320,6 +324,31 @@ struct DecAttnArgs {
   const float* part_sx;    // [batch] or null (fp8 partials: raw sums of e4m3 products)
   const float* part_sw;    // [part_n]
 };
+
+// Host: f(std::integral_constant<int, G>{}) for the instantiated GQA group size G = 1, 2, 4, 7, 8 (every entry point has refused
+// any other by the time it dispatches): the one `switch (G)` behind the launch blocks.
+template <class F>
+static inline void da_dispatch_g(int G, F&& f) {
+  switch (G) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
+
+// Host: split or streaming form?  Enough (kv head, sequence) pairs to fill the chip on their own take the streaming form
+// (decode_attn_stream_kernel: one workgroup per pair, the whole context in one pass, no partials, no combine).
+// VIS_DECODE_ATTN_STREAM=0 keeps the split form (A/B), =2 forces the streaming one (tests at small batch).  Read per launch -
+// not cached - so that a test can compare both forms in one process; graph capture bakes it in.
+static inline bool da_use_stream_form(int Hkv, int batch) {
+  const char* se = getenv("VIS_DECODE_ATTN_STREAM");
+  const int stream_env = se ? atoi(se) : 1;
+  return stream_env == 2 || (stream_env && Hkv * batch >= 128);
+}
+// the streaming launch (decode.hip), also the bf16 batch cross-attention's at Hkv * batch >= 128 (cross_attn.hip)
+int decode_attn_stream_launch(const DecAttnArgs& p, void* out, int batch, hipStream_t stream);
 
 static inline void da_no_parts(DecAttnArgs& p) {
   p.qkv_part = nullptr; p.part_stride = 0; p.part_ks = 0; p.part_n = 0; p.qkv_bias = nullptr; p.part_sx = nullptr; p.part_sw = nullptr;
@@ -382,7 +411,8 @@ struct DecAttnLds {
   __attribute__((aligned(16))) bf16_t raw[G + 2][128];   // chained launch only: the kv group's q heads, k and v rows as handed over
 };
 
-// One (kv head, split, sequence) work item of the split decode attention.  CHAIN = false: the stand-alone launch
+// One (kv head, split, sequence) work item of the split decode SELF-attention: rope, append, attend - always all three (the
+// cross-attention over static keys has split items of its own, csrc/cross_attn.hip).  CHAIN = false: the stand-alone launch
 // (decode_attn_fused_kernel).  CHAIN = true: the same arithmetic inside the chained layer-head launch (decode_chain.hip):
 // the packed projection row is produced by OTHER workgroups of the same launch, so the item first collects its kv group's
 // rows from their granules (`cc`) and leaves its partials as granules for the merging workgroups.
@@ -511,66 +541,47 @@ __device__ __forceinline__ int decode_attn_split_body(DecAttnArgs p, DecAttnLds<
   const int ke = min(ks + DA_MAXKEYS, ctx);
   const int nk = ke - ks;
 
-  const bool cross = !CHAIN && p.q_norm_w != nullptr;  // workgroup-uniform
   bool owner = false;
   CC_STAMP(1);
   // the rope row of this position: requested before the projection rows are awaited (chained launch: they arrive later)
   constexpr int NROT = ((G + 1) * HALF + 255) / 256;
   float rc0[NROT], rs0[NROT], rc1[NROT], rs1[NROT];
-  if (!cross) {
-    const float* cr = p.cos_t + (size_t)slot * HD;
-    const float* sr = p.sin_t + (size_t)slot * HD;
+  const float* cr = p.cos_t + (size_t)slot * HD;
+  const float* sr = p.sin_t + (size_t)slot * HD;
 #pragma unroll
-    for (int k = 0; k < NROT; ++k) {
-      const int d = (tid + 256 * k) & (HALF - 1);
-      rc0[k] = cr[d]; rs0[k] = sr[d]; rc1[k] = cr[HALF + d]; rs1[k] = sr[HALF + d];
-    }
+  for (int k = 0; k < NROT; ++k) {
+    const int d = (tid + 256 * k) & (HALF - 1);
+    rc0[k] = cr[d]; rs0[k] = sr[d]; rc1[k] = cr[HALF + d]; rs1[k] = sr[HALF + d];
   }
   if constexpr (CHAIN) chain_stage_qkv<G>(cc, L, hkv, p.Hq, p.Hkv, tid, split == 0);   // the group's q / k / v rows, as they arrive
   CC_STAMP(2);
-  if (!cross) {
-    // ---- rotate q (G heads) and the new k; stage them as bf16 (exactly what later steps read back)
+  // ---- rotate q (G heads) and the new k; stage them as bf16 (exactly what later steps read back)
 #pragma unroll
-    for (int k = 0; k < NROT; ++k) {
-      const int it = tid + 256 * k;
-      if (it >= (G + 1) * HALF) break;
-      const int g = it / HALF, d = it - g * HALF;
-      const int head = (g < G) ? hkv * G + g : p.Hq + hkv;
-      bf16_t qa, qb;
-      if constexpr (CHAIN) { qa = L.raw[g][d]; qb = L.raw[g][HALF + d]; }
-      else da_qkv2(p, seq, head * HD + d, head * HD + HALF + d, qa, qb);
-      const float a = bf2f(qa), b = bf2f(qb);
-      const bf16_t oa = f2bf(a * rc0[k] - b * rs0[k]);
-      const bf16_t ob = f2bf(b * rc1[k] + a * rs1[k]);
-      bf16_t* dst = (g < G) ? q_s[g] : knew_s;
-      dst[d] = oa;
-      dst[HALF + d] = ob;
-    }
-    for (int it = tid; it < (16 - G) * HD; it += 256) q_s[G + it / HD][it % HD] = 0;
-    if (tid < HD) vnew_s[tid] = CHAIN ? L.raw[G + 1][tid] : da_qkv(p, seq, (p.Hq + p.Hkv + hkv) * HD + tid);
-    __syncthreads();
-    owner = (slot >= ks) && (slot < ke);
-    if (DRAFT != 2 && owner && tid < HD) {  // KV-cache append (no other block reads this row in this launch)
-      Kh[(size_t)slot * HD + tid] = knew_s[tid];
-      Vh[(size_t)slot * HD + tid] = vnew_s[tid];
-    }
-    if constexpr (DRAFT == 1) return nk;
-  } else {
-    // ---- cross-attention: q_norm (RMSNorm over the 128 dims of each head, HF rounding: normalised value to
-    //      bf16, then times the weight), one wave per head
-    for (int g = wave; g < G; g += 4) {
-      const bf16_t* qh = p.qkv + (size_t)(hkv * G + g) * HD;
-      const float a = bf2f(qh[lane]), b = bf2f(qh[lane + 64]);
-      const float ss = wave_sum(a * a + b * b);
-      const float rstd = rsqrtf(ss * (1.0f / HD) + p.q_eps);
-      q_s[g][lane] = f2bf(bf2f(f2bf(a * rstd)) * bf2f(p.q_norm_w[lane]));
-      q_s[g][lane + 64] = f2bf(bf2f(f2bf(b * rstd)) * bf2f(p.q_norm_w[lane + 64]));
-    }
-    for (int it = tid; it < (16 - G) * HD; it += 256) q_s[G + it / HD][it % HD] = 0;
-    if (tid < HD) { knew_s[tid] = 0; vnew_s[tid] = 0; }
-    __syncthreads();
+  for (int k = 0; k < NROT; ++k) {
+    const int it = tid + 256 * k;
+    if (it >= (G + 1) * HALF) break;
+    const int g = it / HALF, d = it - g * HALF;
+    const int head = (g < G) ? hkv * G + g : p.Hq + hkv;
+    bf16_t qa, qb;
+    if constexpr (CHAIN) { qa = L.raw[g][d]; qb = L.raw[g][HALF + d]; }
+    else da_qkv2(p, seq, head * HD + d, head * HD + HALF + d, qa, qb);
+    const float a = bf2f(qa), b = bf2f(qb);
+    const bf16_t oa = f2bf(a * rc0[k] - b * rs0[k]);
+    const bf16_t ob = f2bf(b * rc1[k] + a * rs1[k]);
+    bf16_t* dst = (g < G) ? q_s[g] : knew_s;
+    dst[d] = oa;
+    dst[HALF + d] = ob;
   }
-  const int new_row = cross ? -1 : slot;  // the cache row whose value is still only in knew_s / vnew_s
+  for (int it = tid; it < (16 - G) * HD; it += 256) q_s[G + it / HD][it % HD] = 0;
+  if (tid < HD) vnew_s[tid] = CHAIN ? L.raw[G + 1][tid] : da_qkv(p, seq, (p.Hq + p.Hkv + hkv) * HD + tid);
+  __syncthreads();
+  owner = (slot >= ks) && (slot < ke);
+  if (DRAFT != 2 && owner && tid < HD) {  // KV-cache append (no other block reads this row in this launch)
+    Kh[(size_t)slot * HD + tid] = knew_s[tid];
+    Vh[(size_t)slot * HD + tid] = vnew_s[tid];
+  }
+  if constexpr (DRAFT == 1) return nk;
+  const int new_row = slot;  // the cache row whose value is still only in knew_s / vnew_s
 
   // ---- scores on the MFMA
   bf16x8 qf[4];

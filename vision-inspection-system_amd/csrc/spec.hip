@@ -11,8 +11,7 @@
 //    decode_attn_combine_body (decode_common.hip.h) with the split plan and key order of vis_decode_attn, so output row r and
 //    the cache are, bit for bit, what R successive vis_decode_attn launches at advancing steps leave.  A row at a position
 //    >= cache_tokens returns before it reads or writes anything.
-//  * vis_decode_cross_attn_draft: vis_decode_cross_attn (Mllama's cross layers) for the R rows: one pass over the image's static
-//    K / V serves all rows, each row bit-identical to the single-row launch (the fp8-key form lives in cross_kv.hip).
+//    (The cross layers' form of the same step, vis_decode_cross_attn_draft / _fp8_draft, lives in cross_attn.hip.)
 //  * vis_spec_accept: the greedy pick of every row (vis_argmax_f32's comparison: larger value, ties to the lower id, a row
 //    without a comparable logit picks id 0), the count `a` of leading drafts that equal the pick of the row in front of them,
 //    and the bookkeeping of a step that produced a + 1 tokens.
@@ -28,7 +27,6 @@
 #include "decode_common.hip.h"
 #include <math.h>
 
-#define SP_MAXROWS 4
 #define SP_MAXLOOKUP 8
 
 // ------------------------------------------------------------------------------------------------ vis_decode_attn_draft
@@ -90,206 +88,7 @@ extern "C" int vis_decode_attn_draft(const void* qkv, const void* cos_t, const v
   p.fork_parent = nullptr; p.fork_len = nullptr;
   da_no_parts(p);
   vis_clear_error();
-  switch (G) {
-    case 1: spec_attn_launch<1>(p, (bf16_t*)out, rows, stream); break;
-    case 2: spec_attn_launch<2>(p, (bf16_t*)out, rows, stream); break;
-    case 4: spec_attn_launch<4>(p, (bf16_t*)out, rows, stream); break;
-    case 7: spec_attn_launch<7>(p, (bf16_t*)out, rows, stream); break;
-    default: spec_attn_launch<8>(p, (bf16_t*)out, rows, stream); break;
-  }
-  return vis_check_launch();
-}
-
-// ------------------------------------------------------------------------------------------ vis_decode_cross_attn_draft
-// vis_decode_cross_attn for the R rows of one speculative step.  Every row attends the SAME static keys [0, *nkeys_m1 + 1), so
-// the split's K and V rows are loaded once and serve all rows: the score MFMA's B operand has 16 columns of which the plain
-// kernel uses G (decode_attn_split_body: "heads >= G are zero"); here row r's normalised heads sit in columns r G .. r G + G - 1.
-// An MFMA output column depends on its own B column only, and everything behind the scores - statistics, P, P * V, the merge of
-// the four waves - runs per column with the plain body's key order and accumulation order, so output row r is, bit for bit,
-// vis_decode_cross_attn on q row r alone, whatever the other rows hold.  (vis_decode_cross_attn_batch with a batch stride of 0
-// would read the image's K / V once per row: 212 MB per step at 11B shapes, times R.)
-struct XDraftArgs {
-  const bf16_t* q;         // row r: q + r * q_ld, its leading Hq * 128 columns
-  const bf16_t* q_norm_w;  // [128]
-  const bf16_t* k;         // [Hkv][key_tokens][128]
-  const bf16_t* v;
-  const int* nkeys_m1;     // ONE count for all rows
-  float* part_o;           // [rows][Hq][nsplit][128]
-  float* part_ml;          // [rows][Hq][nsplit][2]
-  int Hq, Hkv, key_tokens, nsplit, rows;
-  float scale_log2, eps;
-  long long q_ld;
-};
-
-// MFMA columns a group size can fill with whole rows: G = 1, 2, 4: 4 rows; G = 7, 8: 2 rows
-template <int G>
-struct XDraftCols { static constexpr int value = (SP_MAXROWS * G <= 16 ? SP_MAXROWS : 16 / G) * G; };
-
-template <int G>
-__global__ __launch_bounds__(256) void cross_attn_draft_kernel(XDraftArgs p) {
-  constexpr int HD = 128;
-  constexpr int CMAX = XDraftCols<G>::value;
-  constexpr int KGRP = DA_MAXKEYS / 16 / 4;  // 16-key groups per wave (2)
-  constexpr int VROWS = DA_MAXKEYS / 4;      // V rows per wave (32)
-  __shared__ __attribute__((aligned(16))) bf16_t q_s[16][HD];   // columns >= rows * G are zero
-  __shared__ __attribute__((aligned(16))) float sc[CMAX][DA_MAXKEYS];
-  __shared__ __attribute__((aligned(16))) float red[4][CMAX][HD];   // 32 KB at 16 columns
-  __shared__ float ml[CMAX][2];
-  const int hkv = blockIdx.x, split = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l15 = lane & 15, h = lane >> 4;
-  const int cols = min(p.rows * G, CMAX);    // (the host has checked rows * G <= 16)
-  const bf16_t* Kr = p.k + (size_t)hkv * p.key_tokens * HD;
-  const bf16_t* Vr = p.v + (size_t)hkv * p.key_tokens * HD;
-  const int ks = split * DA_MAXKEYS;
-
-  // ---- every K / V read of the split up front, ONCE for all rows (clamped rows: addresses do not depend on the key count)
-  u32x4 kreg[KGRP][4];
-#pragma unroll
-  for (int gi = 0; gi < KGRP; ++gi) {
-    const int row = min(ks + (wave + 4 * gi) * 16 + l15, p.key_tokens - 1);
-#pragma unroll
-    for (int ds = 0; ds < 4; ++ds) kreg[gi][ds] = *(const u32x4*)(Kr + (size_t)row * HD + ds * 32 + 8 * h);
-  }
-  uint32_t vreg[VROWS];
-#pragma unroll
-  for (int i = 0; i < VROWS; ++i) {
-    const int row = min(ks + wave + 4 * i, p.key_tokens - 1);
-    vreg[i] = *(const uint32_t*)(Vr + (size_t)row * HD + 2 * lane);
-  }
-
-  const int slot = min(*p.nkeys_m1, p.key_tokens - 1);
-  const int ctx = slot + 1;
-  if (ks >= ctx) return;  // whole block: nothing to attend to (its partials are never read by the combine)
-  const int nk = min(ks + DA_MAXKEYS, ctx) - ks;
-
-  // ---- q_norm of every row's G heads (RMSNorm over the 128 dims, HF rounding), one wave per column
-  for (int c = wave; c < cols; c += 4) {
-    const int r = c / G, g = c - r * G;
-    const bf16_t* qh = p.q + (size_t)r * p.q_ld + (size_t)(hkv * G + g) * HD;
-    const float a = bf2f(qh[lane]), b = bf2f(qh[lane + 64]);
-    const float ss = wave_sum(a * a + b * b);
-    const float rstd = rsqrtf(ss * (1.0f / HD) + p.eps);
-    q_s[c][lane] = f2bf(bf2f(f2bf(a * rstd)) * bf2f(p.q_norm_w[lane]));
-    q_s[c][lane + 64] = f2bf(bf2f(f2bf(b * rstd)) * bf2f(p.q_norm_w[lane + 64]));
-  }
-  for (int it = tid; it < (16 - cols) * HD; it += 256) q_s[cols + it / HD][it % HD] = 0;
-  __syncthreads();
-
-  // ---- scores on the MFMA: one pass over the keys for all columns
-  bf16x8 qf[4];
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) qf[ds] = *(const bf16x8*)(&q_s[l15][ds * 32 + 8 * h]);
-#pragma unroll
-  for (int gi = 0; gi < KGRP; ++gi) {
-    const int kbase = (wave + 4 * gi) * 16;
-    if (kbase < nk) {  // wave-uniform
-      f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ds = 0; ds < 4; ++ds)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kreg[gi][ds]), qf[ds], acc, 0, 0, 0);
-      // acc[r] = S^T[key = kbase + 4h + r][column = l15]
-      if (l15 < cols) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[l15][da_pos(kbase + 4 * h + r)] = acc[r] * p.scale_log2;
-      }
-    }
-  }
-  __syncthreads();
-
-  // ---- per-column softmax statistics over this split (one wave per column)
-  for (int c = wave; c < cols; c += 4) {
-    float mx = -1.0e30f;
-    for (int i = lane; i < nk; i += 64) mx = fmaxf(mx, sc[c][da_pos(i)]);
-    mx = wave_max(mx);
-    float ls = 0.f;
-    for (int i = lane; i < DA_MAXKEYS; i += 64) {      // slots past the split's end get p = 0: P * V runs branch-free
-      const float e = (i < nk) ? exp2f(sc[c][da_pos(i)] - mx) : 0.f;
-      sc[c][da_pos(i)] = e;
-      if (i < nk) ls += e;
-    }
-    ls = wave_sum(ls);
-    if (lane == 0) { ml[c][0] = mx; ml[c][1] = ls; }
-  }
-  __syncthreads();
-
-  // ---- O[c][d] += p[c][key] * V[key][d]; lane owns d = 2 * lane, 2 * lane + 1; the V registers serve every column
-  float v0[VROWS], v1[VROWS];
-#pragma unroll
-  for (int i = 0; i < VROWS; ++i) {
-    uint32_t raw = vreg[i];
-    if (wave + 4 * i >= nk) raw = 0u;      // (a clamped duplicate row: whatever it holds, 0 x 0 adds nothing)
-    v0[i] = __uint_as_float(raw << 16);
-    v1[i] = __uint_as_float(raw & 0xffff0000u);
-  }
-  for (int c = 0; c < cols; ++c) {
-    f32x4 pq[VROWS / 4];
-#pragma unroll
-    for (int q = 0; q < VROWS / 4; ++q) pq[q] = *(const f32x4*)(&sc[c][wave * VROWS + 4 * q]);
-    float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int i = 0; i < VROWS; ++i) {      // keys in ascending order per accumulator, as the plain body
-      const float pw = pq[i >> 2][i & 3];
-      a0 += pw * v0[i];
-      a1 += pw * v1[i];
-    }
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    *(f32x2_*)(&red[wave][c][2 * lane]) = (f32x2_){a0, a1};
-  }
-  __syncthreads();
-  for (int i = tid; i < cols * HD; i += 256) {
-    const int c = i / HD, d = i - c * HD;
-    const int r = c / G, g = c - r * G;
-    const float v = red[0][c][d] + red[1][c][d] + red[2][c][d] + red[3][c][d];
-    const int hq = hkv * G + g;
-    float* po = p.part_o + (size_t)r * p.Hq * p.nsplit * HD;
-    float* pm = p.part_ml + (size_t)r * p.Hq * p.nsplit * 2;
-    po[((size_t)hq * p.nsplit + split) * HD + d] = v;
-    if (d == 0) {
-      pm[((size_t)hq * p.nsplit + split) * 2 + 0] = ml[c][0];
-      pm[((size_t)hq * p.nsplit + split) * 2 + 1] = ml[c][1];
-    }
-  }
-}
-
-// grid (Hq, rows): the plain merge per (head, row), every row over the one shared key count
-__global__ __launch_bounds__(256) void cross_attn_draft_combine_kernel(const float* __restrict__ part_o,
-                                                                       const float* __restrict__ part_ml,
-                                                                       bf16_t* __restrict__ out, int nsplit,
-                                                                       const int* __restrict__ nkeys_m1, int key_tokens) {
-  decode_attn_combine_body(part_o, part_ml, out, nsplit, nkeys_m1, key_tokens, 2);
-}
-
-extern "C" int vis_decode_cross_attn_draft(const void* q, const void* q_norm_w, const void* k, const void* v,
-                                           const void* nkeys_m1, void* part_o, void* part_ml, void* out, int Hq, int Hkv,
-                                           int HD, int key_tokens, int nsplit, float scale, float eps, int rows,
-                                           long long q_ld, hipStream_t stream) {
-  if (!q || !q_norm_w || !k || !v || !nkeys_m1 || !part_o || !part_ml || !out) return VIS_ERR_ARG;
-  if (HD != 128 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) return VIS_ERR_ARG;
-  const int G = Hq / Hkv;
-  if (G != 1 && G != 2 && G != 4 && G != 7 && G != 8) return VIS_ERR_ARG;
-  if (nsplit <= 0 || nsplit > 256 || key_tokens <= 0 || (long long)nsplit * DA_MAXKEYS < key_tokens) return VIS_ERR_ARG;
-  if (rows < 1 || rows > SP_MAXROWS || rows * G > 16) return VIS_ERR_ARG;      // every row's heads in the 16 MFMA columns
-  if (q_ld < (long long)Hq * 128 || (q_ld % 8)) return VIS_ERR_ARG;
-  if (((uintptr_t)k | (uintptr_t)v) & 15) return VIS_ERR_ARG;
-  if (((uintptr_t)nkeys_m1 | (uintptr_t)part_o | (uintptr_t)part_ml) & 3) return VIS_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)q_norm_w | (uintptr_t)out) & 1) return VIS_ERR_ARG;
-  XDraftArgs p;
-  p.q = (const bf16_t*)q; p.q_norm_w = (const bf16_t*)q_norm_w; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v;
-  p.nkeys_m1 = (const int*)nkeys_m1; p.part_o = (float*)part_o; p.part_ml = (float*)part_ml;
-  p.Hq = Hq; p.Hkv = Hkv; p.key_tokens = key_tokens; p.nsplit = nsplit; p.rows = rows;
-  p.scale_log2 = scale * 1.4426950408889634f; p.eps = eps; p.q_ld = q_ld;
-  vis_clear_error();
-  const dim3 grid(Hkv, nsplit), block(256);
-  switch (G) {
-    case 1: hipLaunchKernelGGL(cross_attn_draft_kernel<1>, grid, block, 0, stream, p); break;
-    case 2: hipLaunchKernelGGL(cross_attn_draft_kernel<2>, grid, block, 0, stream, p); break;
-    case 4: hipLaunchKernelGGL(cross_attn_draft_kernel<4>, grid, block, 0, stream, p); break;
-    case 7: hipLaunchKernelGGL(cross_attn_draft_kernel<7>, grid, block, 0, stream, p); break;
-    default: hipLaunchKernelGGL(cross_attn_draft_kernel<8>, grid, block, 0, stream, p); break;
-  }
-  hipLaunchKernelGGL(cross_attn_draft_combine_kernel, dim3(Hq, rows), dim3(256), 0, stream, (const float*)part_o,
-                     (const float*)part_ml, (bf16_t*)out, nsplit, (const int*)nkeys_m1, key_tokens);
+  da_dispatch_g(G, [&](auto g) { spec_attn_launch<decltype(g)::value>(p, (bf16_t*)out, rows, stream); });
   return vis_check_launch();
 }
 

@@ -2094,17 +2094,34 @@ def add_rows(x: torch.Tensor, table: torch.Tensor, idx: torch.Tensor) -> None:
     _check(rc, "vis_add_rows_bf16")
 
 
+def _cross_q_out(name, q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit, B) -> None:
+    """The q / out / count / workspace checks of the single (B None) and batch forms of either key format."""
+    _bf16(q, "q")
+    if B is None:
+        bad = q.numel() != n_q * head_dim or out.numel() != n_q * head_dim or nkeys_m1.dtype != torch.int32
+    else:
+        bad = q.shape[1] != n_q * head_dim or q.stride(1) != 1 or out.shape != (B, n_q * head_dim) or not out.is_contiguous() \
+            or nkeys_m1.dtype != torch.int32 or nkeys_m1.numel() != B
+    if bad:
+        raise HipLibraryError(f"{name}: bad q/out/nkeys")
+    if part_o.numel() < (B or 1) * n_q * nsplit * head_dim or part_ml.numel() < (B or 1) * n_q * nsplit * 2:
+        raise HipLibraryError(f"{name}: workspace too small")
+
+
+def _cross_bf16_kv(name, k, v, lead, n_kv, head_dim) -> None:
+    """bf16 keys / values [Hkv, T, D] behind ``lead`` batch dims (0 or 1; a batch may have any stride, the same for k and v)."""
+    _bf16(k, "k"); _bf16(v, "v")
+    if k.dim() != lead + 3 or k.shape != v.shape or k.shape[lead] != n_kv or k.shape[lead + 2] != head_dim \
+            or not all((t[0] if lead else t).is_contiguous() for t in (k, v)) or (lead and k.stride(0) != v.stride(0)):
+        raise HipLibraryError(f"{name}: bad k/v")
+
+
 def decode_cross_attn(q: torch.Tensor, q_norm_w: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                       nkeys_m1: torch.Tensor, part_o: torch.Tensor, part_ml: torch.Tensor, out: torch.Tensor,
                       n_q: int, n_kv: int, head_dim: int, nsplit: int, scale: float, eps: float) -> None:
     """One new token's cross-attention over static keys/values k, v [Hkv, T, 128] (q_norm applied inside)."""
-    _bf16(q, "q"); _bf16(k, "k"); _bf16(v, "v")
-    if k.shape != v.shape or k.shape[0] != n_kv or k.shape[2] != head_dim or not (k.is_contiguous() and v.is_contiguous()):
-        raise HipLibraryError("decode_cross_attn: bad k/v")
-    if q.numel() != n_q * head_dim or out.numel() != n_q * head_dim or nkeys_m1.dtype != torch.int32:
-        raise HipLibraryError("decode_cross_attn: bad q/out/nkeys")
-    if part_o.numel() < n_q * nsplit * head_dim or part_ml.numel() < n_q * nsplit * 2:
-        raise HipLibraryError("decode_cross_attn: workspace too small")
+    _cross_bf16_kv("decode_cross_attn", k, v, 0, n_kv, head_dim)
+    _cross_q_out("decode_cross_attn", q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit, None)
     rc = load().vis_decode_cross_attn(_ptr(q), _ptr(q_norm_w), _ptr(k), _ptr(v), _ptr(nkeys_m1), _ptr(part_o),
                                       _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, k.shape[1], nsplit, scale, eps,
                                       _stream())
@@ -2116,16 +2133,11 @@ def decode_cross_attn_batch(q: torch.Tensor, q_norm_w: torch.Tensor, k: torch.Te
                             n_q: int, n_kv: int, head_dim: int, nsplit: int, scale: float, eps: float) -> None:
     """Batch of B new tokens, each over ITS OWN static keys/values: q [B, Hq*128], k / v [B, Hkv, T, 128] (any batch
     stride), nkeys_m1 [B] int32, out [B, Hq*128]."""
-    _bf16(q, "q"); _bf16(k, "k"); _bf16(v, "v")
     B = q.shape[0]
-    if k.dim() != 4 or k.shape != v.shape or k.shape[0] != B or k.shape[1] != n_kv or k.shape[3] != head_dim \
-            or not (k[0].is_contiguous() and v[0].is_contiguous()) or k.stride(0) != v.stride(0):
+    _cross_bf16_kv("decode_cross_attn_batch", k, v, 1, n_kv, head_dim)
+    if k.shape[0] != B:
         raise HipLibraryError("decode_cross_attn_batch: bad k/v")
-    if q.shape[1] != n_q * head_dim or q.stride(1) != 1 or out.shape != (B, n_q * head_dim) or not out.is_contiguous() \
-            or nkeys_m1.dtype != torch.int32 or nkeys_m1.numel() != B:
-        raise HipLibraryError("decode_cross_attn_batch: bad q/out/nkeys")
-    if part_o.numel() < B * n_q * nsplit * head_dim or part_ml.numel() < B * n_q * nsplit * 2:
-        raise HipLibraryError("decode_cross_attn_batch: workspace too small")
+    _cross_q_out("decode_cross_attn_batch", q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit, B)
     rc = load().vis_decode_cross_attn_batch(_ptr(q), _ptr(q_norm_w), _ptr(k), _ptr(v), _ptr(nkeys_m1), _ptr(part_o),
                                             _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, k.shape[2], nsplit, scale, eps,
                                             B, q.stride(0), k.stride(0), _stream())
@@ -2144,10 +2156,14 @@ def quantize_cross_kv(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor
 
 
 def _cross_fp8_kv(name, kq, ksc, vq, vsc, lead, n_kv, head_dim) -> None:
+    """fp8 keys / values behind ``lead`` batch dims (0 or 1): uint8 codes [Hkv, T, D], f32 row scales [Hkv, T], T a multiple of
+    64, each sequence's arrays contiguous (a batch may have any stride, one for the codes and one for the scales)."""
     if kq.dtype != torch.uint8 or vq.dtype != torch.uint8 or ksc.dtype != torch.float32 or vsc.dtype != torch.float32:
         raise HipLibraryError(f"{name}: uint8 codes and f32 scales required")
     if kq.dim() != lead + 3 or kq.shape != vq.shape or kq.shape[lead] != n_kv or kq.shape[lead + 2] != head_dim \
-            or ksc.shape != kq.shape[:-1] or vsc.shape != kq.shape[:-1] or kq.shape[lead + 1] % DECODE_KEYS_PER_SPLIT:
+            or ksc.shape != kq.shape[:-1] or vsc.shape != kq.shape[:-1] or kq.shape[lead + 1] % DECODE_KEYS_PER_SPLIT \
+            or not all((t[0] if lead else t).is_contiguous() for t in (kq, vq, ksc, vsc)) \
+            or (lead and (kq.stride(0) != vq.stride(0) or ksc.stride(0) != vsc.stride(0))):
         raise HipLibraryError(f"{name}: bad codes/scales")
 
 
@@ -2157,14 +2173,8 @@ def decode_cross_attn_fp8(q: torch.Tensor, q_norm_w: torch.Tensor, kq: torch.Ten
                           eps: float) -> None:
     """decode_cross_attn over fp8 keys / values: codes kq, vq [Hkv, T, 128] uint8 with row scales ksc, vsc [Hkv, T] f32
     (T a multiple of 64)."""
-    _bf16(q, "q")
     _cross_fp8_kv("decode_cross_attn_fp8", kq, ksc, vq, vsc, 0, n_kv, head_dim)
-    if not (kq.is_contiguous() and vq.is_contiguous() and ksc.is_contiguous() and vsc.is_contiguous()):
-        raise HipLibraryError("decode_cross_attn_fp8: bad codes/scales")
-    if q.numel() != n_q * head_dim or out.numel() != n_q * head_dim or nkeys_m1.dtype != torch.int32:
-        raise HipLibraryError("decode_cross_attn_fp8: bad q/out/nkeys")
-    if part_o.numel() < n_q * nsplit * head_dim or part_ml.numel() < n_q * nsplit * 2:
-        raise HipLibraryError("decode_cross_attn_fp8: workspace too small")
+    _cross_q_out("decode_cross_attn_fp8", q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit, None)
     rc = load().vis_decode_cross_attn_fp8(_ptr(q), _ptr(q_norm_w), _ptr(kq), _ptr(ksc), _ptr(vq), _ptr(vsc), _ptr(nkeys_m1),
                                           _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, kq.shape[1], nsplit,
                                           scale, eps, _stream())
@@ -2177,17 +2187,11 @@ def decode_cross_attn_fp8_batch(q: torch.Tensor, q_norm_w: torch.Tensor, kq: tor
                                 scale: float, eps: float) -> None:
     """Batch of B new tokens, each over ITS OWN fp8 keys / values: q [B, Hq*128], codes [B, Hkv, T, 128], scales [B, Hkv, T]
     (any batch stride, the same for K and V), nkeys_m1 [B] int32, out [B, Hq*128]."""
-    _bf16(q, "q")
     B = q.shape[0]
     _cross_fp8_kv("decode_cross_attn_fp8_batch", kq, ksc, vq, vsc, 1, n_kv, head_dim)
-    if kq.shape[0] != B or not (kq[0].is_contiguous() and vq[0].is_contiguous() and ksc[0].is_contiguous()
-                                and vsc[0].is_contiguous()) or kq.stride(0) != vq.stride(0) or ksc.stride(0) != vsc.stride(0):
+    if kq.shape[0] != B:
         raise HipLibraryError("decode_cross_attn_fp8_batch: bad codes/scales")
-    if q.shape[1] != n_q * head_dim or q.stride(1) != 1 or out.shape != (B, n_q * head_dim) or not out.is_contiguous() \
-            or nkeys_m1.dtype != torch.int32 or nkeys_m1.numel() != B:
-        raise HipLibraryError("decode_cross_attn_fp8_batch: bad q/out/nkeys")
-    if part_o.numel() < B * n_q * nsplit * head_dim or part_ml.numel() < B * n_q * nsplit * 2:
-        raise HipLibraryError("decode_cross_attn_fp8_batch: workspace too small")
+    _cross_q_out("decode_cross_attn_fp8_batch", q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit, B)
     rc = load().vis_decode_cross_attn_fp8_batch(_ptr(q), _ptr(q_norm_w), _ptr(kq), _ptr(ksc), _ptr(vq), _ptr(vsc),
                                                 _ptr(nkeys_m1), _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim,
                                                 kq.shape[2], nsplit, scale, eps, B, q.stride(0), kq.stride(0), ksc.stride(0),
@@ -2216,10 +2220,7 @@ def decode_cross_attn_draft(q: torch.Tensor, q_norm_w: torch.Tensor, k: torch.Te
     (a column slice of wider rows is fine), all rows over the same keys / values k, v [Hkv, T, 128] and the one count
     nkeys_m1 [1]; out [R, Hq*128]; workspaces R x the single-row ones.  R * (Hq / Hkv) <= 16, or the library refuses.  Row r
     is bit-identical to decode_cross_attn on q[r] alone."""
-    _bf16(k, "k"); _bf16(v, "v")
-    if k.dim() != 3 or k.shape != v.shape or k.shape[0] != n_kv or k.shape[2] != head_dim \
-            or not (k.is_contiguous() and v.is_contiguous()):
-        raise HipLibraryError("decode_cross_attn_draft: bad k/v")
+    _cross_bf16_kv("decode_cross_attn_draft", k, v, 0, n_kv, head_dim)
     R = _cross_draft_rows("decode_cross_attn_draft", q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit)
     rc = load().vis_decode_cross_attn_draft(_ptr(q), _ptr(q_norm_w), _ptr(k), _ptr(v), _ptr(nkeys_m1), _ptr(part_o),
                                             _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, k.shape[1], nsplit, scale, eps,
@@ -2234,8 +2235,6 @@ def decode_cross_attn_fp8_draft(q: torch.Tensor, q_norm_w: torch.Tensor, kq: tor
     """decode_cross_attn_draft over fp8 keys / values (decode_cross_attn_fp8's operands): row r is bit-identical to
     decode_cross_attn_fp8 on q[r] alone."""
     _cross_fp8_kv("decode_cross_attn_fp8_draft", kq, ksc, vq, vsc, 0, n_kv, head_dim)
-    if not (kq.is_contiguous() and vq.is_contiguous() and ksc.is_contiguous() and vsc.is_contiguous()):
-        raise HipLibraryError("decode_cross_attn_fp8_draft: bad codes/scales")
     R = _cross_draft_rows("decode_cross_attn_fp8_draft", q, out, nkeys_m1, part_o, part_ml, n_q, head_dim, nsplit)
     rc = load().vis_decode_cross_attn_fp8_draft(_ptr(q), _ptr(q_norm_w), _ptr(kq), _ptr(ksc), _ptr(vq), _ptr(vsc),
                                                 _ptr(nkeys_m1), _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim,

@@ -124,7 +124,7 @@ class MllamaEngine(Generation):
         of mxfp4_gemm_from); a quantised engine decodes the single sequence on the un-chained step.  The prompt pass, the
         vision tower, embedding, norms and both caches stay bf16.
         cross_kv="fp8" (VIS_AUDITOR_CROSS_KV): the decode step reads an e4m3 copy of the image's static cross-attention keys
-        and values (codes + one f32 scale per key row, csrc/cross_kv.hip), written once per prompt pass from the bf16 rows;
+        and values (codes + one f32 scale per key row, csrc/cross_attn.hip), written once per prompt pass from the bf16 rows;
         the bf16 rows stay (the prompt pass reads them), so the copy costs half as much memory again.  Independent of
         decode_weights.  Everything defaults to bf16: the launches of an engine built without these keywords are unchanged.
         speculative=True (VIS_AUDITOR_SPECULATIVE): ``generate`` accepts ``speculative=`` / ``prediction=`` for one greedy
@@ -588,7 +588,7 @@ class MllamaEngine(Generation):
     def _decode_cross_attn(self, L, q: torch.Tensor, att: torch.Tensor, B: int) -> None:
         """Attention of the new token(s) over the image's static keys / values of cross layer ``L`` (DecodeStage hook)."""
         cfg = self.cfg
-        if self.cross_kv == "fp8":      # the e4m3 copy the prompt pass left (csrc/cross_kv.hip)
+        if self.cross_kv == "fp8":      # the e4m3 copy the prompt pass left (csrc/cross_attn.hip)
             if B:
                 fn, nkeys = hip.decode_cross_attn_fp8_batch, self.nkeys_b[:B]
                 kv = (self.xkq_b[:B, L.idx], self.xks_b[:B, L.idx], self.xvq_b[:B, L.idx], self.xvs_b[:B, L.idx])
