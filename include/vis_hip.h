@@ -693,6 +693,17 @@ int vis_spec_accept_sampled(const void* logits, int V, int ld_logits, int rows, 
                             const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
                             void* step_ptr, void* counters, const void* params, vis_stream_t stream);
 
+/* vis_spec_accept_masked (csrc/spec.hip): vis_spec_accept / vis_spec_accept_sampled with row r's pick restricted to the ids
+ * whose bit is set in allow + r * ld_allow (u64 words, vis_schema_mask_rows' rows).  params null: the greedy pick; else
+ * vis_spec_accept_sampled's 8 bytes.  p_r is bit for bit the token vis_argmax_masked_f32 (batch 1) stores for that row with
+ * *step_ptr = step + r (and that inverse temperature and seed); a row without an allowed id picks 0.  Everything behind the
+ * picks is vis_spec_accept's.  Argument checks: vis_spec_accept's, and allow non-null and 8-byte aligned, ld_allow >=
+ * ceil(V / 64), params 4-byte aligned; VIS_ERR_ARG launches nothing.  Two launches. */
+int vis_spec_accept_masked(const void* logits, int V, int ld_logits, int rows, const void* draft, const void* n_draft,
+                           const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
+                           void* step_ptr, void* counters, const void* params, const void* allow, int ld_allow,
+                           vis_stream_t stream);
+
 /* vis_spec_draft: prompt lookup over the history h = prompt_ids[0 .. *prompt_len) followed by tokens[*gen_start ..
  * *step_ptr) (vis_ban_f32's reading), length L.  For m = lookup_max down to lookup_min (1 <= min <= max <= 8) with
  * L > m: the LATEST j < L - m with h[j .. j+m) == h[L-m .. L); the first m with a match writes draft[0 .. d) =
@@ -717,6 +728,32 @@ int vis_spec_draft_pred(const void* prompt_ids, int ld_prompt, const void* promp
                         const void* gen_start, const void* step_ptr, int k, int lookup_max, int lookup_min, int vocab,
                         const void* pred_ids, int ld_pred, const void* pred_len, void* state, void* draft, void* n_draft,
                         vis_stream_t stream);
+
+/* The speculative step under a JSON Schema (csrc/spec_schema.hip; spec.py "grammar").
+ * vis_schema_mask_rows: the allow rows [rows][ld_allow] (rows 1..4) of ONE sequence's step.  Row 0 is vis_schema_mask's row
+ * at *step_ptr (the same fold of tokens[position .. *step_ptr), the same "no token allowed -> EOS ids"); row r >= 1 is the
+ * row of the DFA state behind draft[0 .. r), walked from row 0's state.  From the first r with r > *n_draft (clamped to
+ * 0..rows-1), or whose draft[r-1] is outside [0, V), an EOS id or rejected by the walk, the rows are all-zero.  record: int32
+ * [32]; words 0..3 = DFA state, error bit, position, anchored (anchored 0: the header's start state; an all-zero record is
+ * a sequence whose reply starts at tokens[0]), words 8..16 the launch's counters (zero between launches).  The slot is
+ * written by the workgroup that arrives last, after every workgroup has read it: *step_ptr may advance by any amount
+ * between launches, and a launch repeated at the same step repeats its rows.  Only tokens[] is ever folded.  Token table,
+ * DFA tables, header and capacities: vis_schema_mask's, with its argument checks (rows in the place of batch). */
+int vis_schema_mask_rows(void* record, const void* tokens, int max_tokens, const void* step_ptr, const void* draft,
+                         const void* n_draft, int rows, const void* tok_off, const void* tok_bytes, const void* tok_flags,
+                         const void* eos_ids, int n_eos, int V, void* allow, int ld_allow, const void* header,
+                         const void* trans, const void* byte_class, const void* state_flags, int cap_states,
+                         int cap_classes, vis_stream_t stream);
+/* vis_spec_draft_schema: the drafter that reads the schema (schema_draft.propose).  Folds tokens[position .. *step_ptr)
+ * into the state of vis_schema_mask_rows' record (read only), then follows jump_tok / jump_next (int32 [cap_states]: per
+ * DFA state the longest token spelling a prefix of the bytes the schema forces there, -1 = none, and the state behind it)
+ * up to k (1..3) times, stopping at an entry outside [0, V) / [0, n_states).  n > 0 drafts: draft[0 .. n) and *n_draft = n;
+ * none (also: error state, bad header): draft and *n_draft are left as the drafter in front wrote them.  One workgroup. */
+int vis_spec_draft_schema(const void* record, const void* tokens, int max_tokens, const void* step_ptr, const void* tok_off,
+                          const void* tok_bytes, const void* tok_flags, int V, const void* header, const void* trans,
+                          const void* byte_class, const void* state_flags, int cap_states, int cap_classes,
+                          const void* jump_tok, const void* jump_next, int k, void* draft, void* n_draft,
+                          vis_stream_t stream);
 
 /* ---- Row f2: Llama-3.2-11B-Vision ("mllama") Auditor, reference src/agents/vlm_auditor.py:81-83,:152-158 ---- */
 

@@ -160,18 +160,26 @@ def speculative_kwargs(client, model_id, temperature, others: dict) -> dict:
     VIS_SPECULATIVE_SAMPLED=1 next to either: the dict carries "sampled": True, and it is passed also at a temperature and
     when ``others`` holds nothing but ``seed`` (VIS_SEED) - the reference's requests run at temperature 0.1 / 0.2, so this
     is what turns the step on for them; the reply is the plain sampled reply (spec.check_exclusive).  Any other keyword in
-    ``others`` still means no speculation."""
+    ``others`` still means no speculation.
+    VIS_SPECULATIVE_GRAMMAR=1 next to either: a request that sends the report's schema (VIS_JSON_SCHEMA=1: ``others`` holds
+    that ``response_format``) is no longer excluded and its dict carries "grammar": True - the step masks every row with the
+    schema and drafts the bytes the schema forces (spec.py, schema_draft.py); the reply is the plain schema-constrained
+    reply.  A request without the schema gets the dict without it.  Alone the variable turns nothing on."""
     from .client import CannedResponseClient, LocalVLMClient, is_mllama_model
-    from .spec import auditor_from_env, from_env, sampled_from_env
+    from .spec import auditor_from_env, from_env, grammar_from_env, sampled_from_env
     sp = from_env()
-    excluded = set(others) - {"seed"} if sampled_from_env() else (others or temperature)
+    rf = others.get("response_format")
+    grammar = grammar_from_env() and isinstance(rf, dict) and rf.get("type") == "json_schema"
+    rest = {name: v for name, v in others.items() if not (grammar and name == "response_format")}
+    excluded = set(rest) - {"seed"} if sampled_from_env() else (rest or temperature)
     if excluded or not isinstance(client, (LocalVLMClient, CannedResponseClient)):
         return {}
     if is_mllama_model(model_id):
         sp = auditor_from_env()
     if sp is None:
         return {}
-    return {"speculative": {"method": "ngram", "num_speculative_tokens": sp.k, **({"sampled": True} if sp.sampled else {})}}
+    return {"speculative": {"method": "ngram", "num_speculative_tokens": sp.k, **({"sampled": True} if sp.sampled else {}),
+                            **({"grammar": True} if grammar else {})}}
 
 
 def _logger(name: str) -> logging.Logger:

@@ -225,10 +225,10 @@ class _Completions:
         ``stream=True``: an iterator of ChatCompletionChunk instead of a ChatCompletion (``stream_options``: OpenAI's
         {"include_usage": True}); None or False: the call of before.
         ``speculative`` (extension; vLLM's names): {"method": "ngram", "num_speculative_tokens": k in 1..3[, "prompt_lookup_max": 4,
-        "prompt_lookup_min": 2, "sampled": False]} - lossless n-gram speculative decoding (request.Switches says how): the same
+        "prompt_lookup_min": 2, "sampled": False, "grammar": False, "schema_drafts": True]} - lossless n-gram speculative decoding (request.Switches says how): the same
         text and usage in fewer weight passes where the reply repeats earlier text.  A single request of a Qwen2-VL model only:
         ValueError with ``n`` > 1 or any other sampling / constraint / stop / stream / logprobs keyword, and with a temperature
-        or a seed unless ``"sampled": True`` opts in (the reply is then the plain sampled reply).  None: the call of before.
+        or a seed unless ``"sampled": True`` opts in (the plain sampled reply), and with a json_schema ``response_format`` unless ``"grammar": True`` does (spec.py).  None: the call of before.
         ``prediction`` (OpenAI's Predicted Outputs): {"type": "content", "content": text} - or content as a list of {"type":
         "text", "text": ...} parts - text the reply will probably repeat: the previous reply of a retry, the report of an
         earlier inspection of the same part, a fixed template.  The speculative step drafts from it; the text and
@@ -762,8 +762,8 @@ class LocalVLMClient:
                 raise ValueError(("speculative decoding is" if text is None else "prediction (speculative decoding) is") +
                                  " offered for Qwen2-VL / Qwen2.5-VL models only, unless VIS_AUDITOR_SPECULATIVE=k (1..3) "
                                  "has the Mllama engine built for it")
-            return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp, prediction=text,
-                                       checked=sampled_seed(sp, kw.get("seed"), self.seed))[0]      # no other keyword is on
+            return self._complete_many(model, [messages], temperature, max_tokens, speculative=sp, prediction=text,      # no other
+                                       checked=sampled_seed(sp, kw.get("seed"), self.seed, kw.get("response_format")))[0]      # keyword is on
         out = self.complete_many(model, [messages], temperature, max_tokens, **kw)
         return out if isinstance(out, ChatCompletionStream) else out[0]
 

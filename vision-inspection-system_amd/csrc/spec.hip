@@ -16,6 +16,8 @@
 //    without a comparable logit picks id 0), the count `a` of leading drafts that equal the pick of the row in front of them,
 //    and the bookkeeping of a step that produced a + 1 tokens.
 //  * vis_spec_accept_sampled: the same with the Gumbel-max pick of a sampled request, row r at hash counter *step_ptr + r.
+//  * vis_spec_accept_masked: either of the two with every row's pick restricted to a row of allowed ids (the speculative
+//    step under a JSON Schema, spec_schema.hip).
 //  * vis_spec_draft: prompt lookup - the latest earlier occurrence of the last m ids of the history (m from lookup_max down
 //    to lookup_min) and the ids that followed it.  spec.propose() is its definition.
 //  * vis_spec_draft_pred: the drafter of a request with a prediction (spec.propose_pred() is its definition): a cursor into
@@ -232,6 +234,64 @@ extern "C" int vis_spec_accept_sampled(const void* logits, int V, int ld_logits,
   vis_clear_error();
   hipLaunchKernelGGL(spec_pick_sampled_kernel, dim3(nb, rows), dim3(256), 0, stream, (const float*)logits, V, ld_logits,
                      (const int*)step_ptr, (const SpSampleParams*)params, (float*)ws_val, (int*)ws_idx);
+  hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx, nb, rows,
+                     (const int*)draft, (const int*)n_draft, (const int*)limit, (int*)tokens, max_tokens, (int*)cur_token,
+                     (int*)step_ptr, (int*)counters);
+  return vis_check_launch();
+}
+
+// ----------------------------------------------------------------------------------------------- vis_spec_accept_masked
+// vis_spec_accept / vis_spec_accept_sampled with row r's pick restricted to the ids whose bit is set in allow + r * ld_allow
+// (vis_schema_mask_rows' rows): argmax_stage1_body<MASK>'s loop - the mask test in front of the same expression, the same
+// tie rule - so row r's pick is the token vis_argmax_masked_f32 (batch 1) stores for that row with *step_ptr = step + r, bit
+// for bit; a row without an allowed id picks 0.  params null: the greedy pick.  Stage 2 is spec_accept_kernel itself.
+__global__ __launch_bounds__(256) void spec_pick_masked_kernel(const float* __restrict__ logits, int V, int ld,
+                                                               const int* __restrict__ step_ptr,
+                                                               const SpSampleParams* __restrict__ params,
+                                                               const unsigned long long* __restrict__ allow, int ld_allow,
+                                                               float* __restrict__ bval, int* __restrict__ bidx) {
+  const int tid = threadIdx.x, row = blockIdx.y;
+  const float* __restrict__ x = logits + (size_t)row * ld;
+  const unsigned long long* __restrict__ al = allow + (size_t)row * ld_allow;
+  const float inv_temp = params ? params->inv_temp : 0.f;
+  const unsigned seed = params ? params->seed : 0u;
+  const unsigned step = (unsigned)*step_ptr + (unsigned)row;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = blockIdx.x * 256 + tid; i < V; i += gridDim.x * 256) {
+    if (!((al[i >> 6] >> (i & 63)) & 1ull)) continue;
+    float v = x[i];
+    if (inv_temp > 0.f) v = v * inv_temp + gumbel_noise(seed, step, (unsigned)i);
+    sp_better(best, bi, v, i);
+  }
+  sp_wave_best(best, bi);
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) sp_better(best, bi, sv[w], si[w]);
+    bval[row * 256 + blockIdx.x] = best;
+    bidx[row * 256 + blockIdx.x] = bi;
+  }
+}
+
+extern "C" int vis_spec_accept_masked(const void* logits, int V, int ld_logits, int rows, const void* draft, const void* n_draft,
+                                      const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens,
+                                      void* cur_token, void* step_ptr, void* counters, const void* params, const void* allow,
+                                      int ld_allow, hipStream_t stream) {
+  if (!logits || !draft || !n_draft || !limit || !ws_val || !ws_idx || !tokens || !cur_token || !step_ptr || !counters || !allow)
+    return VIS_ERR_ARG;
+  if (V <= 0 || rows < 1 || rows > SP_MAXROWS || ld_logits < V || max_tokens <= 0) return VIS_ERR_ARG;
+  if (ld_allow < (V + 63) / 64 || ((uintptr_t)allow & 7)) return VIS_ERR_ARG;
+  if (((uintptr_t)logits | (uintptr_t)draft | (uintptr_t)n_draft | (uintptr_t)limit | (uintptr_t)ws_val | (uintptr_t)ws_idx |
+       (uintptr_t)tokens | (uintptr_t)cur_token | (uintptr_t)step_ptr | (uintptr_t)counters | (uintptr_t)params) & 3)
+    return VIS_ERR_ARG;
+  const int nb = min(256, (V + 255) / 256);
+  vis_clear_error();
+  hipLaunchKernelGGL(spec_pick_masked_kernel, dim3(nb, rows), dim3(256), 0, stream, (const float*)logits, V, ld_logits,
+                     (const int*)step_ptr, (const SpSampleParams*)params, (const unsigned long long*)allow, ld_allow,
+                     (float*)ws_val, (int*)ws_idx);
   hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx, nb, rows,
                      (const int*)draft, (const int*)n_draft, (const int*)limit, (int*)tokens, max_tokens, (int*)cur_token,
                      (int*)step_ptr, (int*)counters);

@@ -283,8 +283,14 @@ class DecodeStage(PickStage):
                          prediction)
         if cfg.sampled:      # the row seed the prompt pass's pick just drew with (PickStage._seed_slot's choice for slot 0)
             self._spec.set_params(self.temperature, self._slot_seed.get(0, self.seed))
+        if cfg.grammar:      # the prompt pass's pick was vis_schema_mask's; from here on the rows launch owns the DFA state
+            if not self.schema_on:
+                raise ValueError("speculative: 'grammar' needs a JSON Schema on the request (json_schema=)")
+            self._schema.begin_rows(start, cfg.schema_drafts)
         if self._spec_pred:
             self._spec_draft_pred(cfg.k)
+        if cfg.schema_drafts:
+            self._schema.draft(self.tokens, self.step, cfg.k, self._spec.draft, self._spec.n_draft)
         return self._spec
 
     def _spec_draft_pred(self, k: int) -> None:
@@ -300,7 +306,8 @@ class DecodeStage(PickStage):
         while the request has no image as in the plain step), the lm_head into [R, V] f32, then vis_spec_accept -
         which keeps the drafts the picks confirm and advances ``step`` by 1..R (vis_spec_accept_sampled, the same with the
         sampled pick, when the request's configuration opted in; the only launch that differs) - and vis_spec_draft for the next step
-        (vis_spec_draft_pred instead when the request came with a prediction).
+        (vis_spec_draft_pred instead when the request came with a prediction).  A configuration with ``grammar``: vis_schema_mask_rows
+        ahead of the accept, vis_spec_accept_masked in its place, and with ``schema_drafts`` vis_spec_draft_schema behind the drafter.
         Never the chained launch: the chain is bit-identical to the four launches, so the tokens are the chained step's.
         ``propose`` False leaves the draft row and its count alone (a test plants them)."""
         cfg, fmt, sp = self.cfg, self.decode_weights, self._spec
@@ -325,7 +332,11 @@ class DecodeStage(PickStage):
             gemv_rows(x2, *_wt(L, "gateup_w", fmt), act, norm_w=lw.ln2_w, act=hip.ACT_SWIGLU, eps=eps)
             gemv_rows(act, *_wt(L, "down_w", fmt), x, residual=x2)
         gemv_rows(x, *self.dec_head[fmt], logits, norm_w=self.dec_norm_w, eps=eps)
-        if self._spec_cfg.sampled:      # row r's pick: the plain loop's sampled pick at step + r; 1 / T and the seed from params
+        if self._spec_cfg.grammar:      # row r's pick under the schema's mask in front of row r: the plain masked pick at step + r
+            allow = self._schema.mask_rows(self.tokens, self.step, sp.draft, sp.n_draft, R)
+            hip.spec_accept_masked(logits, sp.draft, sp.n_draft, sp.limit, sp.ws_val, sp.ws_idx, self.tokens, sp.cur, self.step,
+                                   sp.counters, allow, sp.params if self._spec_cfg.sampled else None)
+        elif self._spec_cfg.sampled:      # row r's pick: the plain loop's sampled pick at step + r; 1 / T and the seed from params
             hip.spec_accept_sampled(logits, sp.draft, sp.n_draft, sp.limit, sp.ws_val, sp.ws_idx, self.tokens, sp.cur,
                                     self.step, sp.counters, sp.params)
         else:
@@ -337,6 +348,8 @@ class DecodeStage(PickStage):
             c = self._spec_cfg
             hip.spec_draft(sp.prompt, sp.prompt_len, self.tokens, sp.gen_start, self.step, R - 1, c.lookup_max, c.lookup_min,
                            cfg.vocab, sp.draft, sp.n_draft)
+        if propose and R > 1 and self._spec_cfg.schema_drafts:      # the bytes the schema forces replace the lookup's drafts
+            self._schema.draft(self.tokens, self.step, R - 1, sp.draft, sp.n_draft)
 
     def _decode_cross_attn_draft(self, L: DecodeLayer, q: torch.Tensor, att: torch.Tensor, R: int) -> None:
         """Hook: the cross-attention of layer L for the R rows q [R, Hq * D] (a column view of the packed rows) into att[:R],
@@ -345,13 +358,15 @@ class DecodeStage(PickStage):
 
     def _spec_graph(self, R: int) -> torch.cuda.CUDAGraph:
         """The captured speculative step, keyed by (R, weight format, the lookup window, whether the cross-attention layers run,
-        "pred" when the step ends with the prediction drafter, and "sampled" when its accept is the sampled one): its launches
+        "pred" when the step ends with the prediction drafter, "sampled" when its accept is the sampled one, "grammar" /
+        "schema_drafts" when the schema's launches are in it): its launches
         read everything else - the prediction, its length, the drafter's state, the inverse temperature and the seed - from
         device memory.  The warm-up step advances the request's counters; they are put back before the capture."""
         c = self._spec_cfg
         cross = (("image" if self.has_image else "text"),) if self.dec_n_self != len(self.dec_layers) else ()
         key = ("spec", R, self.decode_weights, c.lookup_max, c.lookup_min) + cross + (("pred",) if self._spec_pred else ()) + \
-            (("sampled",) if c.sampled else ())
+            (("sampled",) if c.sampled else ()) + (("grammar",) if c.grammar else ()) + \
+            (("schema_drafts",) if c.schema_drafts else ())
         if key in self._spec_graphs:
             return self._spec_graphs[key]
         sp = self._spec

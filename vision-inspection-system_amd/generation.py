@@ -186,7 +186,7 @@ class Generation(DecodeStage):
             self.last_timing.update(pred_accepted=st.accepted, pred_rejected=st.rejected)
         toks = self._finish([(0, toks)], eos, ignore_eos, keep_eos=self.keep_eos)[0]
         self._record_logprobs([(0, self.prompt_len - 1, len(toks))])
-        return toks
+        return self._spec_checked(sp, toks)
 
     @staticmethod
     def _mask_error() -> JsonModeError:

@@ -80,6 +80,9 @@ _SIGS = {
     "vis_decode_cross_attn_fp8_draft": "pppppppppp" + "iiiii" + "ff" + "il" + "p",
     "vis_spec_accept": "p" + "iii" + "pppppp" + "i" + "ppp" + "p",
     "vis_spec_accept_sampled": "p" + "iii" + "pppppp" + "i" + "ppp" + "p" + "p",
+    "vis_spec_accept_masked": "p" + "iii" + "pppppp" + "i" + "ppp" + "p" + "pi" + "p",
+    "vis_schema_mask_rows": "pp" + "i" + "ppp" + "i" + "pppp" + "ii" + "p" + "i" + "pppp" + "ii" + "p",
+    "vis_spec_draft_schema": "pp" + "i" + "pppp" + "i" + "pppp" + "ii" + "pp" + "i" + "pp" + "p",
     "vis_spec_draft": "pi" + "pp" + "i" + "pp" + "iiii" + "pp" + "p",
     "vis_spec_draft_pred": "pi" + "pp" + "i" + "pp" + "iiii" + "pi" + "pp" + "pp" + "p",
     "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
@@ -1642,6 +1645,95 @@ def spec_draft(prompt_ids: torch.Tensor, prompt_len: torch.Tensor, tokens: torch
                                _ptr(gen_start), _ptr(step), int(k), int(lookup_max), int(lookup_min), int(vocab), _ptr(draft),
                                _ptr(n_draft), _stream())
     _check(rc, "vis_spec_draft")
+
+
+def spec_accept_masked(logits: torch.Tensor, draft: torch.Tensor, n_draft: torch.Tensor, limit: torch.Tensor,
+                       ws_val: torch.Tensor, ws_idx: torch.Tensor, tokens: torch.Tensor, cur_token: torch.Tensor,
+                       step: torch.Tensor, counters: torch.Tensor, allow: torch.Tensor,
+                       params: Optional[torch.Tensor] = None) -> None:
+    """spec_accept (``params`` None) or spec_accept_sampled with row r's pick restricted to allow[r] (vis_spec_accept_masked):
+    allow int64 [R, >= ceil(V / 64)], schema_mask_rows' rows.  Row r's pick is argmax_masked's token for that row at
+    step[0] + r, bit for bit.  Everything else as spec_accept / spec_accept_sampled."""
+    ints = (draft, n_draft, limit, ws_idx, tokens, cur_token, step, counters) + (() if params is None else (params,))
+    if logits.dtype != torch.float32 or ws_val.dtype != torch.float32 or any(t.dtype != torch.int32 for t in ints):
+        raise HipLibraryError("spec_accept_masked: f32 logits, ws_val / int32 everything else required")
+    if logits.dim() != 2 or not 1 <= logits.shape[0] <= SPEC_MAX_ROWS or logits.stride(1) != 1:
+        raise HipLibraryError("spec_accept_masked: logits must be [1..4, V] with unit column stride")
+    R, V = logits.shape
+    if draft.numel() < max(1, R - 1) or any(t.numel() != 1 for t in (n_draft, limit, cur_token, step)) or counters.numel() != 3 \
+            or (params is not None and params.numel() != 2) or ws_val.numel() < 256 * R or ws_idx.numel() < 256 * R \
+            or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("spec_accept_masked: bad parameter shapes")
+    if allow.dtype != torch.int64 or allow.dim() != 2 or allow.shape[0] != R or allow.shape[1] < (V + 63) // 64 \
+            or allow.stride(1) != 1:
+        raise HipLibraryError("spec_accept_masked: allow must be int64 [R, ceil(V / 64)]")
+    rc = load().vis_spec_accept_masked(_ptr(logits), V, logits.stride(0), R, _ptr(draft), _ptr(n_draft), _ptr(limit),
+                                       _ptr(ws_val), _ptr(ws_idx), _ptr(tokens), tokens.numel(), _ptr(cur_token), _ptr(step),
+                                       _ptr(counters), _ptr(params), _ptr(allow), allow.stride(0), _stream())
+    _check(rc, "vis_spec_accept_masked")
+
+
+SCHEMA_ROWS_RECORD_INTS = 32     # int32 words of vis_schema_mask_rows' record (SR_INTS of csrc/spec_schema.hip)
+
+
+def _schema_tables(name, tok_off, tok_bytes, tok_flags, header, trans, byte_class, state_flags) -> int:
+    V = tok_flags.numel()
+    if tok_off.dtype != torch.int32 or tok_off.numel() != V + 1 or tok_bytes.dtype != torch.uint8 or tok_flags.dtype != torch.uint8:
+        raise HipLibraryError(f"{name}: bad token table")
+    if header.dtype != torch.int32 or header.numel() != 4 or trans.dtype != torch.int16 or trans.dim() != 2 \
+            or byte_class.dtype != torch.uint8 or byte_class.numel() != 256 or state_flags.dtype != torch.uint8 \
+            or state_flags.numel() != trans.shape[0]:
+        raise HipLibraryError(f"{name}: bad DFA tables")
+    if not all(t.is_contiguous() for t in (tok_off, tok_bytes, tok_flags, header, trans, byte_class, state_flags)):
+        raise HipLibraryError(f"{name}: bad strides")
+    return V
+
+
+def schema_mask_rows(record: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, draft: torch.Tensor,
+                     n_draft: torch.Tensor, tok_off: torch.Tensor, tok_bytes: torch.Tensor, tok_flags: torch.Tensor,
+                     eos_ids: torch.Tensor, allow: torch.Tensor, header: torch.Tensor, trans: torch.Tensor,
+                     byte_class: torch.Tensor, state_flags: torch.Tensor) -> None:
+    """The allow rows of ONE sequence's speculative step under a schema (vis_schema_mask_rows): allow int64 [R, >= ceil(V /
+    64)], R = 1..4; row 0 = schema_mask's row at step[0], row r the row behind draft[:r]; rows behind a missing, EOS, out-of-
+    range or rejected draft are zero.  record int32 [32] (zeroed = a reply that starts at tokens[0] in the start state),
+    tokens int32 [T], step / n_draft int32 [1], draft int32 [>= R - 1]; the token table and the DFA as in schema_mask."""
+    V = _schema_tables("schema_mask_rows", tok_off, tok_bytes, tok_flags, header, trans, byte_class, state_flags)
+    ints = (record, tokens, step, draft, n_draft, eos_ids)
+    if any(t.dtype != torch.int32 for t in ints) or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("schema_mask_rows: contiguous int32 record / tokens / step / draft / n_draft / eos_ids required")
+    if allow.dtype != torch.int64 or allow.dim() != 2 or not 1 <= allow.shape[0] <= SPEC_MAX_ROWS \
+            or allow.shape[1] < (V + 63) // 64 or allow.stride(1) != 1:
+        raise HipLibraryError("schema_mask_rows: allow must be int64 [1..4, ceil(V / 64)]")
+    R = allow.shape[0]
+    if record.numel() != SCHEMA_ROWS_RECORD_INTS or tokens.dim() != 1 or step.numel() != 1 or n_draft.numel() != 1 \
+            or draft.numel() < max(1, R - 1):
+        raise HipLibraryError("schema_mask_rows: bad parameter shapes")
+    rc = load().vis_schema_mask_rows(_ptr(record), _ptr(tokens), tokens.numel(), _ptr(step), _ptr(draft), _ptr(n_draft), R,
+                                     _ptr(tok_off), _ptr(tok_bytes), _ptr(tok_flags), _ptr(eos_ids), eos_ids.numel(), V,
+                                     _ptr(allow), allow.stride(0), _ptr(header), _ptr(trans), _ptr(byte_class),
+                                     _ptr(state_flags), trans.shape[0], trans.shape[1], _stream())
+    _check(rc, "vis_schema_mask_rows")
+
+
+def spec_draft_schema(record: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, tok_off: torch.Tensor,
+                      tok_bytes: torch.Tensor, tok_flags: torch.Tensor, header: torch.Tensor, trans: torch.Tensor,
+                      byte_class: torch.Tensor, state_flags: torch.Tensor, jump_tok: torch.Tensor, jump_next: torch.Tensor,
+                      k: int, draft: torch.Tensor, n_draft: torch.Tensor) -> None:
+    """The drafter that reads the schema (vis_spec_draft_schema; schema_draft.propose is its definition): the state of
+    schema_mask_rows' record advanced over tokens[position:step[0]], then up to k jumps through jump_tok / jump_next (int32
+    [cap_states]) into draft / n_draft; with no draft both are left alone."""
+    V = _schema_tables("spec_draft_schema", tok_off, tok_bytes, tok_flags, header, trans, byte_class, state_flags)
+    ints = (record, tokens, step, jump_tok, jump_next, draft, n_draft)
+    if any(t.dtype != torch.int32 for t in ints) or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("spec_draft_schema: contiguous int32 tensors required")
+    if record.numel() != SCHEMA_ROWS_RECORD_INTS or step.numel() != 1 or n_draft.numel() != 1 or draft.numel() < k \
+            or jump_tok.numel() < trans.shape[0] or jump_next.numel() < trans.shape[0]:
+        raise HipLibraryError("spec_draft_schema: bad parameter shapes")
+    rc = load().vis_spec_draft_schema(_ptr(record), _ptr(tokens), tokens.numel(), _ptr(step), _ptr(tok_off), _ptr(tok_bytes),
+                                      _ptr(tok_flags), V, _ptr(header), _ptr(trans), _ptr(byte_class), _ptr(state_flags),
+                                      trans.shape[0], trans.shape[1], _ptr(jump_tok), _ptr(jump_next), int(k), _ptr(draft),
+                                      _ptr(n_draft), _stream())
+    _check(rc, "vis_spec_draft_schema")
 
 
 SPEC_PRED_STATE_INTS = 7     # cursor, last, seen, src, n_out, accepted, rejected (spec.PredState; SP_ST_INTS of csrc/spec.hip)

@@ -76,6 +76,14 @@ class SchemaBuffers(JsonBuffers):
         self.byte_class = torch.zeros(256, dtype=torch.uint8, device=device)
         self.state_flags = torch.zeros(schema.SCHEMA_MAX_STATES, dtype=torch.uint8, device=device)
         self.dfa = None
+        # the speculative step under the schema (spec.py "grammar"): slot 0's record and allow rows of vis_schema_mask_rows,
+        # and schema_draft's jump tables next to ``trans`` - overwritten with the schema, so a captured step serves the next one
+        self.rows_record = torch.zeros(hip.SCHEMA_ROWS_RECORD_INTS, dtype=torch.int32, device=device)
+        self.rows_allow = torch.zeros((hip.SPEC_MAX_ROWS, (vocab + 63) // 64), dtype=torch.int64, device=device)
+        self.jump_tok = torch.full((schema.SCHEMA_MAX_STATES,), -1, dtype=torch.int32, device=device)
+        self.jump_next = torch.full((schema.SCHEMA_MAX_STATES,), -1, dtype=torch.int32, device=device)
+        self._jump_dfa = None
+        self._token_index = None
 
     def load(self, dfa, streams=()) -> None:
         """Make ``dfa`` the schema of the launches that follow.  Called before a request group's first prompt pass, outside
@@ -115,6 +123,46 @@ class SchemaBuffers(JsonBuffers):
     def failed(self, slots) -> list:
         st = self.state.cpu()
         return [bool(st[s, schema.ERR] or st[s, schema.SLOT_INTS + schema.ERR]) for s in slots]
+
+    # ---- the speculative step of slot 0 under the schema
+    def begin_rows(self, start: int, drafts: bool) -> None:
+        """Behind the prompt pass's masked pick of a speculative request: the rows record says "the start state in front of
+        tokens[start]" (the pick's own index), and with ``drafts`` the loaded schema's jump tables are on the device
+        (built once per schema and vocabulary).  Outside any captured graph."""
+        self.rows_record.copy_(torch.tensor([0, 0, start, 0] + [0] * (hip.SCHEMA_ROWS_RECORD_INTS - 4), dtype=torch.int32))
+        if drafts and self._jump_dfa is not self.dfa:
+            from . import schema_draft
+            if self._token_index is None:
+                self._token_index = schema_draft.token_index(self.table)
+            t = schema_draft.build(self.dfa, self.table, self._token_index)
+            self.jump_tok.copy_(torch.from_numpy(t.jump_tok))
+            self.jump_next.copy_(torch.from_numpy(t.jump_next))
+            self._jump_dfa = self.dfa
+
+    def mask_rows(self, tokens: torch.Tensor, step: torch.Tensor, draft: torch.Tensor, n_draft: torch.Tensor,
+                  rows: int) -> torch.Tensor:
+        """vis_schema_mask_rows for the ``rows`` rows of slot 0's step; returns them."""
+        allow = self.rows_allow[:rows]
+        hip.schema_mask_rows(self.rows_record, tokens, step, draft, n_draft, self.off, self.data, self.flags, self.eos, allow,
+                             self.header, self.trans, self.byte_class, self.state_flags)
+        return allow
+
+    def draft(self, tokens: torch.Tensor, step: torch.Tensor, k: int, draft: torch.Tensor, n_draft: torch.Tensor) -> None:
+        """vis_spec_draft_schema behind the accept of slot 0's step (or behind the prompt pass's pick)."""
+        hip.spec_draft_schema(self.rows_record, tokens, step, self.off, self.data, self.flags, self.header, self.trans,
+                              self.byte_class, self.state_flags, self.jump_tok, self.jump_next, k, draft, n_draft)
+
+    def reply_failed(self, toks, ended_on_eos: bool) -> bool:
+        """The failure outcome of a speculative reply, decided as the plain loop's error bit is: a reply the vocabulary
+        could not continue took a forced EOS in a state that does not accept, and the fold sets the bit for exactly that
+        token - one json_schema.advance over the returned tokens, and, where the reply was cut in front of the EOS that
+        ended it, that EOS."""
+        st = schema.initial_state(self.dfa)
+        for t in toks:
+            schema.advance(self.dfa, st, int(t), self.table)
+            if st[1]:
+                return True
+        return ended_on_eos and not self.dfa.state_flags[st[0]] & schema.STATE_ACCEPT
 
 
 def engine_tokenizer(engine):

@@ -212,6 +212,14 @@ class PickStage:
             return []
         return [s for s, bad in zip(slots, self._mask.failed(slots)) if bad]
 
+    def _spec_checked(self, sp, toks: List[int]) -> List[int]:
+        """After a speculative run (``toks``: the reply as _finish cut it): under a ``grammar`` configuration the plain loop's
+        failure outcome - JsonModeError for a reply the vocabulary could not continue - decided from the reply itself."""
+        if sp.grammar and self._schema.reply_failed(toks, self.last_finish[0][0] == "eos"):
+            self.last_finish = [None]
+            raise self._mask_error()
+        return toks
+
     # ------------------------------------------------------------------ nucleus sampling / per-request seeds
     def _begin_sampling(self, top_p, seeded: bool) -> None:
         """Route every pick of the request about to run through vis_sample_f32 when top_p < 1 or it brings its own seeds."""

@@ -77,7 +77,7 @@ class Switches:
     drafted by prompt lookup over prompt + reply through ONE pass over the weights and keeps the drafts the model's own greedy
     picks confirm - the reply is the plain reply token for token, in fewer weight passes where the reply repeats earlier
     text.  Greedy single requests of the Qwen2-VL engines, or of an MllamaEngine built with speculative=True, only:
-    ValueError with any switch above (one token at a time) or, unless the dict says "sampled": True (the plain sampled reply),
+    ValueError with any switch above (one token at a time; "grammar": True lets ``json_schema`` through, spec.py) or, unless the dict says "sampled": True (the plain sampled reply),
     with a temperature or a seed.  Afterwards ``last_timing`` holds ``spec_steps`` / ``spec_proposed`` / ``spec_accepted``.
     ``prediction`` (generate only; generate_batch refuses one other than None): a sequence of token ids the reply will
     probably repeat (OpenAI's Predicted Outputs; at most max_ctx are kept, none = off): the drafts come from it while the

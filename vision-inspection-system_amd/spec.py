@@ -15,7 +15,12 @@ A request may bring a second source of drafts, the caller's prediction of the re
 A request that opts in (``"sampled": True``) may sample: the engines' pick at a temperature is Gumbel-max over a counter hash
 of (seed, step, id), so the token is a pure function of (logits row, seed, step), and row r of a step carries the logits of
 step + r.  vis_spec_accept_sampled takes every row's pick with that counter (``accept_ref_sampled`` walks given picks); the
-reply is then the plain SAMPLED reply token for token - equality, not rejection sampling's equality in distribution."""
+reply is then the plain SAMPLED reply token for token - equality, not rejection sampling's equality in distribution.
+
+A request that opts in (``"grammar": True``) may carry a JSON Schema: the DFA state in front of row r is the state in front of
+row r - 1 walked through draft r - 1, so vis_schema_mask_rows writes every row's mask, vis_spec_accept_masked takes the masked
+picks, and a draft the schema rejects is never the masked pick - the reply is the plain schema-constrained reply.  The schema
+then drafts too (``schema_drafts``, schema_draft.py): the bytes it forces are known before the model is asked."""
 from __future__ import annotations
 
 import os
@@ -30,27 +35,37 @@ ROWS_LDS_MAX = 152 * 1024      # GV_ROWS_LDS_MAX of csrc/decode.hip: the input r
 
 
 class SpecConfig(tuple):
-    """(k, lookup_max, lookup_min[, True]): num_speculative_tokens, prompt_lookup_max, prompt_lookup_min and ``sampled`` - the
-    request's own opt-in: the accept step takes the sampled pick (vis_spec_accept_sampled).  The fourth value stands in the
-    tuple only when it is set, so the record of a request that did not opt in is, value for value, the three-field record
-    of before (what the engines are handed and what a recorded call compares against); SpecConfig(2, 4, 2) ==
-    SpecConfig(2, 4, 2, False)."""
+    """(k, lookup_max, lookup_min[, True][, "grammar"[, "no_schema_drafts"]]): num_speculative_tokens, prompt_lookup_max,
+    prompt_lookup_min and the request's own opt-ins.  ``sampled``: the accept step takes the sampled pick
+    (vis_spec_accept_sampled).  ``grammar``: the request carries a JSON Schema, and the step masks every row's pick with the
+    schema's DFA state in front of that row (vis_schema_mask_rows, vis_spec_accept_masked); ``schema_drafts`` (on with
+    ``grammar`` unless switched off): the schema's forced bytes are drafts too (schema_draft.py, vis_spec_draft_schema).  A
+    value stands in the tuple only when it is set, so the record of a request that did not opt in is, value for value, the
+    three-field record of before (what the engines are handed and what a recorded call compares against); SpecConfig(2, 4, 2)
+    == SpecConfig(2, 4, 2, False) == SpecConfig(2, 4, 2, False, False)."""
     __slots__ = ()
 
-    def __new__(cls, k: int, lookup_max: int, lookup_min: int, sampled: bool = False):
-        return tuple.__new__(cls, (k, lookup_max, lookup_min) + ((True,) if sampled else ()))
+    def __new__(cls, k: int, lookup_max: int, lookup_min: int, sampled: bool = False, grammar: bool = False,
+                schema_drafts: Optional[bool] = None):
+        extra = ((True,) if sampled else ()) + (("grammar",) if grammar else ())
+        if grammar and schema_drafts is False:
+            extra += ("no_schema_drafts",)
+        return tuple.__new__(cls, (k, lookup_max, lookup_min) + extra)
 
     k = property(lambda self: self[0])
     lookup_max = property(lambda self: self[1])
     lookup_min = property(lambda self: self[2])
-    sampled = property(lambda self: len(self) > 3)
+    sampled = property(lambda self: len(self) > 3 and self[3] is True)
+    grammar = property(lambda self: "grammar" in self[3:])
+    schema_drafts = property(lambda self: "grammar" in self[3:] and "no_schema_drafts" not in self[3:])
 
     @property
     def rows(self) -> int:
         return self.k + 1
 
     def __repr__(self) -> str:
-        return f"SpecConfig(k={self.k}, lookup_max={self.lookup_max}, lookup_min={self.lookup_min}, sampled={self.sampled})"
+        more = f", grammar=True, schema_drafts={self.schema_drafts}" if self.grammar else ""
+        return f"SpecConfig(k={self.k}, lookup_max={self.lookup_max}, lookup_min={self.lookup_min}, sampled={self.sampled}{more})"
 
 
 def _int(v, name: str, lo: int, hi: int) -> int:
@@ -61,18 +76,21 @@ def _int(v, name: str, lo: int, hi: int) -> int:
 
 def check_speculative(speculative) -> Optional[SpecConfig]:
     """None (off), the integer k, or {"method": "ngram", "num_speculative_tokens": k[, "prompt_lookup_max": 4,
-    "prompt_lookup_min": 2][, "sampled": False]} (vLLM's names; ``sampled`` is this package's: the request may carry a
-    temperature and a seed, see check_exclusive) -> SpecConfig or None; ValueError otherwise."""
+    "prompt_lookup_min": 2][, "sampled": False][, "grammar": False[, "schema_drafts": True]]} (vLLM's names; ``sampled``,
+    ``grammar`` and ``schema_drafts`` are this package's: the request may carry a temperature and a seed / a JSON Schema, see
+    check_exclusive) -> SpecConfig or None; ValueError otherwise."""
     if speculative is None:
         return None
     if isinstance(speculative, SpecConfig):
         speculative = {"method": "ngram", "num_speculative_tokens": speculative.k, "prompt_lookup_max": speculative.lookup_max,
-                       "prompt_lookup_min": speculative.lookup_min, "sampled": speculative.sampled}
+                       "prompt_lookup_min": speculative.lookup_min, "sampled": speculative.sampled,
+                       **({"grammar": True, "schema_drafts": speculative.schema_drafts} if speculative.grammar else {})}
     if isinstance(speculative, int) and not isinstance(speculative, bool):
         speculative = {"method": "ngram", "num_speculative_tokens": speculative}
     if not isinstance(speculative, dict):
         raise ValueError("speculative must be None, an integer k or a dict with 'method' and 'num_speculative_tokens'")
-    unknown = set(speculative) - {"method", "num_speculative_tokens", "prompt_lookup_max", "prompt_lookup_min", "sampled"}
+    unknown = set(speculative) - {"method", "num_speculative_tokens", "prompt_lookup_max", "prompt_lookup_min", "sampled",
+                                  "grammar", "schema_drafts"}
     if unknown:
         raise ValueError(f"speculative: unknown keys {sorted(unknown)}")
     if speculative.get("method", "ngram") != "ngram":
@@ -85,7 +103,14 @@ def check_speculative(speculative) -> Optional[SpecConfig]:
     sampled = speculative.get("sampled", False)
     if not isinstance(sampled, bool):
         raise ValueError("speculative: sampled must be True or False")
-    return SpecConfig(k, hi, lo, sampled)
+    grammar, drafts = speculative.get("grammar", False), speculative.get("schema_drafts")
+    if not isinstance(grammar, bool):
+        raise ValueError("speculative: grammar must be True or False")
+    if drafts is not None and not isinstance(drafts, bool):
+        raise ValueError("speculative: schema_drafts must be True or False")
+    if drafts and not grammar:
+        raise ValueError("speculative: schema_drafts needs 'grammar': True (the schema's drafts are checked by the schema's mask)")
+    return SpecConfig(k, hi, lo, sampled, grammar, drafts)
 
 
 PRED_DEFAULT = SpecConfig(3, 4, 2)      # what ``prediction`` alone implies: four rows per step, vLLM's lookup window
@@ -141,8 +166,13 @@ def refuse_batch_prediction(prediction) -> None:
 
 def with_prediction(speculative, has_prediction: bool) -> Optional[SpecConfig]:
     """The step configuration of a request: ``speculative`` as check_speculative reads it; a prediction alone implies
-    PRED_DEFAULT (k = 3: with a prediction that holds, the four-row step is the cheapest per token in every weight format)."""
+    PRED_DEFAULT (k = 3: with a prediction that holds, the four-row step is the cheapest per token in every weight format).
+    ``schema_drafts`` next to a prediction is a ValueError: the prediction drafter counts what the accept step kept of the
+    draft row as its own, so it has to be the row's only writer ("schema_drafts": False keeps the schema's mask)."""
     sp = check_speculative(speculative)
+    if sp is not None and sp.schema_drafts and has_prediction:
+        raise ValueError("prediction together with the schema's drafts is not supported: the prediction drafter's accepted / "
+                         "rejected counts assume it owns the draft row; pass 'schema_drafts': False in speculative")
     return PRED_DEFAULT if sp is None and has_prediction else sp
 
 
@@ -153,9 +183,20 @@ def check_exclusive(cfg: Optional[SpecConfig], temperature: float = 0.0, seed=No
     ValueError naming the conflict.  ``what``: how the messages name the request's argument.
     A request that opted in (``cfg.sampled``) may carry ``temperature`` and ``seed``: its pick is Gumbel-max over a counter
     hash, a pure function of (logits row, seed, step), so "the draft equals the pick of the row in front of it" stays exact
-    with the sampled pick at hash counter step + r (vis_spec_accept_sampled).  ``top_p`` and everything else stay refused."""
+    with the sampled pick at hash counter step + r (vis_spec_accept_sampled).  ``top_p`` and everything else stay refused.
+    A request that opted in with ``cfg.grammar`` must carry a JSON Schema (``json_schema``, or a ``response_format`` of type
+    json_schema) and may: the DFA state in front of row r is the state in front of row r - 1 walked through draft r - 1, so
+    every row's mask is the plain step's (vis_schema_mask_rows), and a draft the schema rejects is never the masked pick."""
     if cfg is None:
         return
+    if cfg.grammar:
+        rf = switches.get("response_format")
+        by_format = isinstance(rf, dict) and rf.get("type") == "json_schema"
+        if switches.get("json_schema") is None and not by_format:
+            raise ValueError(f"{what}: 'grammar' needs a JSON Schema on the request (json_schema / response_format of type "
+                             "json_schema)")
+        switches = {name: v for name, v in switches.items()
+                    if name != "json_schema" and not (name == "response_format" and by_format)}
     if cfg.sampled:
         temperature = seed = None
     if temperature:
@@ -175,16 +216,21 @@ def check_exclusive(cfg: Optional[SpecConfig], temperature: float = 0.0, seed=No
                              "speculative step yields several tokens")
 
 
-def sampled_seed(cfg: SpecConfig, seed, default: int):
+def sampled_seed(cfg: SpecConfig, seed, default: int, response_format=None):
     """The client's checked keywords of ONE speculative request (client.engine_keywords' pair: the engine keywords that are
     on, the call's seed).  No other keyword is on; a request that opted in hands ``generate`` the seed the plain single
     request draws with - its own ``seed`` where it brought one, else the client's ``default``.  A request that did not is
-    the call of before: nothing on."""
+    the call of before: nothing on.  A ``grammar`` configuration also hands on the compiled schema of the request's
+    ``response_format`` (check_exclusive has seen that it is one)."""
     from .sampling import check_seed
+    on = {}
+    if cfg.grammar:
+        from .client import schema_of
+        on["json_schema"] = schema_of(response_format)
     if not cfg.sampled:
-        return {}, None
+        return on, None
     seed = check_seed(seed)
-    return {"seed": default if seed is None else seed}, None
+    return {**on, "seed": default if seed is None else seed}, None
 
 
 def sampled_from_env() -> bool:
@@ -196,10 +242,20 @@ def sampled_from_env() -> bool:
     return v == "1"
 
 
+def grammar_from_env() -> bool:
+    """VIS_SPECULATIVE_GRAMMAR (unset, empty or 0 = off; 1 = on; anything else: ValueError): the configurations from_env and
+    auditor_from_env return carry ``grammar``, so the agents' requests that send the report's schema (VIS_JSON_SCHEMA=1) keep
+    speculating.  Alone it turns nothing on."""
+    v = os.environ.get("VIS_SPECULATIVE_GRAMMAR", "").strip()
+    if v not in ("", "0", "1"):
+        raise ValueError("VIS_SPECULATIVE_GRAMMAR must be 0 or 1")
+    return v == "1"
+
+
 def from_env() -> Optional[SpecConfig]:
     """VIS_SPECULATIVE=k (1..3; unset, empty or 0 = off): the agents pass it on requests without an excluded switch.
-    VIS_SPECULATIVE_SAMPLED=1 next to it sets ``sampled`` on the configuration."""
-    sampled = sampled_from_env()
+    VIS_SPECULATIVE_SAMPLED=1 / VIS_SPECULATIVE_GRAMMAR=1 next to it set ``sampled`` / ``grammar`` on the configuration."""
+    sampled, grammar = sampled_from_env(), grammar_from_env()
     v = os.environ.get("VIS_SPECULATIVE", "").strip()
     if v in ("", "0"):
         return None
@@ -207,7 +263,7 @@ def from_env() -> Optional[SpecConfig]:
         k = int(v)
     except ValueError:
         raise ValueError("VIS_SPECULATIVE must be an integer in 0..3") from None
-    return check_speculative({"num_speculative_tokens": k, "sampled": sampled})
+    return check_speculative({"num_speculative_tokens": k, "sampled": sampled, "grammar": grammar})
 
 
 def check_rows_fit(cfg_model, rows: int) -> None:
@@ -230,8 +286,8 @@ def auditor_from_env() -> Optional[SpecConfig]:
     """VIS_AUDITOR_SPECULATIVE=k (1..3; unset, empty or 0 = off; anything else: ValueError): the Auditor's (Mllama) engine is
     built with speculative=True, the clients accept ``speculative`` / ``prediction`` for one request of an mllama model, and
     the agents pass k on a single request to one.  VIS_SPECULATIVE is the Qwen2-VL engines' and is not read here;
-    VIS_SPECULATIVE_SAMPLED=1 sets ``sampled`` on the configuration as in from_env."""
-    sampled = sampled_from_env()
+    VIS_SPECULATIVE_SAMPLED=1 / VIS_SPECULATIVE_GRAMMAR=1 set ``sampled`` / ``grammar`` on the configuration as in from_env."""
+    sampled, grammar = sampled_from_env(), grammar_from_env()
     v = os.environ.get("VIS_AUDITOR_SPECULATIVE", "").strip()
     if v in ("", "0"):
         return None
@@ -241,7 +297,7 @@ def auditor_from_env() -> Optional[SpecConfig]:
         k = -1
     if not 1 <= k <= MAX_K:
         raise ValueError(f"VIS_AUDITOR_SPECULATIVE must be an integer in 0..{MAX_K}")
-    return check_speculative({"num_speculative_tokens": k, "sampled": sampled})
+    return check_speculative({"num_speculative_tokens": k, "sampled": sampled, "grammar": grammar})
 
 
 # ----------------------------------------------------------------------------------------------------- references
