@@ -14,6 +14,7 @@ import torch
 from . import hip, spec
 from .fork import check_fork_tables, fork_layout
 from .pick import PickStage
+from .weights import pad_cols
 
 _LOG = logging.getLogger("vision_inspection_system_amd.engine")
 
@@ -47,17 +48,30 @@ def _wt(L: DecodeLayer, name: str, fmt: str) -> tuple:
     return (getattr(L.w, name),) if fmt == "bf16" else (L.q8 if fmt == "fp8" else L.q4)[name]
 
 
+def quantize_decode_weights(layer_weights: Sequence, lm_head: torch.Tensor, fp8: bool, mxfp4: bool,
+                            pad_down: bool = False) -> tuple:
+    """The decode projections of every layer and the lm_head in the quantised formats asked for, once at load time ->
+    (q8, q4, q8_head, q4_head): a dict per layer over qkv_w / o_w / gateup_w / down_w, name -> (e4m3 codes, row scales) /
+    (MXFP4 codes, block scales), and the lm_head's pair; a format that is off gives an empty list and None.  ``pad_down``:
+    the fp8 MFMA reads down_w (``kpad`` is set) and needs K % 128 == 0 - where K is no such multiple, "down_w_pad" holds the
+    codes with zero columns appended, under the unpadded tensor's scales."""
+    names = ("qkv_w", "o_w", "gateup_w", "down_w")
+    q8 = [{n: hip.quantize_fp8_rows(getattr(lw, n)) for n in names} for lw in layer_weights] if fp8 else []
+    q4 = [{n: hip.quantize_mxfp4_rows(getattr(lw, n)) for n in names} for lw in layer_weights] if mxfp4 else []
+    for q in q8 if pad_down else ():
+        wq, sc = q["down_w"]
+        if wq.shape[1] % 128:
+            q["down_w_pad"] = (pad_cols(wq, 128), sc)
+    return q8, q4, hip.quantize_fp8_rows(lm_head) if fp8 else None, hip.quantize_mxfp4_rows(lm_head) if mxfp4 else None
+
+
 class DecodeStage(PickStage):
     """Base class of the engines: works on ``self``, holds no model knowledge.
 
-    Contract - what it reads of the engine, all present before ``_init_decode_stage()`` runs: ``cfg``, ``w.embed``, ``device``,
-    ``max_ctx``; the activation buffers ``d_*`` (single sequence) and ``b_*`` (batched: rows, stream-K partials, and what the
-    fused and fp8 steps add); the caches ``kcache_b`` / ``vcache_b`` [slots, self layers, ...], the rope tables ``cos_t`` /
-    ``sin_t``, the attention workspace ``part_o`` / ``part_ml``, the counters ``step_b`` / ``cur_b`` and the pick stage's rows -
-    each with its slot-0 view (``kcache``, ``step``, ``cur_token``, ``tokens``, ``logits``); ``prompt_len`` and ``_decoded``;
-    ``nsplit`` and the flags ``fused_proj``, ``fold_qkv``, ``fp8_batched``, ``decode_weights``, ``mxfp4_gemm_from`` (read at
-    every step: tests and tools set them after construction); the chain state ``chain_ws``, ``chain_sync``,
-    ``chain_ctx_limit``, ``_chain_launches``; ``has_image`` where a layer is a cross-attention layer.
+    Contract - what an engine brings before ``_init_decode_state()`` runs: ``cfg``, ``device`` and ``max_ctx`` (a multiple of
+    64); and before the first step: ``w.embed``, the rope tables ``cos_t`` / ``sin_t`` of the single sequence, its layers
+    (``_init_decode_stage``), ``has_image`` where a layer is a cross-attention layer.  Everything else a step reads - caches,
+    counters, activation rows, workspaces, the chain state and the flags - ``_init_decode_state()`` allocates and sets.
     What the models do differently is behind two hooks: ``_decode_rope(B)`` -> (cos, sin, shared_len), the rope tables
     [B, T, D] of the batched self-attention and the number of leading keys every sequence reads from slot 0, and
     ``_decode_cross_attn(L, q, att, B)``, the cross-attention launch of layer L for the single sequence (B == 0) or B slots.
@@ -65,6 +79,147 @@ class DecodeStage(PickStage):
     ``_decode_cross_attn_draft(L, q, att, R)``, that launch for the R rows of a speculative step, and ``xsplit``, its split count.
     An engine supplies ``_ensure_graph(chained=)`` with its own graph key (see ``_captured_step``) and checks its own bounds
     in ``decode()`` before ``_decode_ordered``."""
+
+    @staticmethod
+    def check_decode_weights(cfg, decode_weights: str) -> None:
+        """Refuse an unknown decode precision, or one the model's shapes do not fit (needs no GPU)."""
+        if decode_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError("decode_weights must be 'bf16', 'fp8' or 'mxfp4'")
+        if decode_weights == "mxfp4":
+            dims = {"hidden": cfg.hidden, "heads*head_dim": cfg.heads * cfg.head_dim, "intermediate": cfg.intermediate}
+            bad = [f"{n}={v}" for n, v in dims.items() if v % 32]
+            if bad:
+                raise ValueError("decode_weights='mxfp4' needs MX blocks of 32 inputs: " + ", ".join(bad)
+                                 + " must be multiples of 32")
+
+    @staticmethod
+    def check_mxfp4_gemm_from(cfg, decode_weights: str, mxfp4_gemm_from) -> None:
+        """Refuse a threshold for the MXFP4 MFMA projection that is no integer in 5..64, that comes without
+        decode_weights='mxfp4', or that the model's shapes do not fit (needs no GPU)."""
+        if mxfp4_gemm_from is None:
+            return
+        if isinstance(mxfp4_gemm_from, bool) or not isinstance(mxfp4_gemm_from, int) or not 5 <= mxfp4_gemm_from <= 64:
+            raise ValueError("mxfp4_gemm_from must be None or an integer in 5..64 (smaller batches are the multi-row GEMV's)")
+        if decode_weights != "mxfp4":
+            raise ValueError("mxfp4_gemm_from needs decode_weights='mxfp4'")
+        dims = {"hidden": cfg.hidden, "heads*head_dim": cfg.heads * cfg.head_dim, "intermediate": cfg.intermediate}
+        bad = [f"{n}={v}" for n, v in dims.items() if v % 64]
+        if bad:
+            raise ValueError("mxfp4_gemm_from needs K-steps of 64 inputs: " + ", ".join(bad) + " must be multiples of 64")
+
+    def _init_decode_state(self, max_batch: int, n_self_layers: int, decode_weights: str = "bf16",
+                           mxfp4_gemm_from: Optional[int] = None, decode_splits: int = 0, cross_splits: int = 0,
+                           fused_quantised: bool = True, prefill_fp8: bool = False) -> None:
+        """Everything a decode step works on that is not model knowledge, allocated and set once from an engine's constructor
+        (``cfg``, ``device`` and ``max_ctx`` are set): the per-slot state - self KV caches of ``n_self_layers`` layers, counters,
+        token rows, the pick's rows, each with its slot-0 view, slot 0 doubling as the single sequence - the single-sequence
+        and the batched activation rows, the attention workspace for the larger of ``nsplit`` (``decode_splits``, or one
+        split per hip.DECODE_KEYS_PER_SPLIT keys of context) and ``cross_splits``, what the fused and the fp8 batched steps
+        add, the chain state, the flags every step reads (plain attributes: tests and tools set them afterwards) and the
+        request counters.  Rows that rely on their pad columns, pad scale blocks or first read being zero are zeroed; the
+        rest is uninitialised.  What does not apply is None (``kpad``, ``chain_ws``, ``chain_sync``) or, for the ``b_*`` rows,
+        absent.
+
+        ``fused_quantised``: whether VIS_DECODE_FUSED=1 holds whatever ``decode_weights`` is (Qwen2-VL: its fused step carries
+        fp8 weights too) or for bf16 weights only (Mllama: a quantised engine's batched step is the stream-K or the rows step).
+        ``prefill_fp8``: ``kpad`` is wanted although the batched fp8 step may be off, for an fp8 prompt pass.
+
+        The one rule of ``b_part``, the stream-K partial slabs (16 slots x hip.part_rows(max_batch) rows x the widest
+        projection), kept as ``streamk_part``: allocated when a step can read them - max_batch > 1, and not the fused step
+        with fp8 weights (every projection of it is one launch), and not MXFP4 weights without ``mxfp4_gemm_from`` (every
+        batch size is the rows step's); absent otherwise.  Readers: the stream-K step, and the fused step's long-K bf16 down
+        projection at many sequences."""
+        cfg, dev, bf = self.cfg, self.device, torch.bfloat16
+        Hq, Hkv, D, H, I = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden, cfg.intermediate
+        if not 1 <= max_batch <= 64:
+            raise ValueError("max_batch must be in 1..64 (one, two or four 16-row MFMA blocks of in-flight sequences)")
+        Bm = self.max_batch = max_batch
+        self.decode_weights, self.mxfp4_gemm_from = decode_weights, mxfp4_gemm_from
+        self.nsplit = decode_splits or max(1, -(-self.max_ctx // hip.DECODE_KEYS_PER_SPLIT))
+        # decode-step state is device resident, so the step is one replayable graph
+        self.kcache_b = torch.zeros((Bm, n_self_layers, Hkv, self.max_ctx, D), dtype=bf, device=dev)
+        self.vcache_b = torch.zeros((Bm, n_self_layers, Hkv, self.max_ctx, D), dtype=bf, device=dev)
+        self.step_b = torch.zeros(Bm, dtype=torch.int32, device=dev)
+        self.cur_b = torch.zeros(Bm, dtype=torch.int32, device=dev)
+        self.tokens_b = torch.zeros((Bm, self.max_ctx), dtype=torch.int32, device=dev)
+        self.ws_val = torch.empty(max(256 * Bm, 2048), dtype=torch.float32, device=dev)
+        self.ws_idx = torch.empty(max(256 * Bm, 2048), dtype=torch.int32, device=dev)
+        self.logits_b = torch.empty((Bm, cfg.vocab), dtype=torch.float32, device=dev)
+        self.kcache, self.vcache = self.kcache_b[0], self.vcache_b[0]
+        self.step, self.cur_token = self.step_b[0:1], self.cur_b[0:1]
+        self.tokens, self.logits = self.tokens_b[0], self.logits_b[0]
+        nq = (Hq + 2 * Hkv) * D
+        self.d_x = torch.empty((1, H), dtype=bf, device=dev)
+        self.d_x2 = torch.empty((1, H), dtype=bf, device=dev)
+        self.d_qkv = torch.empty(nq, dtype=bf, device=dev)
+        self.d_attn = torch.empty(Hq * D, dtype=bf, device=dev)
+        self.d_act = torch.empty(I, dtype=bf, device=dev)
+        ns = max(self.nsplit, cross_splits)
+        self.part_o = torch.empty(Bm * Hq * ns * D, dtype=torch.float32, device=dev)
+        self.part_ml = torch.empty(Bm * Hq * ns * 2, dtype=torch.float32, device=dev)
+        if Bm > 1:      # batched-decode activations
+            for name, cols in (("b_x", H), ("b_x2", H), ("b_qkv", nq), ("b_attn", Hq * D), ("b_act", I), ("b_xn", H),
+                               ("b_xn2", H)):
+                setattr(self, name, torch.empty((Bm, cols), dtype=bf, device=dev))
+        # Batched decode, r05 experiment (VIS_DECODE_FUSED=1, OFF by default): every projection as ONE launch - stream + split-K
+        # reduction + epilogue (vis_decode_proj_*: stream-K ranges with a last-arriver reduction, or whole-K column slabs), the
+        # RMSNorm split into the producer's per-column and the consumer's per-row factor; csrc/decode_stream.hip,
+        # csrc/decode_colpar.hip.  Correct and tested, but NOT faster: a cross-CU reduction costs three dependent memory round
+        # trips wherever it runs, and the finalisation launch it replaces already sits at the ~5 us floor of a dependent
+        # load -> store kernel (DESIGN section 4, profiles/r05_decode_step_*.txt: 64 sequences 5.37 -> 6.4 ms per step).
+        self.fused_proj = Bm > 1 and H % 128 == 0 and (fused_quantised or decode_weights == "bf16") \
+            and os.environ.get("VIS_DECODE_FUSED", "0") == "1"
+        # batched decode: the self-attention launch finalises the qkv projection's partial slabs itself (vis_decode_attn_parts,
+        # bit-identical to skinny_finalize + decode_attn); VIS_QKV_FOLD=0 keeps the two launches (A/B)
+        self.fold_qkv = os.environ.get("VIS_QKV_FOLD", "1") == "1"
+        self.streamk_part = Bm > 1 and not (self.fused_proj and decode_weights == "fp8") and \
+            (decode_weights != "mxfp4" or mxfp4_gemm_from is not None)
+        if self.streamk_part:
+            self.b_part = torch.empty(16 * hip.part_rows(Bm) * max(nq, H, 2 * I), dtype=torch.float32, device=dev)
+        # the batched fp8 step carries its activations as e4m3 rows too; the fp8 MFMA needs K % 128 == 0, so the down
+        # projection's input rows (and its weights: quantize_decode_weights) are zero-padded to kpad columns
+        self.fp8_batched = decode_weights == "fp8" and Bm > 1 and H % 128 == 0
+        self.kpad = (I + 127) // 128 * 128 if self.fp8_batched or prefill_fp8 else None
+        if self.fp8_batched:
+            self.b_xq = torch.zeros((Bm, H), dtype=torch.uint8, device=dev)
+            self.b_x2q = torch.zeros((Bm, H), dtype=torch.uint8, device=dev)
+            self.b_actq = torch.zeros((Bm, self.kpad), dtype=torch.uint8, device=dev)       # pad columns stay 0
+            self.b_sx = torch.zeros((3, Bm), dtype=torch.float32, device=dev)
+            if self.fused_proj:   # MX blocks: one E8M0 scale byte per row and 32 columns (pad blocks stay 0 = 2^-127 x code 0)
+                self.b_xqs = torch.zeros((Bm, H // 32), dtype=torch.uint8, device=dev)
+                self.b_x2qs = torch.zeros((Bm, H // 32), dtype=torch.uint8, device=dev)
+                self.b_actqs = torch.zeros((Bm, self.kpad // 32), dtype=torch.uint8, device=dev)
+        if self.fused_proj:
+            self.b_xw = torch.empty((Bm, H), dtype=bf, device=dev)        # x * ln1_w of the next layer (A operand of qkv / lm_head)
+            self.b_x2w = torch.empty((Bm, H), dtype=bf, device=dev)       # x2 * ln2_w (A operand of gate/up)
+            self.b_ssq1 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
+            self.b_ssq2 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
+            f8 = self.fp8_batched
+            shapes = [(nq, H, f8), (H, Hq * D, False), (2 * I, H, f8), (H, self.kpad if f8 else I, f8), (cfg.vocab, H, f8)]
+            need = max(int(hip.load().vis_decode_proj_ws_bytes(Bm, n, k, int(q))) for n, k, q in shapes)
+            if need <= 0:
+                raise ValueError("vis_decode_proj_ws_bytes refused a projection shape of this model")
+            self.b_proj_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        # Single-sequence decode: the head of every self-attention layer (qkv projection -> rope / append / attention -> o
+        # projection) as ONE launch whose stages hand over inside the grid, the lm_head with the pick's first stage in its
+        # epilogue (csrc/decode_chain.hip, _decode_step_rows; bit-identical to the launches it replaces); bf16 weights only.
+        # Contexts up to chain_ctx_limit cached keys decode on it, longer ones on the four launches (same bits): what must be
+        # resident together are the workgroups that wait - projection and merge roles + Hkv attention items per 64 keys of
+        # context (7B shapes: 6208 keys, 11B: 1536, whatever the cache size is).  VIS_DECODE_CHAIN=0 keeps the four launches (A/B).
+        self.chain_ws = self.chain_sync = None
+        self.chain_ctx_limit = 0
+        self._chain_launches = 0                       # host-side count of chained launches on the sync block (epoch guard)
+        if decode_weights == "bf16" and os.environ.get("VIS_DECODE_CHAIN", "1") != "0" \
+                and hip.decode_chain_supported(Hq, Hkv, D, H):
+            limit = hip.decode_chain_ctx_limit(Hq, Hkv, H)
+            if limit > 0:
+                self.chain_ws, self.chain_sync = hip.decode_chain_state(dev, Hq, Hkv, self.nsplit)
+                self.chain_ctx_limit = limit
+        self.slot_prompt_len = [0] * Bm
+        self.prompt_len = self._decoded = self.decode_limit = 0
+        self.temperature, self.seed = 0.0, 0
+        self.last_timing: dict = {}
+        self._prefill_streams: List[torch.cuda.Stream] = []
 
     def _init_decode_stage(self, layers: Sequence[DecodeLayer], norm_w: torch.Tensor, lm_head: torch.Tensor,
                            q8_head: Optional[tuple] = None, q4_head: Optional[tuple] = None) -> None:
@@ -234,8 +389,8 @@ class DecodeStage(PickStage):
                     except hip.ChainRefused as e:
                         # VIS_ERR_UNSUPPORTED and nothing else (a bad argument or a launch error propagates): the grid for
                         # this context length is larger than the device holds resident -> the four launches, same results;
-                        # said once.  An engine that keeps the chain only with a positive decode_chain_ctx_limit and passes
-                        # that bound (MllamaEngine) never gets here.
+                        # said once.  (Rare: the chain is kept only with a positive decode_chain_ctx_limit, and that bound
+                        # is what the launch is given.)
                         if li:
                             raise
                         _LOG.warning("%s - decoding on the four launches per layer head (VIS_MAX_CTX=%d)", e, self.max_ctx)
@@ -505,7 +660,7 @@ class DecodeStage(PickStage):
         per-column and a per-row factor).  5 launches per layer (r04: 9).  fp8 (configs[4]): activations travel as MX blocks
         written by the producing epilogue.  The tanh gates of Mllama's cross-attention layers are folded into o_w / down_w at
         load time, so both layer kinds share the sequence.  ``projections_only``: bench.py's replay of the weight-streaming
-        launches alone.  Returns the number of projection launches.  Opt-in (VIS_DECODE_FUSED=1): Qwen2VLEngine.__init__ has
+        launches alone.  Returns the number of projection launches.  Opt-in (VIS_DECODE_FUSED=1): _init_decode_state has
         the measurements that keep it off by default."""
         cfg = self.cfg
         Hq, Hkv, D, H = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden
@@ -521,7 +676,7 @@ class DecodeStage(PickStage):
         # the NORMALISED row, its consumer takes no row factor): a column slab per workgroup would stream 2.4 MB of x each, and
         # the in-kernel reduction of the stream-K form costs more than the finalisation launch it saves (64 vs 33 + 5 us,
         # profiles/r05_decode_step_b64_streamk.txt).  VIS_DOWN_PAIR=0 forces the single launch (A/B).
-        down_pair = (not fp8) and hasattr(self, "b_part") and os.environ.get("VIS_DOWN_PAIR", "1") != "0" and \
+        down_pair = (not fp8) and self.streamk_part and os.environ.get("VIS_DOWN_PAIR", "1") != "0" and \
             hip.decode_proj_form(B, H, cfg.intermediate, hip.DP_RESID_NORMW, False, False) == "streamk"
         s1_in = None if down_pair else s1
         layers = self.dec_layers

@@ -26,11 +26,11 @@ import numpy as np
 import torch
 
 from . import hip
-from .decode_stage import DecodeLayer
+from .decode_stage import DecodeLayer, quantize_decode_weights
 from .generation import Generation
 from .request import Switches
 from .config import Qwen2VLConfig
-from .weights import DeviceWeights, PATCH_K_PAD
+from .weights import DeviceWeights, PATCH_K_PAD, pad_cols
 
 
 def _round_up(x: int, m: int) -> int:
@@ -142,33 +142,6 @@ class Qwen2VLEngine(Generation):
 
     speculative_supported = True      # generate(.., speculative=): spec.py
 
-    @staticmethod
-    def check_decode_weights(cfg: Qwen2VLConfig, decode_weights: str) -> None:
-        """Refuse an unknown decode precision, or one the model's shapes do not fit (needs no GPU)."""
-        if decode_weights not in ("bf16", "fp8", "mxfp4"):
-            raise ValueError("decode_weights must be 'bf16', 'fp8' or 'mxfp4'")
-        if decode_weights == "mxfp4":
-            dims = {"hidden": cfg.hidden, "heads*head_dim": cfg.heads * cfg.head_dim, "intermediate": cfg.intermediate}
-            bad = [f"{n}={v}" for n, v in dims.items() if v % 32]
-            if bad:
-                raise ValueError("decode_weights='mxfp4' needs MX blocks of 32 inputs: " + ", ".join(bad)
-                                 + " must be multiples of 32")
-
-    @staticmethod
-    def check_mxfp4_gemm_from(cfg: Qwen2VLConfig, decode_weights: str, mxfp4_gemm_from) -> None:
-        """Refuse a threshold for the MXFP4 MFMA projection that is no integer in 5..64, that comes without
-        decode_weights='mxfp4', or that the model's shapes do not fit (needs no GPU)."""
-        if mxfp4_gemm_from is None:
-            return
-        if isinstance(mxfp4_gemm_from, bool) or not isinstance(mxfp4_gemm_from, int) or not 5 <= mxfp4_gemm_from <= 64:
-            raise ValueError("mxfp4_gemm_from must be None or an integer in 5..64 (smaller batches are the multi-row GEMV's)")
-        if decode_weights != "mxfp4":
-            raise ValueError("mxfp4_gemm_from needs decode_weights='mxfp4'")
-        dims = {"hidden": cfg.hidden, "heads*head_dim": cfg.heads * cfg.head_dim, "intermediate": cfg.intermediate}
-        bad = [f"{n}={v}" for n, v in dims.items() if v % 64]
-        if bad:
-            raise ValueError("mxfp4_gemm_from needs K-steps of 64 inputs: " + ", ".join(bad) + " must be multiples of 64")
-
     def __init__(self, cfg: Qwen2VLConfig, weights: DeviceWeights, device, max_ctx: int = 4096,
                  decode_splits: int = 0, max_batch: int = 1, decode_weights: str = "bf16",
                  prefill_dtype: str = "bf16", mxfp4_gemm_from: Optional[int] = None):
@@ -188,136 +161,34 @@ class Qwen2VLEngine(Generation):
         cfg.validate_for_kernels()
         self.check_decode_weights(cfg, decode_weights)
         self.check_mxfp4_gemm_from(cfg, decode_weights, mxfp4_gemm_from)
-        self.mxfp4_gemm_from = mxfp4_gemm_from
+        if prefill_dtype not in ("bf16", "fp8"):
+            raise ValueError("prefill_dtype must be 'bf16' or 'fp8'")
+        if prefill_dtype == "fp8" and (cfg.hidden % 128 or (cfg.heads * cfg.head_dim) % 128):
+            raise ValueError("fp8 prefill needs hidden and heads*head_dim to be multiples of 128")
         hip.load()  # fail loudly when the gfx950 library is missing: there is no other path
         if not torch.cuda.is_available():
             raise hip.HipLibraryError("Qwen2VLEngine needs a ROCm GPU (no CPU fallback exists)")
         self.cfg, self.w, self.device = cfg, weights, torch.device(device)
         self.max_ctx = _round_up(max_ctx, 64)
-        self.nsplit = decode_splits or max(1, -(-self.max_ctx // hip.DECODE_KEYS_PER_SPLIT))
         self.lock = threading.Lock()
-        dev, bf = self.device, torch.bfloat16
-        L, Hkv, Hq, D, H = cfg.layers, cfg.kv_heads, cfg.heads, cfg.head_dim, cfg.hidden
-        if not 1 <= max_batch <= 64:
-            raise ValueError("max_batch must be in 1..64 (one, two or four 16-row MFMA blocks of in-flight sequences)")
-        Bm = self.max_batch = max_batch
-        # per-sequence ("slot") state; slot 0 doubles as the single-sequence engine
-        self.kcache_b = torch.zeros((Bm, L, Hkv, self.max_ctx, D), dtype=bf, device=dev)
-        self.vcache_b = torch.zeros((Bm, L, Hkv, self.max_ctx, D), dtype=bf, device=dev)
-        self.cos_b = torch.zeros((Bm, self.max_ctx, D), dtype=torch.float32, device=dev)
-        self.sin_b = torch.zeros((Bm, self.max_ctx, D), dtype=torch.float32, device=dev)
-        # decode-step state (device resident so the step is one replayable graph)
-        self.step_b = torch.zeros(Bm, dtype=torch.int32, device=dev)
-        self.cur_b = torch.zeros(Bm, dtype=torch.int32, device=dev)
-        self.tokens_b = torch.zeros((Bm, self.max_ctx), dtype=torch.int32, device=dev)
-        self.ws_val = torch.empty(max(256 * Bm, 2048), dtype=torch.float32, device=dev)
-        self.ws_idx = torch.empty(max(256 * Bm, 2048), dtype=torch.int32, device=dev)
-        self.logits_b = torch.empty((Bm, cfg.vocab), dtype=torch.float32, device=dev)
-        self.kcache, self.vcache = self.kcache_b[0], self.vcache_b[0]
+        self.prefill_dtype = prefill_dtype
+        # what the decode stage works on (decode_stage.py): caches, counters, activation rows, workspaces, chain state, flags
+        self._init_decode_state(max_batch, cfg.layers, decode_weights, mxfp4_gemm_from, decode_splits=decode_splits,
+                                prefill_fp8=prefill_dtype == "fp8")
+        dev = self.device
+        # M-RoPE rows differ per request: every slot owns its tables; slot 0 doubles as the single-sequence engine
+        self.cos_b = torch.zeros((max_batch, self.max_ctx, cfg.head_dim), dtype=torch.float32, device=dev)
+        self.sin_b = torch.zeros((max_batch, self.max_ctx, cfg.head_dim), dtype=torch.float32, device=dev)
         self.cos_t, self.sin_t = self.cos_b[0], self.sin_b[0]
-        self.step, self.cur_token = self.step_b[0:1], self.cur_b[0:1]
-        self.tokens, self.logits = self.tokens_b[0], self.logits_b[0]
-        nq = (Hq + 2 * Hkv) * D
-        self.d_x = torch.empty((1, H), dtype=bf, device=dev)
-        self.d_x2 = torch.empty((1, H), dtype=bf, device=dev)
-        self.d_qkv = torch.empty(nq, dtype=bf, device=dev)
-        self.d_attn = torch.empty(Hq * D, dtype=bf, device=dev)
-        self.d_act = torch.empty(cfg.intermediate, dtype=bf, device=dev)
-        self.part_o = torch.empty(Bm * Hq * self.nsplit * D, dtype=torch.float32, device=dev)
-        self.part_ml = torch.empty(Bm * Hq * self.nsplit * 2, dtype=torch.float32, device=dev)
-        if Bm > 1:  # batched-decode activations and the split-K partial workspace
-            self.b_x = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_x2 = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_qkv = torch.empty((Bm, nq), dtype=bf, device=dev)
-            self.b_attn = torch.empty((Bm, Hq * D), dtype=bf, device=dev)
-            self.b_act = torch.empty((Bm, cfg.intermediate), dtype=bf, device=dev)
-            self.b_xn = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_xn2 = torch.empty((Bm, H), dtype=bf, device=dev)
-        # Batched decode, r05 experiment (VIS_DECODE_FUSED=1, OFF by default): every projection as ONE launch - stream + split-K
-        # reduction + epilogue (vis_decode_proj_*: stream-K ranges with a last-arriver reduction, or whole-K column slabs), the
-        # RMSNorm split into the producer's per-column and the consumer's per-row factor; csrc/decode_stream.hip,
-        # csrc/decode_colpar.hip.  Correct and tested, but NOT faster: a cross-CU reduction costs three dependent memory round
-        # trips wherever it runs, and the finalisation launch it replaces already sits at the ~5 us floor of a dependent
-        # load -> store kernel (profiles/r05_decode_step_*.txt: 64 sequences 5.37 -> 6.4 ms per step).
-        self.fused_proj = Bm > 1 and H % 128 == 0 and os.environ.get("VIS_DECODE_FUSED", "0") == "1"
-        # batched decode: the self-attention launch finalises the qkv projection's partial slabs itself (vis_decode_attn_parts,
-        # bit-identical to skinny_finalize + decode_attn); VIS_QKV_FOLD=0 keeps the two launches (A/B)
-        self.fold_qkv = os.environ.get("VIS_QKV_FOLD", "1") == "1"
         # stacked suffix pass: rope / KV write / attention of the group's requests as ONE launch each (vis_*_many, per request
         # bit-identical to the per-request launches); VIS_GROUP_ATTN=0 keeps one launch per request (A/B)
         self.group_attn = os.environ.get("VIS_GROUP_ATTN", "1") == "1"
-        if self.fused_proj:
-            self.b_xw = torch.empty((Bm, H), dtype=bf, device=dev)        # x * ln1_w of the next layer (A operand of qkv / lm_head)
-            self.b_x2w = torch.empty((Bm, H), dtype=bf, device=dev)       # x2 * ln2_w (A operand of gate/up)
-            self.b_ssq1 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
-            self.b_ssq2 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
-        if Bm > 1 and not (self.fused_proj and decode_weights == "fp8") and \
-                (decode_weights != "mxfp4" or mxfp4_gemm_from is not None):
-            # split-K slabs of the r02-r04 pair of launches: the whole step with VIS_DECODE_FUSED=0, and the bf16 down
-            # projection at many sequences in the fused step (_decode_step_fused)
-            self.b_part = torch.empty(16 * hip.part_rows(Bm) * max(nq, H, 2 * cfg.intermediate), dtype=torch.float32,
-                                      device=dev)   # 16 stream-K slots x (16 or 32) rows
-        self.decode_weights = decode_weights
-        # Single-sequence decode: the head of every layer (qkv projection -> rope / append / attention -> o projection) as ONE
-        # launch whose stages hand over inside the grid (csrc/decode_chain.hip; bit-identical to the four launches it
-        # replaces).  VIS_DECODE_CHAIN=0 keeps the four launches (A/B).
-        self.chain_sync: Optional[torch.Tensor] = None
         self._chain_state: Optional[tuple] = None      # (ws, sync) kept while the chain is switched off after a stall
-        self._chain_launches = 0                       # host-side count of chained launches on the sync block (epoch guard)
         self._chain_clean_requests = 0                 # requests served on the four launches since a stall
-        if decode_weights == "bf16" and os.environ.get("VIS_DECODE_CHAIN", "1") != "0" \
-                and hip.decode_chain_supported(Hq, Hkv, D, H):
-            self.chain_ws, self.chain_sync = hip.decode_chain_state(dev, Hq, Hkv, self.nsplit)
-        # contexts up to this many cached keys decode on the chained launch, longer ones on the four launches (same bits):
-        # what must be resident together are the workgroups that wait - projection and merge roles + Hkv attention items per
-        # 64 keys of context (7B shapes: 6208 keys, whatever VIS_MAX_CTX is)
-        self.chain_ctx_limit = hip.decode_chain_ctx_limit(Hq, Hkv, H) if self.chain_sync is not None else 0
-        if self.chain_sync is not None and self.chain_ctx_limit <= 0:
-            self.chain_sync = None
-        self.q8: List[dict] = []
-        self.prefill_dtype = prefill_dtype
-        if prefill_dtype not in ("bf16", "fp8"):
-            raise ValueError("prefill_dtype must be 'bf16' or 'fp8'")
-        if decode_weights == "fp8" or prefill_dtype == "fp8":
-            for lw in weights.llm:
-                self.q8.append({n: hip.quantize_fp8_rows(getattr(lw, n)) for n in ("qkv_w", "o_w", "gateup_w", "down_w")})
-            self.q8_lm_head = hip.quantize_fp8_rows(weights.lm_head)
-        self.q4: List[dict] = []
-        if decode_weights == "mxfp4":
-            for lw in weights.llm:
-                self.q4.append({n: hip.quantize_mxfp4_rows(getattr(lw, n)) for n in ("qkv_w", "o_w", "gateup_w", "down_w")})
-            self.q4_lm_head = hip.quantize_mxfp4_rows(weights.lm_head)
-        self.fp8_batched = False
-        if decode_weights == "fp8" and Bm > 1 and cfg.hidden % 128 == 0:
-            self.fp8_batched = True
-            kp = _round_up(cfg.intermediate, 128)
-            self.b_xq = torch.zeros((Bm, cfg.hidden), dtype=torch.uint8, device=dev)
-            self.b_x2q = torch.zeros((Bm, cfg.hidden), dtype=torch.uint8, device=dev)
-            self.b_actq = torch.zeros((Bm, kp), dtype=torch.uint8, device=dev)       # pad columns stay 0
-            self.b_sx = torch.zeros((3, Bm), dtype=torch.float32, device=dev)
-            if self.fused_proj:   # MX blocks: one E8M0 scale byte per row and 32 columns (pad blocks stay 0 = 2^-127 x code 0)
-                self.b_xqs = torch.zeros((Bm, cfg.hidden // 32), dtype=torch.uint8, device=dev)
-                self.b_x2qs = torch.zeros((Bm, cfg.hidden // 32), dtype=torch.uint8, device=dev)
-                self.b_actqs = torch.zeros((Bm, kp // 32), dtype=torch.uint8, device=dev)
-        if prefill_dtype == "fp8" or self.fp8_batched:   # fp8 MFMA needs K % 128 == 0: zero-pad down's K if necessary
-            self.kpad = _round_up(cfg.intermediate, 128)
-            if self.kpad != cfg.intermediate:
-                for q in self.q8:
-                    wq, sc = q["down_w"]
-                    pad = torch.zeros((wq.shape[0], self.kpad), dtype=torch.uint8, device=wq.device)
-                    pad[:, :cfg.intermediate] = wq
-                    q["down_w_pad"] = (pad, sc)
-            if prefill_dtype == "fp8" and (cfg.hidden % 128 or (cfg.heads * cfg.head_dim) % 128):
-                raise ValueError("fp8 prefill needs hidden and heads*head_dim to be multiples of 128")
-        if self.fused_proj:
-            fp8b = self.fp8_batched
-            kd = self.kpad if fp8b else cfg.intermediate
-            shapes = [(nq, H, fp8b), (H, Hq * D, False), (2 * cfg.intermediate, H, fp8b), (H, kd, fp8b), (cfg.vocab, H, fp8b)]
-            lib = hip.load()
-            need = max(int(lib.vis_decode_proj_ws_bytes(Bm, n, k, 1 if f8 else 0)) for n, k, f8 in shapes)
-            if need <= 0:
-                raise ValueError("vis_decode_proj_ws_bytes refused a projection shape of this model")
-            self.b_proj_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        # the LLM projections in e4m3 for the decode step and / or the fp8 prompt pass, in MXFP4 for the decode step
+        self.q8, self.q4, self.q8_lm_head, self.q4_lm_head = quantize_decode_weights(
+            weights.llm, weights.lm_head, decode_weights == "fp8" or prefill_dtype == "fp8", decode_weights == "mxfp4",
+            pad_down=self.kpad is not None)
         self.vq8: List[dict] = []
         if prefill_dtype == "fp8" and cfg.v_mlp % 128 == 0 and os.environ.get("VIS_VIT_FP8", "1") == "1":
             # ViT block projections in e4m3 too (VIS_VIT_FP8=0 keeps the tower in bf16).  With only the 256x256 fp8 tile
@@ -325,22 +196,12 @@ class Qwen2VLEngine(Generation):
             # with the 128x128 fp8 tile it pays: 39.8 -> 38.3 ms.  K = v_embed is zero-padded to a multiple of 128
             # when necessary (tiny: 320).
             self.vepad = _round_up(cfg.v_embed, 128)
-
-            def q8pad(wt):
-                wq, sc = hip.quantize_fp8_rows(wt)
-                if wq.shape[1] % 128:
-                    pad = torch.zeros((wq.shape[0], _round_up(wq.shape[1], 128)), dtype=torch.uint8, device=wq.device)
-                    pad[:, :wq.shape[1]] = wq
-                    wq = pad
-                return wq, sc
             for b in weights.vit:
-                self.vq8.append({n: q8pad(getattr(b, n)) for n in ("qkv_w", "proj_w", "fc1_w", "fc2_w")})
-        self.slot_prompt_len = [0] * Bm
+                q8 = {n: hip.quantize_fp8_rows(getattr(b, n)) for n in ("qkv_w", "proj_w", "fc1_w", "fc2_w")}
+                self.vq8.append({n: (pad_cols(wq, 128), sc) for n, (wq, sc) in q8.items()})
         # keys [0, batch_shared_len) of the CURRENT batch's slots are identical copies of one text prefix (prefill_many):
         # the batched decode attention reads them from slot 0 (VIS_DECODE_SHARED=0: every sequence reads its own copy)
         self.batch_shared_len = 0
-        self._prefill_streams: List[torch.cuda.Stream] = []
-        self.last_timing: dict = {}
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self.min_shared_prefix = 256     # shorter common prefixes are not worth a separate pass
         # K / V / V^T of text prefixes seen before (prompt caching across requests): the reference's agents put the same
@@ -349,20 +210,16 @@ class Qwen2VLEngine(Generation):
         # at 7B shapes and 960 tokens.
         self._prefix_cache: "collections.OrderedDict[bytes, dict]" = collections.OrderedDict()
         self.prefix_cache_hits = 0
-        self.temperature, self.seed = 0.0, 0
         self._vis_rope_cache: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
         self._rope_cache: Dict[tuple, tuple] = {}
         self._pairs_cache: Dict[tuple, torch.Tensor] = {}
         self._vis_work_cache: Dict[tuple, torch.Tensor] = {}
-        self.prompt_len = 0
-        self._decoded = 0
-        self.decode_limit = 0
         self.last_first_logits: Optional[torch.Tensor] = None
         self.tokenizer = None
-        # what the decode stage needs to know of the model (decode_stage.py); it also sets up the pick stage (pick.py)
+        # what the decode stage needs to know of the model; it also sets up the pick stage (pick.py)
         self._init_decode_stage([DecodeLayer(lw, self.q8[i] if self.q8 else None, self.q4[i] if self.q4 else None, False, i, lw.qkv_b)
                                  for i, lw in enumerate(weights.llm)], weights.final_norm_w, weights.lm_head,
-                                getattr(self, "q8_lm_head", None), getattr(self, "q4_lm_head", None))
+                                self.q8_lm_head, self.q4_lm_head)
 
     # ------------------------------------------------------------------ vision tower
     def vision_forward(self, frames: Sequence[torch.Tensor], split_rows: bool = True) -> torch.Tensor:

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .decode_stage import DecodeLayer
+from .decode_stage import DecodeLayer, quantize_decode_weights
 from .generation import Generation
 from .request import Switches
 from .mllama_weights import MllamaConfig, MllamaDeviceWeights
@@ -98,19 +98,6 @@ class MllamaEngine(Generation):
     """One mllama replica on one GPU.  Not re-entrant: callers serialise through ``self.lock``."""
 
     @staticmethod
-    def check_decode_weights(cfg: MllamaConfig, fmt: str) -> None:
-        """Refuse an unknown decode precision, or one the model's shapes do not fit (needs no GPU): the rules of
-        Qwen2VLEngine.check_decode_weights."""
-        from .engine import Qwen2VLEngine
-        Qwen2VLEngine.check_decode_weights(cfg, fmt)
-
-    @staticmethod
-    def check_mxfp4_gemm_from(cfg: MllamaConfig, fmt: str, mxfp4_gemm_from) -> None:
-        """The rules of Qwen2VLEngine.check_mxfp4_gemm_from (an integer in 5..64, decode_weights='mxfp4' only, multiples of 64)."""
-        from .engine import Qwen2VLEngine
-        Qwen2VLEngine.check_mxfp4_gemm_from(cfg, fmt, mxfp4_gemm_from)
-
-    @staticmethod
     def check_cross_kv(cross_kv: str) -> None:
         if cross_kv not in ("bf16", "fp8"):
             raise ValueError("cross_kv must be 'bf16' or 'fp8'")
@@ -145,19 +132,18 @@ class MllamaEngine(Generation):
         self.max_ctx = _round_up(max_ctx, 64)
         self.lock = threading.Lock()
         dev, bf = self.device, torch.bfloat16
-        Hq, Hkv, D, H = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden
+        Hkv, D = cfg.kv_heads, cfg.head_dim
         self.self_idx = [i for i in range(cfg.layers) if i not in cfg.cross_layers]
         self.n_self, self.n_cross = len(self.self_idx), len(cfg.cross_layers)
         self.TP = cfg.max_tiles * cfg.tile_tokens
         self.Tk = _round_up(self.TP, 64)
-        self.nsplit = max(1, -(-self.max_ctx // hip.DECODE_KEYS_PER_SPLIT))
         self.xsplit = -(-self.Tk // hip.DECODE_KEYS_PER_SPLIT)
-        if not 1 <= max_batch <= 64:
-            raise ValueError("max_batch must be in 1..64")
-        Bm = self.max_batch = max_batch
-        # per-request ("slot") state; slot 0 doubles as the single-sequence engine
-        self.kcache_b = torch.zeros((Bm, self.n_self, Hkv, self.max_ctx, D), dtype=bf, device=dev)
-        self.vcache_b = torch.zeros((Bm, self.n_self, Hkv, self.max_ctx, D), dtype=bf, device=dev)
+        # what the decode stage works on (decode_stage.py): caches, counters, activation rows, workspaces, chain state, flags.
+        # The chained step covers the SELF-attention layers; the eight cross-attention layers keep their launches.
+        self._init_decode_state(max_batch, self.n_self, decode_weights, mxfp4_gemm_from, cross_splits=self.xsplit,
+                                fused_quantised=False)
+        Bm = max_batch
+        # per-request ("slot") cross-attention keys / values of the image; slot 0 doubles as the single-sequence engine
         self.xk_b = torch.zeros((Bm, self.n_cross, Hkv, self.Tk, D), dtype=bf, device=dev)
         self.xv_b = torch.zeros((Bm, self.n_cross, Hkv, self.Tk, D), dtype=bf, device=dev)
         self.cross_kv = cross_kv
@@ -169,109 +155,21 @@ class MllamaEngine(Generation):
         cos, sin = llama3_rope_tables(cfg, self.max_ctx)
         self.cos_t = torch.from_numpy(cos).to(dev)          # plain positions: one table for every sequence
         self.sin_t = torch.from_numpy(sin).to(dev)
-        self.step_b = torch.zeros(Bm, dtype=torch.int32, device=dev)
-        self.cur_b = torch.zeros(Bm, dtype=torch.int32, device=dev)
         self.nkeys_b = torch.zeros(Bm, dtype=torch.int32, device=dev)
-        self.tokens_b = torch.zeros((Bm, self.max_ctx), dtype=torch.int32, device=dev)
-        self.ws_val = torch.empty(max(256 * Bm, 2048), dtype=torch.float32, device=dev)
-        self.ws_idx = torch.empty(max(256 * Bm, 2048), dtype=torch.int32, device=dev)
-        self.logits_b = torch.empty((Bm, cfg.vocab), dtype=torch.float32, device=dev)
-        self.kcache, self.vcache, self.xk, self.xv = self.kcache_b[0], self.vcache_b[0], self.xk_b[0], self.xv_b[0]
-        self.step, self.cur_token, self.nkeys_m1 = self.step_b[0:1], self.cur_b[0:1], self.nkeys_b[0:1]
-        self.tokens, self.logits = self.tokens_b[0], self.logits_b[0]
-        nq = (Hq + 2 * Hkv) * D
-        self.d_x = torch.empty((1, H), dtype=bf, device=dev)
-        self.d_x2 = torch.empty((1, H), dtype=bf, device=dev)
-        self.d_qkv = torch.empty(nq, dtype=bf, device=dev)
-        self.d_attn = torch.empty(Hq * D, dtype=bf, device=dev)
-        self.d_act = torch.empty(cfg.intermediate, dtype=bf, device=dev)
-        ns = max(self.nsplit, self.xsplit)
-        self.part_o = torch.empty(Bm * Hq * ns * D, dtype=torch.float32, device=dev)
-        self.part_ml = torch.empty(Bm * Hq * ns * 2, dtype=torch.float32, device=dev)
-        if Bm > 1:      # batched-decode activations and the stream-K partial workspace
-            self.b_x = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_x2 = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_xn = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_xn2 = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_qkv = torch.empty((Bm, nq), dtype=bf, device=dev)
-            self.b_attn = torch.empty((Bm, Hq * D), dtype=bf, device=dev)
-            self.b_act = torch.empty((Bm, cfg.intermediate), dtype=bf, device=dev)
-        # r05 experiment, OFF by default (VIS_DECODE_FUSED=1): every batched-decode projection as ONE launch (vis_decode_proj_bf16:
-        # stream + split-K reduction + epilogue; Qwen2VLEngine.__init__ says why it is not the default).
-        # (bf16 weights only: a quantised engine's batched step is the stream-K or the rows step)
-        self.fused_proj = Bm > 1 and H % 128 == 0 and decode_weights == "bf16" and os.environ.get("VIS_DECODE_FUSED", "0") == "1"
-        # batched decode: the self-attention launch finalises the qkv projection's partial slabs itself (vis_decode_attn_parts,
-        # bit-identical to skinny_finalize + decode_attn); VIS_QKV_FOLD=0 keeps the two launches (A/B)
-        self.fold_qkv = os.environ.get("VIS_QKV_FOLD", "1") == "1"
-        if self.fused_proj:
-            self.b_xw = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_x2w = torch.empty((Bm, H), dtype=bf, device=dev)
-            self.b_ssq1 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
-            self.b_ssq2 = torch.zeros((H // hip.SSQ_UNIT, hip.SSQ_LD), dtype=torch.float32, device=dev)
-            lib = hip.load()
-            need = max(int(lib.vis_decode_proj_ws_bytes(Bm, n, k, 0)) for n, k in
-                       ((nq, H), (H, Hq * D), (2 * cfg.intermediate, H), (H, cfg.intermediate), (cfg.vocab, H)))
-            if need <= 0:
-                raise ValueError("vis_decode_proj_ws_bytes refused a projection shape of this model")
-            self.b_proj_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
-        if Bm > 1:      # split-K slabs: the whole step with VIS_DECODE_FUSED=0, the long-K down projection at many sequences otherwise
-            self.b_part = torch.empty(16 * hip.part_rows(Bm) * max(nq, H, 2 * cfg.intermediate), dtype=torch.float32,
-                                      device=dev)
-        # Single-sequence decode: the head of every SELF-attention layer (qkv projection -> rope / append / attention -> o
-        # projection) as ONE launch, the lm_head with the pick's first stage in its epilogue - the Inspector's chained step
-        # (csrc/decode_chain.hip, DecodeStage._decode_step; bit-identical to the launches it replaces); the eight
-        # cross-attention layers keep their launches.  It runs while the context stays within what the device holds resident
-        # for this head shape (11B: 768 projection + 32 merge workgroups + 8 attention items per 64 keys -> 1536 keys) and on
-        # the separate launches beyond.  VIS_DECODE_CHAIN=0 = A/B.
-        self.chain_sync: Optional[torch.Tensor] = None
-        self.chain_ctx_limit = 0
-        self._chain_launches = 0
-        if decode_weights == "bf16" and os.environ.get("VIS_DECODE_CHAIN", "1") != "0" \
-                and hip.decode_chain_supported(Hq, Hkv, D, H):
-            lim = hip.decode_chain_ctx_limit(Hq, Hkv, H)
-            if lim > 0:
-                self.chain_ws, self.chain_sync = hip.decode_chain_state(dev, Hq, Hkv, self.nsplit)
-                self.chain_ctx_limit = lim
-        self.slot_prompt_len = [0] * Bm
+        self.xk, self.xv, self.nkeys_m1 = self.xk_b[0], self.xv_b[0], self.nkeys_b[0:1]
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._graphs_b: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self._vis_plans: Dict[tuple, "hip.AttnPlan"] = {}
-        self.temperature, self.seed = 0.0, 0
-        self.prompt_len = 0
-        self._decoded = 0
         self.has_image = False
-        self.decode_limit = 0
         self.tokenizer = None
-        # what the decode stage needs to know of the model (decode_stage.py); it also sets up the pick stage.  Quantised decode
-        # weights as on the Qwen2-VL engine: every layer's four projections (a cross layer's qkv_w is its q projection) and the
-        # lm_head, quantised here once; the batched fp8 step carries its activations as e4m3 rows too.
-        self.decode_weights, self.fp8_batched, self.mxfp4_gemm_from = decode_weights, False, mxfp4_gemm_from
-        names = ("qkv_w", "o_w", "gateup_w", "down_w")
-        q8 = q4 = [None] * len(weights.layers)
-        q8_head = q4_head = None
-        if decode_weights == "fp8":
-            q8 = [{n: hip.quantize_fp8_rows(getattr(lw, n)) for n in names} for lw in weights.layers]
-            q8_head = hip.quantize_fp8_rows(weights.lm_head)
-        elif decode_weights == "mxfp4":
-            q4 = [{n: hip.quantize_mxfp4_rows(getattr(lw, n)) for n in names} for lw in weights.layers]
-            q4_head = hip.quantize_mxfp4_rows(weights.lm_head)
-        if decode_weights == "fp8" and Bm > 1 and H % 128 == 0:
-            self.fp8_batched = True
-            self.kpad = _round_up(cfg.intermediate, 128)       # fp8 MFMA needs K % 128 == 0: zero-pad down's K if necessary
-            self.b_xq = torch.zeros((Bm, H), dtype=torch.uint8, device=dev)
-            self.b_x2q = torch.zeros((Bm, H), dtype=torch.uint8, device=dev)
-            self.b_actq = torch.zeros((Bm, self.kpad), dtype=torch.uint8, device=dev)      # pad columns stay 0
-            self.b_sx = torch.zeros((3, Bm), dtype=torch.float32, device=dev)
-            if self.kpad != cfg.intermediate:
-                for q in q8:
-                    wq, sc = q["down_w"]
-                    pad = torch.zeros((wq.shape[0], self.kpad), dtype=torch.uint8, device=wq.device)
-                    pad[:, :cfg.intermediate] = wq
-                    q["down_w_pad"] = (pad, sc)
+        # what the decode stage needs to know of the model; it also sets up the pick stage.  Quantised decode weights as on
+        # the Qwen2-VL engine: every layer's four projections (a cross layer's qkv_w is its q projection) and the lm_head.
+        q8, q4, q8_head, q4_head = quantize_decode_weights(weights.layers, weights.lm_head, decode_weights == "fp8",
+                                                           decode_weights == "mxfp4", pad_down=self.kpad is not None)
         si = ci = 0
         layers = []
         for i, lw in enumerate(weights.layers):
-            layers.append(DecodeLayer(lw, q8[i], q4[i], lw.cross, ci if lw.cross else si, None))
+            layers.append(DecodeLayer(lw, q8[i] if q8 else None, q4[i] if q4 else None, lw.cross, ci if lw.cross else si, None))
             ci, si = ci + lw.cross, si + (not lw.cross)
         self._init_decode_stage(layers, weights.norm_w, weights.lm_head, q8_head=q8_head, q4_head=q4_head)
 
@@ -697,7 +595,7 @@ class MllamaEngine(Generation):
         # attention grids - the 6432-row tower is 1-1.5 rounds of the chip per projection - is filled by the other's.
         n_streams = max(1, min(n_req, int(os.environ.get("VIS_PREFILL_STREAMS", "2"))))
         cur = torch.cuda.current_stream(self.device)
-        if n_streams > 1 and len(getattr(self, "_prefill_streams", [])) < n_streams:
+        if n_streams > 1 and len(self._prefill_streams) < n_streams:
             self._prefill_streams = [torch.cuda.Stream(device=self.device) for _ in range(n_streams)]
         vb = max(1, int(os.environ.get("VIS_VIT_BATCH", "4"))) if n_streams > 1 else 1
 
