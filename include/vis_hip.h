@@ -729,6 +729,52 @@ int vis_spec_draft_pred(const void* prompt_ids, int ld_prompt, const void* promp
                         const void* pred_ids, int ld_pred, const void* pred_len, void* state, void* draft, void* n_draft,
                         vis_stream_t stream);
 
+/* ---- The speculative step of a BATCH (csrc/spec.hip, spec_batch.py): `batch` in-flight sequences of `rows` rows each run
+ * as batch * rows <= 64 rows of the stream-K projection; packed row b * rows + r is row r of sequence b.
+ *
+ * vis_decode_attn_streams: host only, no launch - 1 when vis_decode_attn would take the streaming form for `batch` sequences
+ * of Hkv kv heads (Hkv * batch >= 128, or VIS_DECODE_ATTN_STREAM says so), else 0.
+ *
+ * vis_decode_attn_draft_batch: vis_decode_attn_draft for `batch` sequences.  Row (b, r) of qkv [batch * rows][qkv_ld] sits at
+ * position step_ptr[b] + r of sequence b: rope row, cache row and keys [0, step_ptr[b] + r] come from sequence b's tables
+ * (cos_t / sin_t + b * tab_bs) and caches (+ b * cache_bs, element strides as in vis_decode_attn); the rows of one sequence
+ * are causal among themselves.  Workspaces part_o [batch * rows][Hq][nsplit][128] / part_ml [..][2] f32, out
+ * [batch * rows][Hq*128].  Three launches (append every row of every sequence, attend, combine) with the split plan, key
+ * order and combine of vis_decode_attn's split form: output row (b, r) and every cache are bit-identical to `rows` successive
+ * vis_decode_attn(batch) launches at advancing steps.  A row at a position >= cache_tokens reads and writes nothing;
+ * step_ptr is not changed.  Split form only: where vis_decode_attn_streams(Hkv, batch) holds - the plain step of these
+ * sequences would stream - VIS_ERR_UNSUPPORTED and nothing is launched.  VIS_ERR_ARG: vis_decode_attn_draft's checks, batch
+ * outside 1..64, batch * rows > 64, cache_bs < Hkv * cache_tokens * 128 or no multiple of 8, tab_bs < 0. */
+int vis_decode_attn_streams(int Hkv, int batch);
+int vis_decode_attn_draft_batch(const void* qkv, const void* cos_t, const void* sin_t, void* k_cache, void* v_cache,
+                                const void* step_ptr, void* part_o, void* part_ml, void* out, int Hq, int Hkv, int HD,
+                                int cache_tokens, int nsplit, float scale, int rows, int batch, long long qkv_ld,
+                                long long cache_bs, long long tab_bs, vis_stream_t stream);
+
+/* vis_spec_gather_batch: the input rows of the step - out[b * rows + r][0 .. D) = table[id][0 .. D) (bf16, D % 8 == 0) with
+ * id = cur_token[b] for r = 0 and draft[b][r - 1] behind it, clamped into [0, n_table) (vis_gather_rows' copy).  draft is
+ * [batch][3].  One launch. */
+int vis_spec_gather_batch(const void* table, const void* cur_token, const void* draft, void* out, int rows, int batch, int D,
+                          int n_table, vis_stream_t stream);
+
+/* vis_spec_accept_batch: vis_spec_accept (params null) or vis_spec_accept_sampled per sequence.  logits
+ * [batch * rows][ld_logits] f32, draft [batch][3], n_draft / limit / cur_token / step_ptr [batch], tokens
+ * [batch][max_tokens], counters [batch][3], params [batch][2] ({float inv_temp, uint32 seed} of sequence b) or null, ws_val
+ * / ws_idx 256 entries per row.  Row (b, r)'s pick is the greedy pick, or the Gumbel-max pick at hash counter
+ * step_ptr[b] + r with sequence b's inverse temperature and seed; every output of sequence b is bit for bit what the
+ * single-sequence entry writes given b's rows and state alone.  Argument checks: vis_spec_accept's, batch outside 1..64,
+ * batch * rows > 64; VIS_ERR_ARG launches nothing.  Two launches. */
+int vis_spec_accept_batch(const void* logits, int V, int ld_logits, int rows, int batch, const void* draft,
+                          const void* n_draft, const void* limit, void* ws_val, void* ws_idx, void* tokens, int max_tokens,
+                          void* cur_token, void* step_ptr, void* counters, const void* params, vis_stream_t stream);
+
+/* vis_spec_draft_batch: vis_spec_draft per sequence, one workgroup each: prompt_ids [batch][ld_prompt], prompt_len /
+ * gen_start / step_ptr / n_draft [batch], tokens [batch][max_tokens], draft [batch][3].  spec.propose() on sequence b's
+ * own history is the definition.  One launch. */
+int vis_spec_draft_batch(const void* prompt_ids, int ld_prompt, const void* prompt_len, const void* tokens, int max_tokens,
+                         const void* gen_start, const void* step_ptr, int k, int lookup_max, int lookup_min, int vocab,
+                         int batch, void* draft, void* n_draft, vis_stream_t stream);
+
 /* The speculative step under a JSON Schema (csrc/spec_schema.hip; spec.py "grammar").
  * vis_schema_mask_rows: the allow rows [rows][ld_allow] (rows 1..4) of ONE sequence's step.  Row 0 is vis_schema_mask's row
  * at *step_ptr (the same fold of tokens[position .. *step_ptr), the same "no token allowed -> EOS ids"); row r >= 1 is the

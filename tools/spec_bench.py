@@ -15,6 +15,12 @@
                                                    # and the sampled speculative step at T = 0.1; the break-even of the last is
                                                    # t_R / t_1 - 1 against the plain sampled step; every time with the spread
                                                    # (min .. max) of its repeats; default out: profiles/spec_sampled.json
+    python tools/spec_bench.py batch [out.json] [formats]     # the speculative step of a BATCH (spec_batch.py): synthetic:7b, per
+                                                   # format (bf16, fp8; one child each), B = 2, 4, 8, 16 sequences: the plain
+                                                   # batched step, then the speculative step at R = 1..4 rows per sequence
+                                                   # (B * R <= 64) in the same process; t_R / t_1 - 1 = the drafts a sequence
+                                                   # must get accepted per step, on average, to break even; every time
+                                                   # [median, min, max] ms; default out: profiles/spec_batch.json
 
 Every measurement runs in a child process of its own under a time limit (step: one child per format); this process never
 opens the GPU.  A child that fails or runs out of time ends the run: nothing more is started on the GPU.  Times are device
@@ -28,7 +34,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-LIMITS = {"kernel": 240, "step": 420}          # seconds per child
+LIMITS = {"kernel": 240, "step": 420, "batch": 540}          # seconds per child
 HQ, HKV, HD, CTX, T, V = 28, 4, 128, 2304, 2560, 152064
 FORMATS = ("bf16", "fp8", "mxfp4")
 
@@ -181,9 +187,69 @@ def sampled_step_times(eng, fmt, ids, n, timed) -> list:
     return rows
 
 
+def batch_times(fmt: str) -> list:
+    """One process: per batch size the plain batched step (captured, 5 x 16 replays), then the speculative step of R rows per
+    sequence.  The speculative steps run with every sequence's limit at -1: the accept launch moves no state, so every replay
+    does the same work at the same positions (context ~390 keys), drafts of the prompt lookup in the rows."""
+    import numpy as np
+    import torch
+    from vision_inspection_system_amd import spec_batch, weights as W
+    from vision_inspection_system_amd.config import Qwen2VLConfig
+    from vision_inspection_system_amd.engine import Qwen2VLEngine
+    from vision_inspection_system_amd.spec import SpecConfig
+    dev = torch.device("cuda:0")
+    cfg = Qwen2VLConfig.qwen2_vl_7b()
+    eng = Qwen2VLEngine(cfg, W.random_device_weights(cfg, dev, 0), dev, max_ctx=1024, max_batch=64, decode_weights=fmt)
+    phrase = np.random.default_rng(0).integers(1000, 100000, 24).tolist()
+    n, reps = 16, 5
+
+    def timed(g):
+        ts = []
+        for _ in range(reps):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(n):
+                g.replay()
+            e.record()
+            torch.cuda.synchronize()
+            ts.append(s.elapsed_time(e) / n)
+        return [round(float(v), 4) for v in (np.median(ts), min(ts), max(ts))]
+
+    rows = []
+    for B in (2, 4, 8, 16):
+        reqs = [([9 + b] + phrase * 16, []) for b in range(B)]      # 385 ids each that repeat themselves every 24
+        eng.prefill_many(reqs, max_new_tokens=600)
+        assert eng._batched_step_kind(B) == "streamk"
+        g = eng._batch_graph(B)
+        for _ in range(4):
+            g.replay()
+        t1 = timed(g)
+        rows.append({"format": fmt, "B": B, "R": 1, "step": "plain batched (stream-K)", "step_ms": t1})
+        print(json.dumps(rows[-1]), flush=True)
+        starts = [eng.slot_prompt_len[b] - 1 for b in range(B)]
+        for R in (1, 2, 3, 4):
+            if B * R > 64:
+                continue
+            sc = SpecConfig(R - 1, 4, 2)
+            spec_batch.buffers(eng).begin([eng._slot_ids[b] for b in range(B)], starts, [-1] * B, 0.0, [0] * B)
+            if R > 1:
+                spec_batch.draft(eng, sc, B)
+            gr = spec_batch.graph(eng, sc, B)
+            for _ in range(4):
+                gr.replay()
+            tr = timed(gr)
+            rows.append({"format": fmt, "B": B, "R": R, "rows": B * R, "step": "speculative batch", "step_ms": tr,
+                         "t_R_over_t_1": round(tr[0] / t1[0], 4), "break_even_accepted_per_step": round(tr[0] / t1[0] - 1, 4)})
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def _child(what: str, arg: str) -> None:
     from vision_inspection_system_amd import hip
     hip.load()
+    if what == "batch":
+        print("RESULT " + json.dumps(batch_times(arg)), flush=True)
+        return
     if what.endswith("_sampled"):
         rows = kernel_times(True) if what == "kernel_sampled" else step_times(arg, True)
     else:
@@ -208,10 +274,19 @@ if __name__ == "__main__":
         _child(sys.argv[2], sys.argv[3])
         sys.exit(0)
     what = sys.argv[1] if len(sys.argv) > 1 else "kernel"
-    if what not in ("kernel", "step", "all", "sampled"):
+    if what not in ("kernel", "step", "all", "sampled", "batch"):
         raise SystemExit(__doc__)
-    out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "spec_sampled.json" if what == "sampled" else "speculative.json")
+    default = {"sampled": "spec_sampled.json", "batch": "spec_batch.json"}.get(what, "speculative.json")
+    out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", default)
     result = {}
+    if what == "batch":
+        fmts = sys.argv[3].split(",") if len(sys.argv) > 3 else ["bf16", "fp8"]
+        if any(f not in ("bf16", "fp8") for f in fmts):
+            raise SystemExit(__doc__)
+        result["times"] = "[median, min, max] of 5 repeats of 16 replayed steps (ms); synthetic:7b, context ~390 keys per sequence"
+        result["acceptance_on_a_real_checkpoint"] = "not measured"
+        result["batch"] = [row for fmt in fmts for row in _run_child("batch", fmt)]
+        result["formats_not_measured"] = [f for f in ("bf16", "fp8") if f not in fmts]
     if what == "sampled":
         fmts = [f for f in (sys.argv[3].split(",") if len(sys.argv) > 3 else FORMATS) if f != "-"]
         if any(f not in FORMATS for f in fmts):

@@ -303,10 +303,11 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
     import torch
     from .engine import Qwen2VLEngine
     from .tokenizer import ByteTokenizer, HFTokenizer
-    from . import weights as W
+    from . import spec_batch, weights as W
+    sbc = spec_batch.from_env()      # VIS_SPECULATIVE_BATCH: a Qwen2-VL engine built with it is another engine, under a key of its own
     if device is None:
         with _ENGINES_LOCK:      # a model that is already loaded / registered on exactly one device: no device query needed
-            hits = [k for k in _ENGINES if k[0] == model_id]
+            hits = [k for k in _ENGINES if k[0] == model_id and sbc is None]
             if any(len(k) > 2 for k in hits):      # mllama entries carry their settings: the entry of the current ones
                 aud = _auditor_key()
                 hits = [k for k in hits if len(k) == 2 or k[2:] == aud]
@@ -314,8 +315,12 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
                 return _ENGINES[hits[0]]
         device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cuda:0"
     key = (model_id, str(device))
+    skey = () if sbc is None else ("batch_speculative",) + key + tuple(sbc)
     with _ENGINES_LOCK:
-        if key in _ENGINES:
+        if skey in _ENGINES:
+            return _ENGINES[skey]
+        # (with the setting on, the plain entry serves only when its engine was built with the same setting by the caller)
+        if key in _ENGINES and (sbc is None or getattr(_ENGINES[key].engine, "batch_speculative", None) == sbc):
             return _ENGINES[key]
         # an mllama engine is cached under its quantisation settings too (VIS_AUDITOR_*, fixed per engine); the variables are
         # read only where an mllama model is loaded or already cached, so a malformed one cannot fail another model's load
@@ -367,8 +372,9 @@ def get_model(model_id: str, device: Optional[str] = None) -> LoadedModel:
         lm = LoadedModel(Qwen2VLEngine(cfg, w, device, max_ctx=max_ctx, max_batch=max_batch,
                                        decode_weights=os.environ.get("VIS_DECODE_WEIGHTS", "bf16"),
                                        prefill_dtype=os.environ.get("VIS_PREFILL_DTYPE", "bf16"),
-                                       mxfp4_gemm_from=_env_int_or_none("VIS_MXFP4_GEMM_FROM")), tok, cfg, model_id)
-        _ENGINES[key] = lm
+                                       mxfp4_gemm_from=_env_int_or_none("VIS_MXFP4_GEMM_FROM"),
+                                       **({} if sbc is None else {"batch_speculative": sbc})), tok, cfg, model_id)
+        _ENGINES[skey or key] = lm
         return lm
 
 
@@ -677,7 +683,7 @@ def register_model(model_id: str, device: str, lm: LoadedModel) -> None:
 
 def unregister_model(model_id: str, device: str) -> None:
     with _ENGINES_LOCK:
-        for k in [k for k in _ENGINES if k[:2] == (model_id, str(device))]:
+        for k in [k for k in _ENGINES if (model_id, str(device)) in (k[:2], k[1:3])]:
             _ENGINES.pop(k)
 
 

@@ -80,6 +80,11 @@ class DecodeStage(PickStage):
     An engine supplies ``_ensure_graph(chained=)`` with its own graph key (see ``_captured_step``) and checks its own bounds
     in ``decode()`` before ``_decode_ordered``."""
 
+    # Speculative decoding of a batch (spec_batch.py), an engine setting: the SpecConfig an engine was built with
+    # (Qwen2VLEngine(batch_speculative=)), stored on the instance only when given; the step's buffers and graphs, on first use.
+    batch_speculative: Optional["spec.SpecConfig"] = None
+    _spec_batch = None
+
     @staticmethod
     def check_decode_weights(cfg, decode_weights: str) -> None:
         """Refuse an unknown decode precision, or one the model's shapes do not fit (needs no GPU)."""
@@ -559,6 +564,16 @@ class DecodeStage(PickStage):
         """Every projection = gemm_decode (weights streamed once for all B sequences, split-K f32 partials) +
         skinny_finalize (row-wise: sum, bias/residual/SwiGLU, and the RMSNorm of the NEXT projection); self-attention and
         cross-attention take the sequence index on the grid."""
+        kind = self._batched_step_kind(B)
+        if kind == "rows":
+            self._decode_step_rows(B)
+        elif kind == "fused":
+            self._decode_step_fused(B)
+        else:
+            self._decode_step_streamk(B)
+
+    def _batched_step_kind(self, B: int) -> str:
+        """Which step B in-flight sequences take: "rows" (the multi-row GEMV), "fused" or "streamk"."""
         # VIS_ROWS_GEMV=<n> (default 0 = off): batches of 2..n (<= 4) sequences decode on the multi-row GEMV instead.  Measured
         # at exact 7B shapes (tools/probes/rows_ab.sh): 2 sequences 3.66 -> 3.20 ms per step (bf16), 2.83 -> 2.65 (e4m3
         # weights); at 3 and 4 the four-row kernel LOSES to the stream-K projection (4.2-4.3 vs 3.7-3.8 ms; fp8 3.8-4.0 vs
@@ -571,16 +586,11 @@ class DecodeStage(PickStage):
         if self.decode_weights == "mxfp4":
             # the multi-row GEMV at every batch size, unless mxfp4_gemm_from hands the larger ones to the MFMA projection
             # (the other arithmetic family, see Qwen2VLEngine.__init__)
-            if self.mxfp4_gemm_from is None or B < self.mxfp4_gemm_from:
-                return self._decode_step_rows(B)
-            return self._decode_step_streamk(B)
+            return "rows" if self.mxfp4_gemm_from is None or B < self.mxfp4_gemm_from else "streamk"
         rows_max = int(os.environ.get("VIS_ROWS_GEMV", "0")) if self.dec_n_self == len(self.dec_layers) else 0
         if 2 <= B <= min(rows_max, 4) and max(self.cfg.intermediate, self.cfg.hidden) * 2 * (2 if B <= 2 else 4) <= 152 * 1024:
-            return self._decode_step_rows(B)
-        if self.fused_proj:
-            self._decode_step_fused(B)
-        else:
-            self._decode_step_streamk(B)
+            return "rows"
+        return "fused" if self.fused_proj else "streamk"
 
     def _decode_step_streamk(self, B: int) -> None:
         """The stream-K batched step.  The first half of a projection writes partial slabs: hip.decode_gemm on the bf16

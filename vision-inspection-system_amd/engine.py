@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, spec_batch
 from .decode_stage import DecodeLayer, quantize_decode_weights
 from .generation import Generation
 from .request import Switches
@@ -144,7 +144,7 @@ class Qwen2VLEngine(Generation):
 
     def __init__(self, cfg: Qwen2VLConfig, weights: DeviceWeights, device, max_ctx: int = 4096,
                  decode_splits: int = 0, max_batch: int = 1, decode_weights: str = "bf16",
-                 prefill_dtype: str = "bf16", mxfp4_gemm_from: Optional[int] = None):
+                 prefill_dtype: str = "bf16", mxfp4_gemm_from: Optional[int] = None, batch_speculative=None):
         """decode_weights="fp8" (BASELINE configs[4] slice, also VIS_DECODE_WEIGHTS=fp8): the single-sequence decode
         step streams OCP-e4m3 copies of the LLM projections and the lm_head (per-output-row f32 scales,
         hip.quantize_fp8_rows at load time) through vis_gemv_fp8w; prefill and the batched decode keep bf16.
@@ -157,8 +157,13 @@ class Qwen2VLEngine(Generation):
         bf16 batched step's launches with every projection on vis_gemm_decode_mxfp4, which streams the FP4 weights ONCE
         for up to 64 sequences.  That makes TWO arithmetic families: the GEMV summation order below n, the MFMA stream-K
         order from n on.  Each is bit-invariant inside itself to batch size and row position; a request whose batch
-        crosses n may differ at near-ties (the trade VIS_ROWS_GEMV makes), which is why it is off by default."""
+        crosses n may differ at near-ties (the trade VIS_ROWS_GEMV makes), which is why it is off by default.
+        batch_speculative=k | {..} (VIS_SPECULATIVE_BATCH, default None = off; spec_batch.py): generate_batch drafts up to k
+        tokens per sequence by prompt lookup and runs B * (k + 1) rows through the stream-K step where it can
+        (spec_batch.eligible) - the replies are the plain replies; a batch that cannot runs the plain step, silently."""
         cfg.validate_for_kernels()
+        if batch_speculative is not None:      # kept off the instance otherwise: the class default None
+            self.batch_speculative = spec_batch.check_setting(batch_speculative)
         self.check_decode_weights(cfg, decode_weights)
         self.check_mxfp4_gemm_from(cfg, decode_weights, mxfp4_gemm_from)
         if prefill_dtype not in ("bf16", "fp8"):

@@ -10,7 +10,7 @@ from typing import List, Sequence
 
 import torch
 
-from . import hip, spec
+from . import hip, spec, spec_batch
 from .ban import check_ban
 from .decode_stage import DecodeStage
 from .fork import check_n_list
@@ -267,7 +267,11 @@ class Generation(DecodeStage):
         # runs to the limit of the longest one
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
-        slots, errors = self.prefill_many(requests, temperature=temperature, seed=seed, max_new_tokens=max_new_tokens,
+        # an engine built with batch_speculative (spec_batch.py): its configuration where this batch may take the speculative
+        # step, else None; the prompt passes then prepare rope rows for the R - 1 positions a step's rows reach past the reply
+        sb = spec_batch.plan(self, n_req, ns, temperature)
+        slots, errors = self.prefill_many(requests, temperature=temperature, seed=seed,
+                                          max_new_tokens=max_new_tokens + (sb.rows - 1 if sb else 0),
                                           seeds=seeds, penalties=penalties, shaping=shaping,
                                           **({} if ban is None else {"ban": ban.rows}))
         ev[1].record()
@@ -289,9 +293,14 @@ class Generation(DecodeStage):
             t = self.tokens_b[:B].cpu()
             return [t[b, starts[b]:starts[b] + n].tolist() for b in range(B)]
 
-        done = 1
-        g = self._batch_graph(B) if use_graph else None
-        while done < max_new_tokens and not self._stream_cancelled():
+        done, spec_t = 1, {}
+        spec_on = sb is not None and len(live) == n_req      # every request live: the plain replies in fewer steps
+        if spec_on:
+            outs, steps, spec_t = spec_batch.run(self, sb, B, starts, max_new_tokens, eos, ignore_eos, use_graph, check_every,
+                                                 temperature)
+            done = steps + 1
+        g = self._batch_graph(B) if use_graph and not spec_on else None
+        while not spec_on and done < max_new_tokens and not self._stream_cancelled():
             if self.stop_on:
                 if self._stop_done(range(B)):
                     break
@@ -305,9 +314,12 @@ class Generation(DecodeStage):
                     self._decode_step_batched(B)
             done += n
         ev[2].record()
-        outs = collect(done)
+        if spec_on:      # its last poll has the tokens; the event has to complete
+            torch.cuda.current_stream().synchronize()
+        else:
+            outs = collect(done)
         # host waiting for the lazy requests' decodes is inside prefill_ms here: it is the time until all prompts are in
         self.last_timing = {"prompt_tokens": longest, "prefill_ms": ev[0].elapsed_time(ev[1]),
-                            "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B}
+                            "decode_ms": ev[1].elapsed_time(ev[2]), "decode_steps": done - 1, "sequences": B, **spec_t}
         return self._gather_choices(choice_slots, errors, outs, starts, eos, ignore_eos, self.keep_eos, ns is not None,
                                     self._mask_error)

@@ -85,6 +85,11 @@ _SIGS = {
     "vis_spec_draft_schema": "pp" + "i" + "pppp" + "i" + "pppp" + "ii" + "pp" + "i" + "pp" + "p",
     "vis_spec_draft": "pi" + "pp" + "i" + "pp" + "iiii" + "pp" + "p",
     "vis_spec_draft_pred": "pi" + "pp" + "i" + "pp" + "iiii" + "pi" + "pp" + "pp" + "p",
+    "vis_decode_attn_streams": "ii",
+    "vis_decode_attn_draft_batch": "ppppppppp" + "iiiii" + "f" + "ii" + "lll" + "p",
+    "vis_spec_gather_batch": "pppp" + "iiii" + "p",
+    "vis_spec_accept_batch": "p" + "iiii" + "pppppp" + "i" + "ppp" + "p" + "p",
+    "vis_spec_draft_batch": "pi" + "pp" + "i" + "pp" + "iiiii" + "pp" + "p",
     "vis_stop_scan": "pp" + "i" + "pppp" + "i" + "pppp" + "iiii" + "p",
     "vis_stream_publish": "pp" + "i" + "pp" + "i" + "pp" + "i" + "pp" + "i" + "p",
     "vis_host_coherent_alloc": "ppl",
@@ -1645,6 +1650,111 @@ def spec_draft(prompt_ids: torch.Tensor, prompt_len: torch.Tensor, tokens: torch
                                _ptr(gen_start), _ptr(step), int(k), int(lookup_max), int(lookup_min), int(vocab), _ptr(draft),
                                _ptr(n_draft), _stream())
     _check(rc, "vis_spec_draft")
+
+
+class AttnStreams(HipLibraryError):
+    """vis_decode_attn_draft_batch returned VIS_ERR_UNSUPPORTED: the plain step of that many sequences takes the streaming
+    attention form, which has no draft form.  Nothing was launched."""
+
+
+def decode_attn_streams(n_kv: int, batch: int) -> bool:
+    """Whether decode_attn takes the streaming form for ``batch`` sequences of ``n_kv`` kv heads (host only, no launch)."""
+    return bool(load().vis_decode_attn_streams(int(n_kv), int(batch)))
+
+
+def decode_attn_draft_batch(qkv: torch.Tensor, cos_t: torch.Tensor, sin_t: torch.Tensor, k_cache: torch.Tensor,
+                            v_cache: torch.Tensor, step: torch.Tensor, part_o: torch.Tensor, part_ml: torch.Tensor,
+                            out: torch.Tensor, n_q: int, n_kv: int, head_dim: int, nsplit: int, scale: float) -> torch.Tensor:
+    """decode_attn_draft for B sequences of R rows each (vis_decode_attn_draft_batch): qkv [B * R, nq*D], row b * R + r at
+    position step[b] + r of sequence b; caches [B, Hkv, T, D], tables [B, T, D], step int32 [B] (left as it is), workspaces
+    for B * R rows, out [B * R, Hq*D].  Row (b, r) and the caches are bit-identical to R successive decode_attn calls on the
+    batch at advancing steps.  AttnStreams where decode_attn_streams(n_kv, B) holds."""
+    _bf16(qkv, "qkv"); _bf16(k_cache, "k_cache"); _bf16(v_cache, "v_cache"); _bf16(out, "out")
+    if step.dtype != torch.int32 or not step.is_contiguous() or cos_t.dtype != torch.float32 or sin_t.dtype != torch.float32:
+        raise HipLibraryError("decode_attn_draft_batch: step int32 / cos,sin f32 required")
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape or v_cache.stride() != k_cache.stride():
+        raise HipLibraryError("decode_attn_draft_batch: batched caches [B, Hkv, T, D] with one stride required")
+    B, kc = k_cache.shape[0], k_cache[0]
+    if kc.shape[0] != n_kv or kc.shape[2] != head_dim or kc.stride(2) != 1 or kc.stride(1) != head_dim \
+            or kc.stride(0) != kc.shape[1] * head_dim:
+        raise HipLibraryError("decode_attn_draft_batch: bad cache shape")
+    T = kc.shape[1]
+    if cos_t.dim() != 3 or cos_t.shape != (B, T, head_dim) or sin_t.shape != cos_t.shape or not cos_t[0].is_contiguous() \
+            or not sin_t[0].is_contiguous() or cos_t.stride(0) != sin_t.stride(0):
+        raise HipLibraryError("decode_attn_draft_batch: cos/sin tables must be [B, cache_tokens, head_dim] with one batch stride")
+    nq = (n_q + 2 * n_kv) * head_dim
+    if qkv.dim() != 2 or qkv.shape[0] % B or not 1 <= qkv.shape[0] // B <= SPEC_MAX_ROWS or qkv.shape[1] != nq \
+            or qkv.stride(1) != 1 or step.numel() != B:
+        raise HipLibraryError("decode_attn_draft_batch: qkv must be [B * (1..4), (Hq + 2 Hkv) * D], step [B]")
+    n = qkv.shape[0]
+    if part_o.dtype != torch.float32 or part_ml.dtype != torch.float32 or part_o.numel() < n * n_q * nsplit * head_dim \
+            or part_ml.numel() < n * n_q * nsplit * 2 or out.shape != (n, n_q * head_dim) or not out.is_contiguous():
+        raise HipLibraryError("decode_attn_draft_batch: workspace/output too small")
+    rc = load().vis_decode_attn_draft_batch(_ptr(qkv), _ptr(cos_t), _ptr(sin_t), _ptr(k_cache), _ptr(v_cache), _ptr(step),
+                                            _ptr(part_o), _ptr(part_ml), _ptr(out), n_q, n_kv, head_dim, T, nsplit, scale,
+                                            n // B, B, qkv.stride(0), k_cache.stride(0), cos_t.stride(0), _stream())
+    if rc == 3:
+        raise AttnStreams(f"vis_decode_attn_draft_batch: {B} sequences of {n_kv} kv heads take the streaming attention form")
+    _check(rc, "vis_decode_attn_draft_batch")
+    return out
+
+
+def spec_gather_batch(table: torch.Tensor, cur_token: torch.Tensor, draft: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """The input rows of a batched speculative step (vis_spec_gather_batch): out [B * R, D] row b * R + r = table[cur_token[b]]
+    for r = 0, table[draft[b, r - 1]] behind it; cur_token int32 [B], draft int32 [B, 3]."""
+    _bf16(table, "spec_gather_batch table"); _bf16(out, "spec_gather_batch out")
+    B = cur_token.numel()
+    if cur_token.dtype != torch.int32 or draft.dtype != torch.int32 or draft.shape != (B, SPEC_MAX_ROWS - 1) \
+            or not (table.is_contiguous() and out.is_contiguous() and cur_token.is_contiguous() and draft.is_contiguous()):
+        raise HipLibraryError("spec_gather_batch: contiguous int32 cur_token [B] / draft [B, 3] and bf16 rows required")
+    if out.dim() != 2 or out.shape[0] % B or not 1 <= out.shape[0] // B <= SPEC_MAX_ROWS or out.shape[1] != table.shape[1]:
+        raise HipLibraryError("spec_gather_batch: out must be [B * (1..4), D]")
+    rc = load().vis_spec_gather_batch(_ptr(table), _ptr(cur_token), _ptr(draft), _ptr(out), out.shape[0] // B, B,
+                                      table.shape[1], table.shape[0], _stream())
+    _check(rc, "vis_spec_gather_batch")
+    return out
+
+
+def spec_accept_batch(logits: torch.Tensor, draft: torch.Tensor, n_draft: torch.Tensor, limit: torch.Tensor,
+                      ws_val: torch.Tensor, ws_idx: torch.Tensor, tokens: torch.Tensor, cur_token: torch.Tensor,
+                      step: torch.Tensor, counters: torch.Tensor, params: Optional[torch.Tensor] = None) -> None:
+    """spec_accept (``params`` None) / spec_accept_sampled per sequence (vis_spec_accept_batch): logits f32 [B * R, V], draft
+    int32 [B, 3], n_draft / limit / cur_token / step int32 [B], tokens int32 [B, T], counters int32 [B, 3], params int32
+    [B, 2] (the bits of sequence b's f32 inv_temp, its uint32 seed), ws_val f32 / ws_idx int32 of >= 256 * B * R entries."""
+    ints = (draft, n_draft, limit, ws_idx, tokens, cur_token, step, counters) + (() if params is None else (params,))
+    if logits.dtype != torch.float32 or ws_val.dtype != torch.float32 or any(t.dtype != torch.int32 for t in ints):
+        raise HipLibraryError("spec_accept_batch: f32 logits, ws_val / int32 everything else required")
+    B = step.numel()
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] % B or not 1 <= logits.shape[0] // B <= SPEC_MAX_ROWS:
+        raise HipLibraryError("spec_accept_batch: logits must be [B * (1..4), V] with unit column stride")
+    n, V = logits.shape
+    if draft.shape != (B, SPEC_MAX_ROWS - 1) or any(t.numel() != B for t in (n_draft, limit, cur_token)) \
+            or tokens.dim() != 2 or tokens.shape[0] != B or counters.shape != (B, 3) \
+            or (params is not None and params.shape != (B, 2)) or ws_val.numel() < 256 * n or ws_idx.numel() < 256 * n \
+            or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("spec_accept_batch: bad parameter shapes")
+    rc = load().vis_spec_accept_batch(_ptr(logits), V, logits.stride(0), n // B, B, _ptr(draft), _ptr(n_draft), _ptr(limit),
+                                      _ptr(ws_val), _ptr(ws_idx), _ptr(tokens), tokens.shape[1], _ptr(cur_token), _ptr(step),
+                                      _ptr(counters), _ptr(params), _stream())
+    _check(rc, "vis_spec_accept_batch")
+
+
+def spec_draft_batch(prompt_ids: torch.Tensor, prompt_len: torch.Tensor, tokens: torch.Tensor, gen_start: torch.Tensor,
+                     step: torch.Tensor, k: int, lookup_max: int, lookup_min: int, vocab: int, draft: torch.Tensor,
+                     n_draft: torch.Tensor) -> None:
+    """spec_draft per sequence (vis_spec_draft_batch): prompt_ids int32 [B, P], tokens int32 [B, T], prompt_len / gen_start /
+    step / n_draft int32 [B], draft int32 [B, 3].  Sequence b's draft equals spec.propose() on its own history."""
+    ints = (prompt_ids, prompt_len, tokens, gen_start, step, draft, n_draft)
+    if any(t.dtype != torch.int32 for t in ints) or not all(t.is_contiguous() for t in ints):
+        raise HipLibraryError("spec_draft_batch: contiguous int32 tensors required")
+    B = step.numel()
+    if any(t.numel() != B for t in (prompt_len, gen_start, n_draft)) or prompt_ids.dim() != 2 or prompt_ids.shape[0] != B \
+            or prompt_ids.shape[1] == 0 or tokens.dim() != 2 or tokens.shape[0] != B or draft.shape != (B, SPEC_MAX_ROWS - 1):
+        raise HipLibraryError("spec_draft_batch: bad parameter shapes")
+    rc = load().vis_spec_draft_batch(_ptr(prompt_ids), prompt_ids.shape[1], _ptr(prompt_len), _ptr(tokens), tokens.shape[1],
+                                     _ptr(gen_start), _ptr(step), int(k), int(lookup_max), int(lookup_min), int(vocab), B,
+                                     _ptr(draft), _ptr(n_draft), _stream())
+    _check(rc, "vis_spec_draft_batch")
 
 
 def spec_accept_masked(logits: torch.Tensor, draft: torch.Tensor, n_draft: torch.Tensor, limit: torch.Tensor,

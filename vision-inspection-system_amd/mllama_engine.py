@@ -104,7 +104,7 @@ class MllamaEngine(Generation):
 
     def __init__(self, cfg: MllamaConfig, weights: MllamaDeviceWeights, device, max_ctx: int = 4096, max_batch: int = 1,
                  decode_weights: str = "bf16", mxfp4_gemm_from: Optional[int] = None, cross_kv: str = "bf16",
-                 speculative: bool = False):
+                 speculative: bool = False, batch_speculative=None):
         """decode_weights="fp8" / "mxfp4" (VIS_AUDITOR_DECODE_WEIGHTS), mxfp4_gemm_from (VIS_AUDITOR_MXFP4_GEMM_FROM): the
         decode projections of EVERY layer - a cross-attention layer's q projection too - and the lm_head are quantised at load
         and decoded as on the Qwen2-VL engine (Qwen2VLEngine.__init__ describes the formats and the two arithmetic families
@@ -119,6 +119,8 @@ class MllamaEngine(Generation):
         layers on vis_decode_cross_attn_draft / _fp8_draft according to cross_kv; every decode_weights format.  Nothing is
         allocated until the first such request, and a request without either argument issues the launches of before."""
         cfg.validate_for_kernels()
+        if batch_speculative is not None:
+            raise ValueError("batch_speculative is the Qwen2-VL / Qwen2.5-VL engine's: batched cross-attention rows have no draft form")
         self.check_decode_weights(cfg, decode_weights)
         self.check_mxfp4_gemm_from(cfg, decode_weights, mxfp4_gemm_from)
         self.check_cross_kv(cross_kv)
