@@ -295,6 +295,11 @@ int vis_argmax_masked_f32(const void* logits, int V, void* ws_val, void* ws_idx,
 int vis_gemv_bf16_argmax_masked(const void* x, const void* W, const void* norm_w, void* logits, int N, int K, int ldw,
                                 float eps, void* ws_val, void* ws_idx, void* tokens, int max_tokens, void* cur_token,
                                 void* step_ptr, float inv_temp, unsigned seed, const void* allow, vis_stream_t stream);
+/* Host only, no launch: the constants with which the shape-specialised bf16 GEMV instances (K = 3584, 18944; single row)
+ * split n_pairs row pairs over n_waves (<= 8192) waves without a division: wave w owns pairs [b(w), b(w + 1)),
+ * b(w) = q w + ((r w) m >> s), which equals floor(n_pairs w / n_waves) for every w in [0, n_waves] (the launchers check
+ * it for every grid they launch; tests/test_gemv_specialised_gpu.py for the grids of its cases). */
+int vis_gemv_partition(int n_pairs, int n_waves, int* q, int* r, unsigned* m, int* s);
 
 /* Nucleus (top_p) sampling with per-row seeds (csrc/sampling.hip).  Row b < batch: logits + b * ld_logits (V f32), allowed
  * set A = every id, or (allow non-null) the ids whose bit is set in allow + b * ld_allow (vis_json_mask's rows).  Order A by

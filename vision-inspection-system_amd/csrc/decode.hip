@@ -115,11 +115,150 @@ __device__ __forceinline__ void gemv_bf16_body(GemvArgs p, const unsigned long l
   }
 }
 
+// The single-row body for K = 512 NCH64 with an odd number of segments per row (NCH64 = 7, K = 3584: gate/up and lm_head
+// of the 7B decode step; 37, K = 18944: its down projection - not instantiated, see gemv_bf16_kernel_shape).
+// Same tasks, same lane -> chunk map, same dot8 order over u and over segments and the same wave_sum as gemv_bf16_body, so
+// every output has its bits; what differs is work the result never needed:
+//  * the wave's pair range comes from gv_part (two multiplies) instead of two 64-bit divisions, and the first weight
+//    load is issued before anything else;
+//  * a register set loads exactly the sweeps of its segment (7; or 8, 8, 8, 8, 5) - the generic body rounds every row up to
+//    a multiple of GV_SEG sweeps and clamps the rest to the row's last chunk: one load in eight at K = 3584;
+//  * the task walk is straight-line code per row pair (gv_pair_tasks): which segment a task is, whether it ends the pair
+//    and which register set holds it are constants;
+//  * x is staged with the loads per thread the length needs;
+//  * the wave index is a scalar, so the pair range, the row numbers and the row addresses live in scalar registers and a
+//    load's address is scalar base + lane offset + immediate.
+template <bool AMAX, bool MASK, int NCH64>
+__device__ __forceinline__ void gemv_bf16_shape_body(GemvArgs p, const unsigned long long* __restrict__ allow) {
+  constexpr int NCH = NCH64 * 64;
+  constexpr int NSEG = (NCH64 + GV_SEG - 1) / GV_SEG;
+  constexpr int LAST = NCH64 - GV_SEG * (NSEG - 1);    // sweeps of a row's last segment
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* xs = (bf16_t*)smem;
+  const int tid = threadIdx.x, lane = tid & 63;
+  // the wave index as a scalar: pair range, row numbers and row addresses then live in scalar registers
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool swiglu = (p.act == GV_ACT_SWIGLU);
+  const int wid = blockIdx.x * 4 + wave;
+  const int p_begin = gv_part(wid, p.part_q, p.part_r, p.part_m, p.part_s);
+  const int p_end = gv_part(wid + 1, p.part_q, p.part_r, p.part_m, p.part_s);
+
+  GvBuf A, B;
+  if (p_begin < p_end) gv_load_n<(NSEG > 1) ? GV_SEG : LAST>(A, p, swiglu, p_begin, lane);  // in flight while x is staged
+
+  if (p.norm_w) gv_stage_x_rmsnorm(p.x, p.norm_w, xs, NCH, NCH * 8, p.eps, tid, lane, wave);
+  else gv_stage_x_n<(NCH + 255) / 256>(p.x, xs, NCH, tid);
+  __syncthreads();
+
+  float a0[1] = {0.f}, a1[1] = {0.f};
+  float best = -INFINITY;       // AMAX: lane 0's running maximum over this wave's rows
+  int bi = 0x7fffffff;
+  const unsigned am_step = AMAX ? (unsigned)*p.am_step : 0u;
+  auto amax_rows = [&](int pr) {      // gemv_bf16_body's
+    if (lane != 0) return;
+    const int o = 2 * pr;
+    float v0 = a0[0], v1 = a1[0];
+    if (p.am_inv_temp > 0.f) {
+      v0 = v0 * p.am_inv_temp + gumbel_noise(p.am_seed, am_step, (unsigned)o);
+      v1 = v1 * p.am_inv_temp + gumbel_noise(p.am_seed, am_step, (unsigned)(o + 1));
+    }
+    bool ok0 = true, ok1 = true;
+    if constexpr (MASK) {
+      const unsigned long long m = allow[o >> 6];
+      ok0 = (m >> (o & 63)) & 1ull;
+      ok1 = (m >> ((o + 1) & 63)) & 1ull;
+    }
+    if (ok0 && (v0 > best || (v0 == best && o < bi))) { best = v0; bi = o; }
+    if (ok1 && o + 1 < p.N && (v1 > best || (v1 == best && o + 1 < bi))) { best = v1; bi = o + 1; }
+  };
+  auto finish = [&](int pair) {
+    gv_finish<1>(p, swiglu, pair, lane, a0, a1);
+    if constexpr (AMAX) amax_rows(pair);
+    a0[0] = 0.f; a1[0] = 0.f;
+  };
+  // two pairs per round: with an odd number of tasks per pair (1 or 5 here) the second pair starts in B and ends in B
+  static_assert(NSEG % 2 == 1, "the pair walk below swaps the register sets after every pair");
+  int pr = p_begin;
+  for (; pr + 2 < p_end; pr += 2) {
+    gv_pair_tasks<NCH64, true>(A, B, p, swiglu, pr, xs, lane, a0[0], a1[0]);
+    finish(pr);
+    gv_pair_tasks<NCH64, true>(B, A, p, swiglu, pr + 1, xs, lane, a0[0], a1[0]);
+    finish(pr + 1);
+  }
+  if (pr + 1 < p_end) {
+    gv_pair_tasks<NCH64, true>(A, B, p, swiglu, pr, xs, lane, a0[0], a1[0]);
+    finish(pr);
+    gv_pair_tasks<NCH64, false>(B, A, p, swiglu, pr + 1, xs, lane, a0[0], a1[0]);
+    finish(pr + 1);
+  } else if (pr < p_end) {
+    gv_pair_tasks<NCH64, false>(A, B, p, swiglu, pr, xs, lane, a0[0], a1[0]);
+    finish(pr);
+  }
+  if constexpr (AMAX) {
+    __shared__ float am_v[4];
+    __shared__ int am_i[4];
+    if (lane == 0) { am_v[wave] = best; am_i[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < 4; ++w)
+        if (am_v[w] > best || (am_v[w] == best && am_i[w] < bi)) { best = am_v[w]; bi = am_i[w]; }
+      p.am_val[blockIdx.x] = best;
+      p.am_idx[blockIdx.x] = bi;
+    }
+  }
+}
+
 template <int NB, bool AMAX = false>
 __global__ __launch_bounds__(256) void gemv_bf16_kernel(GemvArgs p) { gemv_bf16_body<NB, AMAX, false>(p, nullptr); }
 
 __global__ __launch_bounds__(256) void gemv_bf16_argmax_masked_kernel(GemvArgs p, const unsigned long long* allow) {
   gemv_bf16_body<1, true, true>(p, allow);
+}
+
+// The shape-specialised instances.  Only NCH64 = 7 (K = 3584: gate/up, lm_head) is built: 125 - 128 VGPRs against the
+// generic 147 / 155 / 156.  NCH64 = 37 (K = 18944, the down projection) compiles to 152 - 208 VGPRs in every form tried - over
+// the generic instance's budget - so K = 18944 stays on the generic body.
+template <bool AMAX, int NCH64>
+__global__ __launch_bounds__(256) void gemv_bf16_kernel_shape(GemvArgs p) { gemv_bf16_shape_body<AMAX, false, NCH64>(p, nullptr); }
+template <int NCH64>
+__global__ __launch_bounds__(256) void gemv_bf16_argmax_masked_kernel_shape(GemvArgs p, const unsigned long long* allow) {
+  gemv_bf16_shape_body<true, true, NCH64>(p, allow);
+}
+
+// Which single-row instance a launch takes: 7 at K = 3584, 0 (generic) otherwise - and always with VIS_GEMV_GENERIC=1, the
+// A/B and test switch (read per launch, like VIS_DECODE_ATTN_STREAM; graph capture bakes it in).
+static int gv_shape_of(const GemvArgs& p) {
+  if (p.nb != 1 || p.K != 3584) return 0;
+  const char* e = getenv("VIS_GEMV_GENERIC");
+  if (e && atoi(e) != 0) return 0;
+  return p.K / 512;
+}
+
+// The constants of gv_part for a grid of `blocks` workgroups, checked against the division they replace for every wave of
+// the grid (the last few grids checked are remembered: a decode step repeats three).  False: the ranges differ - never
+// seen, the launchers then refuse to launch.
+extern "C" int vis_gemv_partition(int n_pairs, int n_waves, int* q, int* r, unsigned* m, int* s) {
+  if (n_pairs < 0 || n_waves < 1 || n_waves > 8192 || !q || !r || !m || !s) return VIS_ERR_ARG;
+  int L = 0;
+  while ((1 << L) < n_waves) ++L;
+  *q = n_pairs / n_waves;
+  *r = n_pairs % n_waves;
+  *s = 3 * L;
+  *m = (unsigned)(((1ull << *s) + (unsigned)n_waves - 1) / (unsigned)n_waves);
+  return VIS_OK;
+}
+static bool gv_set_partition(GemvArgs& p, int n_pairs, int blocks) {
+  const int n_waves = blocks * 4;
+  if (vis_gemv_partition(n_pairs, n_waves, &p.part_q, &p.part_r, &p.part_m, &p.part_s) != VIS_OK) return false;
+  static thread_local int seen[4][2];
+  static thread_local int seen_next = 0;
+  for (int i = 0; i < 4; ++i)
+    if (seen[i][0] == n_pairs && seen[i][1] == n_waves) return true;
+  for (int wid = 0; wid <= n_waves; ++wid)
+    if (gv_part(wid, p.part_q, p.part_r, p.part_m, p.part_s) != (int)((long long)n_pairs * wid / n_waves)) return false;
+  seen[seen_next][0] = n_pairs; seen[seen_next][1] = n_waves;
+  seen_next = (seen_next + 1) & 3;
+  return true;
 }
 
 static int gemv_bf16_launch(GemvArgs p, hipStream_t stream) {
@@ -130,7 +269,10 @@ static int gemv_bf16_launch(GemvArgs p, hipStream_t stream) {
   if (blocks > 2048) blocks = 2048;
   vis_clear_error();
   if (p.nb == 1) {
-    hipLaunchKernelGGL(gemv_bf16_kernel<1>, dim3(blocks), dim3(256), (size_t)p.K * 2, stream, p);
+    const int shape = gv_shape_of(p);
+    if (shape && !gv_set_partition(p, n_pairs, blocks)) return VIS_ERR_LAUNCH;
+    if (shape == 7) hipLaunchKernelGGL((gemv_bf16_kernel_shape<false, 7>), dim3(blocks), dim3(256), (size_t)p.K * 2, stream, p);
+    else hipLaunchKernelGGL(gemv_bf16_kernel<1>, dim3(blocks), dim3(256), (size_t)p.K * 2, stream, p);
   } else {
     static const bool attr_ok = [] {
       return hipFuncSetAttribute((const void*)gemv_bf16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, GV_ROWS_LDS_MAX) == hipSuccess &&
@@ -1114,8 +1256,11 @@ extern "C" int vis_gemv_bf16_argmax(const void* x, const void* W, const void* no
   int blocks = (n_pairs + 3) / 4;                     // the grid rule of gemv_bf16_launch
   if (blocks > 1024) blocks = 1024 + (blocks - 1024) / 8;
   if (blocks > 2048) blocks = 2048;
+  const int shape = gv_shape_of(p);
+  if (shape && !gv_set_partition(p, n_pairs, blocks)) return VIS_ERR_LAUNCH;
   vis_clear_error();
-  hipLaunchKernelGGL((gemv_bf16_kernel<1, true>), dim3(blocks), dim3(256), (size_t)K * 2, stream, p);
+  if (shape == 7) hipLaunchKernelGGL((gemv_bf16_kernel_shape<true, 7>), dim3(blocks), dim3(256), (size_t)K * 2, stream, p);
+  else hipLaunchKernelGGL((gemv_bf16_kernel<1, true>), dim3(blocks), dim3(256), (size_t)K * 2, stream, p);
   hipLaunchKernelGGL(argmax_merge_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx, blocks,
                      (int*)tokens, max_tokens, (int*)cur_token, (int*)step_ptr);
   return vis_check_launch();
@@ -1141,9 +1286,13 @@ extern "C" int vis_gemv_bf16_argmax_masked(const void* x, const void* W, const v
   int blocks = (n_pairs + 3) / 4;                     // the grid rule of gemv_bf16_launch
   if (blocks > 1024) blocks = 1024 + (blocks - 1024) / 8;
   if (blocks > 2048) blocks = 2048;
+  const int shape = gv_shape_of(p);
+  if (shape && !gv_set_partition(p, n_pairs, blocks)) return VIS_ERR_LAUNCH;
   vis_clear_error();
-  hipLaunchKernelGGL(gemv_bf16_argmax_masked_kernel, dim3(blocks), dim3(256), (size_t)K * 2, stream, p,
-                     (const unsigned long long*)allow);
+  if (shape == 7) hipLaunchKernelGGL(gemv_bf16_argmax_masked_kernel_shape<7>, dim3(blocks), dim3(256), (size_t)K * 2, stream, p,
+                                     (const unsigned long long*)allow);
+  else hipLaunchKernelGGL(gemv_bf16_argmax_masked_kernel, dim3(blocks), dim3(256), (size_t)K * 2, stream, p,
+                          (const unsigned long long*)allow);
   hipLaunchKernelGGL(argmax_merge_masked_kernel, dim3(1), dim3(256), 0, stream, (const float*)ws_val, (const int*)ws_idx,
                      blocks, (int*)tokens, max_tokens, (int*)cur_token, (int*)step_ptr);
   return vis_check_launch();

@@ -28,7 +28,19 @@ struct GemvArgs {
   const int* am_step;
   float am_inv_temp;
   unsigned am_seed;
+  // shape-specialised bf16 instances only (gv_set_partition): n_pairs = part_q * n_waves + part_r, and the magic multiplier
+  // and shift that replace the division by n_waves in gv_part
+  int part_q, part_r, part_s;
+  unsigned part_m;
 };
+
+// First row pair of wave `wid` (the end of wave wid - 1): floor(n_pairs * wid / n_waves) without a division.  With
+// n_pairs = q n_waves + r the value is q wid + floor(r wid / n_waves); r wid < n_waves^2 <= 2^(2 L) for n_waves <= 2^L, and
+// with s = 3 L, m = ceil(2^s / n_waves) the product (r wid) m >> s is that floor exactly (the multiplier's excess
+// e = m n_waves - 2^s < n_waves gives (r wid) e < 2^s).  L <= 13 here (at most 2048 workgroups), so m fits 32 bits.
+__host__ __device__ __forceinline__ int gv_part(int wid, int q, int r, unsigned m, int s) {
+  return q * wid + (int)(((unsigned long long)(unsigned)(r * wid) * m) >> s);
+}
 
 __device__ __forceinline__ float gumbel_noise(unsigned seed, unsigned step, unsigned i) {
   unsigned long long z = ((unsigned long long)seed << 32) ^ ((unsigned long long)step * 0x9E3779B97F4A7C15ull) ^ i;
@@ -109,6 +121,61 @@ __device__ __forceinline__ void gv_consume(const GvBuf& b, const bf16_t* xs, int
       a1[r] = dot8(b.w1[u], xv, a1[r]);
     }
   }
+}
+
+// Shape-specialised forms (gemv_bf16_shape_body, decode.hip): a row holds a whole number of 64-chunk lane sweeps, so a
+// register set loads and consumes exactly the CNT sweeps its segment has - no clamped duplicate load, no zero select.
+// c0 = lane + 64 * GV_SEG * seg.  Lane -> chunk map and dot8 order are gv_load's / gv_consume's.
+template <int CNT>
+__device__ __forceinline__ void gv_load_n(GvBuf& b, const GemvArgs& p, bool swiglu, int pair, int c0) {
+  int r0, r1;
+  gv_rows(p, swiglu, pair, r0, r1);
+  // address = the row's (wave-uniform: scalar) base + the lane's 32-bit byte offset + a constant per sweep (1 KiB apart:
+  // the loads' immediates) - no 64-bit vector address per load, as the clamped index of gv_load needs
+  const char* w0 = (const char*)(p.W + (size_t)r0 * p.ldw);
+  const char* w1 = (const char*)(p.W + (size_t)r1 * p.ldw);
+  // (two lane offsets, 4 KiB apart, because a load's immediate ends at 4095; both kept opaque: folded into W they make one
+  // 64-bit vector base, and every row then needs a vector address of its own)
+  unsigned off = (unsigned)c0 * 16u, off4 = off + 4096u;
+  asm volatile("" : "+v"(off), "+v"(off4));
+#pragma unroll
+  for (int u = 0; u < CNT; ++u) {
+    const unsigned o = (u < 4) ? off : off4;
+    b.w0[u] = __builtin_nontemporal_load((const u32x4*)(w0 + o) + 64 * (u & 3));
+    b.w1[u] = __builtin_nontemporal_load((const u32x4*)(w1 + o) + 64 * (u & 3));
+  }
+}
+
+template <int CNT>
+__device__ __forceinline__ void gv_consume_n(const GvBuf& b, const bf16_t* xs, int c0, float& a0, float& a1) {
+  // x is read from LDS for every task, as in gv_consume: at one segment per row the reads do not depend on the pair, and
+  // hoisted out of the pair loop they would sit in 4 CNT registers for the whole kernel (174 VGPRs against the generic 147)
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int u = 0; u < CNT; ++u) {
+    const u32x4 xv = ((const u32x4*)xs + c0)[64 * u];
+    a0 = dot8(b.w0[u], xv, a0);
+    a1 = dot8(b.w1[u], xv, a1);
+  }
+  // the sums are only read when the pair is finished: unpinned, the straight-line tasks of a pair have their products sunk
+  // behind every segment's loads (K = 18944: all 74 loads of a pair live at once, 256 VGPRs and spills)
+  asm volatile("" : "+v"(a0), "+v"(a1));
+}
+
+// Tasks S .. NSEG - 1 of one row pair of a K = 512 NCH64 row: task S sits in `cur`; the loads of the task after it (the
+// pair's next segment, or segment 0 of the wave's next pair when NEXT) go into `nxt` before `cur` is consumed.  The two
+// sets swap roles from task to task, so the task after the pair's last one is in the last task's `nxt`.
+// NEXT is a template argument so that no load sits under a branch: after a skipped load the compiler has to assume the
+// smaller number of loads in flight and waits for the whole set before the first product (see gv_load).
+template <int NCH64, bool NEXT, int S = 0>
+__device__ __forceinline__ void gv_pair_tasks(GvBuf& cur, GvBuf& nxt, const GemvArgs& p, bool swiglu, int pair,
+                                              const bf16_t* xs, int lane, float& a0, float& a1) {
+  constexpr int NSEG = (NCH64 + GV_SEG - 1) / GV_SEG, LAST = NCH64 - GV_SEG * (NSEG - 1);
+  constexpr int FIRST = NSEG > 1 ? GV_SEG : LAST;
+  if constexpr (S + 1 < NSEG) gv_load_n<(S + 2 < NSEG) ? GV_SEG : LAST>(nxt, p, swiglu, pair, lane + 64 * GV_SEG * (S + 1));
+  else if constexpr (NEXT) gv_load_n<FIRST>(nxt, p, swiglu, pair + 1, lane);
+  gv_consume_n<(S + 1 < NSEG) ? GV_SEG : LAST>(cur, xs, lane + 64 * GV_SEG * S, a0, a1);
+  if constexpr (S + 1 < NSEG) gv_pair_tasks<NCH64, NEXT, S + 1>(nxt, cur, p, swiglu, pair, xs, lane, a0, a1);
 }
 
 template <int NB>
@@ -208,17 +275,23 @@ __device__ __forceinline__ void gv_stage_x_rmsnorm(const bf16_t* __restrict__ x,
 // x -> LDS for long inputs (K > 8192), all global loads of a thread issued before the first LDS store (K = 18944:
 // 10 chunks per thread; a plain load/store loop serialises ~10 L2 round trips in front of the weight stream).  Unconditional clamped
 // loads (a predicated load makes hipcc drain vmcnt per branch); chunks past the end are simply not stored.
+// NST = loads per thread, >= ceil(nch / 256): GV_STAGE_MAX where the length is a run-time value, the exact count where the
+// kernel instance knows it (K = 18944: 10, not 15 of which five are clamped duplicates).
 #define GV_STAGE_MAX 15  // 15 x 256 x 8 = 30720 elements >= the 60 KiB LDS limit of the launchers
-template <bool SWZ = false>
-__device__ __forceinline__ void gv_stage_x(const bf16_t* __restrict__ x, bf16_t* xs, int nch, int tid) {
-  u32x4 v[GV_STAGE_MAX];
+template <int NST, bool SWZ = false>
+__device__ __forceinline__ void gv_stage_x_n(const bf16_t* __restrict__ x, bf16_t* xs, int nch, int tid) {
+  u32x4 v[NST];
 #pragma unroll
-  for (int i = 0; i < GV_STAGE_MAX; ++i) v[i] = *(const u32x4*)(x + (size_t)min(tid + i * 256, nch - 1) * 8);
+  for (int i = 0; i < NST; ++i) v[i] = *(const u32x4*)(x + (size_t)min(tid + i * 256, nch - 1) * 8);
 #pragma unroll
-  for (int i = 0; i < GV_STAGE_MAX; ++i) {
+  for (int i = 0; i < NST; ++i) {
     const int c = tid + i * 256;
     if (c < nch) *(u32x4*)(xs + gv_slot<SWZ>(c) * 8) = v[i];
   }
+}
+template <bool SWZ = false>
+__device__ __forceinline__ void gv_stage_x(const bf16_t* __restrict__ x, bf16_t* xs, int nch, int tid) {
+  gv_stage_x_n<GV_STAGE_MAX, SWZ>(x, xs, nch, tid);
 }
 
 // stage one row of x (optionally RMS-normalised) into LDS; called once per input row

@@ -67,6 +67,7 @@ _SIGS = {
     "vis_schema_mask": "pp" + "i" + "p" * 5 + "iip" + "i" + "pppp" + "iii" + "p",
     "vis_argmax_masked_f32": "p" + "i" + "ppp" + "i" + "pp" + "fu" + "ii" + "p" + "i" + "p",
     "vis_gemv_bf16_argmax_masked": "pppp" + "iii" + "f" + "ppp" + "i" + "pp" + "fu" + "p" + "p",
+    "vis_gemv_partition": "ii" + "pppp",
     "vis_sample_ws_bytes": "ii",
     "vis_sample_f32": "p" + "ii" + "p" + "i" + "ff" + "pp" + "i" + "pp" + "i" + "pp" + "p",
     "vis_penalty_state_bytes": "ii",
@@ -836,6 +837,25 @@ def gemv(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias: Optional[tor
                               w.stride(0), act, 1 if out.dtype == torch.float32 else 0, eps, _stream())
     _check(rc, "vis_gemv_bf16")
     return out
+
+
+def gemv_grid(N: int, act: int = ACT_NONE):
+    """(row pairs, workgroups) of a single-row bf16 gemv launch over N weight rows: the grid rule of csrc/decode.hip."""
+    n_pairs = N // 2 if act == ACT_SWIGLU else (N + 1) // 2
+    blocks = (n_pairs + 3) // 4
+    if blocks > 1024:
+        blocks = 1024 + (blocks - 1024) // 8
+    return n_pairs, min(blocks, 2048)
+
+
+def gemv_partition(n_pairs: int, n_waves: int):
+    """(q, r, m, s) with which the shape-specialised gemv instances split n_pairs row pairs over n_waves waves: wave w owns
+    [b(w), b(w + 1)), b(w) = q * w + ((r * w * m) >> s).  Host arithmetic only (vis_gemv_partition); no GPU needed."""
+    q, r, s, m = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_uint()
+    rc = load().vis_gemv_partition(n_pairs, n_waves, ctypes.addressof(q), ctypes.addressof(r), ctypes.addressof(m),
+                                   ctypes.addressof(s))
+    _check(rc, "vis_gemv_partition")
+    return q.value, r.value, m.value, s.value
 
 
 def quantize_fp8_rows(w: torch.Tensor):
