@@ -164,7 +164,12 @@ __device__ __forceinline__ void chain_merge_head(const gran_t* part_g, gran_t* a
   if (bad) __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int G>
+// X7: K == 3584 and Ko == 3584 (the launcher's promise; Qwen2-VL-7B's head, built for G = 7 only): a weight row is exactly
+// seven lane sweeps, so the projection role takes gv_load_n<7> / gv_consume_n<7> - the same lane -> chunk map and dot8 order
+// as gv_load / gv_consume, without the clamped, zero-selected eighth sweep and with a scalar row base instead of a 64-bit
+// vector address per load.  A template argument, not a branch: hipcc merges the two forms' loads behind a branch into
+// one block that keeps every address in vector registers.
+template <int G, bool X7 = false>
 __global__ __launch_bounds__(256) void decode_chain_kernel(ChainArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -187,22 +192,52 @@ __global__ __launch_bounds__(256) void decode_chain_kernel(ChainArgs p) {
   if (b < p.n_gv) {
     // ------------------------------------------------------------------ projection role
     bf16_t* xs = (bf16_t*)smem;
-    const int wid = b * 4 + wave;
-    if (p.x_idx) p.x += (size_t)min(max(*p.x_idx, 0), p.x_rows - 1) * p.K;   // (vis_gather_rows' clamp)
+    // (X7: the wave index as a scalar - the row bases of gv_load_n live in scalar registers)
+    const int wid = b * 4 + (X7 ? __builtin_amdgcn_readfirstlane(wave) : wave);
+    const bool indexed = (p.x_idx != nullptr);
+    if (indexed) p.x += (size_t)min(max(*p.x_idx, 0), p.x_rows - 1) * p.K;   // (vis_gather_rows' clamp)
     GemvArgs ga;
     ga.W = p.Wqkv; ga.ldw = p.ldw_qkv; ga.N = p.Nqkv;
     const int nch = p.K >> 3, n_pairs_q = p.Nqkv >> 1;
+    const int pair_q = min(wid, n_pairs_q - 1);
     GvBuf A;
-    gv_load(A, ga, false, min(wid, n_pairs_q - 1), 0, lane, nch);   // in flight while x is normalised
-    gv_stage_x_rmsnorm(p.x, p.norm_w, xs, nch, p.K, p.eps, tid, lane, wave);
+    // Vector loads return in issue order, so the ORDER of the requests is the order of the work: x and the norm weight
+    // first, then the bias pair lane 0 adds at the end, then the weight rows - the wave waits for x alone, normalises it
+    // while its weights stream in and finds the bias in a register after the sum.  (Weights first, as this phase began:
+    // the x loads returned behind the wave's 16 KiB of weights, and the norm - two barriers and a reduction - ran after
+    // them instead of under them.)
+    // Only the exact-sweep instance (114 VGPRs) does so.  The generic one sits at 124 VGPRs + 4 AGPRs = 128, the last count
+    // with four waves per SIMD, and every load of its holds a 64-bit vector address: x's 16 registers on top of the weights'
+    // made 135, the early bias pair 126 - 128.  It keeps the order it had: weights, x; sum, bias; sum, residual.
+    [[maybe_unused]] bf16_t bq0 = 0, bq1 = 0;
+    if constexpr (X7) {
+      if (!indexed) {
+        GvXReq xq;
+        gv_stage_x_rmsnorm_request(xq, p.x, p.norm_w, nch, tid);     // (K <= 4096: the launcher)
+        if (p.bqkv) { bq0 = p.bqkv[2 * pair_q]; bq1 = p.bqkv[2 * pair_q + 1]; }
+        gv_load_n<7>(A, ga, false, pair_q, lane);
+        gv_stage_x_rmsnorm_finish(xq, xs, nch, p.K, p.eps, tid, lane, wave);
+      } else {
+        // layer 0 reads the embedding row *x_idx: x's address is a memory round trip away and the weights must not wait
+        // for it, so here the weights go first and x follows them, as it always did
+        if (p.bqkv) { bq0 = p.bqkv[2 * pair_q]; bq1 = p.bqkv[2 * pair_q + 1]; }
+        gv_load_n<7>(A, ga, false, pair_q, lane);
+        gv_stage_x_rmsnorm(p.x, p.norm_w, xs, nch, p.K, p.eps, tid, lane, wave);
+      }
+    } else {
+      gv_load(A, ga, false, pair_q, 0, lane, nch);                   // in flight while x is normalised
+      gv_stage_x_rmsnorm(p.x, p.norm_w, xs, nch, p.K, p.eps, tid, lane, wave);
+    }
     __syncthreads();
     CH_STAMP(1);
     float a0[1] = {0.f}, a1[1] = {0.f};
-    gv_consume<1>(A, xs, p.K, 0, lane, nch, a0, a1);
+    if constexpr (X7) gv_consume_n<7>(A, xs, lane, a0[0], a1[0]);
+    else gv_consume<1>(A, xs, p.K, 0, lane, nch, a0, a1);
     float s0 = wave_sum(a0[0]), s1 = wave_sum(a1[0]);
     if (lane == 0 && wid < n_pairs_q) {
       const int o = 2 * wid;
-      if (p.bqkv) { s0 += bf2f(p.bqkv[o]); s1 += bf2f(p.bqkv[o + 1]); }
+      if constexpr (X7) { if (p.bqkv) { s0 += bf2f(bq0); s1 += bf2f(bq1); } }
+      else { if (p.bqkv) { s0 += bf2f(p.bqkv[o]); s1 += bf2f(p.bqkv[o + 1]); } }
       gr_st(p.qkv_g + wid, (uint32_t)f2bf(s0) | ((uint32_t)f2bf(s1) << 16), tag);
     }
     CH_STAMP(2);
@@ -223,7 +258,13 @@ __global__ __launch_bounds__(256) void decode_chain_kernel(ChainArgs p) {
     GemvArgs go;
     go.W = p.Wo; go.ldw = p.ldw_o; go.N = p.No;
     const int nch_o = p.Ko >> 3;
-    gv_load(A, go, false, min(wid, n_pairs_o - 1), 0, lane, nch_o);
+    const int pair_o = min(wid, n_pairs_o - 1);
+    // the residual pair lane 0 adds after the last sum, requested ahead of the weights (x is 16-byte aligned and No even:
+    // one aligned word): after the sum it was a memory round trip in front of the store that ends the launch
+    [[maybe_unused]] uint32_t res;
+    if constexpr (X7) res = *(const uint32_t*)(p.x + 2 * pair_o);
+    if constexpr (X7) gv_load_n<7>(A, go, false, pair_o, lane);
+    else gv_load(A, go, false, pair_o, 0, lane, nch_o);
     // cue: the last granule of every head (cheap to poll: Hq words) until the FIRST head is out - the heads finish within
     // ~2 us of each other -; from then on the whole row is polled, every granule checked
     if (wave == 0) {
@@ -264,11 +305,13 @@ __global__ __launch_bounds__(256) void decode_chain_kernel(ChainArgs p) {
     __syncthreads();
     CH_STAMP(4);
     a0[0] = 0.f; a1[0] = 0.f;
-    gv_consume<1>(A, xs, p.Ko, 0, lane, nch_o, a0, a1);
+    if constexpr (X7) gv_consume_n<7>(A, xs, lane, a0[0], a1[0]);
+    else gv_consume<1>(A, xs, p.Ko, 0, lane, nch_o, a0, a1);
     s0 = wave_sum(a0[0]); s1 = wave_sum(a1[0]);
     if (lane == 0 && wid < n_pairs_o) {
       const int o = 2 * wid;
-      s0 += bf2f(p.x[o]); s1 += bf2f(p.x[o + 1]);
+      if constexpr (X7) { s0 += bf2f((bf16_t)res); s1 += bf2f((bf16_t)(res >> 16)); }
+      else { s0 += bf2f(p.x[o]); s1 += bf2f(p.x[o + 1]); }
       *(uint32_t*)(p.y + o) = (uint32_t)f2bf(s0) | ((uint32_t)f2bf(s1) << 16);
     }
     // the launch is over for everybody who needed its number: workgroup 0 saw every head merged, which needed every active
@@ -317,7 +360,7 @@ static size_t chain_lds_bytes(int K) {
 // first device's / first K's answer).
 #define CH_RESIDENT_MARGIN 32
 #define CH_MAX_DEVICES 16
-template <int G>
+template <int G, bool X7>
 static int chain_resident_blocks(size_t lds) {
   struct Entry { size_t lds; int blocks; bool attr_set; };
   static Entry cache[CH_MAX_DEVICES] = {};
@@ -325,14 +368,14 @@ static int chain_resident_blocks(size_t lds) {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CH_MAX_DEVICES) return 0;
   Entry& en = cache[dev];
   if (!en.attr_set) {
-    if (hipFuncSetAttribute((const void*)decode_chain_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)) !=
+    if (hipFuncSetAttribute((const void*)decode_chain_kernel<G, X7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * 1024)) !=
         hipSuccess)
       return 0;
     en.attr_set = true;
   }
   if (en.lds == lds && en.blocks > 0) return en.blocks;
   hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, (const void*)decode_chain_kernel<G>) != hipSuccess) return 0;
+  if (hipFuncGetAttributes(&fa, (const void*)decode_chain_kernel<G, X7>) != hipSuccess) return 0;
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   const int vg = ((fa.numRegs > 0 ? fa.numRegs : 512) + 7) / 8 * 8;
@@ -370,12 +413,17 @@ extern "C" long long vis_decode_chain_ws_bytes(int Hq, int Hkv, int nsplit) {
 // item past the context returns at once, whenever it is placed, so the bound counts ceil(ctx_bound / 64) splits, not
 // nsplit.  (Llama-3.2-11B: 768 + 32 + 8 splits-per-64-keys leaves room for 1536 keys; with nsplit counted a 2048-row cache
 // was refused outright.)  vis_decode_chain_ctx_limit gives the largest bound the device holds.
+// the kernel instance of a head shape: the exact-sweep form (X7) where both weight matrices have rows of 3584 and G = 7
+static bool chain_x7(int G, int K, int Ko) { return G == 7 && K == 3584 && Ko == 3584; }
+
 template <int G>
 static int chain_waiting_limit(int Hq, int Hkv, int K) {
   const int Nqkv = (Hq + 2 * Hkv) * 128, Ko = Hq * 128;
   const size_t lds = chain_lds_bytes<G>(K > Ko ? K : Ko);
   if (lds > 64 * 1024) return 0;
-  const int resident = chain_resident_blocks<G>(lds);
+  int resident;
+  if constexpr (G == 7) resident = chain_x7(G, K, Ko) ? chain_resident_blocks<G, true>(lds) : chain_resident_blocks<G, false>(lds);
+  else resident = chain_resident_blocks<G, false>(lds);
   const int fixed = Nqkv / 8 + Hq;
   return resident > fixed ? (resident - fixed) / Hkv : 0;       // attention splits that may be active
 }
@@ -452,7 +500,11 @@ extern "C" int vis_decode_chain(const void* x, const void* x_idx, int x_rows, co
   if (lds > 64 * 1024 || active > chain_split_limit(Hq, Hkv, K)) return VIS_ERR_UNSUPPORTED;
   vis_clear_error();
   da_dispatch_g(G, [&](auto g) {
-    hipLaunchKernelGGL(decode_chain_kernel<decltype(g)::value>, dim3(grid), dim3(256), lds, stream, p);
+    constexpr int G_ = decltype(g)::value;
+    if constexpr (G_ == 7) {
+      if (chain_x7(G_, K, Ko)) { hipLaunchKernelGGL((decode_chain_kernel<7, true>), dim3(grid), dim3(256), lds, stream, p); return; }
+    }
+    hipLaunchKernelGGL((decode_chain_kernel<G_, false>), dim3(grid), dim3(256), lds, stream, p);
   });
   return vis_check_launch();
 }

@@ -220,11 +220,53 @@ __device__ __forceinline__ int gv_slot(int c) { return SWZ ? (c ^ ((c >> 4) & 3)
 // x -> rmsnorm(x) * w -> LDS (bf16, HF rounding order).  x and w are loaded ONCE (both loads issued before the
 // reduction) and normalised from registers: hidden sizes <= 4096 give at most two 16-byte chunks per thread; the
 // re-reading loop of the first version put a second L2 round trip into every norm-fused GEMV's prologue.
+// That form comes in two halves, so that a caller can put other requests between them: vector loads return to a wave in
+// issue order, so what is requested BEFORE x delays the norm and what is requested after it streams in under the norm
+// (the chained layer head asks for x first, then for its weight rows: decode_chain.hip).
+struct GvXReq {
+  u32x4 r0, r1, g0, g1;   // this thread's two chunks of x and of the norm weight (zero past the row's end)
+};
+__device__ __forceinline__ void gv_stage_x_rmsnorm_request(GvXReq& q, const bf16_t* __restrict__ x, const bf16_t* __restrict__ nw,
+                                                           int nch, int tid) {   // nch <= 512
+  const int c0 = tid, c1 = tid + 256;
+  const u32x4 z = (u32x4){0u, 0u, 0u, 0u};
+  q.r0 = (c0 < nch) ? *(const u32x4*)(x + c0 * 8) : z; q.r1 = (c1 < nch) ? *(const u32x4*)(x + c1 * 8) : z;
+  q.g0 = (c0 < nch) ? *(const u32x4*)(nw + c0 * 8) : z; q.g1 = (c1 < nch) ? *(const u32x4*)(nw + c1 * 8) : z;
+}
+template <bool SWZ = false>
+__device__ __forceinline__ void gv_stage_x_rmsnorm_finish(const GvXReq& q, bf16_t* xs, int nch, int K, float eps, int tid, int lane,
+                                                          int wave) {
+  __shared__ float red[4];
+  const int c0 = tid, c1 = tid + 256;
+  float f0[8], f1[8], w0[8], w1[8], o[8];
+  unpack8(q.r0, f0); unpack8(q.r1, f1);
+  float ss = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ss += f0[e] * f0[e] + f1[e] * f1[e];
+  ss = wave_sum(ss);
+  if (lane == 0) red[wave] = ss;
+  __syncthreads();
+  const float rstd = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
+  unpack8(q.g0, w0); unpack8(q.g1, w1);
+  if (c0 < nch) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = bf2f(f2bf(f0[e] * rstd)) * w0[e];
+    *(u32x4*)(xs + gv_slot<SWZ>(c0) * 8) = pack8(o);
+  }
+  if (c1 < nch) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = bf2f(f2bf(f1[e] * rstd)) * w1[e];
+    *(u32x4*)(xs + gv_slot<SWZ>(c1) * 8) = pack8(o);
+  }
+}
+
 template <bool SWZ = false>
 __device__ __forceinline__ void gv_stage_x_rmsnorm(const bf16_t* __restrict__ x, const bf16_t* __restrict__ nw, bf16_t* xs,
                                                    int nch, int K, float eps, int tid, int lane, int wave) {
   __shared__ float red[4];
-  if (nch <= 512) {
+  if (nch <= 512) {     // (= request + finish, kept in one piece: handed through GvXReq the register allocation differs - the
+                        // chained head's generic instance 124 -> 127 VGPRs with none to spare, the multi-row GEMVs 181 -> 182;
+                        // profiles/decode_tail_operands.json)
     const int c0 = tid, c1 = tid + 256;
     const u32x4 z = (u32x4){0u, 0u, 0u, 0u};
     const u32x4 r0 = (c0 < nch) ? *(const u32x4*)(x + c0 * 8) : z, r1 = (c1 < nch) ? *(const u32x4*)(x + c1 * 8) : z;
